@@ -11,6 +11,10 @@ torchrun the ranks come from the environment and must match --gpus.  Every rank 
 subtrees below its round-robin share of the depth-d frontier), so per-GPU work is fixed as N grows (weak scaling); after every step
 the ranks exchange min{incumbent UB, open LB} with the library's RCCL all-reduce (C ABI: omc_allreduce_bounds) -- the one exchange
 of node-parallel B&B; there is no data-path collective.
+
+A plain run sets up, warms up, times the steps and prints the result line (with the roofline of the timed steps' own HIP-event times).
+`--full` adds the runs behind the other figures of the line (latency_b1, branching, time_to_gap, shor_config3, cold_start,
+one_batch_drained, cpu_baseline).  `--dump-outputs DIR` writes what the timed path returned for its last step (see dump_outputs).
 """
 import argparse
 import faulthandler
@@ -54,8 +58,14 @@ def parse():
     ap.add_argument("--early-stop", type=float, default=None, help="early_stop_factor of the relaxation parameters (library default 1.5; 0 = rule off)")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child-arg", default="{}", help=argparse.SUPPRESS)
-    ap.add_argument("--extras", type=int, default=1, help="0: skip latency_b1 / branching / time_to_gap / cpu_baseline (rank 0, N=1 only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the headline: latency_b1, the branching instance, time_to_gap on configs 2 and 1, Shor config 3, "
+                    "cold_start, one_batch_drained and cpu_baseline (rank 0, N=1 only; minutes); a plain run measures the headline alone")
+    ap.add_argument("--extras", type=int, default=1, help="with --full, 0: skip the runs --full adds")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path returned for its last step to DIR/<name>.npy (float64, rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -206,6 +216,32 @@ def _cpu_worker(job):
     else:
         run()
     return its
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, bounds):
+    """--dump-outputs: the results fetch() returned for the last timed batch (one row per node, in staging order) and the (upper, lower)
+    bounds of that step's exchange, one float64 .npy each.  The instance is seeded and the frontier is derived from it deterministically,
+    so the same arguments give the same inputs in every run.  A batch whose results exceed DUMP_MAX_BYTES is written as a fixed, seeded
+    sample of its nodes; node_index.npy names the rows kept."""
+    import numpy as np
+    cols = {"objective": [o["objective"] for o in out], "dual_bound": [o["dual_bound"] for o in out], "status_code": [o["status_code"] for o in out],
+            "iters": [o["iters"] for o in out], "U": [o["U"] for o in out], "lambda_min": [o["lambda_min"] for o in out],
+            "breakpoint_vec": [o["breakpoint_vec"] for o in out]}
+    cols = {name: np.asarray(v, dtype=np.float64) for name, v in cols.items()}
+    B = len(out)
+    row_bytes = 8 + sum(a[0].nbytes for a in cols.values())            # + the node_index entry
+    keep = np.arange(B)
+    if B * row_bytes > DUMP_MAX_BYTES - 4096:
+        keep = np.sort(np.random.default_rng(0).choice(B, (DUMP_MAX_BYTES - 4096) // row_bytes, replace=False))
+    cols = {name: a[keep] for name, a in cols.items()}
+    cols["node_index"] = keep.astype(np.float64)
+    cols["bounds"] = np.asarray(bounds, dtype=np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in cols.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def main():
@@ -362,10 +398,10 @@ def main():
                 eng.solve()
             out_all = eng.fetch(want_Y=False, want_X=False)
             for q in range(args.steps):                      # one bound exchange per batch, as in the step-by-step form
-                exchange(out_all[q * B:(q + 1) * B])
+                bounds = exchange(out_all[q * B:(q + 1) * B])
             out = out_all[(args.steps - 1) * B:]
         else:
-            _, out = step()
+            bounds, out = step()
         for c, v in eng.kernel_stats().items():
             a = kstats.setdefault(c, dict(launches=0, ms=0.0, units=0))
             a["launches"] += v["launches"]; a["ms"] += v["ms"]; a["units"] += v["units"]
@@ -436,9 +472,12 @@ def main():
                                 "the kernels back to back (profiles/ has both)",
                     kernel_ms=per_kernel, kernels=kernel_rooflines)
 
-    eng.tuning_reload_env()                        # the extras run with the library default (or whatever the caller's environment says)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, bounds)
+
     extras = {}
-    if rank == 0 and world == 1 and args.extras:
+    if rank == 0 and world == 1 and args.full and args.extras:
+        eng.tuning_reload_env()                    # the extras run with the library default (or whatever the caller's environment says)
         # ---- single-node-at-a-time (BASELINE config 2 wording): batch 1, the reference's serial order --------------------------------
         sample = nodes[:: max(1, B // 12)][:12]
         e1 = omc_amd.Engine(A, mask, gamma, k, device=local)
@@ -533,7 +572,7 @@ def main():
         if args.cpu_nodes > 0:
             extras["cpu_baseline"] = cpu_baseline_legs(A, mask, gamma, k, cfg["cut_type"], rho_scale, nodes[: args.cpu_nodes], args.depth)
     if rank == 0:
-        print(json.dumps({
+        line = {
             "metric": "B&B node-relaxations/sec, 100x100 k=1", "value": value, "value_note": "nodes returned with a certificate per second; all nodes (certified + SLOW_PROGRESS with values and a valid bound): config.nodes_per_s_all", "unit": "node-relaxations/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -548,10 +587,12 @@ def main():
                        "certified_fraction": certified / B, "certified_nodes_per_s": value, "nodes_per_s_all": value_all,
                        "bounds_exchange": (comm_kind if use_comm else None),
                        "jacobi_sweeps_last_step": info["jacobi_sweeps"], "instance_sha256": data.instance_sha256(A, mask)[:16]},
-            "roofline": roofline, "cpu_baseline": extras.get("cpu_baseline"), "time_to_gap": extras.get("time_to_gap"),
-            "latency_b1": extras.get("latency_b1"), "branching": extras.get("branching"), "branching_shor": extras.get("branching_shor"), "branching_streaming": extras.get("branching_streaming"), "time_to_gap_config1": extras.get("time_to_gap_config1"),
-            "shor_config3": extras.get("shor_config3"), "cold_start": extras.get("cold_start"), "one_batch_drained": extras.get("one_batch_drained"),
-        }))
+            "roofline": roofline}
+        if args.full:
+            for key in ("cpu_baseline", "time_to_gap", "latency_b1", "branching", "branching_shor", "branching_streaming", "time_to_gap_config1",
+                        "shor_config3", "cold_start", "one_batch_drained"):
+                line[key] = extras.get(key)
+        print(json.dumps(line))
     eng.close()
     if dist.is_initialized():
         dist.destroy_process_group()
