@@ -75,6 +75,7 @@ static const char* const OMC_TUNING_KEYS[] = {
   "OMC_CP_SERIES",
   "OMC_DEBUG_MAX_SWEEPS",
   "OMC_DENSE_CHECK",
+  "OMC_DENSE_PROJ",
   "OMC_GLOBAL_NOLDS",
   "OMC_GRAPH_MAX",
   "OMC_GRAPH_TAILS",
@@ -602,14 +603,15 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   }
   w.Mbuf = h->bMbuf.as<double>(); w.Vrow = h->bVrow.as<double>();
   {   // tracked subspace of the cone block (k_cone_sub)
-    ENS(h->bXs, sB * w.np16 * 16 * 8); ENS(h->bsubS, sB * (17 + 256) * 8); ENS(h->bsubI, sB * 14 * sizeof(int));
+    ENS(h->bXs, sB * w.np16 * 16 * 8); ENS(h->bsubS, sB * (17 + 256) * 8); ENS(h->bsubI, sB * 15 * sizeof(int));
     HIPCHK(hipMemsetAsync(h->bXs.p, 0, sB * w.np16 * 16 * 8, h->stream));
     HIPCHK(hipMemsetAsync(h->bsubS.p, 0, sB * (17 + 256) * 8, h->stream));
-    HIPCHK(hipMemsetAsync(h->bsubI.p, 0, sB * 14 * sizeof(int), h->stream));
+    HIPCHK(hipMemsetAsync(h->bsubI.p, 0, sB * 15 * sizeof(int), h->stream));
     w.Xs = h->bXs.as<double>(); w.sub_theta = h->bsubS.as<double>(); w.trM = h->bsubS.as<double>() + sB * 16;
     w.sub_on = h->bsubI.as<int>(); w.cone_done = h->bsubI.as<int>() + sB; w.sub_stat = h->bsubI.as<int>() + 2 * sB; w.sub_wait = h->bsubI.as<int>() + 10 * sB; w.sub_nfail = h->bsubI.as<int>() + 11 * sB;
     w.V3 = h->tun.get("OMC_SMALL_COLD") ? nullptr : h->bsubS.as<double>() + sB * 17; w.v3valid = h->bsubI.as<int>() + 12 * sB;
     w.ws_first = h->bsubI.as<int>() + 13 * sB; w.ws_phase = 0;
+    w.w1_fac = nullptr;     // factored W1: decided below, once k_global's variant is known
     w.sub_guard = h->tun.get("OMC_SUB_GUARD") ? atoi(h->tun.get("OMC_SUB_GUARD")) : 2;
     w.sub_qmax = h->tun.get("OMC_SUB_QMAX") ? atoi(h->tun.get("OMC_SUB_QMAX")) : 24;
     w.sub_chunk = h->tun.get("OMC_SUB_CHUNK") ? atoi(h->tun.get("OMC_SUB_CHUNK")) : 3;
@@ -636,6 +638,9 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   w.Y = h->bY.as<double>(); w.Yp = h->bYp.as<double>(); w.U = h->bU.as<double>();
   w.Yx = nullptr;
   if (!shor && !P.accel && !h->tun.get("OMC_NO_YX")) { ENS(h->bYx, sB * n * n * 8); w.Yx = h->bYx.as<double>(); }      // 2 Y - Yp for the column gathers (k_aa rewrites Y and Yp behind k_global's back)
+  // with Yx the column kernels never read Yp (k_aa and the Shor kernels, its only other readers, run without Yx; k_setup rewrites it at
+  // every start; the state pool does not keep it): k_global stops storing it
+  w.skip_yp = (w.Yx && !h->tun.get("OMC_DENSE_PROJ")) ? 1 : 0;
   w.D1 = h->bD1.as<double>(); w.D3 = h->bD3.as<double>(); w.W1 = h->bW1.as<double>(); w.E3 = h->bE3.as<double>();
   w.dS = h->bdS.as<double>();
   {
@@ -785,6 +790,10 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
       ENS(h->bglob, sB * w.glob_scratch_stride * 8);
       w.glob_scratch = h->bglob.as<double>();
     }
+    // factored W1 (OmcWS::w1_fac): k_global stages the accepted Ritz vectors of a slot (at most 16 n doubles) in its NNQP scratch, which
+    // holds NNQP_PMAX (NNQP_PMAX + 1) / 2 doubles.  Off in Shor mode (its W1 views are other arrays) and with OMC_DENSE_PROJ=1.
+    if (!shor && w.sub_enable && h->glob_use_lds && (size_t)16 * n <= (size_t)NNQP_PMAX * (NNQP_PMAX + 1) / 2 && !h->tun.get("OMC_DENSE_PROJ"))
+      w.w1_fac = h->bsubI.as<int>() + 14 * sB;
     {
       const int N3 = rmax + k; const int Npm = (N3 + 1) & ~1, ldm = Npm | 1;
       h->small_lds = ((size_t)n * rmax + (size_t)N3 * N3 + (size_t)Npm * ldm + 2 * Npm + (size_t)rmax * k + 8 + (size_t)n * 16 + 4) * 8 + (size_t)(Npm + 2) * 4 + 16;   // + Q' staging (n x 16)

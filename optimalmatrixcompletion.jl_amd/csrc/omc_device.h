@@ -58,6 +58,10 @@ struct OmcWS {
   double* U;              // n*k
   double *D1, *D3;        // n*n scaled duals of the two full-Y cone blocks
   double *W1, *E3;        // n*n: clip(Y-D1) ; Q dS Q'
+  // factored W1 (NULL: off, W1 is always stored dense).  w1_fac[b] = 1: this iteration's k_cone_sub<0> call was accepted and left W1 as
+  // its factors (Xs, sub_theta) instead of storing it; k_global forms the entries it needs from them (bit-identical) and resets the flag
+  int* w1_fac;            // B
+  int skip_yp;            // 1: k_global does not store Yp (nothing reads it once Yx exists)
   double* Qb;             // n*rmax: orthonormal basis of the row functionals of node b; rr[b] columns used
   int* rr;                // B
   double *Vt, *D3V, *W3V, *Q3V;  // rmax*k

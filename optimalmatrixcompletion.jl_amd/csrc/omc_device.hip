@@ -98,7 +98,7 @@ __global__ void k_setup(OmcWS w) {
     if (tid < 16) w.sub_theta[(size_t)b * 16 + tid] = w.ptheta[(size_t)lf * 16 + tid];
     fr2 = block_sum(fr2, red); tr1 = block_sum(tr1, red);
     if (tid == 0) {
-      w.fro2[b] = fr2; w.trM[b] = tr1; w.sub_on[b] = (w.sub_enable && w.pscal[(size_t)lf * 4 + 1] != 0.0) ? 1 : 0; w.sub_wait[b] = 0; w.sub_nfail[b] = 0; w.cone_done[b] = 0; w.v3valid[b] = 0; w.sub_onC[b] = 0; w.confirm[b] = 1; w.lb_est[b] = -1e300; w.vvalid[b] = 0; if (w.vvalidC) w.vvalidC[b] = 0; if (w.ws_first) w.ws_first[b] = w.sub_on[b] ? 0 : 1;
+      w.fro2[b] = fr2; w.trM[b] = tr1; w.sub_on[b] = (w.sub_enable && w.pscal[(size_t)lf * 4 + 1] != 0.0) ? 1 : 0; w.sub_wait[b] = 0; w.sub_nfail[b] = 0; w.cone_done[b] = 0; if (w.w1_fac) w.w1_fac[b] = 0; w.v3valid[b] = 0; w.sub_onC[b] = 0; w.confirm[b] = 1; w.lb_est[b] = -1e300; w.vvalid[b] = 0; if (w.vvalidC) w.vvalidC[b] = 0; if (w.ws_first) w.ws_first[b] = w.sub_on[b] ? 0 : 1;
     }
     // Vt = Q_child' U_parent, U = Q_child Vt
     for (int e = tid; e < rm * k; e += T) {
@@ -132,7 +132,7 @@ __global__ void k_setup(OmcWS w) {
       w.Vrow[(size_t)b * NP * NP + e] = 0.0;
     }
     if (tid == 0) {
-      w.fro2[b] = d0 * d0 * n; w.trM[b] = d0 * n; w.sub_on[b] = 0; w.sub_wait[b] = 0; w.sub_nfail[b] = 0; w.cone_done[b] = 0; w.v3valid[b] = 0; w.sub_onC[b] = 0; w.confirm[b] = 1; w.lb_est[b] = -1e300; w.vvalid[b] = 0; if (w.vvalidC) w.vvalidC[b] = 0; if (w.ws_first) w.ws_first[b] = w.sub_on[b] ? 0 : 1;
+      w.fro2[b] = d0 * d0 * n; w.trM[b] = d0 * n; w.sub_on[b] = 0; w.sub_wait[b] = 0; w.sub_nfail[b] = 0; w.cone_done[b] = 0; if (w.w1_fac) w.w1_fac[b] = 0; w.v3valid[b] = 0; w.sub_onC[b] = 0; w.confirm[b] = 1; w.lb_est[b] = -1e300; w.vvalid[b] = 0; if (w.vvalidC) w.vvalidC[b] = 0; if (w.ws_first) w.ws_first[b] = w.sub_on[b] ? 0 : 1;
     }
   }
   for (int e = tid; e < n * k; e += T) w.U[(size_t)b * n * k + e] = 0.0;
@@ -1604,14 +1604,16 @@ __global__ void __launch_bounds__(256) k_cone_sub(OmcWS w) {
     s_nsel = c;
   }
   __syncthreads();
-  double* Wout = w.W1 + (size_t)b * n * n;
-  auto entry0 = [&](int, int) { return 0.0; };
-  auto store = [&](int i, int j, double v, double) { Wout[(size_t)j * n + i] = v; Wout[(size_t)i * n + j] = v; };
   SUBSTAMP(10);
-  spectral_rebuild(Xa, LD, n, sel, wgt, s_nsel, 0.0, entry0, store);
+  if (!w.w1_fac) {       // factored mode: W1 stays as (Xs, sub_theta); k_global forms its entries with this rebuild's arithmetic (w1_entry)
+    double* Wout = w.W1 + (size_t)b * n * n;
+    auto entry0 = [&](int, int) { return 0.0; };
+    auto store = [&](int i, int j, double v, double) { Wout[(size_t)j * n + i] = v; Wout[(size_t)i * n + j] = v; };
+    spectral_rebuild(Xa, LD, n, sel, wgt, s_nsel, 0.0, entry0, store);
+  }
   SUBSTAMP(11);
   if (prof && tid == 0) { w.stamps[12] += 1.0; w.stamps[13] += steps; w.stamps[14] += nrr; }
-  if (tid == 0) w.cone_done[b] = 1;
+  if (tid == 0) { w.cone_done[b] = 1; if (w.w1_fac) w.w1_fac[b] = 1; }
 }
 
 // Mbuf <- Y - U U' (zero padded), fro2, trace for the harvested slots whose separation vector k_cone_sub<2> will compute
@@ -1928,6 +1930,19 @@ __global__ void __launch_bounds__(256) k_small(OmcWS w, int mode) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Factored W1 (w.w1_fac): k_global forms the entries of W1 = clip(Y - D1, 0, 1) from the Ritz pairs of an accepted k_cone_sub<0> call
+// with spectral_rebuild's own arithmetic -- the accepted pairs (theta > 0) in ascending index, the weight min(theta, clip_hi) applied to
+// the vector of the smaller index, the larger index on the left (the dense store mirrors the lower triangle) -- so every entry is
+// bit-identical to the dense array.  Xf: the nf accepted vectors (ld n), wf their weights.
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double w1_entry(const double* Xf, const double* wf, int nf, int n, int i, int j) {
+  const int p = (i > j) ? i : j, q = (i > j) ? j : i;
+  double acc = 0.0;
+  for (int c = 0; c < nf; ++c) { const double* x = Xf + (size_t)c * n; acc += x[p] * (x[q] * wf[c]); }
+  return acc;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // k_global: consensus average + projection on the rows + dual updates (one workgroup per node)
 //   tY = [rho_f N.Y + gamma/2 LL + rho (rx W1 + (1-rx) Y + D1) + rho (Y + (1-rx) D3 + rx E3)] / (rho wY1)
 //   tV = rx W3V + (1-rx) Vt + D3V ;  tU = Q tV
@@ -1974,16 +1989,53 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   //    column-major copy of Lambda written by k_colprox, zero where a row is not observed -- straight from L2)
   const double* lamD = w.lamD + (size_t)b * m * n;
   const int nt16 = (n + 15) >> 4;
+  // factored W1 (w1_fac[b]: this iteration's k_cone_sub<0> call was accepted and stored no dense W1): the accepted Ritz vectors are staged
+  // in s_Gp, idle outside step 4 (the host keeps 16 n within it), for steps 2 and 6.  Each entry goes through an empty asm, as a loaded
+  // value would, so that the expressions that use it contract exactly as they do with the dense load.
+  const bool f1 = w.w1_fac && w.w1_fac[b];
+  const int NP = w.np16;
+  const double* Xs = w.Xs + (size_t)b * NP * 16;
+  double* Xf = s_Gp;
+  __shared__ int s_fsel[16], s_fn; __shared__ double s_fw[16];
+  auto stage_w1 = [&]() {
+    for (int e = tid; e < s_fn * n; e += T) { const int c = e / n, i = e - c * n; Xf[e] = Xs[(size_t)s_fsel[c] * NP + i]; }
+    __syncthreads();
+  };
+  if (f1) {
+    if (tid == 0) {
+      int c = 0;
+      for (int t = 0; t < 16; ++t) { const double th = w.sub_theta[(size_t)b * 16 + t]; if (th > 0.0) { s_fsel[c] = t; s_fw[c] = fmin(th, w.clip_hi); ++c; } }
+      s_fn = c;
+    }
+    __syncthreads();
+    stage_w1();
+  }
+  auto w1_at = [&](size_t e, int i, int j) {
+    double v = f1 ? w1_entry(Xf, s_fw, s_fn, n, i, j) : W1[e];
+    asm("" : "+v"(v));
+    return v;
+  };
   STAMP(8);
   // 2. cone + multiplicity part of the target (lower triangle), then the Lambda term, then the weights
-  for (int e = tid; e < n * n; e += T) {
-    const int i = e % n, j = e / n;
-    if (i < j) continue;
-    double y = Y[e];
+  // two entries per trip, as in step 6: the loads of both before the arithmetic of either
+  struct In2 { double y, nc, d1, d3, e3; };
+  auto load2 = [&](int e) { In2 v; v.y = Y[e]; v.nc = w.Ncnt[e]; v.d1 = D1[e]; v.d3 = D3[e]; v.e3 = E3[e]; return v; };
+  auto target2 = [&](int e, int i, int j, double w1, const In2& v) {
+    const double y = v.y;
     // Shor mode: the third copy of Y is the big cone's (over-relaxed projection + its scaled dual) instead of the column blocks
     const double first = w.shor ? rho * (rx * w.shP0[(size_t)b * w.shN * w.shN + (size_t)j * w.shN + i] + (1.0 - rx) * y + w.shD0[(size_t)b * w.shN * w.shN + (size_t)j * w.shN + i])
-                                : rho_f * w.Ncnt[e] * y;
-    tY[TRIX(i, j)] = first + rho * (rx * W1[e] + (1.0 - rx) * y + D1[e]) + rho * (y + (1.0 - rx) * D3[e] + rx * E3[e]);
+                                : rho_f * v.nc * y;
+    tY[TRIX(i, j)] = first + rho * (rx * w1 + (1.0 - rx) * y + v.d1) + rho * (y + (1.0 - rx) * v.d3 + rx * v.e3);
+  };
+  for (int e = tid; e < n * n; e += 2 * T) {
+    const int eb = e + T;
+    const int i = e % n, j = e / n, ib = (eb < n * n) ? eb % n : 0, jb = (eb < n * n) ? eb / n : 1;
+    const bool lo = i >= j, lob = (eb < n * n) && ib >= jb;      // lower triangle only
+    if (!lo && !lob) continue;
+    const double w1 = lo ? w1_at(e, i, j) : 0.0, w1b = lob ? w1_at(eb, ib, jb) : 0.0;      // first: the arithmetic of an entry stays in one basic block, as with the dense load
+    const In2 v = load2(lo ? e : eb), vb = load2(lob ? eb : e);
+    if (lo) target2(e, i, j, w1, v);
+    if (lob) target2(eb, ib, jb, w1b, vb);
   }
   for (int e = tid; e < r * k; e += T) {
     int a = e % r, j = e / r;
@@ -2096,7 +2148,6 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   }
   __syncthreads();
   double rp2 = 0.0, rd2 = 0.0, fr2 = 0.0, tr1 = 0.0;
-  const int NP = w.np16;
   double* Mb = w.Mbuf + (size_t)b * NP * NP;
   for (int e = tid; e < r * k; e += T) {
     int a = e % r, j = e / r;
@@ -2141,17 +2192,22 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   const int nact = s_nact, nstg = (nact < GL_XS) ? nact : GL_XS;      // the first GL_XS active cut vectors are read from LDS
   for (int e = tid; e < nstg * n; e += T) { const int a = e / n, i = e - a * n; xs[e] = cutx[(size_t)s_act[a] * n + i]; }
   __syncthreads();
-  for (int e = tid; e < n * n; e += T) {
-    const int i = e % n, j = e / n;
+  if (f1) stage_w1();       // step 4 used s_Gp
+  // two entries per trip (e and e + T: the order in which each thread adds its terms to the partial sums is unchanged): every load of
+  // both is issued before the first store, twice the bytes in flight per wave
+  auto corr_at = [&](int i, int j) {
     double corr = (i == j) ? s_trace_mu : 0.0;
     for (int a = 0; a < nstg; ++a) { const double* x = xs + (size_t)a * n; corr += s_mu[a] * (x[i] * x[j]); }             // (x_i x_j) first: exactly symmetric in (i, j)
     for (int a = nstg; a < nact; ++a) { const double* x = cutx + (size_t)s_act[a] * n; corr += s_mu[a] * (x[i] * x[j]); }
-    const size_t a1 = (size_t)j * n + i;
-    const double t = tY[TRIX(i, j)];
-    const double yn = t - corr / w.wY1[a1];
-    const double yold = Y[a1];
-    const double w1 = W1[a1], e3 = E3[a1], d3 = D3[a1];
-    const double d1n = D1[a1] + rx * w1 + (1.0 - rx) * yold - yn;
+    return corr;
+  };
+  struct In6 { double t, wy, yold, e3, d3, d1; };
+  auto load6 = [&](size_t a1, int i, int j) { In6 v; v.t = tY[TRIX(i, j)]; v.wy = w.wY1[a1]; v.yold = Y[a1]; v.e3 = E3[a1]; v.d3 = D3[a1]; v.d1 = D1[a1]; return v; };
+  auto update6 = [&](size_t a1, int i, int j, double w1, double corr, const In6& v) {
+    const double yn = v.t - corr / v.wy;
+    const double yold = v.yold;
+    const double e3 = v.e3, d3 = v.d3;
+    const double d1n = v.d1 + rx * w1 + (1.0 - rx) * yold - yn;
     const double w3y = yold - d3 + e3;                 // projection output of the small-cone block
     const double d3n = (1.0 - rx) * d3 + yold + rx * e3 - yn;
     D1[a1] = d1n; D3[a1] = d3n;
@@ -2161,15 +2217,26 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
     if (i == j) tr1 += mv;
     rp2 += (w1 - yn) * (w1 - yn) + (w3y - yn) * (w3y - yn);
     rd2 += (yn - yold) * (yn - yold);
-    Yp[a1] = yold; Y[a1] = yn;
+    if (!w.skip_yp) Yp[a1] = yold;
+    Y[a1] = yn;
     if (w.Yx) w.Yx[(size_t)b * n * n + a1] = 2.0 * yn - yold;      // the matrix the column prox of the next iteration gathers
+  };
+  for (int e = tid; e < n * n; e += 2 * T) {
+    const int eb = e + T; const bool two = eb < n * n;
+    const int i = e % n, j = e / n, ib = two ? eb % n : i, jb = two ? eb / n : j;
+    const size_t a1 = (size_t)j * n + i, a1b = (size_t)jb * n + ib;
+    const double w1 = w1_at(a1, i, j), w1b = two ? w1_at(a1b, ib, jb) : 0.0;      // first (see step 2)
+    const double corr = corr_at(i, j), corrb = two ? corr_at(ib, jb) : 0.0;
+    const In6 v = load6(a1, i, j), vb = load6(a1b, ib, jb);
+    update6(a1, i, j, w1, corr, v);
+    if (two) update6(a1b, ib, jb, w1b, corrb, vb);
   }
   STAMP(13);
   rp2 = block_sum(rp2, red);
   rd2 = block_sum(rd2, red);
   fr2 = block_sum(fr2, red);
   tr1 = block_sum(tr1, red);
-  if (tid == 0) { w.rp[b] = sqrt(rp2); w.rd[b] = sqrt(rd2); w.fro2[b] = fr2; w.trM[b] = tr1; w.cone_done[b] = 0; w.iters[b] += 1; if (w.ws_first) w.ws_first[b] = (!w.sub_on[b] || w.sub_wait[b] > 0) ? 1 : 0; DIAG_CYC(4, b); }
+  if (tid == 0) { w.rp[b] = sqrt(rp2); w.rd[b] = sqrt(rd2); w.fro2[b] = fr2; w.trM[b] = tr1; w.cone_done[b] = 0; if (w.w1_fac) w.w1_fac[b] = 0; w.iters[b] += 1; if (w.ws_first) w.ws_first[b] = (!w.sub_on[b] || w.sub_wait[b] > 0) ? 1 : 0; DIAG_CYC(4, b); }
 }
 
 // ---------------------------------------------------------------------------------------------------------
