@@ -309,9 +309,9 @@ int omc_last_solver_info(omc_instance* h, double* info);
 int omc_last_subspace_stats(omc_instance* h, int64_t* out);
 /* the same eight counters for the order-(n+m) cone of the last Shor-mode solve */
 int omc_last_shor_subspace_stats(omc_instance* h, int64_t* out);
-/* Tuning / diagnostic knobs (OMC_STREAMS, OMC_GRAPH_MAX, OMC_NO_COLPROX_PAIR, ...: the list is OMC_TUNING_KEYS in omc_api.cpp, each documented
- * where it is used).  The library reads the environment at omc_instance_create and nowhere else; omc_tuning_set overrides one knob of an
- * instance (value NULL removes it), omc_tuning_reload_env reads the environment again.  No counterpart in the reference (its knobs are the
+/* Tuning / diagnostic knobs (OMC_STREAMS, OMC_GRAPH_MAX, OMC_NO_COLPROX_PAIR, ...: the table is OMC_KNOBS in omc_api.cpp, each knob documented
+ * at its field of struct Tuning).  The library reads the environment at omc_instance_create and nowhere else; omc_tuning_set overrides one knob of an
+ * instance (value NULL restores its default; an unknown name is refused), omc_tuning_reload_env reads the environment again.  No counterpart in the reference (its knobs are the
  * Mosek parameters of OMC.jl:1482-1500). */
 int omc_tuning_set(omc_instance* h, const char* name, const char* value);
 int omc_tuning_reload_env(omc_instance* h);

@@ -46,6 +46,10 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 struct DevBuf {
   void* p = nullptr; size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   int ensure(size_t bytes) {
     if (bytes <= cap) return 0;
     if (p) (void)hipFree(p);
@@ -63,55 +67,42 @@ struct DevBuf {
 // Tuning knobs.  The environment is read in ONE place -- tuning_from_env, called by omc_instance_create and by omc_tuning_reload_env -- and a
 // caller that does not want its environment to matter sets the knobs through omc_tuning_set; nothing else in the library calls getenv
 // (behaviour of the shipped library depended on the caller's environment at every solve, one knob even per iteration).
-static const char* const OMC_TUNING_KEYS[] = {
-  "OMC_ALTMIN_NOLDS",
-  "OMC_CERT_SUB",
-  "OMC_COLD_CHECK",
-  "OMC_COLPROX_FIRST",
-  "OMC_COLPROX_KEEPB",
-  "OMC_COLPROX_NO_XCD",
-  "OMC_CONE_512",
-  "OMC_CP_MAXPASS",
-  "OMC_CP_SERIES",
-  "OMC_DEBUG_MAX_SWEEPS",
-  "OMC_DENSE_CHECK",
-  "OMC_DENSE_PROJ",
-  "OMC_GLOBAL_NOLDS",
-  "OMC_GRAPH_MAX",
-  "OMC_GRAPH_TAILS",
-  "OMC_GRAPH_SHARED_EVENTS",
-  "OMC_GROUPS",
-  "OMC_JACOBI_TAU",
-  "OMC_NO_COLPROX_PAIR",
-  "OMC_NO_COLPROX_WIDE",
-  "OMC_NO_GRAPH",
-  "OMC_NO_SEP_SUB",
-  "OMC_NO_SLOT_LIST",
-  "OMC_NO_SUBSPACE",
-  "OMC_NO_WARMSTART",
-  "OMC_NO_WS_SPLIT",
-  "OMC_NO_YX",
-  "OMC_SEGV_TRACE",
-  "OMC_REFILL_EVERY",
-  "OMC_SHOR_DEBUG",
-  "OMC_SHOR_EXPLICIT",
-  "OMC_SHOR_NO_SUBSPACE",
-  "OMC_SLOTS",
-  "OMC_SMALL_COLD",
-  "OMC_STREAMS",
-  "OMC_SUB_ADAPT",
-  "OMC_SUB_CHUNK",
-  "OMC_SUB_DEBUG",
-  "OMC_SUB_GUARD",
-  "OMC_SUB_LAZY",
-  "OMC_SUB_QMAX",
-  "OMC_SUB_TOL",
-  "OMC_TIMING_STRIDE",
-};
+// A flag is on when its variable is set to any value ("0" included); a number is atoi of the value when set, its default otherwise.
 struct Tuning {
-  std::unordered_map<std::string, std::string> kv;
-  const char* get(const char* name) const { auto it = kv.find(name); return it == kv.end() ? nullptr : it->second.c_str(); }
+  bool altmin_nolds = false;       // OMC_ALTMIN_NOLDS: the altmin kernel on its global slab even where its LDS would do
+  bool colprox_no_xcd = false;     // OMC_COLPROX_NO_XCD: no XCD-local placement of the column workgroups
+  bool cone_512 = false;           // OMC_CONE_512: 512-thread form of the full eigen-kernel at large orders
+  bool dense_proj = false;         // OMC_DENSE_PROJ: dense W1 and the Yp store instead of the factored projections
+  bool global_nolds = false;       // OMC_GLOBAL_NOLDS: k_global's target in its L2-resident scratch instead of LDS
+  bool no_colprox_pair = false;    // OMC_NO_COLPROX_PAIR: k_colprox for every column
+  bool no_graph = false;           // OMC_NO_GRAPH: no hipGraph replay of the iteration body
+  bool no_subspace = false;        // OMC_NO_SUBSPACE: no tracked subspace (k_cone_sub) for the cone block
+  bool no_ws_split = false;        // OMC_NO_WS_SPLIT: the full eigen-kernel as one launch after k_cone_sub
+  bool segv_trace = false;         // OMC_SEGV_TRACE: print the native frames of a crashing thread
+  bool shor_explicit = false;      // OMC_SHOR_EXPLICIT: rank k > 1 Shor batches by the Shor engine even where the base engine would serve them
+  bool shor_no_subspace = false;   // OMC_SHOR_NO_SUBSPACE: no tracked subspace for the order-(n+m) cone of Shor mode
+  int graph_max = 16;              // OMC_GRAPH_MAX: hipGraph replay for batches staged with at most this many nodes
+  int streams = 4;                 // OMC_STREAMS: <= 1 serialises a solve on one stream
+  int sub_debug = 0;               // OMC_SUB_DEBUG: diagnostics of k_cone_sub (3: histograms for omc_debug_stamps)
+  int sub_qmax = 24;               // OMC_SUB_QMAX: step budget of k_cone_sub
+  int timing_stride = 1;           // OMC_TIMING_STRIDE: event timing of every s-th iteration, 0 = none
 };
+struct Knob { const char* name; bool Tuning::*flag; int Tuning::*num; };
+static const Knob OMC_KNOBS[] = {
+  {"OMC_ALTMIN_NOLDS", &Tuning::altmin_nolds, nullptr},      {"OMC_COLPROX_NO_XCD", &Tuning::colprox_no_xcd, nullptr},
+  {"OMC_CONE_512", &Tuning::cone_512, nullptr},              {"OMC_DENSE_PROJ", &Tuning::dense_proj, nullptr},
+  {"OMC_GLOBAL_NOLDS", &Tuning::global_nolds, nullptr},      {"OMC_NO_COLPROX_PAIR", &Tuning::no_colprox_pair, nullptr},
+  {"OMC_NO_GRAPH", &Tuning::no_graph, nullptr},              {"OMC_NO_SUBSPACE", &Tuning::no_subspace, nullptr},
+  {"OMC_NO_WS_SPLIT", &Tuning::no_ws_split, nullptr},        {"OMC_SEGV_TRACE", &Tuning::segv_trace, nullptr},
+  {"OMC_SHOR_EXPLICIT", &Tuning::shor_explicit, nullptr},    {"OMC_SHOR_NO_SUBSPACE", &Tuning::shor_no_subspace, nullptr},
+  {"OMC_GRAPH_MAX", nullptr, &Tuning::graph_max},            {"OMC_STREAMS", nullptr, &Tuning::streams},
+  {"OMC_SUB_DEBUG", nullptr, &Tuning::sub_debug},            {"OMC_SUB_QMAX", nullptr, &Tuning::sub_qmax},
+  {"OMC_TIMING_STRIDE", nullptr, &Tuning::timing_stride},
+};
+static void knob_set(Tuning& t, const Knob& kb, const char* value) {      // value NULL: the default
+  if (kb.flag) t.*kb.flag = value != nullptr;
+  else t.*kb.num = value ? atoi(value) : Tuning{}.*kb.num;
+}
 // diagnostics (OMC_SEGV_TRACE=1 at instance creation): print the native frames of a crashing thread before the default action runs
 static void omc_segv_trace(int sig) {
   void* fr[64];
@@ -123,8 +114,7 @@ static void omc_segv_trace(int sig) {
   raise(sig);
 }
 static void tuning_from_env(Tuning& t) {
-  t.kv.clear();
-  for (const char* key : OMC_TUNING_KEYS) if (const char* v = getenv(key)) t.kv[key] = v;
+  for (const Knob& kb : OMC_KNOBS) knob_set(t, kb, getenv(kb.name));
 }
 
 struct omc_instance {
@@ -136,11 +126,11 @@ struct omc_instance {
   std::vector<int> row_ptr, row_idx; std::vector<double> row_val;
   DevBuf drow_ptr, drow_idx, drow_val, aR, arkind, arcut, arbi, arbj, arcoef, arrhs, acutx, aU0, aU, aV, aobj, aint, aG, aG2;
   hipStream_t stream = nullptr;
-  // per slot group: main / column / small-cone streams and fork, join, done events (see omc_relax_solve)
   Tuning tun;
-  hipStream_t gs[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
-  hipEvent_t gev[2][5] = {{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}};
-  hipEvent_t gevc[2][5] = {{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}};      // the same fork / join events for bodies recorded under stream capture: an event is never used both inside a captured graph and eagerly
+  // main / column / small-cone streams of an iteration and its fork, join, done events (see omc_relax_solve)
+  hipStream_t gs[3] = {};
+  hipEvent_t gev[5] = {};
+  hipEvent_t gevc[5] = {};      // the same fork / join events for bodies recorded under stream capture: an event is never used both inside a captured graph and eagerly
   hipEvent_t ev_main = nullptr;
   DevBuf dA, dmask, dcol_ptr, dcol_idx, dcol_val, dNcnt, dwY, dsolo, dwide;
   int nwide = 0;      // columns outside the pairs with at most 64 observed rows (k_colprox_wide)
@@ -230,7 +220,7 @@ int omc_instance_create(int n, int m, int k, const double* A, const uint8_t* mas
   HIPCHK(hipSetDevice(device));
   omc_instance* h = new omc_instance();
   tuning_from_env(h->tun);
-  if (h->tun.get("OMC_SEGV_TRACE")) { signal(SIGSEGV, omc_segv_trace); signal(SIGABRT, omc_segv_trace); }
+  if (h->tun.segv_trace) { signal(SIGSEGV, omc_segv_trace); signal(SIGABRT, omc_segv_trace); }
   struct Guard { omc_instance*& p; ~Guard() { if (p) omc_instance_destroy(p); } } guard{h};     // every early return below frees the handle
   h->n = n; h->m = m; h->k = k; h->gamma = gamma; h->device = device;
   h->A.assign(A, A + (size_t)n * m);
@@ -270,8 +260,7 @@ int omc_instance_create(int n, int m, int k, const double* A, const uint8_t* mas
   if ((rc = upload(h->dcol_ptr, h->col_ptr.data(), sizeof(int) * (m + 1), h->stream))) return rc;
   {
     std::vector<int> solo, wide;
-    const bool no_wide = h->tun.get("OMC_NO_COLPROX_WIDE") != nullptr;      // read at creation: the column lists are built here
-    auto place = [&](int j) { const int c = h->col_ptr[j + 1] - h->col_ptr[j]; if (c == 0) return; if (c <= 64 && !no_wide) wide.push_back(j); else solo.push_back(j); };
+    auto place = [&](int j) { const int c = h->col_ptr[j + 1] - h->col_ptr[j]; if (c == 0) return; if (c <= 64) wide.push_back(j); else solo.push_back(j); };
     for (int j0 = 0; j0 < m; j0 += 2) {
       const int j1 = j0 + 1;
       const int c0 = h->col_ptr[j0 + 1] - h->col_ptr[j0], c1 = (j1 < m) ? h->col_ptr[j1 + 1] - h->col_ptr[j1] : 0;
@@ -309,30 +298,11 @@ void omc_instance_destroy(omc_instance* h) {
   if (h->worker.joinable()) h->worker.join();
   (void)hipSetDevice(h->device);
   (void)omc_comm_destroy(h);
-  h->bcomm.release(); h->amobj.release();
-  DevBuf* all[] = {&h->dwide, &h->bYx, &h->dsolo, &h->dA, &h->dmask, &h->dcol_ptr, &h->dcol_idx, &h->dcol_val, &h->dNcnt, &h->dwY, &h->bY, &h->bYp, &h->bU,
-                   &h->bD1, &h->bD3, &h->bW1, &h->bE3, &h->bQb, &h->brr, &h->bsm, &h->bdS, &h->bsmall, &h->bchk,
-                   &h->balpha, &h->balphaX, &h->bsval, &h->bMchk,
-                   &h->bR, &h->brkind, &h->brcut, &h->brbi, &h->brbj, &h->brcoef, &h->brrhs, &h->bcutx, &h->bG, &h->blam,
-                   &h->bsubz, &h->bscal, &h->bbx, &h->bint, &h->bcp, &h->bcone, &h->bglob, &h->bXout, &h->bThout, &h->bXin, &h->bMbuf, &h->bVrow, &h->bXs, &h->bsubS, &h->bsubI, &h->bslotlist, &h->bgap, &h->bvotes, &h->blamDX, &h->bXsC, &h->bsubSC, &h->bsubIC,
-                   &h->brho, &h->brhon, &h->blamD, &h->bslotint, &h->boY, &h->boU, &h->boal, &h->bobx, &h->boscal, &h->boint, &h->drow_ptr, &h->drow_idx, &h->drow_val, &h->aR, &h->arkind, &h->arcut, &h->arbi, &h->arbj, &h->arcoef, &h->arrhs, &h->acutx,
-                   &h->aU0, &h->aU, &h->aV, &h->aobj, &h->aint, &h->aG, &h->aG2,
-                   &h->bobjcol, &h->baaF, &h->baaG, &h->baaZ, &h->baaS, &h->baaI, &h->bMbufC, &h->bVrowC, &h->bchkS, &h->bchkI, &h->sbits, &h->scb, &h->scx, &h->scz, &h->soff, &h->stot, &h->sout, &h->shi, &h->slo, &h->sexist, &h->shist, &h->sohi, &h->solo, &h->scnt,
-                   &h->sgInts, &h->sgBytes, &h->sgGroups, &h->sgNodeGroup, &h->sAh, &h->sX, &h->sW, &h->sTh, &h->sV1, &h->sV2, &h->sV3, &h->sD0, &h->sP0, &h->sMbufB, &h->sVrowB,
-                   &h->sTq, &h->sPq, &h->sNq, &h->sD5x, &h->sD5t, &h->snu5, &h->sP5x, &h->scolpart, &h->sminpart, &h->sminpart2, &h->sfroB, &h->svvB, &h->se1, &h->se2,
-                   &h->soX, &h->soW, &h->soTh, &h->sbigscr, &h->soV, &h->sXsB, &h->ssubSB, &h->ssubIB,
-                   &h->pY, &h->pD1, &h->pD3, &h->pU, &h->palpha, &h->psval, &h->pXs, &h->ptheta, &h->pscal, &h->bwarmL, &h->bwarmS};
-  for (DevBuf* b : all) b->release();
+  for (hipStream_t q : {h->stream, h->gs[0], h->gs[1], h->gs[2], h->append_stream, h->fetch_stream}) if (q) (void)hipStreamDestroy(q);
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  for (int g = 0; g < 2; ++g) {
-    for (int q = 0; q < 4; ++q) if (h->gs[g][q]) (void)hipStreamDestroy(h->gs[g][q]);
-    for (int q = 0; q < 5; ++q) { if (h->gev[g][q]) (void)hipEventDestroy(h->gev[g][q]); if (h->gevc[g][q]) (void)hipEventDestroy(h->gevc[g][q]); }
-  }
+  for (int q = 0; q < 5; ++q) for (hipEvent_t e : {h->gev[q], h->gevc[q]}) if (e) (void)hipEventDestroy(e);
   if (h->ev_main) (void)hipEventDestroy(h->ev_main);
-  if (h->append_stream) (void)hipStreamDestroy(h->append_stream);
-  if (h->fetch_stream) (void)hipStreamDestroy(h->fetch_stream);
-  delete h;
+  delete h;      // the device buffers free themselves
 }
 
 // piece table of the disjunctive cuts (OMC.jl:1580-1678): lo <= v <= hi, g(v) = slope*v + icpt
@@ -358,20 +328,24 @@ static int cut_piece(int cut_type, int dir, double vhat, int q1, double* lo, dou
   return -1;
 }
 
-static hipEvent_t next_event(omc_instance* h) {
-  if (h->ev_used == h->ev_pool.size()) {
-    hipEvent_t e; (void)hipEventCreate(&e); h->ev_pool.push_back(e);
+// Per-kernel timing: a pair of pool events brackets a launch; the pool is drained by finish_events.  If an event cannot be created, or one of
+// the two records fails, the launch runs (and is counted) untimed.
+static bool next_event_pair(omc_instance* h) {
+  while (h->ev_pool.size() < h->ev_used + 2) {
+    hipEvent_t e;
+    if (hipEventCreate(&e) != hipSuccess) return false;
+    h->ev_pool.push_back(e);
   }
-  return h->ev_pool[h->ev_used++];
+  return true;
 }
-#define TIMED_ON(strm, cls, units_, call)             \
-  do {                                               \
-    hipEvent_t e0_ = next_event(h), e1_ = next_event(h); \
-    (void)hipEventRecord(e0_, strm);                 \
-    call;                                            \
-    (void)hipEventRecord(e1_, strm);                 \
-    h->ev_class.push_back(cls);                      \
-    h->launches[cls] += 1; h->units[cls] += (units_); \
+#define TIMED_ON(strm, cls, units_, call)                                                                     \
+  do {                                                                                                        \
+    const bool t0_ = next_event_pair(h) && hipEventRecord(h->ev_pool[h->ev_used], strm) == hipSuccess;        \
+    call;                                                                                                     \
+    if (t0_ && hipEventRecord(h->ev_pool[h->ev_used + 1], strm) == hipSuccess) {                              \
+      h->ev_used += 2; h->ev_class.push_back(cls);                                                            \
+    }                                                                                                         \
+    h->launches[cls] += 1; h->units[cls] += (units_);                                                         \
   } while (0)
 #define TIMED(cls, units_, call) TIMED_ON(h->stream, cls, units_, call)
 
@@ -486,6 +460,75 @@ static int pack_nodes(omc_instance* h, const omc_relax_params& P, int cut_type, 
   return 0;
 }
 
+// row, cut and Q descriptors of the B nodes of `pk` (padded to the workspace's Rmax rows, Lmax cuts and rmax subspace columns) into the per-node
+// arrays of the workspace from node `first` on: `rows` >= B nodes are written, those beyond B zero (omc_relax_stage writes every row up to the
+// capacity, omc_relax_append its own rows only)
+static int put_descriptors(const OmcWS& w, const NodePack& pk, int B, size_t rows, size_t first, const int* L, const double* cut_x, hipStream_t s) {
+  const size_t n = w.n, k = w.k, Rm = w.Rmax, Lm = w.Lmax, rm = w.rmax;
+  std::vector<int> hR(rows, 0), hrr(rows, 0), hk(rows * Rm, 0), hc(rows * Rm, 0), hbi(rows * Rm, 0), hbj(rows * Rm, 0);
+  std::vector<double> hcoef(rows * Rm * k, 0.0), hrhs(rows * Rm, 0.0), hx(rows * Lm * n, 0.0), hQ(rows * n * rm, 0.0);
+  long cutbase = 0;
+  for (int b = 0; b < B; ++b) {
+    hR[b] = (int)pk.rk[b].size();
+    for (int r = 0; r < hR[b]; ++r) {
+      hk[(size_t)b * Rm + r] = pk.rk[b][r]; hc[(size_t)b * Rm + r] = pk.rc[b][r];
+      hbi[(size_t)b * Rm + r] = pk.rbi[b][r]; hbj[(size_t)b * Rm + r] = pk.rbj[b][r];
+      hrhs[(size_t)b * Rm + r] = pk.rrhs[b][r];
+      for (size_t j = 0; j < k; ++j) hcoef[((size_t)b * Rm + r) * k + j] = pk.rcoef[b][(size_t)r * k + j];
+    }
+    const int Lb = L ? L[b] : 0;
+    for (int l = 0; l < Lb; ++l) memcpy(&hx[((size_t)b * Lm + l) * n], cut_x + (size_t)(cutbase + l) * n, sizeof(double) * n);
+    cutbase += Lb;
+    memcpy(&hQ[(size_t)b * n * rm], pk.Qn[b].data(), sizeof(double) * pk.Qn[b].size());
+    hrr[b] = pk.rrv[b];
+  }
+  HIPCHK(hipMemcpyAsync(w.R + first, hR.data(), sizeof(int) * hR.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(w.rkind + first * Rm, hk.data(), sizeof(int) * hk.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(w.rcut + first * Rm, hc.data(), sizeof(int) * hc.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(w.rbi + first * Rm, hbi.data(), sizeof(int) * hbi.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(w.rbj + first * Rm, hbj.data(), sizeof(int) * hbj.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(w.rcoef + first * Rm * k, hcoef.data(), 8 * hcoef.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(w.rrhs + first * Rm, hrhs.data(), 8 * hrhs.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(w.cutx + first * Lm * n, hx.data(), 8 * hx.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(w.Qb + first * n * rm, hQ.data(), 8 * hQ.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(w.rr + first, hrr.data(), sizeof(int) * hrr.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));          // the host arrays die with this call
+  return 0;
+}
+
+// Geometry of the warm-started eigen-kernel (k_cone_ws) at order N: lanes per pair so that 512 threads cover the N/2 pairs, rows padded to
+// lpp*rpl (<= 20 rows per lane).  G lives in LDS when it fits, else in a per-node global scratch (L2 resident) of `scratch` bytes with 16 lanes
+// per pair (a wave per pair at orders 513 .. 1024).  lpp = 0: more than 32 rows per lane, beyond the kernel (WS_JROWS).
+struct WsGeometry { int lpp, ldw; size_t lds; bool use_lds; size_t scratch; };
+static WsGeometry ws_geometry(int N) {
+  const int Np2 = (N + 1) & ~1;
+  auto bytes = [Np2](int ld) { return ((size_t)Np2 * ld + 3 * Np2) * 8 + (size_t)(Np2 + 2) * 4 + 64; };
+  int lpp = 16; while (lpp > 4 && lpp * (Np2 / 2) > 512) lpp >>= 1;
+  int rpl = (((N + lpp - 1) / lpp) + 1) & ~1, Nrp = rpl * lpp;
+  int ldw = Nrp + ((16 - (Nrp & 31)) & 31);                 // 16 (mod 32): neighbouring columns start 32 LDS banks apart
+  if (bytes(ldw) > OMC_MAX_DYN_LDS) ldw = Nrp + 2;          // does not fit: plain padding
+  WsGeometry g{0, ldw, bytes(ldw), false, 0};
+  g.use_lds = g.lds <= OMC_MAX_DYN_LDS;
+  if (!g.use_lds) {
+    lpp = 16; rpl = (((N + 15) / 16) + 1) & ~1; Nrp = rpl * 16;
+    if (rpl > 32 && N <= 1024) { lpp = 64; rpl = (((N + 63) / 64) + 1) & ~1; Nrp = rpl * 64; }
+    g.ldw = Nrp + 2; g.scratch = bytes(g.ldw);
+  }
+  g.lpp = rpl <= 32 ? lpp : 0;
+  return g;
+}
+
+// fixed parameters of the eigen-kernels and the column kernel (OmcWS fields)
+static constexpr double JACOBI_TAU = 0.0;      // rotation threshold of the cold Jacobi sweeps (0: the kernel's 1e-10)
+static constexpr int MAX_SWEEPS = 30;          // sweep cap of the cold Jacobi kernel
+static constexpr int CP_SERIES = 6;            // Neumann-series order of k_colprox_pair's finish
+static constexpr int CP_MAXPASS = 60;          // cap on the secular passes of k_colprox_pair
+static constexpr int SUB_GUARD = 2;            // Ritz values of the tracked block that must stay negative
+static constexpr int SUB_CHUNK = 3;            // power steps per chunk of k_cone_sub
+static constexpr int SUB_LAZY = 1;             // orthonormalise once per chunk instead of after every step
+static constexpr double SUB_TOL = 1e-10;       // residual floor of k_cone_sub
+static constexpr double SUB_ADAPT = 1e-3;      // residual target of k_cone_sub relative to the last dual residual
+
 int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int cut_type, const int* L,
                     const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir, const double* U_lower,
                     const double* U_upper) {
@@ -511,9 +554,7 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   // ---- rows and row subspaces (host) ---------------------------------------------------------------------
   NodePack pk;
   { int rcp = pack_nodes(h, P, cut_type, B, L, cut_x, cut_Uhat, cut_dir, U_lower, U_upper, pk); if (rcp) return rcp; }
-  auto& rk = pk.rk; auto& rc = pk.rc; auto& rbi = pk.rbi; auto& rbj = pk.rbj; auto& rcoef = pk.rcoef; auto& rrhs = pk.rrhs; auto& Qn = pk.Qn; auto& rrv = pk.rrv;
   int Rmax = pk.Rmax, rmax = pk.rmax, Lmax = pk.Lmax;
-  long cutbase = 0;
   // omc_relax_reserve: room for nodes appended later (default U bounds, at most reserve_cuts cuts each)
   const int extra_nodes = shor ? 0 : h->reserve_nodes, extra_cuts = shor ? 0 : h->reserve_cuts;
   h->reserve_nodes = 0; h->reserve_cuts = 0;
@@ -527,15 +568,13 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   memset(&w, 0, sizeof(w));
   // continuous batching: S slots relax B nodes; a slot that finishes is harvested and re-used for the next pending node
   const int Bcap = B + extra_nodes;      // with omc_relax_reserve the slots are sized for the nodes that may still come
-  int S = (P.slots > 0) ? std::min(P.slots, Bcap) : std::min(Bcap, 256);
-  if (h->tun.get("OMC_SLOTS")) S = std::max(1, std::min(Bcap, atoi(h->tun.get("OMC_SLOTS"))));
+  const int S = (P.slots > 0) ? std::min(P.slots, Bcap) : std::min(Bcap, 256);
   h->Btot = B; h->Btot_live.store(B); h->node_cap = B + extra_nodes; h->staged_cut_type = cut_type; { std::lock_guard<std::mutex> lk(h->append_mu); h->append_closed = false; }
   { std::lock_guard<std::mutex> lk(h->done_mu); h->done_q.clear(); h->done_read = 0; }
   h->hold.store(0);
   w.b0 = 0; w.nB = S;
   w.B = S; w.Btot = B; w.max_iters = P.max_iters; w.n = n; w.m = m; w.k = k; w.nnz = h->nnz; w.Rmax = Rmax; w.Lmax = std::max(Lmax, 1); w.rmax = rmax;
-  w.jacobi_tau = h->tun.get("OMC_JACOBI_TAU") ? atof(h->tun.get("OMC_JACOBI_TAU")) : 0.0;
-  w.max_sweeps = h->tun.get("OMC_DEBUG_MAX_SWEEPS") ? atoi(h->tun.get("OMC_DEBUG_MAX_SWEEPS")) : 30;
+  w.jacobi_tau = JACOBI_TAU; w.max_sweeps = MAX_SWEEPS;
   w.breakpoints = P.breakpoints; w.stall_checks = P.stall_checks > 0 ? P.stall_checks : 1000000;
   w.gamma = h->gamma; w.sumA2 = h->sumA2;
   {
@@ -575,7 +614,8 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   int rc_ = 0;
   if ((rc_ = upload(h->dwY, wY.data(), sizeof(double) * n * n, h->stream))) return rc_;
   w.col_ptr = h->dcol_ptr.as<int>(); w.col_idx = h->dcol_idx.as<int>(); w.col_val = h->dcol_val.as<double>();
-  w.cp_pair = h->tun.get("OMC_NO_COLPROX_PAIR") ? 0 : 1; w.cone_512 = h->tun.get("OMC_CONE_512") ? 1 : 0; w.cp_series = h->tun.get("OMC_CP_SERIES") ? atoi(h->tun.get("OMC_CP_SERIES")) : 6; w.cp_maxpass = h->tun.get("OMC_CP_MAXPASS") ? atoi(h->tun.get("OMC_CP_MAXPASS")) : 60; w.cp_xcd = h->tun.get("OMC_COLPROX_NO_XCD") ? 0 : 1; w.cp_nsolo = h->nsolo; w.cp_solo = h->nsolo ? h->dsolo.as<int>() : nullptr;
+  w.cp_pair = h->tun.no_colprox_pair ? 0 : 1; w.cone_512 = h->tun.cone_512 ? 1 : 0; w.cp_series = CP_SERIES; w.cp_maxpass = CP_MAXPASS; w.cp_xcd = h->tun.colprox_no_xcd ? 0 : 1;
+  w.cp_nsolo = h->nsolo; w.cp_solo = h->nsolo ? h->dsolo.as<int>() : nullptr;
   w.cp_nwide = h->nwide; w.cp_wide = h->nwide ? h->dwide.as<int>() : nullptr;
   w.Ncnt = h->dNcnt.as<double>(); w.wY1 = h->dwY.as<double>();
   w.row_ptr = h->drow_ptr.as<int>(); w.row_idx = h->drow_idx.as<int>();
@@ -596,7 +636,7 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   HIPCHK(hipMemsetAsync(h->blamD.p, 0, sB * m * n * 8, h->stream));
   w.lamD = h->blamD.as<double>();
   w.lamDX = nullptr;
-  if (n > 144 || h->tun.get("OMC_DENSE_CHECK") || shor) {      // large orders: the certificate matrix takes Lambda Lambda' from one MFMA product
+  if (n > 144 || shor) {      // large orders: the certificate matrix takes Lambda Lambda' from one MFMA product
     ENS(h->blamDX, sB * m * n * 8);
     HIPCHK(hipMemsetAsync(h->blamDX.p, 0, sB * m * n * 8, h->stream));
     w.lamDX = h->blamDX.as<double>();
@@ -609,16 +649,11 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
     HIPCHK(hipMemsetAsync(h->bsubI.p, 0, sB * 15 * sizeof(int), h->stream));
     w.Xs = h->bXs.as<double>(); w.sub_theta = h->bsubS.as<double>(); w.trM = h->bsubS.as<double>() + sB * 16;
     w.sub_on = h->bsubI.as<int>(); w.cone_done = h->bsubI.as<int>() + sB; w.sub_stat = h->bsubI.as<int>() + 2 * sB; w.sub_wait = h->bsubI.as<int>() + 10 * sB; w.sub_nfail = h->bsubI.as<int>() + 11 * sB;
-    w.V3 = h->tun.get("OMC_SMALL_COLD") ? nullptr : h->bsubS.as<double>() + sB * 17; w.v3valid = h->bsubI.as<int>() + 12 * sB;
+    w.V3 = h->bsubS.as<double>() + sB * 17; w.v3valid = h->bsubI.as<int>() + 12 * sB;
     w.ws_first = h->bsubI.as<int>() + 13 * sB; w.ws_phase = 0;
     w.w1_fac = nullptr;     // factored W1: decided below, once k_global's variant is known
-    w.sub_guard = h->tun.get("OMC_SUB_GUARD") ? atoi(h->tun.get("OMC_SUB_GUARD")) : 2;
-    w.sub_qmax = h->tun.get("OMC_SUB_QMAX") ? atoi(h->tun.get("OMC_SUB_QMAX")) : 24;
-    w.sub_chunk = h->tun.get("OMC_SUB_CHUNK") ? atoi(h->tun.get("OMC_SUB_CHUNK")) : 3;
-    w.sub_lazy = h->tun.get("OMC_SUB_LAZY") ? atoi(h->tun.get("OMC_SUB_LAZY")) : 1;
-    w.sub_tol = h->tun.get("OMC_SUB_TOL") ? atof(h->tun.get("OMC_SUB_TOL")) : 1e-10;
-    w.sub_adapt = h->tun.get("OMC_SUB_ADAPT") ? atof(h->tun.get("OMC_SUB_ADAPT")) : 1e-3;
-    w.sub_debug = h->tun.get("OMC_SUB_DEBUG") ? atoi(h->tun.get("OMC_SUB_DEBUG")) : 0;
+    w.sub_guard = SUB_GUARD; w.sub_qmax = h->tun.sub_qmax; w.sub_chunk = SUB_CHUNK; w.sub_lazy = SUB_LAZY;
+    w.sub_tol = SUB_TOL; w.sub_adapt = SUB_ADAPT; w.sub_debug = h->tun.sub_debug;
     w.sub_enable = 0;     // decided below, once the cone kernel variant is known
     ENS(h->bXsC, sB * w.np16 * 16 * 8); ENS(h->bsubSC, sB * 18 * 8); ENS(h->bsubIC, sB * 3 * sizeof(int));
     HIPCHK(hipMemsetAsync(h->bXsC.p, 0, sB * w.np16 * 16 * 8, h->stream));
@@ -628,7 +663,7 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
     w.sub_onC = h->bsubIC.as<int>(); w.confirm = h->bsubIC.as<int>() + sB; w.sep_done = nullptr;
     w.cert_enable = 0;
   }
-  if (!h->tun.get("OMC_COLD_CHECK")) {   // warm-started eigenvalues for the certificate matrix
+  {   // warm-started eigenvalues for the certificate matrix
     ENS(h->bMbufC, sB * w.np16 * w.np16 * 8); ENS(h->bVrowC, sB * w.np16 * w.np16 * 8); ENS(h->bchkS, sB * 8); ENS(h->bchkI, sB * sizeof(int));
     HIPCHK(hipMemsetAsync(h->bMbufC.p, 0, sB * w.np16 * w.np16 * 8, h->stream));
     HIPCHK(hipMemsetAsync(h->bVrowC.p, 0, sB * w.np16 * w.np16 * 8, h->stream));   // its zero padding feeds the branch-free K loop of the MFMA GEMM: 0 x garbage could be NaN
@@ -637,10 +672,10 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   }
   w.Y = h->bY.as<double>(); w.Yp = h->bYp.as<double>(); w.U = h->bU.as<double>();
   w.Yx = nullptr;
-  if (!shor && !P.accel && !h->tun.get("OMC_NO_YX")) { ENS(h->bYx, sB * n * n * 8); w.Yx = h->bYx.as<double>(); }      // 2 Y - Yp for the column gathers (k_aa rewrites Y and Yp behind k_global's back)
+  if (!shor && !P.accel) { ENS(h->bYx, sB * n * n * 8); w.Yx = h->bYx.as<double>(); }      // 2 Y - Yp for the column gathers (k_aa rewrites Y and Yp behind k_global's back)
   // with Yx the column kernels never read Yp (k_aa and the Shor kernels, its only other readers, run without Yx; k_setup rewrites it at
   // every start; the state pool does not keep it): k_global stops storing it
-  w.skip_yp = (w.Yx && !h->tun.get("OMC_DENSE_PROJ")) ? 1 : 0;
+  w.skip_yp = (w.Yx && !h->tun.dense_proj) ? 1 : 0;
   w.D1 = h->bD1.as<double>(); w.D3 = h->bD3.as<double>(); w.W1 = h->bW1.as<double>(); w.E3 = h->bE3.as<double>();
   w.dS = h->bdS.as<double>();
   {
@@ -702,48 +737,18 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
     w.psval = h->psval.as<double>(); w.pXs = h->pXs.as<double>(); w.ptheta = h->ptheta.as<double>(); w.pscal = h->pscal.as<double>();
   }
   h->warm_load.clear(); h->warm_save.clear();
-  // Q upload
-  {
-    std::vector<double> hQ(sN * n * rmax, 0.0);
-    for (int b = 0; b < B; ++b) memcpy(&hQ[(size_t)b * n * rmax], Qn[b].data(), sizeof(double) * Qn[b].size());
-    if ((rc_ = upload(h->bQb, hQ.data(), sizeof(double) * hQ.size(), h->stream))) return rc_;
-    rrv.resize(sN, 0);
-    if ((rc_ = upload(h->brr, rrv.data(), sizeof(int) * sN, h->stream))) return rc_;
-    HIPCHK(hipStreamSynchronize(h->stream));          // hQ dies with this block
-    w.Qb = h->bQb.as<double>(); w.rr = h->brr.as<int>();
-  }
-  // rows upload (padded to Rmax)
-  std::vector<int> hR(sN, 0), hk(sN * Rmax, 0), hc(sN * Rmax, 0), hbi(sN * Rmax, 0), hbj(sN * Rmax, 0);
-  std::vector<double> hcoef(sN * Rmax * k, 0.0), hrhs(sN * Rmax, 0.0), hx(sN * w.Lmax * n, 0.0);
-  cutbase = 0;
-  for (int b = 0; b < B; ++b) {
-    hR[b] = (int)rk[b].size();
-    for (int r = 0; r < hR[b]; ++r) {
-      hk[(size_t)b * Rmax + r] = rk[b][r]; hc[(size_t)b * Rmax + r] = rc[b][r];
-      hbi[(size_t)b * Rmax + r] = rbi[b][r]; hbj[(size_t)b * Rmax + r] = rbj[b][r];
-      hrhs[(size_t)b * Rmax + r] = rrhs[b][r];
-      for (int j = 0; j < k; ++j) hcoef[((size_t)b * Rmax + r) * k + j] = rcoef[b][(size_t)r * k + j];
-    }
-    const int Lb = L ? L[b] : 0;
-    for (int l = 0; l < Lb; ++l)
-      memcpy(&hx[((size_t)b * w.Lmax + l) * n], cut_x + (size_t)(cutbase + l) * n, sizeof(double) * n);
-    cutbase += Lb;
-  }
-  if ((rc_ = upload(h->bR, hR.data(), sizeof(int) * sN, h->stream))) return rc_;
-  if ((rc_ = upload(h->brkind, hk.data(), sizeof(int) * hk.size(), h->stream))) return rc_;
-  if ((rc_ = upload(h->brcut, hc.data(), sizeof(int) * hc.size(), h->stream))) return rc_;
-  if ((rc_ = upload(h->brbi, hbi.data(), sizeof(int) * hbi.size(), h->stream))) return rc_;
-  if ((rc_ = upload(h->brbj, hbj.data(), sizeof(int) * hbj.size(), h->stream))) return rc_;
-  if ((rc_ = upload(h->brcoef, hcoef.data(), sizeof(double) * hcoef.size(), h->stream))) return rc_;
-  if ((rc_ = upload(h->brrhs, hrhs.data(), sizeof(double) * hrhs.size(), h->stream))) return rc_;
-  if ((rc_ = upload(h->bcutx, hx.data(), sizeof(double) * hx.size(), h->stream))) return rc_;
-  w.R = h->bR.as<int>(); w.rkind = h->brkind.as<int>(); w.rcut = h->brcut.as<int>(); w.rbi = h->brbi.as<int>();
-  w.rbj = h->brbj.as<int>(); w.rcoef = h->brcoef.as<double>(); w.rrhs = h->brrhs.as<double>(); w.cutx = h->bcutx.as<double>();
+  // Q, row and cut descriptors, one row per node up to the capacity
+  ENS(h->bQb, sN * n * rmax * 8); ENS(h->brr, sN * sizeof(int)); ENS(h->bR, sN * sizeof(int));
+  ENS(h->brkind, sN * Rmax * sizeof(int)); ENS(h->brcut, sN * Rmax * sizeof(int)); ENS(h->brbi, sN * Rmax * sizeof(int)); ENS(h->brbj, sN * Rmax * sizeof(int));
+  ENS(h->brcoef, sN * Rmax * k * 8); ENS(h->brrhs, sN * Rmax * 8); ENS(h->bcutx, sN * w.Lmax * n * 8);
+  w.Qb = h->bQb.as<double>(); w.rr = h->brr.as<int>(); w.R = h->bR.as<int>(); w.rkind = h->brkind.as<int>(); w.rcut = h->brcut.as<int>();
+  w.rbi = h->brbi.as<int>(); w.rbj = h->brbj.as<int>(); w.rcoef = h->brcoef.as<double>(); w.rrhs = h->brrhs.as<double>(); w.cutx = h->bcutx.as<double>();
+  if ((rc_ = put_descriptors(w, pk, B, sN, 0, L, cut_x, h->stream))) return rc_;
   // LDS / scratch decisions
   {
     const int c_lds = std::min(h->cmax, 64);
     w.cp_lds_c = c_lds;
-    w.cp_keepB = (c_lds <= 40 || h->tun.get("OMC_COLPROX_KEEPB")) ? 1 : 0;
+    w.cp_keepB = c_lds <= 40 ? 1 : 0;
     w.cp_lds_doubles = w.cp_keepB ? c_lds * c_lds + 5 * c_lds + 8 : c_lds * (c_lds + 1) / 2 + 4 * c_lds + 8;
     if ((size_t)4 * w.cp_lds_doubles * 8 > OMC_MAX_DYN_LDS) { w.cp_lds_c = 48; w.cp_lds_doubles = 48 * 48 + 5 * 48 + 8; w.cp_keepB = 1; }
     if (h->cmax > w.cp_lds_c) {
@@ -755,36 +760,22 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
     h->cone_lds = cone_bytes(n);
     h->cone_use_lds = h->cone_lds <= OMC_MAX_DYN_LDS;
     {
-      // warm-started kernel: lanes per pair so that 512 threads cover the n/2 pairs, rows padded to lpp*rpl (<= 20 rows per lane).
-      // G lives in LDS when it fits, else in the per-node global scratch (L2 resident) with 16 lanes per pair.
-      const int Np2 = (n + 1) & ~1;
-      int lpp = 16; while (lpp > 4 && lpp * (Np2 / 2) > 512) lpp >>= 1;
-      int rpl = (((n + lpp - 1) / lpp) + 1) & ~1, Nrp = rpl * lpp;
-      int ldw = Nrp + ((16 - (Nrp & 31)) & 31);                 // 16 (mod 32): neighbouring columns start 32 LDS banks apart
-      if (((size_t)Np2 * ldw + 3 * Np2) * 8 + (size_t)(Np2 + 2) * 4 + 64 > OMC_MAX_DYN_LDS) ldw = Nrp + 2;   // does not fit: plain padding
-      h->ws_lds = ((size_t)Np2 * ldw + 3 * Np2) * 8 + (size_t)(Np2 + 2) * 4 + 64;
-      h->ws_use_lds = h->ws_lds <= OMC_MAX_DYN_LDS;
-      w.ws_ld = ldw;
-      if (!h->ws_use_lds) {
-        lpp = 16; rpl = (((n + 15) / 16) + 1) & ~1; Nrp = rpl * 16; ldw = Nrp + 2; w.ws_ld = ldw;
-        if (rpl > 32 && n <= 1024) { lpp = 64; rpl = (((n + 63) / 64) + 1) & ~1; Nrp = rpl * 64; ldw = Nrp + 2; w.ws_ld = ldw; }      // orders 513 .. 1024: a wave per pair
-        const size_t need = ((size_t)Np2 * ldw + 3 * Np2) * 8 + (size_t)(Np2 + 2) * 4 + 64;
-        if (need / 8 + 8 > w.cone_scratch_stride) {
-          w.cone_scratch_stride = need / 8 + 8;
-          ENS(h->bcone, sB * w.cone_scratch_stride * 8);
-          w.cone_scratch = h->bcone.as<double>();
-        }
+      const WsGeometry g = ws_geometry(n);
+      h->ws_lpp = g.lpp; h->ws_lds = g.lds; h->ws_use_lds = g.use_lds; w.ws_ld = g.ldw;
+      if (g.scratch) {
+        w.cone_scratch_stride = g.scratch / 8 + 8;
+        ENS(h->bcone, sB * w.cone_scratch_stride * 8);
+        w.cone_scratch = h->bcone.as<double>();
       }
-      h->ws_lpp = (rpl <= 32 && h->tun.get("OMC_NO_WARMSTART") == nullptr) ? lpp : 0;   // WS_JROWS
       // subspace tracking needs the warm-started kernel as its seed / fall-back and at least 3 x 16 rows
-      w.sub_enable = (h->ws_lpp && n >= 48 && omc_cone_sub_lds(w.np16) <= OMC_MAX_DYN_LDS && !h->tun.get("OMC_NO_SUBSPACE")) ? 1 : 0;
+      w.sub_enable = (h->ws_lpp && n >= 48 && omc_cone_sub_lds(w.np16) <= OMC_MAX_DYN_LDS && !h->tun.no_subspace) ? 1 : 0;
       w.sub_zscratch = nullptr;
       if (w.sub_enable && w.np16 > 512) { ENS(h->bsubz, sB * 16 * (size_t)(w.np16 + 2) * 8); w.sub_zscratch = h->bsubz.as<double>(); }
-      w.cert_enable = (w.sub_enable && w.MbufC && (h->tun.get("OMC_CERT_SUB") || w.np16 > 512)) ? 1 : 0;      // large orders: the certificate eigenvalues by the tracked block too (rigorous confirmation before anything is reported)
-      w.sep_done = (w.sub_enable && !h->tun.get("OMC_NO_SEP_SUB")) ? h->bsubIC.as<int>() + 2 * sB : nullptr;   // opt-in: measured no gain (the eigenvalues are not what the check spends its time on) and fewer rigorous samples of the bound
+      w.cert_enable = (w.sub_enable && w.np16 > 512) ? 1 : 0;      // large orders: the certificate eigenvalues by the tracked block too (rigorous confirmation before anything is reported)
+      w.sep_done = w.sub_enable ? h->bsubIC.as<int>() + 2 * sB : nullptr;
     }
     h->glob_lds = ((size_t)n * (n + 1) / 2 + (size_t)n * k + (size_t)rmax * k + 3 * Rmax + 8 + 16 * (size_t)n) * 8 + 16;   // packed lower triangle of the target; 16 = GL_XS staged cut vectors
-    h->glob_use_lds = (h->glob_lds + 20 * 1024 <= OMC_MAX_DYN_LDS) && !h->tun.get("OMC_GLOBAL_NOLDS");   // + the static LDS of k_global (NNQP scratch for NNQP_PMAX = 64 passive rows)
+    h->glob_use_lds = (h->glob_lds + 20 * 1024 <= OMC_MAX_DYN_LDS) && !h->tun.global_nolds;   // + the static LDS of k_global (NNQP scratch for NNQP_PMAX = 64 passive rows)
     if (!h->glob_use_lds) {
       w.glob_scratch_stride = h->glob_lds / 8 + 8;
       ENS(h->bglob, sB * w.glob_scratch_stride * 8);
@@ -792,7 +783,7 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
     }
     // factored W1 (OmcWS::w1_fac): k_global stages the accepted Ritz vectors of a slot (at most 16 n doubles) in its NNQP scratch, which
     // holds NNQP_PMAX (NNQP_PMAX + 1) / 2 doubles.  Off in Shor mode (its W1 views are other arrays) and with OMC_DENSE_PROJ=1.
-    if (!shor && w.sub_enable && h->glob_use_lds && (size_t)16 * n <= (size_t)NNQP_PMAX * (NNQP_PMAX + 1) / 2 && !h->tun.get("OMC_DENSE_PROJ"))
+    if (!shor && w.sub_enable && h->glob_use_lds && (size_t)16 * n <= (size_t)NNQP_PMAX * (NNQP_PMAX + 1) / 2 && !h->tun.dense_proj)
       w.w1_fac = h->bsubI.as<int>() + 14 * sB;
     {
       const int N3 = rmax + k; const int Npm = (N3 + 1) & ~1, ldm = Npm | 1;
@@ -857,11 +848,14 @@ int omc_relax_set_warm(omc_instance* h, int B, const int* load_from, const int* 
   return 0;
 }
 
+static constexpr int REFILL_EVERY = 3;      // finished slots are harvested and refilled at every third check (see omc_relax_solve)
+
 int omc_relax_solve(omc_instance* h) {
   if (!h || !h->staged) return fail(OMC_ERR_ARGUMENT, "omc_relax_solve: nothing staged");
   HIPCHK(hipSetDevice(h->device));
   const OmcWS& w = h->ws;
   const omc_relax_params& P = h->params;
+  const Tuning tun = h->tun;      // copied once: omc_tuning_set may run on the caller's thread while a submitted solve runs on the worker
   for (int c = 0; c < OMC_KERNEL_NCLASS; ++c) { h->launches[c] = 0; h->ms[c] = 0; h->units[c] = 0; }
   h->ev_used = 0; h->ev_class.clear();
   auto t0 = std::chrono::steady_clock::now();
@@ -894,26 +888,19 @@ int omc_relax_solve(omc_instance* h) {
   // cone: Y - D1 -> W1; small cone: Y, D3, V -> E3, W3*): a main stream (cone, then the global step) and two side streams
   // (columns, small cone) forked and joined by events, so that the latency-bound column waves and the small workgroups
   // share the CUs with the LDS-bound cone kernel (measured on config 2, 2048 slots: 212 -> 235 node-relaxations/s).
-  // OMC_STREAMS=1 serialises everything on one stream (kernel-by-kernel measurements).  OMC_GROUPS=2 additionally splits
-  // the slots in two groups with their own stream triple, meeting only at the certificate checks, so that one group's
-  // global step overlaps the other's cone kernel: measured slower (219/s), kept for experiments only.
-  const bool multi = !(h->tun.get("OMC_STREAMS") && atoi(h->tun.get("OMC_STREAMS")) <= 1);
-  const int G = (multi && S >= 64 && h->tun.get("OMC_GROUPS") && atoi(h->tun.get("OMC_GROUPS")) == 2) ? 2 : 1;
+  // OMC_STREAMS=1 serialises everything on one stream (kernel-by-kernel measurements).
+  const bool multi = tun.streams > 1;
   if (multi && !h->ev_main) {
-    for (int g = 0; g < 2; ++g) {
-      for (int q = 0; q < 4; ++q) HIPCHK(hipStreamCreateWithFlags(&h->gs[g][q], hipStreamNonBlocking));
-      for (int q = 0; q < 5; ++q) { HIPCHK(hipEventCreateWithFlags(&h->gev[g][q], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&h->gevc[g][q], hipEventDisableTiming)); }
-    }
+    for (hipStream_t& q : h->gs) HIPCHK(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
+    for (int q = 0; q < 5; ++q) { HIPCHK(hipEventCreateWithFlags(&h->gev[q], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&h->gevc[q], hipEventDisableTiming)); }
     HIPCHK(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
   }
+  const hipStream_t sm = multi ? h->gs[0] : s, sb = multi ? h->gs[1] : s, sc = multi ? h->gs[2] : s;
   // compact list of the slots that hold a running node: the per-iteration kernels launch over it (rebuilt when slots finish or are refilled)
   std::vector<char> parked(S, 0);      // finished, waiting for the next harvest
   int check_index = 0;
-  const int refill_every = std::max(1, h->tun.get("OMC_REFILL_EVERY") ? atoi(h->tun.get("OMC_REFILL_EVERY")) : 3);
   std::vector<int> alist(S);
-  for (int b = 0; b < S; ++b) alist[b] = b;
-  int nlist = S;
-  const bool use_list = !(h->tun.get("OMC_NO_SLOT_LIST"));
+  int nlist = 0;
   auto push_list = [&]() -> int {
     nlist = 0;
     for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && !parked[b]) alist[nlist++] = b;
@@ -922,86 +909,94 @@ int omc_relax_solve(omc_instance* h) {
     return 0;
   };
   { int rc = push_list(); if (rc) return rc; }
-  int gb0[2] = {0, 0}, gnB[2] = {S, 0}, gact[2] = {nactive, 0};
-  if (G == 2) { gnB[0] = S / 2; gb0[1] = S / 2; gnB[1] = S - S / 2; gact[0] = gnB[0]; gact[1] = gnB[1]; }
+  int gact = nactive;      // slots that run (hold a node, not parked): the units of an iteration's launches
+  auto recount = [&]() {
+    nactive = 0; gact = 0;
+    for (int b = 0; b < S; ++b) if (node_of[b] >= 0) { ++nactive; if (!parked[b]) ++gact; }
+  };
+  // nodes [next, Btot) that never got a slot: status `st` without values
+  auto close_unslotted = [&](int st) -> int {
+    if (next >= Btot) return 0;
+    const size_t c = (size_t)(Btot - next);
+    std::vector<int> stv(c, st), itz(c, 0);
+    std::vector<double> inf(c, 1e300), ninf(c, -1e300);
+    HIPCHK(hipMemcpyAsync(w.ostatus + next, stv.data(), sizeof(int) * c, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.oiters + next, itz.data(), sizeof(int) * c, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.oobj + next, inf.data(), 8 * c, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.olb + next, ninf.data(), 8 * c, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    next = Btot;
+    return 0;
+  };
   bool timed_out = false;
   h->total_sweeps = 0;
-  bool wait_main = true;     // group streams must wait for the work queued on the main stream (setup, checks, refills)
+  bool wait_main = true;     // the iteration streams must wait for the work queued on the main stream (setup, checks, refills)
   // Small batches are launch-bound (batch 1: ~190 us of launches, event records and waits around ~115 us of kernels per iteration):
-  // the body of an iteration (fork, three concurrent blocks, join, global step) is captured once into a hipGraph and replayed; it is
-  // captured again only when the number of live slots changes.  Per-kernel HIP-event timing is not available inside a graph, so the
-  // large batches that the bench times keep the eager path.
-  // hipGraph replay of the iteration body for small batches (measured at batch 1: 266 instead of 322 us per iteration).  Since the end of round 3
-  // only for batches that are small FROM THE START (<= OMC_GRAPH_MAX = 16 nodes staged: one capture per solve): the draining tail of a large batch
-  // re-captured the graph at every harvest, and a sporadic host crash inside omc_relax_solve was seen three times in the round, always in or after
-  // solves on that path, never with replay off; not located.  OMC_GRAPH_TAILS=1 restores replay in the tails.
-  const int graph_max_cfg = h->tun.get("OMC_GRAPH_MAX") ? atoi(h->tun.get("OMC_GRAPH_MAX")) : 16;
-  const int graph_max = (Btot <= graph_max_cfg || h->tun.get("OMC_GRAPH_TAILS")) ? graph_max_cfg : 0;
-  const bool shared_events = h->tun.get("OMC_GRAPH_SHARED_EVENTS") != nullptr;      // diagnostics: the pre-fix behaviour (captured and eager bodies use the same fork / join events)
-  const bool no_graph = h->tun.get("OMC_NO_GRAPH") != nullptr;      // read once per solve, not per iteration
-  const int timing_stride = h->tun.get("OMC_TIMING_STRIDE") ? atoi(h->tun.get("OMC_TIMING_STRIDE")) : 1;
+  // the body of an iteration (fork, three concurrent blocks, join, global step) is captured once into a hipGraph and replayed.  Per-kernel
+  // HIP-event timing is not available inside a graph, so the large batches that the bench times keep the eager path.
+  // hipGraph replay of the iteration body for small batches (measured at batch 1: 266 instead of 322 us per iteration), only for batches that
+  // are small FROM THE START (<= OMC_GRAPH_MAX = 16 nodes staged: one capture per solve): the draining tail of a large batch re-captured the graph
+  // at every harvest, and a sporadic host crash inside omc_relax_solve was seen three times in round 3, always in or after solves on that path,
+  // never with replay off; not located.
+  const int graph_max = Btot <= tun.graph_max ? tun.graph_max : 0;
   hipGraphExec_t gexec[2] = {nullptr, nullptr}; int gexec_n = -1;
   struct GraphGuard { hipGraphExec_t* e; ~GraphGuard() { for (int q = 0; q < 2; ++q) if (e[q]) (void)hipGraphExecDestroy(e[q]); } } gguard{gexec};
-  auto body = [&](int g, const OmcWS& wg, bool timed, bool with_aa, bool capturing) -> int {
-    hipEvent_t* const ev = (capturing && !shared_events) ? h->gevc[g] : h->gev[g];
-    hipStream_t sm = multi ? h->gs[g][0] : s, sb = multi ? h->gs[g][1] : s, sc = multi ? h->gs[g][2] : s;
+  // The full eigen-kernel runs the slots that have no tracked block (or are backing off) -- a handful per launch, each a long single-workgroup
+  // job, known before the iteration starts (ws_first) -- on a stream of its own beside k_cone_sub; what k_cone_sub then could not do (a failed
+  // call, ~1 in 30 000) is a second, almost empty launch behind both.  One launch after k_cone_sub made every iteration wait for the sum.
+  const bool split = multi && !tun.no_ws_split && w.sub_enable && h->ws_lpp && w.ws_first;
+  auto body = [&](const OmcWS& wg, bool timed, bool with_aa, bool capturing) -> int {
+    hipEvent_t* const ev = capturing ? h->gevc : h->gev;
     if (multi) {
       HIPCHK(hipEventRecord(ev[0], sm));
       HIPCHK(hipStreamWaitEvent(sb, ev[0], 0)); HIPCHK(hipStreamWaitEvent(sc, ev[0], 0));
     }
 #define MAYBE_TIMED(strm, cls, units_, call) do { if (timed) TIMED_ON(strm, cls, units_, call); else { call; } } while (0)
-    // the cone workgroups are few (two per CU, long serial phases) and the column waves many: the cone kernel goes first so that its
-    // workgroups are resident when the column kernel floods the wave slots (OMC_COLPROX_FIRST=1 restores the other order)
-    const bool colprox_first = h->tun.get("OMC_COLPROX_FIRST") != nullptr;
     if (shor) {
       // Shor mode: clip on the main stream, the order-(n+m) cone on the second, small cone + order-5 blocks on the third; then the
       // global step: rows / Y (base kernel), columns (X, W, Theta, duals of the big cone), duals of the order-5 blocks, per-slot sums
       OmcWS wb = h->wbig; wb.b0 = wg.b0; wb.nB = wg.nB; wb.slot_list = wg.slot_list;
-      if (w.sub_enable) MAYBE_TIMED(sm, OMC_KERNEL_CONESUB, gact[g], omc_launch_cone_sub(&wg, sm));
+      if (w.sub_enable) MAYBE_TIMED(sm, OMC_KERNEL_CONESUB, gact, omc_launch_cone_sub(&wg, sm));
       if (wb.sub_enable) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, 0, omc_launch_cone_sub(&wb, sb));
-      if (h->big_lpp) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact[g], omc_launch_cone_ws(&wb, h->big_lpp, h->big_use_lds, h->big_lds, sb));
-      else MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact[g], omc_launch_cone(&wb, CONE_BIG, h->big_cone_lds_ok, h->big_cone_lds, sb));
-      if (h->ws_lpp) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact[g], omc_launch_cone_ws(&wg, h->ws_lpp, h->ws_use_lds, h->ws_lds, sm));
-      else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact[g], omc_launch_cone(&wg, CONE_CLIP01, h->cone_use_lds, h->cone_lds, sm));
-      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact[g], omc_launch_small(&wg, SMALL_PROJ, h->small_use_lds, h->small_lds, sc));
-      MAYBE_TIMED(sc, OMC_KERNEL_SHOR_MINORS, gact[g], { omc_shor_launch_minor_pre(&sw, sc); omc_shor_launch_vkeys(&sw, sc); });
+      if (h->big_lpp) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone_ws(&wb, h->big_lpp, h->big_use_lds, h->big_lds, sb));
+      else MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone(&wb, CONE_BIG, h->big_cone_lds_ok, h->big_cone_lds, sb));
+      if (h->ws_lpp) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, h->ws_lpp, h->ws_use_lds, h->ws_lds, sm));
+      else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, h->cone_use_lds, h->cone_lds, sm));
+      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, h->small_use_lds, h->small_lds, sc));
+      MAYBE_TIMED(sc, OMC_KERNEL_SHOR_MINORS, gact, { omc_shor_launch_minor_pre(&sw, sc); omc_shor_launch_vkeys(&sw, sc); });
       if (multi) {
         HIPCHK(hipEventRecord(ev[1], sb)); HIPCHK(hipEventRecord(ev[2], sc));
         HIPCHK(hipStreamWaitEvent(sm, ev[1], 0)); HIPCHK(hipStreamWaitEvent(sm, ev[2], 0));
       }
-      MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact[g], omc_launch_global(&wg, h->glob_use_lds, h->glob_lds, sm));
-      MAYBE_TIMED(sm, OMC_KERNEL_SHOR_COLS, gact[g], omc_shor_launch_cols(&sw, sm));
-      MAYBE_TIMED(sm, OMC_KERNEL_SHOR_MINORS, gact[g], { omc_shor_launch_minor_post(&sw, sm); omc_shor_launch_reduce(&sw, sm); });
+      MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, h->glob_use_lds, h->glob_lds, sm));
+      MAYBE_TIMED(sm, OMC_KERNEL_SHOR_COLS, gact, omc_shor_launch_cols(&sw, sm));
+      MAYBE_TIMED(sm, OMC_KERNEL_SHOR_MINORS, gact, { omc_shor_launch_minor_post(&sw, sm); omc_shor_launch_reduce(&sw, sm); });
       return 0;
     }
-    // The full eigen-kernel runs the slots that have no tracked block (or are backing off) -- a handful per launch, each a long single-workgroup
-    // job, known before the iteration starts (ws_first) -- on a stream of its own beside k_cone_sub; what k_cone_sub then could not do (a failed
-    // call, ~1 in 30 000) is a second, almost empty launch behind both.  One launch after k_cone_sub made every iteration wait for the sum.
-    const bool ws_split_ok = h->tun.get("OMC_NO_WS_SPLIT") == nullptr;
-    const bool split = multi && ws_split_ok && w.sub_enable && h->ws_lpp && w.ws_first;
     if (split) {      // on the small-cone stream, behind k_small (a fifth stream would share a hardware queue with one of the other four: measured, k_small then ran behind it)
-      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact[g], omc_launch_small(&wg, SMALL_PROJ, h->small_use_lds, h->small_lds, sc));
+      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, h->small_use_lds, h->small_lds, sc));
       OmcWS wA = wg; wA.ws_phase = 1;
-      MAYBE_TIMED(sc, OMC_KERNEL_CONE, gact[g], omc_launch_cone_ws(&wA, h->ws_lpp, h->ws_use_lds, h->ws_lds, sc));
+      MAYBE_TIMED(sc, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wA, h->ws_lpp, h->ws_use_lds, h->ws_lds, sc));
       HIPCHK(hipEventRecord(ev[4], sc));
     }
-    if (colprox_first) MAYBE_TIMED(sb, OMC_KERNEL_COLPROX, (int64_t)gact[g] * w.m, omc_launch_colprox(&wg, 0, sb));
-    if (w.sub_enable) MAYBE_TIMED(sm, OMC_KERNEL_CONESUB, gact[g], omc_launch_cone_sub(&wg, sm));
-    if (!colprox_first) MAYBE_TIMED(sb, OMC_KERNEL_COLPROX, (int64_t)gact[g] * w.m, omc_launch_colprox(&wg, 0, sb));
+    // the cone workgroups are few (two per CU, long serial phases) and the column waves many: the cone kernel goes first so that its
+    // workgroups are resident when the column kernel floods the wave slots
+    if (w.sub_enable) MAYBE_TIMED(sm, OMC_KERNEL_CONESUB, gact, omc_launch_cone_sub(&wg, sm));
+    MAYBE_TIMED(sb, OMC_KERNEL_COLPROX, (int64_t)gact * w.m, omc_launch_colprox(&wg, 0, sb));
     if (split) {
       HIPCHK(hipStreamWaitEvent(sm, ev[4], 0));
       OmcWS wB = wg; wB.ws_phase = 2;
       MAYBE_TIMED(sm, OMC_KERNEL_CONE, 0, omc_launch_cone_ws(&wB, h->ws_lpp, h->ws_use_lds, h->ws_lds, sm));
     }
-    else if (h->ws_lpp) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact[g], omc_launch_cone_ws(&wg, h->ws_lpp, h->ws_use_lds, h->ws_lds, sm));
-    else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact[g], omc_launch_cone(&wg, CONE_CLIP01, h->cone_use_lds, h->cone_lds, sm));
-    if (!split) MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact[g], omc_launch_small(&wg, SMALL_PROJ, h->small_use_lds, h->small_lds, sc));
+    else if (h->ws_lpp) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, h->ws_lpp, h->ws_use_lds, h->ws_lds, sm));
+    else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, h->cone_use_lds, h->cone_lds, sm));
+    if (!split) MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, h->small_use_lds, h->small_lds, sc));
     if (multi) {
       HIPCHK(hipEventRecord(ev[1], sb)); HIPCHK(hipEventRecord(ev[2], sc));
       HIPCHK(hipStreamWaitEvent(sm, ev[1], 0)); HIPCHK(hipStreamWaitEvent(sm, ev[2], 0));
     }
-    MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact[g], omc_launch_global(&wg, h->glob_use_lds, h->glob_lds, sm));
-    if (with_aa) MAYBE_TIMED(sm, OMC_KERNEL_ACCEL, gact[g], omc_launch_aa(&wg, sm));
+    MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, h->glob_use_lds, h->glob_lds, sm));
+    if (with_aa) MAYBE_TIMED(sm, OMC_KERNEL_ACCEL, gact, omc_launch_aa(&wg, sm));
     return 0;
   };
   // nodes appended while every slot was idle (or while the loop was about to end): hand them to idle slots
@@ -1012,8 +1007,7 @@ int omc_relax_solve(omc_instance* h) {
     if (!ninit2) return 0;
     int rc = push_flags(init2, fin2); if (rc) return rc;
     TIMED(OMC_KERNEL_SETUP, ninit2, omc_launch_setup(&w, s));
-    nactive = 0; gact[0] = gact[1] = 0;
-    for (int b = 0; b < S; ++b) if (node_of[b] >= 0) { ++nactive; if (!parked[b]) ++gact[(G == 2 && b >= gb0[1]) ? 1 : 0]; }
+    recount();
     rc = push_list(); if (rc) return rc;
     wait_main = true;
     return 0;
@@ -1023,16 +1017,7 @@ int omc_relax_solve(omc_instance* h) {
       {   // the end of the batch is decided under the lock omc_relax_append takes: a node is either seen here or refused there
         std::lock_guard<std::mutex> lk(h->append_mu);
         Btot = h->Btot_live.load();
-        if (timed_out && next < Btot) {      // appended after the time limit struck: reported as TIME_LIMIT without values, like the nodes that never got a slot
-          std::vector<int> st(Btot - next, OMC_ST_TIME), itz(Btot - next, 0);
-          std::vector<double> inf(Btot - next, 1e300), ninf(Btot - next, -1e300);
-          HIPCHK(hipMemcpyAsync(w.ostatus + next, st.data(), sizeof(int) * st.size(), hipMemcpyHostToDevice, s));
-          HIPCHK(hipMemcpyAsync(w.oiters + next, itz.data(), sizeof(int) * itz.size(), hipMemcpyHostToDevice, s));
-          HIPCHK(hipMemcpyAsync(w.oobj + next, inf.data(), 8 * inf.size(), hipMemcpyHostToDevice, s));
-          HIPCHK(hipMemcpyAsync(w.olb + next, ninf.data(), 8 * ninf.size(), hipMemcpyHostToDevice, s));
-          HIPCHK(hipStreamSynchronize(s));
-          next = Btot;
-        }
+        if (timed_out) { int rc = close_unslotted(OMC_ST_TIME); if (rc) return rc; }      // appended after the time limit struck
         if (next >= Btot) {
           const double el_idle = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
           if (!h->hold.load() || el_idle > P.time_limit) { h->append_closed = true; break; }
@@ -1047,13 +1032,10 @@ int omc_relax_solve(omc_instance* h) {
     if (multi && wait_main) HIPCHK(hipEventRecord(h->ev_main, s));
     // per-kernel HIP-event timing brackets every launch of a sampled iteration (two event records per kernel: ~25 us of queue bubbles per
     // iteration at small batches); OMC_TIMING_STRIDE=s samples every s-th iteration (averages per launch are over the sampled launches), 0 = none
-    const bool sampled = timing_stride > 0 && (it % timing_stride) == 0;
-    const bool use_graph = multi && G == 1 && use_list && nlist <= graph_max && !no_graph && !(sampled && timing_stride > 1);
-    for (int g = 0; g < G; ++g) {
-      if (gact[g] == 0) continue;
-      OmcWS wg = w; wg.b0 = gb0[g]; wg.nB = gnB[g];
-      if (use_list && G == 1) { wg.slot_list = h->bslotlist.as<int>(); wg.b0 = 0; wg.nB = nlist; }
-      hipStream_t sm = multi ? h->gs[g][0] : s;
+    const bool sampled = tun.timing_stride > 0 && (it % tun.timing_stride) == 0;
+    const bool use_graph = multi && nlist <= graph_max && !tun.no_graph && !(sampled && tun.timing_stride > 1);
+    if (gact > 0) {
+      OmcWS wg = w; wg.slot_list = h->bslotlist.as<int>(); wg.b0 = 0; wg.nB = nlist;
       if (multi && wait_main) HIPCHK(hipStreamWaitEvent(sm, h->ev_main, 0));
       if (use_graph) {
         if (gexec_n != nlist) {      // (re)capture: one graph without and one with the acceleration kernel at its end
@@ -1061,7 +1043,7 @@ int omc_relax_solve(omc_instance* h) {
           for (int q = 0; q < (w.accel ? 2 : 1); ++q) {
             hipGraph_t gr = nullptr;
             HIPCHK(hipStreamBeginCapture(sm, hipStreamCaptureModeThreadLocal));
-            int rc = body(g, wg, false, q == 1, true);
+            int rc = body(wg, false, q == 1, true);
             hipError_t ce = hipStreamEndCapture(sm, &gr);
             if (rc) { if (gr) (void)hipGraphDestroy(gr); return rc; }
             HIPCHK(ce);
@@ -1073,11 +1055,11 @@ int omc_relax_solve(omc_instance* h) {
         }
         const int q = (!is_check && w.accel) ? 1 : 0;
         HIPCHK(hipGraphLaunch(gexec[q], sm));
-        h->launches[OMC_KERNEL_GLOBAL] += 1; h->units[OMC_KERNEL_GLOBAL] += gact[g];
+        h->launches[OMC_KERNEL_GLOBAL] += 1; h->units[OMC_KERNEL_GLOBAL] += gact;
       } else {
-        int rc = body(g, wg, sampled, !is_check && w.accel, false); if (rc) return rc;
+        int rc = body(wg, sampled, !is_check && w.accel, false); if (rc) return rc;
       }
-      if (multi && is_check) { HIPCHK(hipEventRecord(h->gev[g][3], sm)); HIPCHK(hipStreamWaitEvent(s, h->gev[g][3], 0)); }
+      if (multi && is_check) { HIPCHK(hipEventRecord(h->gev[3], sm)); HIPCHK(hipStreamWaitEvent(s, h->gev[3], 0)); }
     }
     wait_main = false;
     if (!is_check) continue;
@@ -1096,7 +1078,7 @@ int omc_relax_solve(omc_instance* h) {
         OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, h->ws_lpp, h->ws_use_lds, h->ws_lds, s);
         omc_launch_check_final(&w, timed_out ? OMC_ST_TIME : 0, 1, s);
       } else {
-        if (h->ws_lpp && w.MbufC) { OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, h->ws_lpp, h->ws_use_lds, h->ws_lds, s); }
+        if (h->ws_lpp) { OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, h->ws_lpp, h->ws_use_lds, h->ws_lds, s); }
         else omc_launch_cone(&w, CONE_EVALS, h->cone_use_lds, h->cone_lds, s);
         omc_launch_check_final(&w, timed_out ? OMC_ST_TIME : 0, 2, s);      // per-slot iteration cap is applied on the device
       }
@@ -1105,6 +1087,7 @@ int omc_relax_solve(omc_instance* h) {
     });
     HIPCHK(hipMemcpyAsync(done.data(), w.done, sizeof(int) * S, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    finish_events(h);      // every timed launch of the interval has joined s (the side streams join sm before k_global, sm joins s at a check)
     Btot = h->Btot_live.load();
     if (P.first_wins) {   // the first certified node ends the batch (penalty autotune): everything still running is harvested as it stands
       std::vector<int> stv(S);
@@ -1116,23 +1099,14 @@ int omc_relax_solve(omc_instance* h) {
         for (int b = 0; b < S; ++b) done[b] = 1;
         HIPCHK(hipMemcpyAsync(w.done, done.data(), sizeof(int) * S, hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (next < Btot) {   // nodes that never got a slot
-          std::vector<int> st(Btot - next, OMC_ST_SLOW), itz(Btot - next, 0);
-          std::vector<double> inf(Btot - next, 1e300), ninf(Btot - next, -1e300);
-          HIPCHK(hipMemcpyAsync(w.ostatus + next, st.data(), sizeof(int) * st.size(), hipMemcpyHostToDevice, s));
-          HIPCHK(hipMemcpyAsync(w.oiters + next, itz.data(), sizeof(int) * itz.size(), hipMemcpyHostToDevice, s));
-          HIPCHK(hipMemcpyAsync(w.oobj + next, inf.data(), 8 * inf.size(), hipMemcpyHostToDevice, s));
-          HIPCHK(hipMemcpyAsync(w.olb + next, ninf.data(), 8 * ninf.size(), hipMemcpyHostToDevice, s));
-          HIPCHK(hipStreamSynchronize(s));
-          next = Btot;
-        }
+        int rc = close_unslotted(OMC_ST_SLOW); if (rc) return rc;
       }
     }
     // harvest finished slots, hand them the next pending nodes
-    // Harvest and refill every `refill_every`-th check only (or when nothing is left running): a refilled slot spends its first dozen
+    // Harvest and refill every REFILL_EVERY-th check only (or when nothing is left running): a refilled slot spends its first dozen
     // iterations in the full eigendecomposition, the straggler of every launch it is part of, and each harvest is 1 - 3 ms of few-workgroup
     // kernels on the main stream -- batching them halves the launches that carry young slots.  A finished slot waits (done = 1, skipped
-    // by every kernel and left out of the slot list) for at most refill_every - 1 check intervals.
+    // by every kernel and left out of the slot list) for at most REFILL_EVERY - 1 check intervals.
     std::vector<int> init(S, 0), fin(S, 0);
     int nfin = 0, nlive = 0, nnew = 0;
     for (int b = 0; b < S; ++b) {
@@ -1140,9 +1114,9 @@ int omc_relax_solve(omc_instance* h) {
       if (done[b]) { ++nfin; if (!parked[b]) { parked[b] = 1; ++nnew; } } else ++nlive;
     }
     ++check_index;
-    // with pending nodes: every refill_every-th check, at once when the live slots no longer fill the chip; without: the finished slots can
+    // with pending nodes: every REFILL_EVERY-th check, at once when the live slots no longer fill the chip; without: the finished slots can
     // wait longer (nothing to hand them), until nothing runs any more
-    const bool harvest_now = nfin > 0 && (nlive == 0 || (next < Btot ? (check_index % refill_every == 0 || nlive < 256) : (check_index % (4 * refill_every) == 0)));
+    const bool harvest_now = nfin > 0 && (nlive == 0 || (next < Btot ? (check_index % REFILL_EVERY == 0 || nlive < 256) : (check_index % (4 * REFILL_EVERY) == 0)));
     if (harvest_now) for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && done[b]) { fin[b] = 1; parked[b] = 0; }
     if (!harvest_now) nfin = 0;
     if (nfin) {
@@ -1169,21 +1143,10 @@ int omc_relax_solve(omc_instance* h) {
       { std::lock_guard<std::mutex> lk(h->done_mu); h->done_q.insert(h->done_q.end(), harvested_ids.begin(), harvested_ids.end()); }
       if (ninit) { if (shor) omc_shor_launch_setup(&sw, s); TIMED(OMC_KERNEL_SETUP, ninit, omc_launch_setup(&w, s)); }
     }
-    nactive = 0; gact[0] = gact[1] = 0;
-    for (int b = 0; b < S; ++b) if (node_of[b] >= 0) { ++nactive; if (!parked[b]) ++gact[(G == 2 && b >= gb0[1]) ? 1 : 0]; }
+    recount();
     if (nfin || nnew) { int rc = push_list(); if (rc) return rc; }
     if (next < Btot && !timed_out && nactive < S) { int rc = refill_idle(); if (rc) return rc; }      // appended nodes for slots that had gone idle
-    if (timed_out && next < Btot) {
-      // nodes that never got a slot: report TIME_LIMIT without values
-      std::vector<int> st(Btot - next, OMC_ST_TIME), itz(Btot - next, 0);
-      std::vector<double> inf(Btot - next, 1e300), ninf(Btot - next, -1e300);
-      HIPCHK(hipMemcpyAsync(w.ostatus + next, st.data(), sizeof(int) * st.size(), hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(w.oiters + next, itz.data(), sizeof(int) * itz.size(), hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(w.oobj + next, inf.data(), 8 * inf.size(), hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(w.olb + next, ninf.data(), 8 * ninf.size(), hipMemcpyHostToDevice, s));
-      HIPCHK(hipStreamSynchronize(s));
-      next = Btot;
-    }
+    if (timed_out) { int rc = close_unslotted(OMC_ST_TIME); if (rc) return rc; }
   }
   {
     std::vector<int> sw(S);
@@ -1203,7 +1166,6 @@ int omc_relax_solve(omc_instance* h) {
     HIPCHK(hipStreamSynchronize(s));
     for (int q = 0; q < 8; ++q) h->big_sub_tot[q] = 0;
     for (int b = 0; b < S; ++b) for (int q = 0; q < 8; ++q) h->big_sub_tot[q] += ss[8 * b + q];
-    if (h->tun.get("OMC_SHOR_DEBUG")) for (int b = 0; b < S && b < 4; ++b) fprintf(stderr, "slot %d big-cone subspace: calls %d steps %d fallbacks %d seeds %d\n", b, ss[8 * b], ss[8 * b + 1], ss[8 * b + 2], ss[8 * b + 3]);
     HIPCHK(hipMemsetAsync(h->wbig.sub_stat, 0, sizeof(int) * ss.size(), s));
   }
   HIPCHK(hipGetLastError());
@@ -1240,23 +1202,6 @@ int omc_relax_append(omc_instance* h, int B2, const int* L, const double* cut_x,
   NodePack pk;
   { int rcp = pack_nodes(h, h->params, h->staged_cut_type, B2, L, cut_x, cut_Uhat, cut_dir, nullptr, nullptr, pk); if (rcp) return rcp; }
   if (pk.Rmax > w.Rmax || pk.rmax > w.rmax || pk.Lmax > w.Lmax) return fail(OMC_ERR_ARGUMENT, "omc_relax_append: a node has more cuts than omc_relax_reserve allowed for");
-  const size_t n = h->n, k = h->k, Rm = w.Rmax, rm = w.rmax, Lm = w.Lmax;
-  std::vector<int> hR(B2), hk((size_t)B2 * Rm, 0), hc((size_t)B2 * Rm, 0), hbi((size_t)B2 * Rm, 0), hbj((size_t)B2 * Rm, 0);
-  std::vector<double> hcoef((size_t)B2 * Rm * k, 0.0), hrhs((size_t)B2 * Rm, 0.0), hx((size_t)B2 * Lm * n, 0.0), hQ((size_t)B2 * n * rm, 0.0), hrho(B2, w.rho);
-  long cutbase = 0;
-  for (int b = 0; b < B2; ++b) {
-    hR[b] = (int)pk.rk[b].size();
-    for (int r = 0; r < hR[b]; ++r) {
-      hk[(size_t)b * Rm + r] = pk.rk[b][r]; hc[(size_t)b * Rm + r] = pk.rc[b][r];
-      hbi[(size_t)b * Rm + r] = pk.rbi[b][r]; hbj[(size_t)b * Rm + r] = pk.rbj[b][r];
-      hrhs[(size_t)b * Rm + r] = pk.rrhs[b][r];
-      for (size_t j = 0; j < k; ++j) hcoef[((size_t)b * Rm + r) * k + j] = pk.rcoef[b][(size_t)r * k + j];
-    }
-    const int Lb = L ? L[b] : 0;
-    for (int l = 0; l < Lb; ++l) memcpy(&hx[((size_t)b * Lm + l) * n], cut_x + (size_t)(cutbase + l) * n, sizeof(double) * n);
-    cutbase += Lb;
-    memcpy(&hQ[(size_t)b * n * rm], pk.Qn[b].data(), sizeof(double) * pk.Qn[b].size());
-  }
   if ((load_from || save_to) && !(w.load_from && w.save_to)) return fail(OMC_ERR_ARGUMENT, "omc_relax_append: warm-start indices need a state pool created before the batch was staged");
   for (int b = 0; b < B2; ++b) {
     if (load_from && load_from[b] >= h->pool_cap) return fail(OMC_ERR_ARGUMENT, "load_from index beyond the pool");
@@ -1266,16 +1211,8 @@ int omc_relax_append(omc_instance* h, int B2, const int* L, const double* cut_x,
   hipStream_t as = h->append_stream;
   const size_t f = (size_t)first;
   // the running kernels read the descriptors of nodes below Btot_live only: these rows are not visible to them until the counter moves
-  HIPCHK(hipMemcpyAsync(w.R + f, hR.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
-  HIPCHK(hipMemcpyAsync(w.rkind + f * Rm, hk.data(), sizeof(int) * hk.size(), hipMemcpyHostToDevice, as));
-  HIPCHK(hipMemcpyAsync(w.rcut + f * Rm, hc.data(), sizeof(int) * hc.size(), hipMemcpyHostToDevice, as));
-  HIPCHK(hipMemcpyAsync(w.rbi + f * Rm, hbi.data(), sizeof(int) * hbi.size(), hipMemcpyHostToDevice, as));
-  HIPCHK(hipMemcpyAsync(w.rbj + f * Rm, hbj.data(), sizeof(int) * hbj.size(), hipMemcpyHostToDevice, as));
-  HIPCHK(hipMemcpyAsync(w.rcoef + f * Rm * k, hcoef.data(), 8 * hcoef.size(), hipMemcpyHostToDevice, as));
-  HIPCHK(hipMemcpyAsync(w.rrhs + f * Rm, hrhs.data(), 8 * hrhs.size(), hipMemcpyHostToDevice, as));
-  HIPCHK(hipMemcpyAsync(w.cutx + f * Lm * n, hx.data(), 8 * hx.size(), hipMemcpyHostToDevice, as));
-  HIPCHK(hipMemcpyAsync(w.Qb + f * n * rm, hQ.data(), 8 * hQ.size(), hipMemcpyHostToDevice, as));
-  HIPCHK(hipMemcpyAsync(w.rr + f, pk.rrv.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
+  { int rc = put_descriptors(w, pk, B2, B2, f, L, cut_x, as); if (rc) return rc; }
+  std::vector<double> hrho(B2, w.rho);
   HIPCHK(hipMemcpyAsync(const_cast<double*>(w.rho_node) + f, hrho.data(), 8 * (size_t)B2, hipMemcpyHostToDevice, as));
   if (load_from) HIPCHK(hipMemcpyAsync(const_cast<int*>(w.load_from) + f, load_from, sizeof(int) * B2, hipMemcpyHostToDevice, as));
   if (save_to) HIPCHK(hipMemcpyAsync(const_cast<int*>(w.save_to) + f, save_to, sizeof(int) * B2, hipMemcpyHostToDevice, as));
@@ -1561,7 +1498,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   if (h->k > 1) {
     bool all_free = true;
     for (int g = 0; g < NG && all_free; ++g) for (int j = 0; j < m; ++j) if (gh[g].ctype[j] != 0) { all_free = false; break; }
-    if (all_free && !h->tun.get("OMC_SHOR_EXPLICIT")) {
+    if (all_free && !h->tun.shor_explicit) {
       int rc0 = omc_relax_stage(h, B, params, cut_type, L, cut_x, cut_Uhat, cut_dir, U_lower, U_upper);
       if (rc0) return rc0;
       h->shor_via_base = true;
@@ -1658,23 +1595,11 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   wb.n = N; wb.np16 = NPb; wb.Mbuf = sh.MbufB; wb.Vrow = sh.VrowB; wb.vvalid = sh.vvalidB; wb.fro2 = sh.fro2B; wb.W1 = sh.P0;
   wb.sub_enable = 0; wb.cert_enable = 0; wb.ws_mode = 0; wb.clip_hi = 1e300; wb.sub_debug = 0; wb.ws_first = nullptr; wb.ws_phase = 0;
   {
-    const int Np2 = (N + 1) & ~1;
-    int lpp = 16; while (lpp > 4 && lpp * (Np2 / 2) > 512) lpp >>= 1;
-    int rpl = (((N + lpp - 1) / lpp) + 1) & ~1, Nrp = rpl * lpp;
-    int ldw = Nrp + ((16 - (Nrp & 31)) & 31);
-    if (((size_t)Np2 * ldw + 3 * Np2) * 8 + (size_t)(Np2 + 2) * 4 + 64 > OMC_MAX_DYN_LDS) ldw = Nrp + 2;
-    h->big_lds = ((size_t)Np2 * ldw + 3 * Np2) * 8 + (size_t)(Np2 + 2) * 4 + 64;
-    h->big_use_lds = h->big_lds <= OMC_MAX_DYN_LDS;
-    wb.ws_ld = ldw;
-    size_t need = 0;
-    if (!h->big_use_lds) {
-      lpp = 16; rpl = (((N + 15) / 16) + 1) & ~1; Nrp = rpl * 16; ldw = Nrp + 2; wb.ws_ld = ldw;
-      if (rpl > 32 && N <= 1024) { lpp = 64; rpl = (((N + 63) / 64) + 1) & ~1; Nrp = rpl * 64; ldw = Nrp + 2; wb.ws_ld = ldw; }
-      need = ((size_t)Np2 * ldw + 3 * Np2) * 8 + (size_t)(Np2 + 2) * 4 + 64;
-    }
-    h->big_lpp = (rpl <= 32 && h->tun.get("OMC_NO_WARMSTART") == nullptr) ? lpp : 0;
+    const WsGeometry g = ws_geometry(N);
+    h->big_lpp = g.lpp; h->big_lds = g.lds; h->big_use_lds = g.use_lds; wb.ws_ld = g.ldw;
+    size_t need = g.scratch;
     // generic cold kernel (orders beyond the warm-started one): Np x (Np | 1) matrix + 2 Np doubles + Np ints
-    const int ldc = Np2 | 1;
+    const int Np2 = (N + 1) & ~1, ldc = Np2 | 1;
     h->big_cone_lds = ((size_t)Np2 * ldc + 2 * Np2) * 8 + (size_t)Np2 * 4 + 16;
     h->big_cone_lds_ok = h->big_cone_lds <= OMC_MAX_DYN_LDS;
     if (!h->big_lpp && !h->big_cone_lds_ok) need = std::max(need, h->big_cone_lds);
@@ -1687,7 +1612,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   // the big cone's input has a handful of positive eigenvalues once the iterate has settled (measured: 2 - 5 of n + m): the tracked-subspace
   // kernel of the base engine follows them; the warm-started full kernel seeds the block and is the fall-back
   wb.trM = sh.trB;
-  if (h->big_lpp && N >= 48 && omc_cone_sub_lds(NPb) <= OMC_MAX_DYN_LDS && !h->tun.get("OMC_NO_SUBSPACE") && !h->tun.get("OMC_SHOR_NO_SUBSPACE")) {
+  if (h->big_lpp && N >= 48 && omc_cone_sub_lds(NPb) <= OMC_MAX_DYN_LDS && !h->tun.no_subspace && !h->tun.shor_no_subspace) {
     ENS(h->sXsB, sB * NPb * 16 * 8); ENS(h->ssubSB, sB * 16 * 8); ENS(h->ssubIB, sB * 12 * sizeof(int));
     HIPCHK(hipMemsetAsync(h->sXsB.p, 0, sB * NPb * 16 * 8, s));
     HIPCHK(hipMemsetAsync(h->ssubSB.p, 0, sB * 16 * 8, s));
@@ -1936,7 +1861,7 @@ int omc_altmin_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q
                               : ((size_t)4 * n * k + (size_t)2 * n * k * k + (size_t)k * m + 2 * Rmax + 8) * 8;
   w.scratch = nullptr; w.scratch_stride = 0;
   size_t lds_launch = lds;
-  if (lds + 8 * 1024 > ((k == 1) ? (size_t)OMC_MAX_DYN_LDS - 8 * 1024 : (size_t)128 * 1024) || h->tun.get("OMC_ALTMIN_NOLDS")) {
+  if (lds + 8 * 1024 > ((k == 1) ? (size_t)OMC_MAX_DYN_LDS - 8 * 1024 : (size_t)128 * 1024) || h->tun.altmin_nolds) {
     // the problem does not fit the LDS (config 5: 1000 x 1000, k = 2 needs 144 KB): the same kernel runs on a per-problem global slab
     w.scratch_stride = lds / 8 + 8;
     ENS(h->aG2, (size_t)B * w.scratch_stride * 8);
@@ -2183,11 +2108,8 @@ int omc_debug_residuals(omc_instance* h, double* rp, double* rd) {
 
 int omc_tuning_set(omc_instance* h, const char* name, const char* value) {
   if (!h || !name) return fail(OMC_ERR_ARGUMENT, "omc_tuning_set: handle or name is NULL");
-  bool known = false;
-  for (const char* key : OMC_TUNING_KEYS) if (!strcmp(key, name)) known = true;
-  if (!known) return fail(OMC_ERR_ARGUMENT, "omc_tuning_set: unknown knob");
-  if (value) h->tun.kv[name] = value; else h->tun.kv.erase(name);
-  return 0;
+  for (const Knob& kb : OMC_KNOBS) if (!strcmp(kb.name, name)) { knob_set(h->tun, kb, value); return 0; }
+  return fail(OMC_ERR_ARGUMENT, "omc_tuning_set: unknown knob");
 }
 
 int omc_tuning_reload_env(omc_instance* h) {
@@ -2198,7 +2120,7 @@ int omc_tuning_reload_env(omc_instance* h) {
 
 int omc_debug_stamps(omc_instance* h, double* out32) {
   if (!h || !out32 || !h->ws.stamps) return fail(OMC_ERR_ARGUMENT, "no stamps");
-  if (h->tun.get("OMC_SUB_DEBUG") && atoi(h->tun.get("OMC_SUB_DEBUG")) == 3 && h->ws.B >= 8) {      // diagnostics: three histograms (tools/diagnostics/gpu_nkeep_hist.py passes 96 doubles)
+  if (h->tun.sub_debug == 3 && h->ws.B >= 8) {      // diagnostics: three histograms (tools/diagnostics/gpu_nkeep_hist.py passes 96 doubles)
     HIPCHK(hipMemcpy(out32, h->ws.stamps, 96 * 8, hipMemcpyDeviceToHost));
     return 0;
   }

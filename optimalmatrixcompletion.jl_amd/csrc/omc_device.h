@@ -128,7 +128,7 @@ struct OmcWS {
   double* Yx;                // B*n*n: 2 Y - Yp, written by k_global (and k_setup) for the column gathers of k_colprox* (one load per entry instead of two); NULL with acceleration or Shor mode
   int cone_512;              // diagnostics (OMC_CONE_512): the 512-thread form of the L2-resident eigen-kernel at orders 193..256
   int cp_series;             // Neumann-series order of k_colprox_pair's finish (6; 3 = the second-order finish of colprox_reg)
-  int cp_maxpass;            // diagnostics (OMC_CP_MAXPASS): cap on the secular passes of k_colprox_pair; 60 = the algorithm
+  int cp_maxpass;            // cap on the secular passes of k_colprox_pair (CP_MAXPASS = 60 in omc_api.cpp: the algorithm)
   int cp_xcd;                // 1: column-prox workgroups placed XCD-locally (xcd_block); 0 (OMC_COLPROX_NO_XCD): plain blockIdx.x
   double* cone_scratch; size_t cone_scratch_stride; // per node when N is too large for LDS
   double* glob_scratch; size_t glob_scratch_stride;
