@@ -19,13 +19,13 @@ struct AltminWS {
   double* mobj;            // B: master objective (OMC.jl:2352-2358) of X = U V, evaluated on the device from the factors
   double* G;               // B*Rmax*Rmax scratch
   double* scratch; size_t scratch_stride;   // per-problem global slab that replaces the dynamic LDS when the problem does not fit it (NULL: LDS)
+  size_t lds_bytes;        // dynamic LDS of the launch (0 with the slab); stride and bytes from altmin_plan (omc_layout.h)
 };
 
 #ifdef __cplusplus
 extern "C" {
 #endif
-void omc_launch_altmin(const void* ws, size_t lds_bytes, hipStream_t s);
-void omc_launch_altmin_k(const void* ws, size_t lds_bytes, hipStream_t s);
+void omc_launch_altmin(const AltminWS* w, hipStream_t s);
 int omc_altmin_set_lds(void);
 #ifdef __cplusplus
 }

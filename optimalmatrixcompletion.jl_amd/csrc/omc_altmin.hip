@@ -40,19 +40,16 @@ __global__ void __launch_bounds__(256) k_altmin(AltminWS w) {
   // problems that do not fit the LDS (config 5: 1000 x 1000) keep the same state in a per-problem global slab (L2 / HBM): same code, flat addresses
   double* sm = w.scratch ? w.scratch + (size_t)blockIdx.x * w.scratch_stride : sm_lds;
   __shared__ double red[32];
-  __shared__ double s_Gp[NNQP_PMAX * (NNQP_PMAX + 1) / 2];
+  __shared__ double s_Gp[NNQP_GP_DOUBLES];
   __shared__ double s_sv[NNQP_PMAX], s_tmp[NNQP_PMAX];
   __shared__ int s_pl[NNQP_PMAX];
   __shared__ int s_stop, s_ov;
   const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
   const int n = w.n, m = w.m, R = w.R[b];
-  double* u = sm;            // n
-  double* v = u + n;         // m
-  double* h = v + m;         // n
-  double* g = h + n;         // n
-  double* u0 = g + n;        // n  unconstrained-in-rows point for the current theta
-  double* cvec = u0 + n;     // Rmax
-  double* mu = cvec + w.Rmax;  // Rmax
+  const Altmin1Layout L = altmin1_layout(n, m, w.Rmax);
+  double *u = sm, *v = sm + L.v, *h = sm + L.h, *g = sm + L.g;      // n, m, n, n
+  double* u0 = sm + L.u0;    // n  unconstrained-in-rows point for the current theta
+  double *cvec = sm + L.cvec, *mu = sm + L.mu;      // Rmax each
   double* G = w.G + (size_t)b * w.Rmax * w.Rmax;
   double* objs = w.objectives + (size_t)b * w.max_iters;
   for (int i = tid; i < n; i += T) u[i] = w.U0[(size_t)b * n + i];
@@ -226,7 +223,7 @@ __global__ void __launch_bounds__(256) k_altmin_k(AltminWS w) {
   extern __shared__ double sm_lds[];
   double* sm = w.scratch ? w.scratch + (size_t)blockIdx.x * w.scratch_stride : sm_lds;
   __shared__ double red[32];
-  __shared__ double s_Gp[NNQP_PMAX * (NNQP_PMAX + 1) / 2];
+  __shared__ double s_Gp[NNQP_GP_DOUBLES];
   __shared__ double s_sv[NNQP_PMAX], s_tmp[NNQP_PMAX];
   __shared__ int s_pl[NNQP_PMAX];
   __shared__ double s_th[AK_QMAX], s_th2[AK_QMAX], s_q[AK_QMAX], s_qt[AK_QMAX], s_W[AK_QMAX * AK_KMAX], s_rad[AK_QMAX];
@@ -234,15 +231,13 @@ __global__ void __launch_bounds__(256) k_altmin_k(AltminWS w) {
   __shared__ int s_act[AK_QMAX], s_nact, s_flag, s_stop, s_ov;
   const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
   const int n = w.n, m = w.m, k = w.k, kk = k * k, mq = k * k, R = w.R[b];
+  const AltminKLayout L = altmink_layout(n, m, k, w.Rmax);
   double* u = sm;                 // n*k, row i at u + i*k  (accepted iterate)
-  double* ut = u + n * k;         // candidate of the last evaluation
-  double* u0 = ut + n * k;
-  double* g = u0 + n * k;
-  double* H = g + n * k;          // n*k*k
-  double* Hinv = H + n * kk;
-  double* v = Hinv + n * kk;      // k*m, column j at v + j*k
-  double* cvec = v + k * m;
-  double* mu = cvec + w.Rmax;
+  double* ut = sm + L.ut;         // candidate of the last evaluation
+  double *u0 = sm + L.u0, *g = sm + L.g;
+  double *H = sm + L.H, *Hinv = sm + L.Hinv;      // n*k*k each
+  double* v = sm + L.v;           // k*m, column j at v + j*k
+  double *cvec = sm + L.cvec, *mu = sm + L.mu;
   double* G = w.G + (size_t)b * w.Rmax * w.Rmax;
   double* objs = w.objectives + (size_t)b * w.max_iters;
   for (int e = tid; e < n * k; e += T) { const int i = e % n, a = e / n; u[i * k + a] = w.U0[(size_t)b * n * k + e]; }   // input is column-major n x k
@@ -564,14 +559,9 @@ __global__ void __launch_bounds__(256) k_altmin_k(AltminWS w) {
   }
 }
 
-extern "C" void omc_launch_altmin_k(const void* ws, size_t lds_bytes, hipStream_t s) {
-  const AltminWS* w = (const AltminWS*)ws;
-  hipLaunchKernelGGL(k_altmin_k, dim3(w->B), dim3(256), lds_bytes, s, *w);
-}
-
-extern "C" void omc_launch_altmin(const void* ws, size_t lds_bytes, hipStream_t s) {
-  const AltminWS* w = (const AltminWS*)ws;
-  hipLaunchKernelGGL(k_altmin, dim3(w->B), dim3(256), lds_bytes, s, *w);
+extern "C" void omc_launch_altmin(const AltminWS* w, hipStream_t s) {      // rank-1 or rank-k kernel, launch bytes from the descriptor (altmin_plan)
+  if (w->k == 1) hipLaunchKernelGGL(k_altmin, dim3(w->B), dim3(256), w->lds_bytes, s, *w);
+  else hipLaunchKernelGGL(k_altmin_k, dim3(w->B), dim3(256), w->lds_bytes, s, *w);
 }
 extern "C" int omc_altmin_set_lds(void) {
   // k_altmin_k holds ~20 KB of static LDS (Newton scratch, NNQP): its dynamic budget is 128 KB

@@ -142,11 +142,9 @@ struct omc_instance {
   DevBuf bslotlist, bgap, bvotes, blamDX, bXsC, bsubSC, bsubIC;
   DevBuf bsubz, bscal, bbx, bint, bcp, bcone, bglob, bXout, bThout, bXin, bMbuf, bVrow, bXs, bsubS, bsubI;
   long long sub_tot[8] = {0};
-  int ws_lpp = 0, ws_use_lds = 0; size_t ws_lds = 0;
   OmcWS ws{};
   omc_relax_params params{};
   bool staged = false;
-  int cone_use_lds = 0, glob_use_lds = 0, small_use_lds = 0; size_t cone_lds = 0, glob_lds = 0, small_lds = 0;
   double last_solve_seconds = 0; long long total_sweeps = 0; int last_iters_total = 0;
   std::thread worker; std::atomic<int> worker_running{0}, nodes_done{0}; int worker_rc = 0; std::string worker_err;
   // appending nodes to a staged / running batch (omc_relax_reserve, omc_relax_append): descriptor and output arrays are sized for node_cap nodes,
@@ -164,7 +162,7 @@ struct omc_instance {
   // Shor-mode relaxation (omc_relax_stage_shor): index structures of the distinct lists, explicit X / W / Theta state, view of the workspace
   // through which the base eigen-kernels project the order-(n+m) cone
   bool shor_req = false, shor_on = false, shor_keep_V = false, shor_via_base = false; std::vector<int> shor_slackrow; DevBuf soV; double shor_rho = 0.05, shor_r4 = 0.0, shor_r5 = 2.0;      // r4 = 0: automatic per list
-  ShWS sh{}; OmcWS wbig{}; int big_lpp = 0, big_use_lds = 0, big_cone_lds_ok = 0; size_t big_lds = 0, big_cone_lds = 0;
+  ShWS sh{}; OmcWS wbig{};
   DevBuf sgInts, sgBytes, sgGroups, sgNodeGroup, sAh, sX, sW, sTh, sV1, sV2, sV3, sD0, sP0, sMbufB, sVrowB, sTq, sPq, sNq, sD5x, sD5t, snu5, sP5x,
       scolpart, sminpart, sminpart2, sfroB, svvB, se1, se2, soX, soW, soTh, sbigscr, sXsB, ssubSB, ssubIB;
   long long big_sub_tot[8] = {0};
@@ -496,36 +494,12 @@ static int put_descriptors(const OmcWS& w, const NodePack& pk, int B, size_t row
   return 0;
 }
 
-// Geometry of the warm-started eigen-kernel (k_cone_ws) at order N: lanes per pair so that 512 threads cover the N/2 pairs, rows padded to
-// lpp*rpl (<= 20 rows per lane).  G lives in LDS when it fits, else in a per-node global scratch (L2 resident) of `scratch` bytes with 16 lanes
-// per pair (a wave per pair at orders 513 .. 1024).  lpp = 0: more than 32 rows per lane, beyond the kernel (WS_JROWS).
-struct WsGeometry { int lpp, ldw; size_t lds; bool use_lds; size_t scratch; };
-static WsGeometry ws_geometry(int N) {
-  const int Np2 = (N + 1) & ~1;
-  auto bytes = [Np2](int ld) { return ((size_t)Np2 * ld + 3 * Np2) * 8 + (size_t)(Np2 + 2) * 4 + 64; };
-  int lpp = 16; while (lpp > 4 && lpp * (Np2 / 2) > 512) lpp >>= 1;
-  int rpl = (((N + lpp - 1) / lpp) + 1) & ~1, Nrp = rpl * lpp;
-  int ldw = Nrp + ((16 - (Nrp & 31)) & 31);                 // 16 (mod 32): neighbouring columns start 32 LDS banks apart
-  if (bytes(ldw) > OMC_MAX_DYN_LDS) ldw = Nrp + 2;          // does not fit: plain padding
-  WsGeometry g{0, ldw, bytes(ldw), false, 0};
-  g.use_lds = g.lds <= OMC_MAX_DYN_LDS;
-  if (!g.use_lds) {
-    lpp = 16; rpl = (((N + 15) / 16) + 1) & ~1; Nrp = rpl * 16;
-    if (rpl > 32 && N <= 1024) { lpp = 64; rpl = (((N + 63) / 64) + 1) & ~1; Nrp = rpl * 64; }
-    g.ldw = Nrp + 2; g.scratch = bytes(g.ldw);
-  }
-  g.lpp = rpl <= 32 ? lpp : 0;
-  return g;
-}
-
 // fixed parameters of the eigen-kernels and the column kernel (OmcWS fields)
-static constexpr double JACOBI_TAU = 0.0;      // rotation threshold of the cold Jacobi sweeps (0: the kernel's 1e-10)
-static constexpr int MAX_SWEEPS = 30;          // sweep cap of the cold Jacobi kernel
+static constexpr int MAX_SWEEPS = 30;          // sweep cap of the warm-started Jacobi kernel (k_cone_ws)
 static constexpr int CP_SERIES = 6;            // Neumann-series order of k_colprox_pair's finish
 static constexpr int CP_MAXPASS = 60;          // cap on the secular passes of k_colprox_pair
 static constexpr int SUB_GUARD = 2;            // Ritz values of the tracked block that must stay negative
 static constexpr int SUB_CHUNK = 3;            // power steps per chunk of k_cone_sub
-static constexpr int SUB_LAZY = 1;             // orthonormalise once per chunk instead of after every step
 static constexpr double SUB_TOL = 1e-10;       // residual floor of k_cone_sub
 static constexpr double SUB_ADAPT = 1e-3;      // residual target of k_cone_sub relative to the last dual residual
 
@@ -572,9 +546,9 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   h->Btot = B; h->Btot_live.store(B); h->node_cap = B + extra_nodes; h->staged_cut_type = cut_type; { std::lock_guard<std::mutex> lk(h->append_mu); h->append_closed = false; }
   { std::lock_guard<std::mutex> lk(h->done_mu); h->done_q.clear(); h->done_read = 0; }
   h->hold.store(0);
-  w.b0 = 0; w.nB = S;
+  w.nB = S;
   w.B = S; w.Btot = B; w.max_iters = P.max_iters; w.n = n; w.m = m; w.k = k; w.nnz = h->nnz; w.Rmax = Rmax; w.Lmax = std::max(Lmax, 1); w.rmax = rmax;
-  w.jacobi_tau = JACOBI_TAU; w.max_sweeps = MAX_SWEEPS;
+  w.max_sweeps = MAX_SWEEPS;
   w.breakpoints = P.breakpoints; w.stall_checks = P.stall_checks > 0 ? P.stall_checks : 1000000;
   w.gamma = h->gamma; w.sumA2 = h->sumA2;
   {
@@ -652,7 +626,7 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
     w.V3 = h->bsubS.as<double>() + sB * 17; w.v3valid = h->bsubI.as<int>() + 12 * sB;
     w.ws_first = h->bsubI.as<int>() + 13 * sB; w.ws_phase = 0;
     w.w1_fac = nullptr;     // factored W1: decided below, once k_global's variant is known
-    w.sub_guard = SUB_GUARD; w.sub_qmax = h->tun.sub_qmax; w.sub_chunk = SUB_CHUNK; w.sub_lazy = SUB_LAZY;
+    w.sub_guard = SUB_GUARD; w.sub_qmax = h->tun.sub_qmax; w.sub_chunk = SUB_CHUNK;
     w.sub_tol = SUB_TOL; w.sub_adapt = SUB_ADAPT; w.sub_debug = h->tun.sub_debug;
     w.sub_enable = 0;     // decided below, once the cone kernel variant is known
     ENS(h->bXsC, sB * w.np16 * 16 * 8); ENS(h->bsubSC, sB * 18 * 8); ENS(h->bsubIC, sB * 3 * sizeof(int));
@@ -744,58 +718,22 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   w.Qb = h->bQb.as<double>(); w.rr = h->brr.as<int>(); w.R = h->bR.as<int>(); w.rkind = h->brkind.as<int>(); w.rcut = h->brcut.as<int>();
   w.rbi = h->brbi.as<int>(); w.rbj = h->brbj.as<int>(); w.rcoef = h->brcoef.as<double>(); w.rrhs = h->brrhs.as<double>(); w.cutx = h->bcutx.as<double>();
   if ((rc_ = put_descriptors(w, pk, B, sN, 0, L, cut_x, h->stream))) return rc_;
-  // LDS / scratch decisions
-  {
-    const int c_lds = std::min(h->cmax, 64);
-    w.cp_lds_c = c_lds;
-    w.cp_keepB = c_lds <= 40 ? 1 : 0;
-    w.cp_lds_doubles = w.cp_keepB ? c_lds * c_lds + 5 * c_lds + 8 : c_lds * (c_lds + 1) / 2 + 4 * c_lds + 8;
-    if ((size_t)4 * w.cp_lds_doubles * 8 > OMC_MAX_DYN_LDS) { w.cp_lds_c = 48; w.cp_lds_doubles = 48 * 48 + 5 * 48 + 8; w.cp_keepB = 1; }
-    if (h->cmax > w.cp_lds_c) {
-      w.cp_scratch_stride = (size_t)h->cmax * h->cmax + 5 * (size_t)h->cmax + 8;
-      ENS(h->bcp, sB * m * w.cp_scratch_stride * 8);
-      w.cp_scratch = h->bcp.as<double>();
-    }
-    auto cone_bytes = [](int Nn) { int Np = (Nn + 1) & ~1; int ld = Np | 1; return ((size_t)Np * ld + 2 * Np) * 8 + (size_t)Np * 4 + 16; };
-    h->cone_lds = cone_bytes(n);
-    h->cone_use_lds = h->cone_lds <= OMC_MAX_DYN_LDS;
-    {
-      const WsGeometry g = ws_geometry(n);
-      h->ws_lpp = g.lpp; h->ws_lds = g.lds; h->ws_use_lds = g.use_lds; w.ws_ld = g.ldw;
-      if (g.scratch) {
-        w.cone_scratch_stride = g.scratch / 8 + 8;
-        ENS(h->bcone, sB * w.cone_scratch_stride * 8);
-        w.cone_scratch = h->bcone.as<double>();
-      }
-      // subspace tracking needs the warm-started kernel as its seed / fall-back and at least 3 x 16 rows
-      w.sub_enable = (h->ws_lpp && n >= 48 && omc_cone_sub_lds(w.np16) <= OMC_MAX_DYN_LDS && !h->tun.no_subspace) ? 1 : 0;
-      w.sub_zscratch = nullptr;
-      if (w.sub_enable && w.np16 > 512) { ENS(h->bsubz, sB * 16 * (size_t)(w.np16 + 2) * 8); w.sub_zscratch = h->bsubz.as<double>(); }
-      w.cert_enable = (w.sub_enable && w.np16 > 512) ? 1 : 0;      // large orders: the certificate eigenvalues by the tracked block too (rigorous confirmation before anything is reported)
-      w.sep_done = w.sub_enable ? h->bsubIC.as<int>() + 2 * sB : nullptr;
-    }
-    h->glob_lds = ((size_t)n * (n + 1) / 2 + (size_t)n * k + (size_t)rmax * k + 3 * Rmax + 8 + 16 * (size_t)n) * 8 + 16;   // packed lower triangle of the target; 16 = GL_XS staged cut vectors
-    h->glob_use_lds = (h->glob_lds + 20 * 1024 <= OMC_MAX_DYN_LDS) && !h->tun.global_nolds;   // + the static LDS of k_global (NNQP scratch for NNQP_PMAX = 64 passive rows)
-    if (!h->glob_use_lds) {
-      w.glob_scratch_stride = h->glob_lds / 8 + 8;
-      ENS(h->bglob, sB * w.glob_scratch_stride * 8);
-      w.glob_scratch = h->bglob.as<double>();
-    }
-    // factored W1 (OmcWS::w1_fac): k_global stages the accepted Ritz vectors of a slot (at most 16 n doubles) in its NNQP scratch, which
-    // holds NNQP_PMAX (NNQP_PMAX + 1) / 2 doubles.  Off in Shor mode (its W1 views are other arrays) and with OMC_DENSE_PROJ=1.
-    if (!shor && w.sub_enable && h->glob_use_lds && (size_t)16 * n <= (size_t)NNQP_PMAX * (NNQP_PMAX + 1) / 2 && !h->tun.dense_proj)
-      w.w1_fac = h->bsubI.as<int>() + 14 * sB;
-    {
-      const int N3 = rmax + k; const int Npm = (N3 + 1) & ~1, ldm = Npm | 1;
-      h->small_lds = ((size_t)n * rmax + (size_t)N3 * N3 + (size_t)Npm * ldm + 2 * Npm + (size_t)rmax * k + 8 + (size_t)n * 16 + 4) * 8 + (size_t)(Npm + 2) * 4 + 16;   // + Q' staging (n x 16)
-      h->small_use_lds = h->small_lds + 1024 <= OMC_MAX_DYN_LDS;
-      if (!h->small_use_lds) {
-        w.small_scratch_stride = h->small_lds / 8 + 8;
-        ENS(h->bsmall, sB * w.small_scratch_stride * 8);
-        w.small_scratch = h->bsmall.as<double>();
-      }
-    }
-  }
+  // LDS / scratch decisions: one planner (omc_layout.h), the slabs allocated from the strides it reports
+  w.geo = omc_plan_geometry(n, w.np16, k, rmax, Rmax, h->cmax, h->tun.global_nolds);
+  if (w.geo.cp_scratch_stride) { ENS(h->bcp, sB * m * w.geo.cp_scratch_stride * 8); w.cp_scratch = h->bcp.as<double>(); }
+  if (w.geo.ws.slab_stride) { ENS(h->bcone, sB * w.geo.ws.slab_stride * 8); w.cone_scratch = h->bcone.as<double>(); }
+  if (w.geo.glob.slab_stride) { ENS(h->bglob, sB * w.geo.glob.slab_stride * 8); w.glob_scratch = h->bglob.as<double>(); }
+  if (w.geo.small.slab_stride) { ENS(h->bsmall, sB * w.geo.small.slab_stride * 8); w.small_scratch = h->bsmall.as<double>(); }
+  // subspace tracking needs the warm-started kernel as its seed / fall-back and at least 3 x 16 rows
+  w.sub_enable = (w.geo.ws_lpp && n >= 48 && w.geo.sub_lds <= OMC_MAX_DYN_LDS && !h->tun.no_subspace) ? 1 : 0;
+  w.sub_zscratch = nullptr;
+  if (w.sub_enable && w.np16 > 512) { ENS(h->bsubz, sB * 16 * (size_t)(w.np16 + 2) * 8); w.sub_zscratch = h->bsubz.as<double>(); }
+  w.cert_enable = (w.sub_enable && w.np16 > 512) ? 1 : 0;      // large orders: the certificate eigenvalues by the tracked block too (rigorous confirmation before anything is reported)
+  w.sep_done = w.sub_enable ? h->bsubIC.as<int>() + 2 * sB : nullptr;
+  // factored W1 (OmcWS::w1_fac): k_global stages the accepted Ritz vectors of a slot in its NNQP scratch (LDS variant only; glob_w1_fits).
+  // Off in Shor mode (its W1 views are other arrays) and with OMC_DENSE_PROJ=1.
+  if (!shor && w.sub_enable && w.geo.glob.use_lds && glob_w1_fits(n) && !h->tun.dense_proj)
+    w.w1_fac = h->bsubI.as<int>() + 14 * sB;
   HIPCHK(hipMemsetAsync(w.sweeps, 0, sizeof(int) * S, h->stream));
   HIPCHK(hipMemsetAsync(w.stamps, 0, (32 + 8 * (size_t)S) * 8, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -944,7 +882,7 @@ int omc_relax_solve(omc_instance* h) {
   // The full eigen-kernel runs the slots that have no tracked block (or are backing off) -- a handful per launch, each a long single-workgroup
   // job, known before the iteration starts (ws_first) -- on a stream of its own beside k_cone_sub; what k_cone_sub then could not do (a failed
   // call, ~1 in 30 000) is a second, almost empty launch behind both.  One launch after k_cone_sub made every iteration wait for the sum.
-  const bool split = multi && !tun.no_ws_split && w.sub_enable && h->ws_lpp && w.ws_first;
+  const bool split = multi && !tun.no_ws_split && w.sub_enable && w.geo.ws_lpp && w.ws_first;
   auto body = [&](const OmcWS& wg, bool timed, bool with_aa, bool capturing) -> int {
     hipEvent_t* const ev = capturing ? h->gevc : h->gev;
     if (multi) {
@@ -955,28 +893,28 @@ int omc_relax_solve(omc_instance* h) {
     if (shor) {
       // Shor mode: clip on the main stream, the order-(n+m) cone on the second, small cone + order-5 blocks on the third; then the
       // global step: rows / Y (base kernel), columns (X, W, Theta, duals of the big cone), duals of the order-5 blocks, per-slot sums
-      OmcWS wb = h->wbig; wb.b0 = wg.b0; wb.nB = wg.nB; wb.slot_list = wg.slot_list;
+      OmcWS wb = h->wbig; wb.nB = wg.nB; wb.slot_list = wg.slot_list;
       if (w.sub_enable) MAYBE_TIMED(sm, OMC_KERNEL_CONESUB, gact, omc_launch_cone_sub(&wg, sm));
       if (wb.sub_enable) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, 0, omc_launch_cone_sub(&wb, sb));
-      if (h->big_lpp) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone_ws(&wb, h->big_lpp, h->big_use_lds, h->big_lds, sb));
-      else MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone(&wb, CONE_BIG, h->big_cone_lds_ok, h->big_cone_lds, sb));
-      if (h->ws_lpp) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, h->ws_lpp, h->ws_use_lds, h->ws_lds, sm));
-      else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, h->cone_use_lds, h->cone_lds, sm));
-      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, h->small_use_lds, h->small_lds, sc));
+      if (wb.geo.ws_lpp) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone_ws(&wb, sb));
+      else MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone(&wb, CONE_BIG, sb));
+      if (w.geo.ws_lpp) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
+      else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, sm));
+      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
       MAYBE_TIMED(sc, OMC_KERNEL_SHOR_MINORS, gact, { omc_shor_launch_minor_pre(&sw, sc); omc_shor_launch_vkeys(&sw, sc); });
       if (multi) {
         HIPCHK(hipEventRecord(ev[1], sb)); HIPCHK(hipEventRecord(ev[2], sc));
         HIPCHK(hipStreamWaitEvent(sm, ev[1], 0)); HIPCHK(hipStreamWaitEvent(sm, ev[2], 0));
       }
-      MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, h->glob_use_lds, h->glob_lds, sm));
+      MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, sm));
       MAYBE_TIMED(sm, OMC_KERNEL_SHOR_COLS, gact, omc_shor_launch_cols(&sw, sm));
       MAYBE_TIMED(sm, OMC_KERNEL_SHOR_MINORS, gact, { omc_shor_launch_minor_post(&sw, sm); omc_shor_launch_reduce(&sw, sm); });
       return 0;
     }
     if (split) {      // on the small-cone stream, behind k_small (a fifth stream would share a hardware queue with one of the other four: measured, k_small then ran behind it)
-      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, h->small_use_lds, h->small_lds, sc));
+      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
       OmcWS wA = wg; wA.ws_phase = 1;
-      MAYBE_TIMED(sc, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wA, h->ws_lpp, h->ws_use_lds, h->ws_lds, sc));
+      MAYBE_TIMED(sc, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wA, sc));
       HIPCHK(hipEventRecord(ev[4], sc));
     }
     // the cone workgroups are few (two per CU, long serial phases) and the column waves many: the cone kernel goes first so that its
@@ -986,16 +924,16 @@ int omc_relax_solve(omc_instance* h) {
     if (split) {
       HIPCHK(hipStreamWaitEvent(sm, ev[4], 0));
       OmcWS wB = wg; wB.ws_phase = 2;
-      MAYBE_TIMED(sm, OMC_KERNEL_CONE, 0, omc_launch_cone_ws(&wB, h->ws_lpp, h->ws_use_lds, h->ws_lds, sm));
+      MAYBE_TIMED(sm, OMC_KERNEL_CONE, 0, omc_launch_cone_ws(&wB, sm));
     }
-    else if (h->ws_lpp) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, h->ws_lpp, h->ws_use_lds, h->ws_lds, sm));
-    else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, h->cone_use_lds, h->cone_lds, sm));
-    if (!split) MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, h->small_use_lds, h->small_lds, sc));
+    else if (w.geo.ws_lpp) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
+    else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, sm));
+    if (!split) MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
     if (multi) {
       HIPCHK(hipEventRecord(ev[1], sb)); HIPCHK(hipEventRecord(ev[2], sc));
       HIPCHK(hipStreamWaitEvent(sm, ev[1], 0)); HIPCHK(hipStreamWaitEvent(sm, ev[2], 0));
     }
-    MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, h->glob_use_lds, h->glob_lds, sm));
+    MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, sm));
     if (with_aa) MAYBE_TIMED(sm, OMC_KERNEL_ACCEL, gact, omc_launch_aa(&wg, sm));
     return 0;
   };
@@ -1035,7 +973,7 @@ int omc_relax_solve(omc_instance* h) {
     const bool sampled = tun.timing_stride > 0 && (it % tun.timing_stride) == 0;
     const bool use_graph = multi && nlist <= graph_max && !tun.no_graph && !(sampled && tun.timing_stride > 1);
     if (gact > 0) {
-      OmcWS wg = w; wg.slot_list = h->bslotlist.as<int>(); wg.b0 = 0; wg.nB = nlist;
+      OmcWS wg = w; wg.slot_list = h->bslotlist.as<int>(); wg.nB = nlist;
       if (multi && wait_main) HIPCHK(hipStreamWaitEvent(sm, h->ev_main, 0));
       if (use_graph) {
         if (gexec_n != nlist) {      // (re)capture: one graph without and one with the acceleration kernel at its end
@@ -1075,11 +1013,11 @@ int omc_relax_solve(omc_instance* h) {
       if (w.cert_enable) {        // estimate by the tracked block, decisions, rigorous evaluation of the slots that are about to finish
         omc_launch_cert_sub(&w, s);
         omc_launch_check_final(&w, timed_out ? OMC_ST_TIME : 0, 0, s);
-        OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, h->ws_lpp, h->ws_use_lds, h->ws_lds, s);
+        OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, s);
         omc_launch_check_final(&w, timed_out ? OMC_ST_TIME : 0, 1, s);
       } else {
-        if (h->ws_lpp) { OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, h->ws_lpp, h->ws_use_lds, h->ws_lds, s); }
-        else omc_launch_cone(&w, CONE_EVALS, h->cone_use_lds, h->cone_lds, s);
+        if (w.geo.ws_lpp) { OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, s); }
+        else omc_launch_cone(&w, CONE_EVALS, s);
         omc_launch_check_final(&w, timed_out ? OMC_ST_TIME : 0, 2, s);      // per-slot iteration cap is applied on the device
       }
       if (w.bump_max > 0) { if (shor) omc_shor_launch_rescale(&sw, s); omc_launch_rho_rescale(&w, s); }
@@ -1123,9 +1061,9 @@ int omc_relax_solve(omc_instance* h) {
       int rc = push_flags(init, fin); if (rc) return rc;
       TIMED(OMC_KERNEL_HARVEST, nfin, {
         if (w.save_to) omc_launch_state_save(&w, s);                              // warm-start pool: before the recovery overwrites the iterate U = Q Vt
-        omc_launch_small(&w, SMALL_RECOVER, h->small_use_lds, h->small_lds, s);   // a U with U U' <= Y and the same Q'U
+        omc_launch_small(&w, SMALL_RECOVER, s);   // a U with U U' <= Y and the same Q'U
         if (w.sep_done) omc_launch_sep_sub(&w, s);                                // separation vector from the tracked block where there is one
-        omc_launch_cone(&w, CONE_SEP, h->cone_use_lds, h->cone_lds, s);           // separation vector (OMC.jl:2466-2477)
+        omc_launch_cone(&w, CONE_SEP, s);           // separation vector (OMC.jl:2466-2477)
         omc_launch_harvest(&w, s);
         if (shor) omc_shor_launch_harvest(&sw, s);
       });
@@ -1594,25 +1532,13 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   wb = w;
   wb.n = N; wb.np16 = NPb; wb.Mbuf = sh.MbufB; wb.Vrow = sh.VrowB; wb.vvalid = sh.vvalidB; wb.fro2 = sh.fro2B; wb.W1 = sh.P0;
   wb.sub_enable = 0; wb.cert_enable = 0; wb.ws_mode = 0; wb.clip_hi = 1e300; wb.sub_debug = 0; wb.ws_first = nullptr; wb.ws_phase = 0;
-  {
-    const WsGeometry g = ws_geometry(N);
-    h->big_lpp = g.lpp; h->big_lds = g.lds; h->big_use_lds = g.use_lds; wb.ws_ld = g.ldw;
-    size_t need = g.scratch;
-    // generic cold kernel (orders beyond the warm-started one): Np x (Np | 1) matrix + 2 Np doubles + Np ints
-    const int Np2 = (N + 1) & ~1, ldc = Np2 | 1;
-    h->big_cone_lds = ((size_t)Np2 * ldc + 2 * Np2) * 8 + (size_t)Np2 * 4 + 16;
-    h->big_cone_lds_ok = h->big_cone_lds <= OMC_MAX_DYN_LDS;
-    if (!h->big_lpp && !h->big_cone_lds_ok) need = std::max(need, h->big_cone_lds);
-    if (need) {
-      wb.cone_scratch_stride = need / 8 + 8;
-      ENS(h->sbigscr, sB * wb.cone_scratch_stride * 8);
-      wb.cone_scratch = h->sbigscr.as<double>();
-    }
-  }
+  // the view's own geometry (only the eigen-kernels are launched through it)
+  wb.geo = omc_plan_geometry(N, NPb, wb.k, wb.rmax, wb.Rmax, h->cmax, h->tun.global_nolds);
+  if (wb.geo.ws.slab_stride) { ENS(h->sbigscr, sB * wb.geo.ws.slab_stride * 8); wb.cone_scratch = h->sbigscr.as<double>(); }
   // the big cone's input has a handful of positive eigenvalues once the iterate has settled (measured: 2 - 5 of n + m): the tracked-subspace
   // kernel of the base engine follows them; the warm-started full kernel seeds the block and is the fall-back
   wb.trM = sh.trB;
-  if (h->big_lpp && N >= 48 && omc_cone_sub_lds(NPb) <= OMC_MAX_DYN_LDS && !h->tun.no_subspace && !h->tun.shor_no_subspace) {
+  if (wb.geo.ws_lpp && N >= 48 && wb.geo.sub_lds <= OMC_MAX_DYN_LDS && !h->tun.no_subspace && !h->tun.shor_no_subspace) {
     ENS(h->sXsB, sB * NPb * 16 * 8); ENS(h->ssubSB, sB * 16 * 8); ENS(h->ssubIB, sB * 12 * sizeof(int));
     HIPCHK(hipMemsetAsync(h->sXsB.p, 0, sB * NPb * 16 * 8, s));
     HIPCHK(hipMemsetAsync(h->ssubSB.p, 0, sB * 16 * 8, s));
@@ -1718,7 +1644,7 @@ int omc_separation_batch(omc_instance* h, int B, int breakpoints, const double* 
   const size_t n = h->n, k = h->k;
   HIPCHK(hipMemcpyAsync(w.Y, Y, 8 * (size_t)B * n * n, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(w.U, U, 8 * (size_t)B * n * k, hipMemcpyHostToDevice, h->stream));
-  omc_launch_cone(&w, CONE_SEP, h->cone_use_lds, h->cone_lds, h->stream);
+  omc_launch_cone(&w, CONE_SEP, h->stream);
   std::vector<double> ev(2 * (size_t)B);
   HIPCHK(hipMemcpyAsync(ev.data(), w.lmin, 16 * (size_t)B, hipMemcpyDeviceToHost, h->stream));
   if (x) HIPCHK(hipMemcpyAsync(x, w.bx, 8 * (size_t)B * n, hipMemcpyDeviceToHost, h->stream));
@@ -1741,7 +1667,7 @@ int omc_round_Y_batch(omc_instance* h, int B, const double* Y, double* U_rounded
   const OmcWS& w = h->ws;
   const size_t n = h->n, k = h->k;
   HIPCHK(hipMemcpyAsync(w.Y, Y, 8 * (size_t)B * n * n, hipMemcpyHostToDevice, h->stream));
-  omc_launch_cone(&w, CONE_TOPK, h->cone_use_lds, h->cone_lds, h->stream);
+  omc_launch_cone(&w, CONE_TOPK, h->stream);
   HIPCHK(hipMemcpyAsync(U_rounded, w.U, 8 * (size_t)B * n * k, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
@@ -1764,7 +1690,7 @@ int omc_left_singular_batch(omc_instance* h, int B, const double* X, double* U_o
   ENS(h->bXin, (size_t)B * n * m * 8);
   HIPCHK(hipMemcpyAsync(h->bXin.p, X, 8 * (size_t)B * n * m, hipMemcpyHostToDevice, h->stream));
   omc_launch_gram_XXt(&w, h->bXin.as<double>(), B, h->stream);
-  omc_launch_cone(&w, CONE_TOPK, h->cone_use_lds, h->cone_lds, h->stream);
+  omc_launch_cone(&w, CONE_TOPK, h->stream);
   HIPCHK(hipMemcpyAsync(U_out, w.U, 8 * (size_t)B * n * k, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
@@ -1857,18 +1783,11 @@ int omc_altmin_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q
   w.rcoef = h->arcoef.as<double>(); w.rrhs = h->arrhs.as<double>(); w.cutx = h->acutx.as<double>();
   w.U0 = h->aU0.as<double>(); w.U = h->aU.as<double>(); w.V = h->aV.as<double>(); w.objectives = h->aobj.as<double>();
   w.converged = h->aint.as<int>(); w.n_iters = h->aint.as<int>() + B; w.G = h->aG.as<double>(); w.mobj = h->amobj.as<double>();
-  const size_t lds = (k == 1) ? ((size_t)4 * n + m + 2 * Rmax + 8) * 8
-                              : ((size_t)4 * n * k + (size_t)2 * n * k * k + (size_t)k * m + 2 * Rmax + 8) * 8;
-  w.scratch = nullptr; w.scratch_stride = 0;
-  size_t lds_launch = lds;
-  if (lds + 8 * 1024 > ((k == 1) ? (size_t)OMC_MAX_DYN_LDS - 8 * 1024 : (size_t)128 * 1024) || h->tun.altmin_nolds) {
-    // the problem does not fit the LDS (config 5: 1000 x 1000, k = 2 needs 144 KB): the same kernel runs on a per-problem global slab
-    w.scratch_stride = lds / 8 + 8;
-    ENS(h->aG2, (size_t)B * w.scratch_stride * 8);
-    w.scratch = h->aG2.as<double>();
-    lds_launch = 0;
-  }
-  if (k == 1) omc_launch_altmin(&w, lds_launch, s); else omc_launch_altmin_k(&w, lds_launch, s);
+  // a problem that does not fit the LDS (config 5: 1000 x 1000, k = 2 needs 144 KB) runs the same kernel on a per-problem global slab
+  const KernelPlan ap = altmin_plan(n, m, k, Rmax, h->tun.altmin_nolds);
+  w.scratch = nullptr; w.scratch_stride = ap.slab_stride; w.lds_bytes = ap.lds_bytes;
+  if (ap.slab_stride) { ENS(h->aG2, (size_t)B * ap.slab_stride * 8); w.scratch = h->aG2.as<double>(); }
+  omc_launch_altmin(&w, s);
   HIPCHK(hipMemcpyAsync(U, w.U, 8 * sB * n * k, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(V, w.V, 8 * sB * m * k, hipMemcpyDeviceToHost, s));
   if (objectives) HIPCHK(hipMemcpyAsync(objectives, w.objectives, 8 * sB * max_iters, hipMemcpyDeviceToHost, s));
@@ -2144,7 +2063,7 @@ int omc_debug_diag(omc_instance* h, double* out /* 8 * slots */) {
 int omc_last_solver_info(omc_instance* h, double* info) {
   if (!h || !info) return fail(OMC_ERR_ARGUMENT, "NULL argument");
   info[0] = h->last_solve_seconds; info[1] = (double)h->total_sweeps; info[2] = h->ws.rho; info[3] = (double)h->ws.rmax;
-  info[4] = (double)h->cone_use_lds; info[5] = (double)h->glob_use_lds; info[6] = (double)h->small_use_lds; info[7] = (double)h->ws.Rmax;
+  info[4] = (double)h->ws.geo.cone.use_lds; info[5] = (double)h->ws.geo.glob.use_lds; info[6] = (double)h->ws.geo.small.use_lds; info[7] = (double)h->ws.Rmax;
   return 0;
 }
 

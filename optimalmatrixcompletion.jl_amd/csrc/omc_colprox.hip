@@ -181,7 +181,7 @@ __device__ __forceinline__ void colprox_sweep(const OmcWS& w, const int b, const
   // accepted when the first term left out is below 2e-15 of the first kept.  K = 3 (colprox_reg's second-order finish) when cp |d| ||z|| / ||y|| < 1e-5,
   // else K = 6, which carries steps up to cp |d| ||A^-1|| ~ 5e-3 -- the size s moves per ADMM iteration until late in a solve; with K = 3
   // alone the kernel averaged more than two inversions per column pair.  A step the series cannot carry is taken as before (s <- s + d, invert).
-  const int ser_max = (w.cp_series > 0) ? w.cp_series : 3;
+  const double ser_lim = (w.cp_series >= 6) ? 5e-3 : 1e-5;      // largest relative step the series carries (order 6 / order 3)
   int npass = 0; double dr_first = -1.0; int why = 0;      // diagnostics (OMC_SUB_DEBUG=4)
   for (int it = 0; it <= 60; ++it) {
     if (!__any(!fin)) break;
@@ -219,7 +219,7 @@ __device__ __forceinline__ void colprox_sweep(const OmcWS& w, const int b, const
             const double dr = (yy > 0.0) ? cp * fabs(d) * sqrt(zz / yy) : 1.0;
             if (dr_first < 0.0) { dr_first = dr; why = guarded ? 1 : 0; }
             if (fabs(d) <= 1e-13 * fmax(1.0, fabs(s))) { fin = true; yout = v[0]; }      // the current solve is the answer
-            else if (!guarded && dr < ((ser_max >= 6) ? 5e-3 : 1e-5)) { want_ser = true; dstep = d; big = dr >= 1e-5; }
+            else if (!guarded && dr < ser_lim) { want_ser = true; dstep = d; big = dr >= 1e-5; }
             else s = sn;
           }
         }

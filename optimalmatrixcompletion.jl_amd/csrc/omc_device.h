@@ -1,4 +1,5 @@
-// omc_device.h -- workspace descriptor shared by the kernels (omc_device.hip) and the host API (omc_api.cpp)
+// omc_device.h -- workspace descriptor shared by the kernels (omc_device.hip) and the host API (omc_api.cpp), and the launchers, which
+// take the kernel variant (LDS or slab, lanes per pair) and the launch bytes from the geometry the descriptor carries (w->geo)
 #ifndef OMC_DEVICE_H
 #define OMC_DEVICE_H
 #include <hip/hip_runtime.h>
@@ -22,14 +23,13 @@
 #define OMC_ST_TIME 2
 #define OMC_ST_INFEASIBLE 3
 
-#define NNQP_PMAX 64
-#define OMC_MAX_DYN_LDS (144 * 1024)
+#include "omc_layout.h"
 
 struct OmcWS {
   // sizes
   // B = number of SLOTS (state arrays, grid size); Btot = number of nodes of the staged batch (descriptor and output arrays).
   // node_of[b] = node currently relaxed in slot b.
-  int b0, nB;   // slot range [b0, b0 + nB) handled by a launch of the per-iteration kernels (the slots are split in groups that run on their own streams)
+  int nB;       // workgroups (slots) of a launch of the per-iteration kernels: the first nB entries of slot_list (every slot without a list)
   int B, Btot, n, m, k, nnz, Rmax, Lmax, breakpoints, rmax, stall_checks, np16, max_sweeps, max_iters;
   int *node_of, *init, *fin;   // B
   const int* slot_list;        // compact list of the slots that hold a node (rebuilt by the host at every check): the per-iteration kernels launch over it
@@ -38,7 +38,7 @@ struct OmcWS {
   const double* rho_node;      // Btot: initial penalty of each node
   double *oY, *oU, *oalphaX, *obx, *oobj, *olb, *olmin, *orho; int *ostatus, *oiters;   // per-node outputs
   // parameters
-  double gamma, rho, rho_f_ratio, relax, eps_gap, eps_feas, sumA2, jacobi_tau;   // rho: batch default (rho_b holds the per-node value)
+  double gamma, rho, rho_f_ratio, relax, eps_gap, eps_feas, sumA2;   // rho: batch default (rho_b holds the per-node value)
   double* rho_b;          // B: ADMM penalty of node b (bumped on the device)
   double* bfac;           // B: rescale factor decided at the last check (1 = none)
   int *nbump, *lastbump;  // B
@@ -76,15 +76,14 @@ struct OmcWS {
   int* vvalid;            // B: Vrow holds eigenvectors
   // the same triple for the certificate matrix Mchk (k_cone_ws with ws_mode = 1 returns the k smallest eigenvalues only)
   double *MbufC, *VrowC, *fro2c; int* vvalidC; int ws_mode;
-  int ws_ld;              // leading dimension of G in k_cone_ws (chosen on the host: 16 mod 32 when it fits)
   // tracked top-16 subspace of the cone input (k_cone_sub): once Y has settled, clip(M, 0, 1) = sum over the FEW positive eigenpairs
   // (config 2: 2 of 100), so only the dominant invariant subspace is followed from one ADMM iteration to the next
-  int sub_enable, sub_qmax, sub_chunk, sub_debug, sub_lazy; double sub_tol, sub_adapt;   // sub_lazy: orthonormalise once per chunk instead of after every power step
+  int sub_enable, sub_qmax, sub_chunk, sub_debug; double sub_tol, sub_adapt;   // the block is orthonormalised once per chunk of sub_chunk power steps
   double* sub_zscratch;   // B * 16 * (np16 + 2): Z block of k_cone_sub for orders beyond 512 (NULL below)
   double* Xs;             // B * np16 * 16: orthonormal Ritz basis (column-major, ld = np16, zero padded rows)
   double* sub_theta;      // B * 16: Ritz values of the last accepted call
   double* trM;            // B: trace of Mbuf (with fro2 it bounds the untracked part of the spectrum)
-  double* V3; int* v3valid;  // B * 256, B: eigenvectors of the last small-cone projection (order <= 16), warm start of the next one (NULL: cold every time)
+  double* V3; int* v3valid;  // B * 256, B: eigenvectors of the last small-cone projection (order <= 16), warm start of the next one
   int *sub_wait, *sub_nfail; // B: iterations left before the subspace is tried again after a failure ; failures so far (back-off)
   int *sub_on, *cone_done;   // B: slot follows the subspace ; this iteration's W1 has been written by k_cone_sub
   // the slots the full kernel must project this iteration are known before it starts (no block yet, or backing off): ws_first[b], written by
@@ -119,8 +118,8 @@ struct OmcWS {
   int *done, *status, *iters, *sweeps, *stall;
   int* rowov;             // B: 1 = the last row projection overflowed its passive set (NNQP_PMAX): the iterate may violate rows
   // scratch
-  double* cp_scratch;  size_t cp_scratch_stride;   // per wave (B*m waves) when a column is too large for LDS
-  int cp_lds_c; int cp_lds_doubles; int cp_keepB;   // cp_keepB = 0: dense columns, B is gathered again instead of kept in LDS
+  OmcGeom geo;           // LDS-or-slab decisions, launch bytes and slab strides of the kernels (omc_plan_geometry, omc_layout.h)
+  double* cp_scratch;    // per wave (B*m waves, geo.cp_scratch_stride) when a column is too large for LDS
   // k_colprox_pair: two columns per wave (32 lanes each, matrix rows in registers) for the column pairs (2p, 2p + 1) whose columns hold at
   // most 32 observed rows each; the other columns (cp_solo, cp_nsolo of them) keep the one-column-per-wave kernel
   int cp_pair; int cp_nsolo; const int* cp_solo;
@@ -130,9 +129,7 @@ struct OmcWS {
   int cp_series;             // Neumann-series order of k_colprox_pair's finish (6; 3 = the second-order finish of colprox_reg)
   int cp_maxpass;            // cap on the secular passes of k_colprox_pair (CP_MAXPASS = 60 in omc_api.cpp: the algorithm)
   int cp_xcd;                // 1: column-prox workgroups placed XCD-locally (xcd_block); 0 (OMC_COLPROX_NO_XCD): plain blockIdx.x
-  double* cone_scratch; size_t cone_scratch_stride; // per node when N is too large for LDS
-  double* glob_scratch; size_t glob_scratch_stride;
-  double* small_scratch; size_t small_scratch_stride;
+  double *cone_scratch, *glob_scratch, *small_scratch;   // per-slot slabs of the kernels whose block does not fit the LDS (strides in geo)
   double* chk_scratch;   // B*n*k
   double* stamps;        // 32 doubles (diagnostic builds)
   // Anderson acceleration (k_aa): per slot a ring of (aa_mem + 1) residuals f = T(z) - z and images g = T(z) of the state
@@ -150,12 +147,11 @@ extern "C" {
 #endif
 void omc_launch_setup(const OmcWS* w, hipStream_t s);
 void omc_launch_colprox(const OmcWS* w, int mode, hipStream_t s);
-void omc_launch_cone(const OmcWS* w, int mode, int use_lds, size_t lds_bytes, hipStream_t s);
-void omc_launch_global(const OmcWS* w, int use_lds, size_t lds_bytes, hipStream_t s);
-void omc_launch_small(const OmcWS* w, int mode, int use_lds, size_t lds_bytes, hipStream_t s);
-void omc_launch_cone_ws(const OmcWS* w, int lpp, int use_lds, size_t lds_bytes, hipStream_t s);
+void omc_launch_cone(const OmcWS* w, int mode, hipStream_t s);
+void omc_launch_global(const OmcWS* w, hipStream_t s);
+void omc_launch_small(const OmcWS* w, int mode, hipStream_t s);
+void omc_launch_cone_ws(const OmcWS* w, hipStream_t s);
 void omc_launch_cone_sub(const OmcWS* w, hipStream_t s);
-size_t omc_cone_sub_lds(int np16);
 void omc_launch_check_zero(const OmcWS* w, hipStream_t s);
 void omc_launch_check_build(const OmcWS* w, hipStream_t s);
 void omc_launch_check_final(const OmcWS* w, int last, int phase, hipStream_t s);

@@ -202,13 +202,9 @@ __global__ void k_setup(OmcWS w) {
 template <class PT>
 __device__ __forceinline__ void colprox_body(const OmcWS& w, int mode, int b, int j, int off, int c, int lane, PT base) {
   const int n = w.n;
-  const size_t tri = (size_t)c * (c + 1) / 2;
+  const CpBodyLayout L = cp_body_layout(c);
   auto Bm = base;
-  auto Lm = Bm + tri;
-  auto va = Lm + tri;
-  auto vy = va + c;
-  auto vz = vy + c;
-  auto vo = vz + c;
+  auto Lm = Bm + L.Lm, va = Bm + L.va, vy = Bm + L.vy, vz = Bm + L.vz, vo = Bm + L.vo;
   const int* idx = w.col_idx + off;
   const double g = w.gamma;
   const double* Y = w.Y + (size_t)b * n * n;
@@ -331,12 +327,11 @@ __device__ __forceinline__ void colprox_reg(const OmcWS& w, int mode, int b, int
   const int tri = (c * (c + 1)) >> 1;
   // dense instances (columns with more than 40 observed rows): B is not kept beside L -- a second factorization gathers it again from
   // L2 -- which halves the LDS per wave and doubles the waves per CU
-  const bool keepB = w.cp_keepB != 0;
+  const bool keepB = w.geo.cp_keepB != 0;
+  const CpRegLayout L = cp_reg_layout(c, keepB);
   auto Bm = base;
-  auto Lm = keepB ? Bm + tri : base;
-  auto vo = Lm + tri;
-  auto pinv = vo + c;
-  auto sidx = (int*)(pinv + c);
+  auto Lm = Bm + L.Lm, vo = Bm + L.vo, pinv = Bm + L.pinv;
+  auto sidx = (int*)(Bm + L.sidx);
   const double gm = w.gamma;
   const double* Y = w.Y + (size_t)b * n * n;
   const double* Yp = w.Yp + (size_t)b * n * n;
@@ -481,8 +476,8 @@ __global__ void __launch_bounds__(256) k_colprox(OmcWS w, int mode) {
   if (c == 0) { if (mode == 1 && lane == 0) { w.objcol[(size_t)b * w.m + j] = 0.0; w.c0col[(size_t)b * w.m + j] = 0.0; } return; }
   DIAG_T0();
   // two inlined copies so that the LDS copy compiles to ds_read/ds_write (not flat) instructions
-  if (c <= w.cp_lds_c) colprox_reg(w, mode, b, j, off, c, lane, smem + (size_t)wave_in_blk * w.cp_lds_doubles);   // cp_lds_c <= 64
-  else colprox_body(w, mode, b, j, off, c, lane, w.cp_scratch + ((size_t)b * w.m + j) * w.cp_scratch_stride);
+  if (c <= w.geo.cp_lds_c) colprox_reg(w, mode, b, j, off, c, lane, smem + (size_t)wave_in_blk * w.geo.cp_lds_doubles);   // cp_lds_c <= 64
+  else colprox_body(w, mode, b, j, off, c, lane, w.cp_scratch + ((size_t)b * w.m + j) * w.geo.cp_scratch_stride);
   if (lane == 0 && mode == 0) DIAG_CYC(0, b);
 }
 
@@ -810,12 +805,12 @@ __global__ void __launch_bounds__(512) k_cone(OmcWS w, int mode) {
   if (mode == CONE_SEP && w.sep_done && w.sep_done[b]) return;      // k_cone_sub<2> has delivered the separation vector
   const int n = w.n, k = w.k;
   const int N = n;
-  const int Np = (N + 1) & ~1, ld = Np | 1;
+  const ConeLayout L = cone_layout(N);
+  const int Np = L.Np, ld = L.ld;
   // with USE_LDS the pointers stay in the LDS address space (ds_read/ds_write, not flat)
-  auto Gm = [&]() { if constexpr (USE_LDS) return (double*)smem; else return w.cone_scratch + (size_t)b * w.cone_scratch_stride; }();
-  auto ev = Gm + (size_t)Np * ld;
-  auto wgt = ev + Np;
-  int* sel = (int*)(wgt + Np);
+  auto Gm = [&]() { if constexpr (USE_LDS) return (double*)smem; else return w.cone_scratch + (size_t)b * w.geo.cone.slab_stride; }();
+  auto ev = Gm + L.ev, wgt = Gm + L.wgt;
+  int* sel = (int*)(Gm + L.sel);
   auto entry = [&](int i, int j) { return cone_M_entry(w, b, mode, i, j); };
   // eigenvalues only (certificate): their error is second order in the residual cross products, 1e-9 is ample
   const double sigma = eig_frontend(Gm, ev, N, Np, ld, entry, red, &s_cnt, w.sweeps + b, (mode == CONE_EVALS) ? 1e-9 : 1e-14);
@@ -930,8 +925,6 @@ __global__ void __launch_bounds__(512) k_cone(OmcWS w, int mode) {
 // Inputs written by k_global / k_setup: Mbuf (NP16 x NP16, zero padded), fro2, Vrow (row-major V), vvalid.
 // ---------------------------------------------------------------------------------------------------------
 typedef double double4v __attribute__((ext_vector_type(4)));
-#define SUBP 16   // tracked subspace dimension of k_cone_sub
-#define SUBG 2    // default of w.sub_guard: Ritz values that must stay negative (4 until round 3: nodes whose Y - D1 keeps 13-14 positive eigenvalues -- ~1 % of the slot-iterations at depth 11 -- then sent EVERY launch through the full kernel)
 
 template <int LPP, bool USE_LDS, int RPL2, int TPB = 512>   // RPL2 = rows per lane / 2 as a compile-time constant (0: run-time bound)
 __global__ void __launch_bounds__(TPB) k_cone_ws(OmcWS w) {
@@ -946,17 +939,16 @@ __global__ void __launch_bounds__(TPB) k_cone_ws(OmcWS w) {
   }
   if (w.ws_mode && w.cert_enable && !w.confirm[b]) return;       // the estimate of k_cone_sub<1> is enough for this check
   const int n = w.n, N = n, NP = w.np16;
-  const int Np = (N + 1) & ~1;
   // lane lg of a pair group owns the CONTIGUOUS rows [lg*rpl, (lg+1)*rpl): 16-byte LDS reads, rpl even, ld even
-  const int rpl = (((N + LPP - 1) / LPP) + 1) & ~1, Nrp = rpl * LPP;
+  const int rpl = ws_rpl(N, LPP), Nrp = rpl * LPP;
   // leading dimension = 16 (mod 32) doubles and rows interleaved over the lanes of a pair group (lane lg owns the 16-byte chunks
   // lg, lg + LPP, ...): a group then reads 128 contiguous bytes = 32 banks, and the groups of neighbouring pairs (columns p, p + 1)
   // start 32 banks apart -- the contiguous-rows layout with ld = Nrp + 2 lost 36 % of the LDS cycles to bank conflicts (PMC)
-  const int ld = w.ws_ld;
-  auto Gm = [&]() { if constexpr (USE_LDS) return (double*)smem; else return w.cone_scratch + (size_t)b * w.cone_scratch_stride; }();
-  auto ev = Gm + (size_t)Np * ld;
-  auto wgt = ev + Np;
-  int* sel = (int*)(wgt + Np);
+  const ConeLayout L = cone_carve(N, w.geo.ws_ld);
+  const int Np = L.Np, ld = L.ld;
+  auto Gm = [&]() { if constexpr (USE_LDS) return (double*)smem; else return w.cone_scratch + (size_t)b * w.geo.ws.slab_stride; }();
+  auto ev = Gm + L.ev, wgt = Gm + L.wgt;
+  int* sel = (int*)(Gm + L.sel);
   const int evals_only = w.ws_mode;   // 1: certificate matrix (k_check_build), return sum of min(lambda_i, 0) over the k smallest
   const double* Mb = (evals_only ? w.MbufC : w.Mbuf) + (size_t)b * NP * NP;
   double* Vr = (evals_only ? w.VrowC : w.Vrow) + (size_t)b * NP * NP;
@@ -1021,7 +1013,7 @@ __global__ void __launch_bounds__(TPB) k_cone_ws(OmcWS w) {
     const int npairs = Np >> 1;
     // rotation threshold 1e-10 (relative cross product): the projection error it leaves, ~1e-10 ||M||, is far below the
     // ADMM tolerances; 1e-14 would force a second rotating sweep that changes nothing the solver can see
-    const double tau = (w.jacobi_tau > 0.0) ? w.jacobi_tau : 1e-10, tau2 = tau * tau;
+    const double tau = 1e-10, tau2 = tau * tau;
     int sweeps = 0;
     for (; sweeps < w.max_sweeps; ++sweeps) {
       for (int t = wv; t < Np; t += nw) {
@@ -1211,12 +1203,12 @@ __global__ void __launch_bounds__(TPB) k_cone_ws(OmcWS w) {
 // block X of SUBP = 16 orthonormal vectors, warm-started from the previous ADMM iteration:
 //     `chunk` steps of  X <- orth((M + s I) X)   (v_mfma_f64_16x16x4_f64 for M X and the Gram matrix, Cholesky-QR),
 //     Rayleigh-Ritz on the 16 x 16 projection (in-wave Jacobi), residuals || M x - theta x || of every Ritz pair with theta >= 0;
-//     accepted when they are below sub_tol ||M||_F and at least SUBG Ritz values are negative (so that no positive eigenvalue
+//     accepted when they are below sub_tol ||M||_F and at least sub_guard Ritz values are negative (so that no positive eigenvalue
 //     hides outside the block); otherwise more steps, and after sub_qmax steps the slot falls back to the full kernel.
 // The shift s centres the untracked spectrum [lo, theta_min]; lo comes from the first two moments of M (trace and Frobenius
 // norm, written by k_global) by Samuelson's inequality, so it is a rigorous bound, not a guess.
 // One 256-thread workgroup per slot, ~38 KB of LDS: four workgroups per CU.  The full kernel (k_cone_ws) seeds X from its
-// eigenvectors whenever it finds at most SUBP - SUBG positive eigenvalues.
+// eigenvectors whenever it finds at most SUBP - sub_guard positive eigenvalues.
 // ---------------------------------------------------------------------------------------------------------
 
 // MODE 0: the cone block (above).  MODE 1: the certificate -- the k most negative eigenvalues of the Lagrangian matrix Mchk (k_check_build)
@@ -1244,20 +1236,14 @@ __global__ void __launch_bounds__(256) k_cone_sub(OmcWS w) {
       if (!w.sub_onC[b]) { if (threadIdx.x == 0) w.confirm[b] = 1; return; }           // no block yet: the full kernel evaluates (and seeds)
     }
   }
-  const int n = w.n, NP = w.np16, nt = NP >> 4, LD = NP + 2;
+  const SubLayout L = sub_layout(w.np16);
+  const int n = w.n, NP = w.np16, nt = NP >> 4, LD = L.LD;
   const int wv = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
   double* Xa = smem;                     // SUBP x LD   X (column j at Xa + j*LD)
   // orders beyond 512 (config 5: n = 1000): the two SUBP x LD blocks no longer fit the LDS together -- Z lives in a per-slot global slab (L2) there
-  const bool zglob = NP > 512;
-  double* Za = zglob ? w.sub_zscratch + (size_t)b * SUBP * LD : Xa + (size_t)SUBP * LD;   // SUBP x LD   Z = M X, then Y = Z + s X
-  double* Cs = zglob ? Xa + (size_t)SUBP * LD : Za + (size_t)SUBP * LD;   // 4 partial 16 x 16 products
-  double* Hs = Cs + 4 * 256;             // 16 x 17: Gram matrix / Cholesky factor / H / Ritz rotation
-  double* Gj = Hs + 16 * 17;             // 16 x 17: Jacobi work
-  double* th = Gj + 16 * 17;             // 16 Ritz values
-  double* evj = th + 16;                 // 16 squared norms
-  double* red = evj + 16;                // 32
-  double* wgt = red + 32;                // 16
-  int* sel = (int*)(wgt + 16);           // 16
+  double* Za = L.zglob ? w.sub_zscratch + (size_t)b * SUBP * LD : Xa + L.Za;   // SUBP x LD   Z = M X, then Y = Z + s X
+  double* Cs = Xa + L.Cs, *Hs = Xa + L.Hs, *Gj = Xa + L.Gj, *th = Xa + L.th, *evj = Xa + L.evj, *red = Xa + L.red, *wgt = Xa + L.wgt;
+  int* sel = (int*)(Xa + L.sel);
   const double* Mb = ((MODE == 1) ? w.MbufC : w.Mbuf) + (size_t)b * NP * NP;      // MODE 2: k_sep_prepare has put Y - U U' there
   double* Xg = ((MODE == 1) ? w.XsC : w.Xs) + (size_t)b * NP * SUBP;
   double* thg = ((MODE == 1) ? w.sub_thetaC : w.sub_theta) + (size_t)b * SUBP;
@@ -1265,7 +1251,7 @@ __global__ void __launch_bounds__(256) k_cone_sub(OmcWS w) {
   const double fro2 = (MODE == 1) ? w.fro2c[b] : w.fro2[b], nF = sqrt(fro2), trM = (MODE == 1) ? -w.trMc[b] : w.trM[b];
   // inexact projections are harmless while the ADMM iterate itself still moves (errors proportional to the step are summable):
   // the residual target follows the last dual residual ||Y_new - Y_old|| down to sub_tol
-  const double tol_eff = (MODE == 2) ? 1e-11 : (MODE == 1) ? 1e-9 : ((w.sub_adapt > 0.0) ? fmin(1e-6, fmax(w.sub_tol, w.sub_adapt * w.rd[b] / fmax(nF, 1e-300))) : w.sub_tol);
+  const double tol_eff = (MODE == 2) ? 1e-11 : (MODE == 1) ? 1e-9 : fmin(1e-6, fmax(w.sub_tol, w.sub_adapt * w.rd[b] / fmax(nF, 1e-300)));
   for (int e = tid; e < SUBP * NP; e += T) { const int j = e / NP, r = e - j * NP; Xa[(size_t)j * LD + r] = Xg[e]; }
   if (tid < SUBP) th[tid] = thg[tid];
   __syncthreads();
@@ -1364,7 +1350,7 @@ __global__ void __launch_bounds__(256) k_cone_sub(OmcWS w) {
       mul_MX(shift);
       __syncthreads();
       SUBSTAMP(2);
-      if (MODE != 2 && w.sub_lazy && c + 1 < chunk) {
+      if (MODE != 2 && c + 1 < chunk) {
         // inside a chunk the block is only rescaled: the span after `chunk` steps is the same, and the condition of the block grows by
         // at most (largest / smallest shifted Ritz value)^chunk, which the orthonormalisation at the end of the chunk absorbs (it is
         // repeated once when its pivots say the block had become ill-conditioned)
@@ -1412,7 +1398,7 @@ __global__ void __launch_bounds__(256) k_cone_sub(OmcWS w) {
 #pragma unroll
             for (int r = 0; r < SUBP; ++r) Hs[r * 17 + lane] = (r >= lane) ? z[r] : 0.0;       // Linv[r][j = lane]
           }
-          if (lane == 0) { s_flag = bad; s_cond = (pass == 0 && w.sub_lazy && dmin < 1e-6 * dmax) ? 1 : 0; }   // pivot ratio ~ cond(block)^2
+          if (lane == 0) { s_flag = bad; s_cond = (pass == 0 && dmin < 1e-6 * dmax) ? 1 : 0; }   // pivot ratio ~ cond(block)^2
         }
         __syncthreads();
         SUBSTAMP(4);
@@ -1709,17 +1695,15 @@ __global__ void __launch_bounds__(256) k_small(OmcWS w, int mode) {
   const int r = w.rr[nb];
   const int N3 = (mode == SMALL_PROJ) ? r + k : r;
   const int Np = (N3 + 1) & ~1, ld = Np | 1;
-  auto base = [&]() { if constexpr (USE_LDS) return (double*)smem; else return w.small_scratch + (size_t)b * w.small_scratch_stride; }();
+  auto base = [&]() { if constexpr (USE_LDS) return (double*)smem; else return w.small_scratch + (size_t)b * w.geo.small.slab_stride; }();
+  const SmallLayout L = small_layout(n, rm, k);
+  const int ld3 = L.ld3;
   double* T1 = base;                         // n x r
-  double* M3 = T1 + (size_t)n * rm;          // N3max x N3max  (column-major, ld3 = rm + k)
-  const int ld3 = rm + k;
-  double* Gm = M3 + (size_t)ld3 * ld3;       // Jacobi work
-  const int Npm = (rm + k + 1) & ~1, ldm = Npm | 1;
-  double* ev = Gm + (size_t)Npm * ldm;
-  double* wgt = ev + Npm;
-  int* sel = (int*)(wgt + Npm);
-  double* Cc = (double*)(sel + Npm + (Npm & 1));  // r x k coefficients (recover)
-  double* Qs = Cc + (size_t)rm * k + 2;          // n x 16: Q' padded with zero columns (LDS variant only, r <= 16)
+  double* M3 = base + L.M3;                  // N3max x N3max  (column-major, ld3 = rm + k)
+  double *Gm = base + L.Gm, *ev = base + L.ev, *wgt = base + L.wgt;      // Jacobi work
+  int* sel = (int*)(base + L.sel);
+  double* Cc = base + L.Cc;                  // r x k coefficients (recover)
+  double* Qs = base + L.Qs;                  // n x 16: Q' padded with zero columns (LDS variant only, r <= 16)
   const double* Q = w.Qb + (size_t)nb * n * rm;
   const double* Y = w.Y + (size_t)b * n * n;
   const double* D3 = w.D3 + (size_t)b * n * n;
@@ -1787,7 +1771,7 @@ __global__ void __launch_bounds__(256) k_small(OmcWS w, int mode) {
   if (N3 == 0) return;
   auto entry = [&](int i, int j) { return M3[(size_t)j * ld3 + i]; };
   double sigma;
-  if (mode == SMALL_PROJ && Np <= 16 && w.V3) {
+  if (mode == SMALL_PROJ && Np <= 16) {
     // order <= 16: one-sided Jacobi inside one wave on G = (M3 + sigma I) V_prev -- M3 moves little from one ADMM iteration to the next,
     // so the columns start almost orthogonal (two sweeps instead of the six of a cold start); the normalised columns are the eigenvectors
     // and are kept for the next iteration
@@ -1949,27 +1933,25 @@ __device__ __forceinline__ double w1_entry(const double* Xf, const double* wf, i
 //   mu = argmin 1/2 mu'G1 mu - c'mu, mu >= 0 (c = A t - b) ;  lam = rho mu
 //   Yn = tY - A_Y' mu / wY1 ;  Vn = tV - Q'(A_U' mu)/2
 // ---------------------------------------------------------------------------------------------------------
-#define GL_XS 16   // cut vectors staged per pass of k_global (one MFMA column block)
 template <bool USE_LDS>
 __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   extern __shared__ double smem[];
   __shared__ double red[32];
-  __shared__ double s_Gp[NNQP_PMAX * (NNQP_PMAX + 1) / 2];
+  __shared__ double s_Gp[NNQP_GP_DOUBLES];      // NNQP scratch; between the row projections it holds the Ritz vectors of the factored W1 (glob_w1_fits)
   __shared__ double s_sv[NNQP_PMAX], s_tmp[NNQP_PMAX];
   __shared__ int s_pl[NNQP_PMAX];
   const int b = slot_of(w, blockIdx.x), tid = threadIdx.x, T = blockDim.x;
   if (w.done[b]) return;
   const int nb = w.node_of[b];
   const int n = w.n, k = w.k, m = w.m, rm = w.rmax;
+  const GlobLayout L = glob_layout(n, k, rm, w.Rmax);
   const int R = w.R[nb], r = w.rr[nb];
   // The target is symmetric: only its lower triangle is kept, packed by rows (entry (i, j), i >= j, at i (i + 1) / 2 + j) -- 40 KB instead
   // of 80 KB at n = 100, which is what lets two workgroups share a CU.
-  auto tY = [&]() { if constexpr (USE_LDS) return (double*)smem; else return w.glob_scratch + (size_t)b * w.glob_scratch_stride; }();
+  auto tY = [&]() { if constexpr (USE_LDS) return (double*)smem; else return w.glob_scratch + (size_t)b * w.geo.glob.slab_stride; }();
   auto TRIX = [](int i, int j) { return (i >= j) ? ((i * (i + 1)) >> 1) + j : ((j * (j + 1)) >> 1) + i; };
-  double* tU = tY + (size_t)n * (n + 1) / 2;       // n*k   (tU, then the full-space U correction)
-  double* tV = tU + (size_t)n * k;       // rm*k
-  double* cvec = tV + (size_t)rm * k;    // Rmax
-  double* mu = cvec + w.Rmax;            // Rmax
+  double* tU = tY + L.tU;                // n*k   (tU, then the full-space U correction)
+  double *tV = tY + L.tV, *cvec = tY + L.cvec, *mu = tY + L.mu;      // rm*k, Rmax, Rmax
   double* lam = w.lam + (size_t)b * w.Rmax;
   double* Y = w.Y + (size_t)b * n * n;
   double* Yp = w.Yp + (size_t)b * n * n;
@@ -1990,7 +1972,7 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   const double* lamD = w.lamD + (size_t)b * m * n;
   const int nt16 = (n + 15) >> 4;
   // factored W1 (w1_fac[b]: this iteration's k_cone_sub<0> call was accepted and stored no dense W1): the accepted Ritz vectors are staged
-  // in s_Gp, idle outside step 4 (the host keeps 16 n within it), for steps 2 and 6.  Each entry goes through an empty asm, as a loaded
+  // in s_Gp, idle outside step 4 (glob_w1_fits keeps 16 n within it), for steps 2 and 6.  Each entry goes through an empty asm, as a loaded
   // value would, so that the expressions that use it contract exactly as they do with the dense load.
   const bool f1 = w.w1_fac && w.w1_fac[b];
   const int NP = w.np16;
@@ -2061,8 +2043,7 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   //    staged as the columns of X, wave w forms the 16-row tiles w, w + nw, .. of tY X and reduces x_i (tY X)_i over its rows; the
   //    waves' partial sums are added in a fixed order.
   const double* cutx = w.cutx + (size_t)nb * w.Lmax * n;
-  double* xs = mu + w.Rmax;                              // GL_XS * n: staged cut vectors
-  double* qrow = xs + (size_t)GL_XS * n;                 // Rmax: x' tY x of the cut rows
+  double *xs = tY + L.xs, *qrow = tY + L.qrow;           // GL_XS * n: staged cut vectors ; Rmax: x' tY x of the cut rows
   __shared__ int s_crow[GL_XS]; __shared__ int s_nc, s_rnext; __shared__ double s_qp[8][GL_XS];   // 512 threads = 8 waves
   if (tid == 0) s_rnext = 0;
   for (;;) {
@@ -2248,7 +2229,6 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
 // ---------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(512) k_check_build(OmcWS w) {
   __shared__ double red[32];
-  extern __shared__ double smem[];   // n*k doubles: cU
   const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
   if (w.done[b]) return;
   const int nb = w.node_of[b];
@@ -2320,18 +2300,17 @@ __global__ void __launch_bounds__(512) k_check_build(OmcWS w) {
     for (int j = 0; j < k; ++j) cst -= rho * w.Q3T[(size_t)b * k * k + (size_t)j * k + j];
     w.cpen[b] = pen; w.cst[b] = cst;
   }
-  if (w.MbufC) {   // zero-padded copy + Frobenius norm for the warm-started eigenvalue kernel
-    const int NP = w.np16;
-    double fr2 = 0.0, tr1 = 0.0;
-    for (int e = tid; e < n * n; e += T) {
-      const int i = e % n, j = e / n;
-      const double mv = 0.5 * (M[e] + M[(size_t)i * n + j]);
-      w.MbufC[(size_t)b * NP * NP + (size_t)j * NP + i] = mv; fr2 += mv * mv; if (i == j) tr1 += mv;
-    }
-    fr2 = block_sum(fr2, red);
-    tr1 = block_sum(tr1, red);
-    if (tid == 0) { w.fro2c[b] = fr2; w.trMc[b] = tr1; }
+  // zero-padded copy + Frobenius norm for the warm-started eigenvalue kernel
+  const int NP = w.np16;
+  double fr2 = 0.0, tr1 = 0.0;
+  for (int e = tid; e < n * n; e += T) {
+    const int i = e % n, j = e / n;
+    const double mv = 0.5 * (M[e] + M[(size_t)i * n + j]);
+    w.MbufC[(size_t)b * NP * NP + (size_t)j * NP + i] = mv; fr2 += mv * mv; if (i == j) tr1 += mv;
   }
+  fr2 = block_sum(fr2, red);
+  tr1 = block_sum(tr1, red);
+  if (tid == 0) { w.fro2c[b] = fr2; w.trMc[b] = tr1; }
 }
 
 // phase 2: the bound of this check is rigorous for every slot (no certificate estimator).  With the estimator (k_cone_sub<1>):
@@ -2696,8 +2675,9 @@ __global__ void __launch_bounds__(256) k_eval_objective(int n, int m, double gam
 // host-callable launchers
 // ---------------------------------------------------------------------------------------------------------
 template <int LPP>
-static void launch_ws_lds(const OmcWS* w, int rpl2, size_t lds_bytes, hipStream_t s) {
-  switch (rpl2) {   // straight-line (branch-free) row loops for the common sizes, run-time bound otherwise
+static void launch_ws_lds(const OmcWS* w, hipStream_t s) {
+  const size_t lds_bytes = w->geo.ws.lds_bytes;
+  switch (w->geo.ws_rpl2) {   // straight-line (branch-free) row loops for the common sizes, run-time bound otherwise
     case 4: hipLaunchKernelGGL((k_cone_ws<LPP, true, 4>), dim3(w->nB), dim3(512), lds_bytes, s, *w); break;
     case 5: hipLaunchKernelGGL((k_cone_ws<LPP, true, 5>), dim3(w->nB), dim3(512), lds_bytes, s, *w); break;
     case 6: hipLaunchKernelGGL((k_cone_ws<LPP, true, 6>), dim3(w->nB), dim3(512), lds_bytes, s, *w); break;
@@ -2724,18 +2704,18 @@ void omc_launch_colprox(const OmcWS* w, int mode, hipStream_t s) {
   }
   const int waves = w->nB * ((mode == 0 && w->cp_pair) ? w->cp_nsolo : w->m);
   const int blocks = (waves + wpb - 1) / wpb;
-  hipLaunchKernelGGL(k_colprox, dim3(blocks), dim3(wpb * 64), (size_t)wpb * w->cp_lds_doubles * sizeof(double), s, *w, mode);
+  hipLaunchKernelGGL(k_colprox, dim3(blocks), dim3(wpb * 64), (size_t)wpb * w->geo.cp_lds_doubles * sizeof(double), s, *w, mode);
 }
-void omc_launch_cone(const OmcWS* w, int mode, int use_lds, size_t lds_bytes, hipStream_t s) {
-  if (use_lds) hipLaunchKernelGGL(k_cone<true>, dim3(w->nB), dim3(512), lds_bytes, s, *w, mode);
+void omc_launch_cone(const OmcWS* w, int mode, hipStream_t s) {
+  if (w->geo.cone.use_lds) hipLaunchKernelGGL(k_cone<true>, dim3(w->nB), dim3(512), w->geo.cone.lds_bytes, s, *w, mode);
   else hipLaunchKernelGGL(k_cone<false>, dim3(w->nB), dim3(512), 0, s, *w, mode);
 }
-void omc_launch_cone_ws(const OmcWS* w, int lpp, int use_lds, size_t lds_bytes, hipStream_t s) {
-  const int rpl2 = ((((w->n + lpp - 1) / lpp) + 1) & ~1) >> 1;
-  if (use_lds) {
-    if (lpp == 16) launch_ws_lds<16>(w, rpl2, lds_bytes, s);
-    else if (lpp == 8) launch_ws_lds<8>(w, rpl2, lds_bytes, s);
-    else launch_ws_lds<4>(w, rpl2, lds_bytes, s);
+void omc_launch_cone_ws(const OmcWS* w, hipStream_t s) {
+  const int lpp = w->geo.ws_lpp, rpl2 = w->geo.ws_rpl2;
+  if (w->geo.ws.use_lds) {
+    if (lpp == 16) launch_ws_lds<16>(w, s);
+    else if (lpp == 8) launch_ws_lds<8>(w, s);
+    else launch_ws_lds<4>(w, s);
   } else {
     // L2-resident G (n > 144): 1024 threads = 64 pair groups halve the passes per step (the kernel is bound by L2 latency there)
     if (lpp == 64) {      // orders 513 .. 1024: a whole wave per column pair (16 rows per lane), G in global scratch
@@ -2746,23 +2726,22 @@ void omc_launch_cone_ws(const OmcWS* w, int lpp, int use_lds, size_t lds_bytes, 
     else hipLaunchKernelGGL((k_cone_ws<16, false, 0>), dim3(w->nB), dim3(512), 0, s, *w);
   }
 }
-size_t omc_cone_sub_lds(int np16) { return ((size_t)(np16 > 512 ? 1 : 2) * SUBP * (np16 + 2) + 4 * 256 + 2 * 16 * 17 + 16 + 16 + 32 + 16 + 8) * sizeof(double); }
 void omc_launch_cone_sub(const OmcWS* w, hipStream_t s) {
-  hipLaunchKernelGGL(k_cone_sub<0>, dim3(w->nB), dim3(256), omc_cone_sub_lds(w->np16), s, *w);
+  hipLaunchKernelGGL(k_cone_sub<0>, dim3(w->nB), dim3(256), w->geo.sub_lds, s, *w);
 }
 void omc_launch_sep_sub(const OmcWS* w, hipStream_t s) {
   hipLaunchKernelGGL(k_sep_prepare, dim3(w->B), dim3(256), 0, s, *w);
-  hipLaunchKernelGGL(k_cone_sub<2>, dim3(w->B), dim3(256), omc_cone_sub_lds(w->np16), s, *w);
+  hipLaunchKernelGGL(k_cone_sub<2>, dim3(w->B), dim3(256), w->geo.sub_lds, s, *w);
 }
 void omc_launch_cert_sub(const OmcWS* w, hipStream_t s) {
-  hipLaunchKernelGGL(k_cone_sub<1>, dim3(w->B), dim3(256), omc_cone_sub_lds(w->np16), s, *w);
+  hipLaunchKernelGGL(k_cone_sub<1>, dim3(w->B), dim3(256), w->geo.sub_lds, s, *w);
 }
-void omc_launch_small(const OmcWS* w, int mode, int use_lds, size_t lds_bytes, hipStream_t s) {
-  if (use_lds) hipLaunchKernelGGL(k_small<true>, dim3(w->nB), dim3(256), lds_bytes, s, *w, mode);
+void omc_launch_small(const OmcWS* w, int mode, hipStream_t s) {
+  if (w->geo.small.use_lds) hipLaunchKernelGGL(k_small<true>, dim3(w->nB), dim3(256), w->geo.small.lds_bytes, s, *w, mode);
   else hipLaunchKernelGGL(k_small<false>, dim3(w->nB), dim3(256), 0, s, *w, mode);
 }
-void omc_launch_global(const OmcWS* w, int use_lds, size_t lds_bytes, hipStream_t s) {
-  if (use_lds) hipLaunchKernelGGL(k_global<true>, dim3(w->nB), dim3(512), lds_bytes, s, *w);
+void omc_launch_global(const OmcWS* w, hipStream_t s) {
+  if (w->geo.glob.use_lds) hipLaunchKernelGGL(k_global<true>, dim3(w->nB), dim3(512), w->geo.glob.lds_bytes, s, *w);
   else hipLaunchKernelGGL(k_global<false>, dim3(w->nB), dim3(512), 0, s, *w);
 }
 void omc_launch_check_zero(const OmcWS* w, hipStream_t s) { hipLaunchKernelGGL(k_zero_check, dim3((w->B + 63) / 64), dim3(64), 0, s, *w); }

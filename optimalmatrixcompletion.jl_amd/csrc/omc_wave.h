@@ -7,7 +7,7 @@
 #define WAVE 64
 
 // slot of the i-th workgroup of a launch over the compact list of live slots
-__device__ __forceinline__ int slot_of(const OmcWS& w, int i) { return w.slot_list ? w.slot_list[w.b0 + i] : w.b0 + i; }
+__device__ __forceinline__ int slot_of(const OmcWS& w, int i) { return w.slot_list ? w.slot_list[i] : i; }
 
 // logical workgroup id of this block with consecutive ids on one XCD (blocks are dealt round-robin over the 8 XCDs, so block b and b + 1
 // have different L2s): a bijection of [0, gridDim.x) for any grid size; a placement hint only, the results do not depend on it
