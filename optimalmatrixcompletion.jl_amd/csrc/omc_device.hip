@@ -1626,52 +1626,76 @@ __global__ void __launch_bounds__(256) k_sep_prepare(OmcWS w) {
 
 // ---------------------------------------------------------------------------------------------------------
 // C = L L' for a dense column-major n x m matrix L (zero off the support of the observed pattern) by v_mfma_f64_16x16x4_f64,
-// one 16 x 16 tile of the lower triangle per wave and pass, operands straight from L2.  store(i, j, v) receives every entry of
+// NT 16 x 16 tiles of the lower triangle per wave and pass, operands straight from L2.  store(i, j, v) receives every entry of
 // the tile with i >= j inside the matrix.  k_global (every order) and k_check_build (n > 144) use it: the per-entry walk over the CSR
 // lists that it replaced did a fifth of the flops and cost 41 us of 108 per node at n = 100, 4.8 ms at n = 200.
 // ---------------------------------------------------------------------------------------------------------
-template <class StoreF>
+// NT tiles of one wave at once (tile0, tile0 + nw, ..): independent accumulators, the operand loads of all NT issued together.  The K order
+// of a tile does not depend on NT, so every tile is bit-identical to the one-tile form.
+template <int NT, class StoreF>
+__device__ __forceinline__ void mfma_LLt_tiles(const double* L, int n, int m, int tile0, int nw, int li, int lk, StoreF& store) {
+  const int m4 = m & ~3;
+  int ti[NT], tj[NT];
+  double ma[NT], mb[NT];
+  const double *La[NT], *Lb[NT];
+  double4v acc[NT];
+  double aq[NT][4], bq[NT][4];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int tile = tile0 + t * nw;
+    int r = (int)((sqrtf(8.0f * (float)tile + 1.0f) - 1.0f) * 0.5f);
+    while (r * (r + 1) / 2 > tile) --r;
+    while ((r + 1) * (r + 2) / 2 <= tile) ++r;
+    ti[t] = r; tj[t] = tile - r * (r + 1) / 2;
+    const int ia = (ti[t] << 4) + li, jb = (tj[t] << 4) + li;
+    ma[t] = (ia < n) ? 1.0 : 0.0; mb[t] = (jb < n) ? 1.0 : 0.0;
+    La[t] = L + ((ia < n) ? ia : n - 1);
+    Lb[t] = L + ((jb < n) ? jb : n - 1);
+    acc[t] = double4v{0.0, 0.0, 0.0, 0.0};
+  }
+  if (m4 >= 16) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { aq[t][u] = La[t][(size_t)(4 * u + lk) * n]; bq[t][u] = Lb[t][(size_t)(4 * u + lk) * n]; }
+  }
+  int k0 = 0;
+  for (; k0 + 16 <= m4; k0 += 16) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      int kn = k0 + 16 + 4 * u + lk;
+      kn = (kn < m4) ? kn : kn - 16;              // re-reads a valid column at the end; the value is not used
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const double a = aq[t][u] * ma[t], bv = bq[t][u] * mb[t];
+        aq[t][u] = La[t][(size_t)kn * n]; bq[t][u] = Lb[t][(size_t)kn * n];
+        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, acc[t], 0, 0, 0);
+      }
+    }
+  }
+  for (; k0 < m; k0 += 4) {                       // remainder (< 16 columns), guarded
+    const int kk = k0 + lk;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const double a = (kk < m) ? La[t][(size_t)kk * n] * ma[t] : 0.0, bv = (kk < m) ? Lb[t][(size_t)kk * n] * mb[t] : 0.0;
+      acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, acc[t], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = (ti[t] << 4) + lk + 4 * r, j = (tj[t] << 4) + li;
+      if (i < n && j < n && i >= j) store(i, j, acc[t][r]);
+    }
+}
+template <int NT, class StoreF>
 __device__ __forceinline__ void mfma_LLt(const double* L, int n, int m, StoreF store) {
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, nw = blockDim.x >> 6, li = lane & 15, lk = lane >> 4;
   const int nt = (n + 15) >> 4, ntile = nt * (nt + 1) / 2;
-  const int m4 = m & ~3;
-  for (int tile = wv; tile < ntile; tile += nw) {
-    int ti = (int)((sqrtf(8.0f * (float)tile + 1.0f) - 1.0f) * 0.5f);
-    while (ti * (ti + 1) / 2 > tile) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= tile) ++ti;
-    const int tj = tile - ti * (ti + 1) / 2;
-    const int ia = (ti << 4) + li, jb = (tj << 4) + li;
-    const double ma = (ia < n) ? 1.0 : 0.0, mb = (jb < n) ? 1.0 : 0.0;
-    const double* La = L + ((ia < n) ? ia : n - 1);
-    const double* Lb = L + ((jb < n) ? jb : n - 1);
-    double4v acc = {0.0, 0.0, 0.0, 0.0};
-    double aq[4], bq[4];
-    if (m4 >= 16) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { aq[u] = La[(size_t)(4 * u + lk) * n]; bq[u] = Lb[(size_t)(4 * u + lk) * n]; }
-    }
-    int k0 = 0;
-    for (; k0 + 16 <= m4; k0 += 16) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const double a = aq[u] * ma, bv = bq[u] * mb;
-        int kn = k0 + 16 + 4 * u + lk;
-        kn = (kn < m4) ? kn : kn - 16;              // re-reads a valid column at the end; the value is not used
-        aq[u] = La[(size_t)kn * n]; bq[u] = Lb[(size_t)kn * n];
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, acc, 0, 0, 0);
-      }
-    }
-    for (; k0 < m; k0 += 4) {                       // remainder (< 16 columns), guarded
-      const int kk = k0 + lk;
-      const double a = (kk < m) ? La[(size_t)kk * n] * ma : 0.0, bv = (kk < m) ? Lb[(size_t)kk * n] * mb : 0.0;
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = (ti << 4) + lk + 4 * r, j = (tj << 4) + li;
-      if (i < n && j < n && i >= j) store(i, j, acc[r]);
-    }
-  }
+  int tile = wv;
+  for (; tile + (NT - 1) * nw < ntile; tile += NT * nw) mfma_LLt_tiles<NT>(L, n, m, tile, nw, li, lk, store);
+  if constexpr (NT > 1) for (; tile < ntile; tile += nw) mfma_LLt_tiles<1>(L, n, m, tile, nw, li, lk, store);      // what is left of an odd count
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1981,7 +2005,6 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   __shared__ int s_fsel[16], s_fn; __shared__ double s_fw[16];
   auto stage_w1 = [&]() {
     for (int e = tid; e < s_fn * n; e += T) { const int c = e / n, i = e - c * n; Xf[e] = Xs[(size_t)s_fsel[c] * NP + i]; }
-    __syncthreads();
   };
   if (f1) {
     if (tid == 0) {
@@ -1991,6 +2014,7 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
     }
     __syncthreads();
     stage_w1();
+    __syncthreads();
   }
   auto w1_at = [&](size_t e, int i, int j) {
     double v = f1 ? w1_entry(Xf, s_fw, s_fn, n, i, j) : W1[e];
@@ -1998,8 +2022,19 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
     return v;
   };
   STAMP(8);
-  // 2. cone + multiplicity part of the target (lower triangle), then the Lambda term, then the weights
-  // two entries per trip, as in step 6: the loads of both before the arithmetic of either
+  // 2. cone + multiplicity part of the target (lower triangle), then the Lambda term and the weights
+  // The n (n + 1) / 2 entries of the lower triangle are walked column by column (q = column offset + i - j: consecutive lanes on consecutive
+  // rows of one column, all lanes busy), four entries per thread and trip with the loads of all four before the arithmetic of any.  No sums
+  // here: every entry is computed on its own, so the thread that owns it does not matter.
+  const int ntri = (n * (n + 1)) >> 1;
+  auto tri_ij = [&](int q, int& i, int& j) {      // q -> (i, j), i >= j; column j starts at j n - j (j - 1) / 2
+    const float tn = (float)(2 * n + 1);
+    int c = (int)(0.5f * (tn - sqrtf(tn * tn - 8.0f * (float)q)));
+    c = (c < 0) ? 0 : (c > n - 1 ? n - 1 : c);
+    while (c * n - ((c * (c - 1)) >> 1) > q) --c;
+    while ((c + 1) * n - ((c * (c + 1)) >> 1) <= q) ++c;
+    j = c; i = c + q - (c * n - ((c * (c - 1)) >> 1));
+  };
   struct In2 { double y, nc, d1, d3, e3; };
   auto load2 = [&](int e) { In2 v; v.y = Y[e]; v.nc = w.Ncnt[e]; v.d1 = D1[e]; v.d3 = D3[e]; v.e3 = E3[e]; return v; };
   auto target2 = [&](int e, int i, int j, double w1, const In2& v) {
@@ -2009,15 +2044,21 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
                                 : rho_f * v.nc * y;
     tY[TRIX(i, j)] = first + rho * (rx * w1 + (1.0 - rx) * y + v.d1) + rho * (y + (1.0 - rx) * v.d3 + rx * v.e3);
   };
-  for (int e = tid; e < n * n; e += 2 * T) {
-    const int eb = e + T;
-    const int i = e % n, j = e / n, ib = (eb < n * n) ? eb % n : 0, jb = (eb < n * n) ? eb / n : 1;
-    const bool lo = i >= j, lob = (eb < n * n) && ib >= jb;      // lower triangle only
-    if (!lo && !lob) continue;
-    const double w1 = lo ? w1_at(e, i, j) : 0.0, w1b = lob ? w1_at(eb, ib, jb) : 0.0;      // first: the arithmetic of an entry stays in one basic block, as with the dense load
-    const In2 v = load2(lo ? e : eb), vb = load2(lob ? eb : e);
-    if (lo) target2(e, i, j, w1, v);
-    if (lob) target2(eb, ib, jb, w1b, vb);
+  for (int q0 = tid; q0 < ntri; q0 += 4 * T) {
+    int ii[4], jj[4], ee[4]; bool ok[4]; double w1[4]; In2 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int q = q0 + u * T;
+      ok[u] = q < ntri;
+      tri_ij(ok[u] ? q : q0, ii[u], jj[u]);
+      ee[u] = jj[u] * n + ii[u];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) w1[u] = ok[u] ? w1_at(ee[u], ii[u], jj[u]) : 0.0;      // first: the arithmetic of an entry stays in one basic block, as with the dense load
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = load2(ee[u]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) if (ok[u]) target2(ee[u], ii[u], jj[u], w1[u], v[u]);
   }
   for (int e = tid; e < r * k; e += T) {
     int a = e % r, j = e / r;
@@ -2025,13 +2066,25 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   }
   for (int e = tid; e < R; e += T) mu[e] = lam[e] / rho;
   __syncthreads();
-  if (!w.shor) mfma_LLt(lamD, n, m, [&](int i, int j, double v) { tY[TRIX(i, j)] += 0.5 * g * v; });      // one wave owns a tile: deterministic
-  __syncthreads();
-  for (int e = tid; e < n * n; e += T) {
-    const int i = e % n, j = e / n;
-    if (i >= j) tY[TRIX(i, j)] /= (rho * w.wY1[e]);
+  STAMP(14);
+  // the Lambda term and the division by the weights in one visit of the entry (one wave owns a tile: deterministic); Shor mode has no
+  // Lambda term and divides in a pass over the triangle
+  if (!w.shor) {
+    mfma_LLt<2>(lamD, n, m, [&](int i, int j, double v) {
+      const int t = TRIX(i, j);
+      double x = tY[t];
+      x += 0.5 * g * v;
+      tY[t] = x / (rho * w.wY1[(size_t)j * n + i]);
+    });
+    STAMP(15);
+  } else {
+    for (int q = tid; q < ntri; q += T) {
+      int i, j; tri_ij(q, i, j);
+      tY[TRIX(i, j)] /= (rho * w.wY1[(size_t)j * n + i]);
+    }
+    STAMP(28);
   }
-  for (int e = tid; e < n * k; e += T) {
+  for (int e = tid; e < n * k; e += T) {      // reads tV only (written before the barrier above)
     int i = e % n, j = e / n;
     double acc = 0.0;
     for (int a = 0; a < r; ++a) acc += Q[(size_t)a * n + i] * tV[(size_t)j * rm + a];
@@ -2048,10 +2101,20 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   if (tid == 0) s_rnext = 0;
   for (;;) {
     __syncthreads();
-    if (tid == 0) {
-      int c = 0, rr = s_rnext;
-      for (; rr < R && c < GL_XS; ++rr) if (w.rkind[(size_t)nb * w.Rmax + rr] == ROW_CUT) s_crow[c++] = rr;
-      s_nc = c; s_rnext = rr;
+    if (tid < WAVE) {      // the next (up to) GL_XS cut rows from s_rnext on, in ascending order: 64 rows per ballot
+      int c = 0, rr0 = s_rnext, rn = R;
+      const unsigned long long below = (1ull << tid) - 1ull;
+      for (; rr0 < R && c < GL_XS; rr0 += WAVE) {
+        const int rr = rr0 + tid;
+        const bool cut = rr < R && w.rkind[(size_t)nb * w.Rmax + rr] == ROW_CUT;
+        const unsigned long long mk = __ballot(cut);
+        const int pos = c + __popcll(mk & below);
+        if (cut && pos < GL_XS) s_crow[pos] = rr;
+        const unsigned long long last = __ballot(cut && pos == GL_XS - 1);      // the row that fills the pass: the next pass starts behind it
+        if (last) rn = rr0 + __builtin_ctzll(last) + 1;
+        c += __popcll(mk);
+      }
+      if (tid == 0) { s_nc = (c < GL_XS) ? c : GL_XS; s_rnext = rn; }
     }
     __syncthreads();
     const int nc = s_nc, rnext = s_rnext;
@@ -2091,42 +2154,89 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
     if (rnext >= R) break;
   }
   __syncthreads();
-  {   // one WAVE per row (wave-level reductions, no workgroup barrier per row)
+  {   // one WAVE per row (wave-level reductions, no workgroup barrier per row).  Lane l fetches the descriptor (kind, cut index, first
+      // coefficient, right-hand side) of the wave's l-th row ahead of the loop, 64 rows at a time: a row then waits for its vector only,
+      // not for a chain of dependent loads.
     const int wv_ = tid >> 6, lane_ = tid & 63, nw_ = T >> 6;
-    for (int rr = wv_; rr < R; rr += nw_) {
-      const int kind = w.rkind[(size_t)nb * w.Rmax + rr];
+    int mk = 0, mc = 0; double mf = 0.0, mr = 0.0;
+    int it = 0;
+    for (int rr = wv_; rr < R; rr += nw_, ++it) {
+      if ((it & 63) == 0) {
+        const int r2 = rr + nw_ * lane_;
+        if (r2 < R) { const size_t d = (size_t)nb * w.Rmax + r2; mk = w.rkind[d]; mc = w.rcut[d]; mf = w.rcoef[d * k]; mr = w.rrhs[d]; }
+      }
+      const int kind = __shfl(mk, it & 63, WAVE);
       double acc = 0.0;
       if (kind == ROW_TRACE) {
         for (int i = lane_; i < n; i += WAVE) acc += tY[TRIX(i, i)];
       } else if (kind == ROW_BOX) {
         if (lane_ == 0) acc = w.rcoef[((size_t)nb * w.Rmax + rr) * k] * tU[(size_t)w.rbj[(size_t)nb * w.Rmax + rr] * n + w.rbi[(size_t)nb * w.Rmax + rr]];
       } else {
-        const double* x = cutx + (size_t)w.rcut[(size_t)nb * w.Rmax + rr] * n;
+        const double* x = cutx + (size_t)__shfl(mc, it & 63, WAVE) * n;
         const double* cf = w.rcoef + ((size_t)nb * w.Rmax + rr) * k;
+        const double c0 = __shfl(mf, it & 63, WAVE);
         if (kind == ROW_CUT && lane_ == 0) acc = qrow[rr];
         for (int j = 0; j < k; ++j) {
-          const double cj = cf[j];
+          const double cj = (j == 0) ? c0 : cf[j];
           if (cj != 0.0) for (int i = lane_; i < n; i += WAVE) acc += cj * x[i] * tU[(size_t)j * n + i];
         }
       }
       const double tot = wave_sum(acc);
-      if (lane_ == 0) cvec[rr] = tot - w.rrhs[(size_t)nb * w.Rmax + rr];
+      const double rhs = __shfl(mr, it & 63, WAVE);
+      if (lane_ == 0) cvec[rr] = tot - rhs;
     }
+  }
+  // the slot's Gram matrix goes to xs (idle until step 6 stages the active cut vectors) when it fits: the row projection reads it in
+  // dependent steps on one wave
+  const double* G = w.G + (size_t)b * w.Rmax * w.Rmax;
+  const bool gstage = (size_t)w.Rmax * w.Rmax <= (size_t)GL_XS * n;
+  if (gstage) {
+    for (int e = tid; e < R * w.Rmax; e += T) xs[e] = G[e];
+    G = xs;
   }
   __syncthreads();
   STAMP(10);
   // 4. multipliers (mu = lam / rho)
-  if (tid < WAVE) { const int ov = wave_nnqp(w.G + (size_t)b * w.Rmax * w.Rmax, w.Rmax, cvec, mu, R, s_Gp, s_sv, s_tmp, s_pl, tid); if (tid == 0) w.rowov[b] = ov; }
+  if (tid < WAVE) { const int ov = wave_nnqp(G, w.Rmax, cvec, mu, R, s_Gp, s_sv, s_tmp, s_pl, tid); if (tid == 0) w.rowov[b] = ov; }
   __syncthreads();
   for (int e = tid; e < R; e += T) lam[e] = rho * mu[e];
+  // The rows with mu != 0, listed once in ascending order by wave 0 (s_pl, the projection's passive list, is idle again; the projection
+  // leaves at most NNQP_PMAX of them): all of them for step 5, the cut rows among them (s_act, s_mu) and the sum over the trace rows for
+  // step 6.  The sums that use the lists add their terms in this order, as the loops over all rows did.
+  __shared__ int s_nact; __shared__ int s_act[NNQP_PMAX]; __shared__ double s_mu[NNQP_PMAX]; __shared__ double s_trace_mu;
+  int& s_nnz = s_nc;      // step 3 is over: its counter holds the length of the list
+  if (tid < WAVE) {
+    int c0 = 0, c2 = 0; double tm = 0.0;
+    const unsigned long long below = (1ull << tid) - 1ull;
+    for (int r0 = 0; r0 < R; r0 += WAVE) {
+      const int rr = r0 + tid;
+      const double mv = (rr < R) ? mu[rr] : 0.0;
+      const int kind = (mv != 0.0) ? w.rkind[(size_t)nb * w.Rmax + rr] : -1;
+      const unsigned long long nz = __ballot(mv != 0.0), cut = __ballot(kind == ROW_CUT);
+      unsigned long long trc = __ballot(kind == ROW_TRACE);
+      const int p0 = c0 + __popcll(nz & below), p2 = c2 + __popcll(cut & below);
+      if (mv != 0.0 && p0 < NNQP_PMAX) s_pl[p0] = rr;
+      if (kind == ROW_CUT && p2 < NNQP_PMAX) { s_act[p2] = w.rcut[(size_t)nb * w.Rmax + rr]; s_mu[p2] = mv; }
+      for (; trc; trc &= trc - 1) tm += mu[r0 + __builtin_ctzll(trc)];
+      c0 += __popcll(nz); c2 += __popcll(cut);
+    }
+    if (tid == 0) { s_nnz = (c0 < NNQP_PMAX) ? c0 : NNQP_PMAX; s_nact = (c2 < NNQP_PMAX) ? c2 : NNQP_PMAX; s_trace_mu = tm; }
+  }
+  __syncthreads();
   STAMP(11);
   // 5. U-space correction  corr = A_U' mu / 2  (n x k, stored over tU)  and Vn = tV - Q' corr
+  const int nnz = s_nnz;
   for (int e = tid; e < n * k; e += T) {
     int i = e % n, j = e / n;
     double corr = 0.0;
-    for (int rr = 0; rr < R; ++rr) { double mv = mu[rr]; if (mv != 0.0) corr += mv * rowU_entry(w, nb, rr, i, j); }
+    for (int c = 0; c < nnz; ++c) { const int rr = s_pl[c]; corr += mu[rr] * rowU_entry(w, nb, rr, i, j); }
     tU[e] = 0.5 * corr;
   }
+  // for step 6: the first GL_XS active cut vectors go to xs (the projection is done with the Gram matrix there), the Ritz vectors of the
+  // factored W1 back to s_Gp
+  const int nact = s_nact, nstg = (nact < GL_XS) ? nact : GL_XS;
+  for (int e = tid; e < nstg * n; e += T) { const int a = e / n, i = e - a * n; xs[e] = cutx[(size_t)s_act[a] * n + i]; }
+  if (f1) stage_w1();
   __syncthreads();
   double rp2 = 0.0, rd2 = 0.0, fr2 = 0.0, tr1 = 0.0;
   double* Mb = w.Mbuf + (size_t)b * NP * NP;
@@ -2156,24 +2266,7 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   }
   STAMP(12);
   // 6. Y: every thread owns one entry (all quantities are symmetric, so no mirrored stores: coalesced reads and writes);
-  //    the active cut rows are staged once in LDS
-  __shared__ int s_nact; __shared__ int s_act[NNQP_PMAX]; __shared__ double s_mu[NNQP_PMAX]; __shared__ double s_trace_mu;
-  if (tid == 0) {
-    int c2 = 0; double tm = 0.0;
-    for (int rr = 0; rr < R; ++rr) {
-      const double mv = mu[rr];
-      if (mv == 0.0) continue;
-      const int kind = w.rkind[(size_t)nb * w.Rmax + rr];
-      if (kind == ROW_TRACE) tm += mv;
-      else if (kind == ROW_CUT && c2 < NNQP_PMAX) { s_act[c2] = w.rcut[(size_t)nb * w.Rmax + rr]; s_mu[c2] = mv; ++c2; }
-    }
-    s_nact = c2; s_trace_mu = tm;
-  }
-  __syncthreads();
-  const int nact = s_nact, nstg = (nact < GL_XS) ? nact : GL_XS;      // the first GL_XS active cut vectors are read from LDS
-  for (int e = tid; e < nstg * n; e += T) { const int a = e / n, i = e - a * n; xs[e] = cutx[(size_t)s_act[a] * n + i]; }
-  __syncthreads();
-  if (f1) stage_w1();       // step 4 used s_Gp
+  //    the active cut rows were staged in LDS beside step 5
   // two entries per trip (e and e + T: the order in which each thread adds its terms to the partial sums is unchanged): every load of
   // both is issued before the first store, twice the bytes in flight per wave
   auto corr_at = [&](int i, int j) {
@@ -2202,9 +2295,13 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
     Y[a1] = yn;
     if (w.Yx) w.Yx[(size_t)b * n * n + a1] = 2.0 * yn - yold;      // the matrix the column prox of the next iteration gathers
   };
+  const int di6 = (2 * T) % n, dj6 = (2 * T) / n;      // (i, j) of e and of e + T advance by 2 T entries per trip: no division per entry
+  int i6 = tid % n, j6 = tid / n, ib6 = (tid + T) % n, jb6 = (tid + T) / n;
   for (int e = tid; e < n * n; e += 2 * T) {
     const int eb = e + T; const bool two = eb < n * n;
-    const int i = e % n, j = e / n, ib = two ? eb % n : i, jb = two ? eb / n : j;
+    const int i = i6, j = j6, ib = two ? ib6 : i, jb = two ? jb6 : j;
+    i6 += di6; j6 += dj6; if (i6 >= n) { i6 -= n; ++j6; }
+    ib6 += di6; jb6 += dj6; if (ib6 >= n) { ib6 -= n; ++jb6; }
     const size_t a1 = (size_t)j * n + i, a1b = (size_t)jb * n + ib;
     const double w1 = w1_at(a1, i, j), w1b = two ? w1_at(a1b, ib, jb) : 0.0;      // first (see step 2)
     const double corr = corr_at(i, j), corrb = two ? corr_at(ib, jb) : 0.0;
@@ -2267,7 +2364,7 @@ __global__ void __launch_bounds__(512) k_check_build(OmcWS w) {
   __syncthreads();
   const double* al = w.alphaX + (size_t)b * w.nnz;
   if (w.lamDX) {     // dense copy of the exact multipliers (k_colprox mode 1): one MFMA product instead of m scattered rank-one updates
-    mfma_LLt(w.lamDX + (size_t)b * m * n, n, m, [&](int i, int j, double v) {
+    mfma_LLt<1>(w.lamDX + (size_t)b * m * n, n, m, [&](int i, int j, double v) {
       const double t = 0.5 * g * v;
       M[(size_t)j * n + i] -= t;
       if (i != j) M[(size_t)i * n + j] -= t;
@@ -2691,7 +2788,7 @@ static void launch_ws_lds(const OmcWS* w, hipStream_t s) {
 __global__ void __launch_bounds__(256) k_gram_XXt(OmcWS w, const double* X) {
   const int b = blockIdx.x, n = w.n;
   double* Y = w.Y + (size_t)b * n * n;
-  mfma_LLt(X + (size_t)b * n * w.m, n, w.m, [&](int i, int j, double v) { Y[(size_t)j * n + i] = v; Y[(size_t)i * n + j] = v; });
+  mfma_LLt<1>(X + (size_t)b * n * w.m, n, w.m, [&](int i, int j, double v) { Y[(size_t)j * n + i] = v; Y[(size_t)i * n + j] = v; });
 }
 extern "C" {
 void omc_launch_gram_XXt(const OmcWS* w, const double* X, int B, hipStream_t s) { hipLaunchKernelGGL(k_gram_XXt, dim3(B), dim3(256), 0, s, *w, X); }
