@@ -262,6 +262,12 @@ int omc_violated_shor_minors(omc_instance* h, const double* X, int n_classes, co
                              int64_t* minors, int* n_out);
 /* device milliseconds and candidate count of the last omc_shor_indexes / omc_violated_shor_minors call */
 int omc_shor_last_stats(omc_instance* h, double* ms, int64_t* candidates);
+/* How the last omc_violated_shor_minors call selected: out[0] = 1 if it streamed (no key per candidate in memory; taken when 16 bytes per
+ * candidate exceed the knob OMC_SHOR_SELECT_KB, default 1 GiB, 0 = never), out[1] = tiles of row pairs it walked, out[2] = compactions of
+ * the survivor buffer, out[3] = bytes of candidate keys (materialised: 16 per candidate) or of the survivor buffer (streamed:
+ * max(budget, 16 (K + 8192 + largest candidate count of one row pair)), K the number of minors returned) it asked the device for.  The
+ * output scratch of the select, 16 (K + 8192 + 16) bytes on either path, is not included.  The results do not depend on the path. */
+int omc_shor_last_select_stats(omc_instance* h, int64_t out[4]);
 
 /* ---- multi-GPU: node-parallel B&B, one process per GPU ------------------------------------------------------
  * Nodes are independent given (A, indices, gamma): every rank holds its own omc_instance on its own device and relaxes its shard

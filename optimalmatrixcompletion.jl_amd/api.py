@@ -483,6 +483,13 @@ class Engine:
         _lib.check(self._lib.omc_shor_last_stats(self._h, _lib.ptr(ms), _lib.ptr(c)))
         return {"ms": float(ms[0]), "candidates": int(c[0])}
 
+    def shor_last_select_stats(self):
+        """How the last generate_violated_Shor_minors call selected (omc_shor_last_select_stats): `streamed` is 1 when no key per candidate
+        was kept in device memory (knob OMC_SHOR_SELECT_KB), `peak_bytes` the key / survivor memory it asked for."""
+        o = np.zeros(4, dtype=np.int64)
+        _lib.check(self._lib.omc_shor_last_select_stats(self._h, _lib.ptr(o)))
+        return {"streamed": int(o[0]), "tiles": int(o[1]), "compactions": int(o[2]), "peak_bytes": int(o[3])}
+
     def evaluate_objective(self, X):
         X = np.asarray(X, dtype=np.float64)
         single = X.ndim == 2

@@ -21,6 +21,12 @@ void omc_shor_launch_enum_tuples(int n, int m, int W, const uint64_t* bits, int 
 void omc_shor_launch_enum_keys(int n, int m, int W, const uint64_t* bits, int kind, int la, int lb, const long long* off,
                                long long npairs, const double* X, int k, const uint64_t* existing, long long n_existing,
                                uint64_t* hi, uint64_t* lo, unsigned long long* n_excluded, hipStream_t s);
+/* pairs [t0, t1) of one segment: candidates with key >= (thi, tlo) that are not in `existing` are appended to (hi, lo)[0 .. cap) at
+ * *counter, which keeps counting past cap (then *overflow = 1 and the survivor is dropped) */
+void omc_shor_launch_enum_stream(int n, int m, int W, const uint64_t* bits, int kind, int la, int lb, long long t0, long long t1,
+                                 const double* X, int k, const uint64_t* existing, long long n_existing, uint64_t thi, uint64_t tlo,
+                                 uint64_t* hi, uint64_t* lo, unsigned long long* counter, unsigned long long cap, unsigned int* overflow,
+                                 hipStream_t s);
 void omc_shor_launch_hist(long long N, const uint64_t* hi, const uint64_t* lo, uint64_t phi, uint64_t plo, int level,
                           unsigned long long* hist, hipStream_t s);
 void omc_shor_launch_emit(long long N, const uint64_t* hi, const uint64_t* lo, uint64_t bhi, uint64_t blo, uint64_t* ohi, uint64_t* olo,

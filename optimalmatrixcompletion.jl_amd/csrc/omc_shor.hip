@@ -16,6 +16,9 @@
 // consecutive lanes write consecutive 32-byte tuples).  The same enumerator feeds the violated-minor scorer, which
 // writes a 128-bit key (score bits, tuple rank) per candidate; the top n_minors are found by an MSD radix select over
 // the keys (8-bit digits, LDS histograms), i.e. the reference's partialsort! on (score, tuple) tuples, rev = true.
+// When the keys of all candidates would not fit a memory budget the scorer does not write them: a third writer of the
+// enumerator keeps only the candidates at or above a threshold key and appends them to a bounded survivor buffer, and the
+// host raises the threshold between tiles of row pairs by running the same radix select on that buffer.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "omc_shor.h"
@@ -95,7 +98,10 @@ __global__ void __launch_bounds__(1024) k_shor_seg_scan(int kind, int la, int lb
 }
 
 // ---- enumeration: one wave per row pair ---------------------------------------------------------------------------
+// A writer is either positional (kWave = false: called per candidate with its index in the push order) or wave-wide (kWave = true:
+// called by all 64 lanes of the wave for each group of 64 consecutive candidates, `on` false in the lanes past the end).
 struct TupleWriter {   // a10: 1-based (i1, i2, j1, j2) as Int64, the reference's NTuple{4, Int}
+  static constexpr bool kWave = false;
   long long* out;
   __device__ __forceinline__ void operator()(long long idx, int i1, int i2, int j1, int j2) const {
     long long* o = out + 4 * idx;
@@ -103,6 +109,7 @@ struct TupleWriter {   // a10: 1-based (i1, i2, j1, j2) as Int64, the reference'
   }
 };
 struct KeyWriter {     // a11: (score bits, tuple rank); candidates found in `existing` become the lowest key (0, 0)
+  static constexpr bool kWave = false;
   const double* X; int k, n, m;
   const uint64_t* existing; long long n_existing;
   uint64_t *hi, *lo; unsigned long long* n_excluded;
@@ -123,14 +130,64 @@ struct KeyWriter {     // a11: (score bits, tuple rank); candidates found in `ex
   }
 };
 
+// a11 without materialised keys: the key of KeyWriter is formed in registers and kept only if it is >= the threshold (thi, tlo) of the
+// launch (kernel arguments, hence scalar registers: nothing is read per candidate).  Only a candidate that passes is looked up in
+// `existing`.  Survivors are appended to (hi, lo)[0 .. cap): one atomic per wave and group of 64 candidates reserves the slots, the
+// lane's slot is its rank among the passing lanes.  The counter keeps counting past `cap`; those survivors are dropped and the flag set.
+struct StreamWriter {
+  static constexpr bool kWave = true;
+  const double* X; int k, n, m;
+  const uint64_t* existing; long long n_existing;
+  uint64_t thi, tlo;
+  uint64_t *hi, *lo; unsigned long long* counter; unsigned long long cap; unsigned int* overflow;
+  __device__ __forceinline__ void operator()(bool on, int i1, int i2, int j1, int j2) const {
+#pragma clang fp contract(off)   // the same expression, in the same order, as KeyWriter: identical doubles
+    const uint64_t key = (((uint64_t)i1 * n + i2) * m + j1) * m + j2 + 1;
+    const double* x11 = X + (size_t)k * (i1 + (size_t)n * j1);
+    const double* x22 = X + (size_t)k * (i2 + (size_t)n * j2);
+    const double* x12 = X + (size_t)k * (i1 + (size_t)n * j2);
+    const double* x21 = X + (size_t)k * (i2 + (size_t)n * j1);
+    double s = 0.0;
+    for (int t = 0; t < k; ++t) { const double p1 = x11[t] * x22[t], p2 = x12[t] * x21[t]; s = s + fabs(p1 - p2); }
+    const uint64_t h = (uint64_t)__double_as_longlong(s);
+    bool pass = on && (h > thi || (h == thi && key >= tlo));
+    if (pass) {
+      long long a = 0, b = n_existing;
+      while (a < b) { const long long c = (a + b) >> 1; if (existing[c] < key) a = c + 1; else b = c; }
+      if (a < n_existing && existing[a] == key) pass = false;
+    }
+    const unsigned long long vote = __ballot(pass);
+    if (vote == 0ULL) return;                        // wave-uniform
+    const int lane = threadIdx.x & 63;
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(counter, (unsigned long long)__popcll(vote));
+    base = __shfl(base, 0, SH_WAVE);
+    if (pass) {
+      const unsigned long long p = base + __builtin_amdgcn_mbcnt_hi((unsigned)(vote >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)vote, 0u));
+      if (p < cap) { hi[p] = h; lo[p] = key; }
+      else *overflow = 1u;
+    }
+  }
+};
+
+__device__ __forceinline__ void combo_from_index(int e, int na, double bq, int& p, int& q) {
+  // e = p (2 na - p - 1) / 2 + (q - p - 1), 0 <= p < q < na
+  p = (int)floor((bq - sqrt(bq * bq - 8.0 * (double)e)) * 0.5);
+  if (p < 0) p = 0;
+  while (p > 0 && p * (2 * na - p - 1) / 2 > e) --p;
+  while ((p + 1) * (2 * na - (p + 1) - 1) / 2 <= e) ++p;
+  q = e - p * (2 * na - p - 1) / 2 + p + 1;
+}
+
+// pairs [t0, t1) of the segment; a positional writer gets the candidate's index off[t] + e
 template <class F>
 __global__ void __launch_bounds__(256) k_shor_enum(int n, int m, int W, const uint64_t* bits, int kind, int la, int lb_,
-                                                   const long long* off, long long npairs, F f) {
+                                                   const long long* off, long long t0, long long t1, F f) {
   extern __shared__ int s_lists[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wpb = blockDim.x >> 6;
   int* LA = s_lists + (size_t)wv * 2 * m;
   int* LB = LA + m;
-  for (long long t = (long long)blockIdx.x * wpb + wv; t < npairs; t += (long long)gridDim.x * wpb) {
+  for (long long t = t0 + (long long)blockIdx.x * wpb + wv; t < t1; t += (long long)gridDim.x * wpb) {
     int i1, i2;
     pair_from_index(t, n, i1, i2);
     const uint64_t* r1 = bits + (size_t)i1 * W;
@@ -149,24 +206,41 @@ __global__ void __launch_bounds__(256) k_shor_enum(int n, int m, int W, const ui
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const long long o = off[t];
     if (kind == SH_COMBO) {
       const int cnt = na * (na - 1) / 2;
       const double bq = 2.0 * na - 1.0;
-      for (int e = lane; e < cnt; e += SH_WAVE) {
-        int p = (int)floor((bq - sqrt(bq * bq - 8.0 * (double)e)) * 0.5);
-        if (p < 0) p = 0;
-        while (p > 0 && p * (2 * na - p - 1) / 2 > e) --p;
-        while ((p + 1) * (2 * na - (p + 1) - 1) / 2 <= e) ++p;
-        const int q = e - p * (2 * na - p - 1) / 2 + p + 1;
-        f(o + e, i1, i2, LA[p], LA[q]);
+      if constexpr (F::kWave) {
+        for (int e0 = 0; e0 < cnt; e0 += SH_WAVE) {
+          const bool on = e0 + lane < cnt;
+          int p, q;
+          combo_from_index(on ? e0 + lane : 0, na, bq, p, q);   // cnt > 0: na >= 2, index 0 is a valid candidate
+          f(on, i1, i2, LA[p], LA[q]);
+        }
+      } else {
+        const long long o = off[t];
+        for (int e = lane; e < cnt; e += SH_WAVE) {
+          int p, q;
+          combo_from_index(e, na, bq, p, q);
+          f(o + e, i1, i2, LA[p], LA[q]);
+        }
       }
     } else {
       const unsigned cnt = (unsigned)na * (unsigned)nb;   // m <= 8192: fits 32 bits
-      for (unsigned e = lane; e < cnt; e += SH_WAVE) {
-        const int p = (int)(e / (unsigned)nb), q = (int)(e - (unsigned)p * (unsigned)nb);
-        const int ja = LA[p], jb = LB[q];
-        f(o + e, i1, i2, min(ja, jb), max(ja, jb));
+      if constexpr (F::kWave) {
+        for (unsigned e0 = 0; e0 < cnt; e0 += SH_WAVE) {
+          const bool on = e0 + lane < cnt;
+          const unsigned e = on ? e0 + lane : 0u;
+          const int p = (int)(e / (unsigned)nb), q = (int)(e - (unsigned)p * (unsigned)nb);
+          const int ja = LA[p], jb = LB[q];
+          f(on, i1, i2, min(ja, jb), max(ja, jb));
+        }
+      } else {
+        const long long o = off[t];
+        for (unsigned e = lane; e < cnt; e += SH_WAVE) {
+          const int p = (int)(e / (unsigned)nb), q = (int)(e - (unsigned)p * (unsigned)nb);
+          const int ja = LA[p], jb = LB[q];
+          f(o + e, i1, i2, min(ja, jb), max(ja, jb));
+        }
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -232,7 +306,7 @@ void omc_shor_launch_enum_tuples(int n, int m, int W, const uint64_t* bits, int 
   enum_geometry(m, npairs, wpb, blocks, lds);
   if (blocks <= 0) return;
   TupleWriter f{out};
-  hipLaunchKernelGGL(k_shor_enum<TupleWriter>, dim3(blocks), dim3(wpb * 64), lds, s, n, m, W, bits, kind, la, lb, off, npairs, f);
+  hipLaunchKernelGGL(k_shor_enum<TupleWriter>, dim3(blocks), dim3(wpb * 64), lds, s, n, m, W, bits, kind, la, lb, off, 0LL, npairs, f);
 }
 void omc_shor_launch_enum_keys(int n, int m, int W, const uint64_t* bits, int kind, int la, int lb, const long long* off,
                                long long npairs, const double* X, int k, const uint64_t* existing, long long n_existing,
@@ -241,7 +315,17 @@ void omc_shor_launch_enum_keys(int n, int m, int W, const uint64_t* bits, int ki
   enum_geometry(m, npairs, wpb, blocks, lds);
   if (blocks <= 0) return;
   KeyWriter f{X, k, n, m, existing, n_existing, hi, lo, n_excluded};
-  hipLaunchKernelGGL(k_shor_enum<KeyWriter>, dim3(blocks), dim3(wpb * 64), lds, s, n, m, W, bits, kind, la, lb, off, npairs, f);
+  hipLaunchKernelGGL(k_shor_enum<KeyWriter>, dim3(blocks), dim3(wpb * 64), lds, s, n, m, W, bits, kind, la, lb, off, 0LL, npairs, f);
+}
+void omc_shor_launch_enum_stream(int n, int m, int W, const uint64_t* bits, int kind, int la, int lb, long long t0, long long t1,
+                                 const double* X, int k, const uint64_t* existing, long long n_existing, uint64_t thi, uint64_t tlo,
+                                 uint64_t* hi, uint64_t* lo, unsigned long long* counter, unsigned long long cap, unsigned int* overflow,
+                                 hipStream_t s) {
+  int wpb, blocks; size_t lds;
+  enum_geometry(m, t1 - t0, wpb, blocks, lds);
+  if (blocks <= 0) return;
+  StreamWriter f{X, k, n, m, existing, n_existing, thi, tlo, hi, lo, counter, cap, overflow};
+  hipLaunchKernelGGL(k_shor_enum<StreamWriter>, dim3(blocks), dim3(wpb * 64), lds, s, n, m, W, bits, kind, la, lb, nullptr, t0, t1, f);
 }
 void omc_shor_launch_hist(long long N, const uint64_t* hi, const uint64_t* lo, uint64_t phi, uint64_t plo, int level,
                           unsigned long long* hist, hipStream_t s) {
