@@ -244,6 +244,27 @@ int omc_round_Y_batch(omc_instance* h, int B, const double* Y, double* U_rounded
  * (OMC.jl:524, 564, 921).  Gram product X X' on the matrix cores, then the k dominant eigenvectors; sign as omc_round_Y_batch. */
 int omc_left_singular_batch(omc_instance* h, int B, const double* X, double* U_out);
 
+/* ---- the cone projections on their own (OMC.jl:1554-1556 are the cones they serve) -----------------------
+ * Spectral clip of B symmetric matrices of order N (column-major, N*N doubles each):
+ * P = V diag(min(max(lambda, lo), hi)) V'.  lo = 0, hi = +inf is the projection on the PSD cone; lo = 0, hi = 1 the clip of
+ * 0 <= Y <= I.  evals (B*N, ascending) and V (B*N*N, columns in the order of evals) may be NULL.  V0 (may be NULL): an
+ * orthonormal starting basis per matrix, e.g. the V of an earlier call on a nearby matrix (the solver's warm start).
+ * algo: 0 = what a relaxation at this order uses under the instance's knobs, 1 = single-workgroup kernels, 2 = multi-workgroup.
+ * N is independent of the instance's n and m; N >= 2; OMC_ERR_UNSUPPORTED above 4096.  The kernels clip at 0 from below:
+ * OMC_ERR_UNSUPPORTED for lo != 0, and for evals / V where the single-workgroup path is the cold kernel, which returns P only
+ * (orders 129 - 144 and above 1024). */
+int omc_psd_project_batch(omc_instance* h, int B, int N, const double* M, double lo, double hi, int algo,
+                          const double* V0, double* P, double* evals, double* V);
+/* out[5] of the multi-workgroup eigen-kernels in the last omc_relax_solve (base cone and big cone of Shor mode together), or of the last
+ * omc_psd_project_batch (either algo): calls, most sweeps of one call (at the last check of a solve), calls that used up their sweep
+ * budget without meeting the stop rule, most sweeps of one call overall, device microseconds of the last omc_psd_project_batch
+ * (the kernels alone, transfers outside; 0 after a solve) */
+int omc_last_cone_multi_stats(omc_instance* h, int64_t* out);
+/* The sweep budget omc_relax_solve gives the next multi-workgroup calls of a cone at a certificate check.  interval_max: most sweeps of
+ * one call since the last check, 0 when that interval had no call.  What the last interval needed + 2, at most the full bound (30); the
+ * full bound after an interval without a call (the next call starts from a stale basis). */
+int omc_cone_multi_budget(int interval_max);
+
 /* ---- Shor minors ------------------------------------------------------------------------------------------
  * generate_rank1_matrix_completion_Shor_constraints_indexes (OMC.jl:2545-2612): the 2 x 2 minors (i1 < i2, j1 < j2) whose
  * four cells hold exactly p observed entries, for every p of `num_entries_present` in turn (values outside 0..4

@@ -422,6 +422,43 @@ class Engine:
         _lib.check(self._lib.omc_left_singular_batch(self._h, B, _lib.ptr(Xb), _lib.ptr(U)))
         return [U[b].reshape((n, k), order="F") for b in range(B)]
 
+    def psd_project(self, M, lo=0.0, hi=np.inf, algo=0, V0=None, want_evals=False, want_V=False):
+        """Spectral clip P = V diag(min(max(lambda, lo), hi)) V' of one symmetric matrix (N x N) or a batch (B x N x N) by the eigen-kernels of
+        the relaxation (omc_psd_project_batch; the cones of OMC.jl:1554-1556).  algo: 0 = what a relaxation at this order uses, 1 = single-
+        workgroup kernels, 2 = multi-workgroup.  V0: orthonormal starting basis (the V of an earlier call on a nearby matrix).  Returns P, or
+        (P, evals, V) with the parts asked for (evals ascending, V's columns in their order), shaped like M."""
+        Ma = np.asarray(M, dtype=np.float64)
+        single = Ma.ndim == 2
+        Mb = Ma[None] if single else Ma
+        if Mb.ndim != 3 or Mb.shape[1] != Mb.shape[2]:
+            raise ValueError("psd_project: M must be N x N or B x N x N")
+        B, N = Mb.shape[0], Mb.shape[1]
+        flat = lambda X: np.ascontiguousarray(np.stack([np.asfortranarray(x).ravel(order="F") for x in X]))
+        Mf = flat(Mb)
+        V0f = None
+        if V0 is not None:
+            V0b = np.asarray(V0, dtype=np.float64)
+            V0b = V0b[None] if V0b.ndim == 2 else V0b
+            if V0b.shape != Mb.shape:
+                raise ValueError("psd_project: V0 must have the shape of M")
+            V0f = flat(V0b)
+        P = np.zeros((B, N * N))
+        ev = np.zeros((B, N)) if want_evals else None
+        V = np.zeros((B, N * N)) if want_V else None
+        _lib.check(self._lib.omc_psd_project_batch(self._h, B, N, _lib.ptr(Mf), float(lo), float(hi), int(algo), _lib.ptr(V0f), _lib.ptr(P),
+                                                   _lib.ptr(ev), _lib.ptr(V)))
+        unflat = lambda X: np.stack([X[b].reshape((N, N), order="F") for b in range(B)])
+        out = [unflat(P)] + ([ev] if want_evals else []) + ([unflat(V)] if want_V else [])
+        if single:
+            out = [o[0] for o in out]
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def cone_multi_stats(self):
+        """Sweep accounting of the multi-workgroup eigen-kernels in the last solve, or of the last psd_project call (omc_last_cone_multi_stats)."""
+        out = np.zeros(5, np.int64)
+        _lib.check(self._lib.omc_last_cone_multi_stats(self._h, _lib.ptr(out)))
+        return dict(calls=int(out[0]), last_sweeps=int(out[1]), exhausted=int(out[2]), max_sweeps=int(out[3]), device_us=int(out[4]))
+
     def alternating_minimization(self, U_initials, nodes=None, disjunctive_cuts_type="linear", eps=1e-5, max_iters=100,
                                  time_limit=3600.0, reference_quirk_q1=True):
         """Batch form of OMC.jl:1979-2279 (use_disjunctive_cuts = true).  Returns dicts with the reference's keys

@@ -81,6 +81,7 @@ struct Tuning {
   bool segv_trace = false;         // OMC_SEGV_TRACE: print the native frames of a crashing thread
   bool shor_explicit = false;      // OMC_SHOR_EXPLICIT: rank k > 1 Shor batches by the Shor engine even where the base engine would serve them
   bool shor_no_subspace = false;   // OMC_SHOR_NO_SUBSPACE: no tracked subspace for the order-(n+m) cone of Shor mode
+  int cone_multi_min = 1025;       // OMC_CONE_MULTI_MIN: cone orders from this value on (never below 145) take the multi-workgroup eigen-kernels; the default is where only the cold kernel existed
   int graph_max = 16;              // OMC_GRAPH_MAX: hipGraph replay for batches staged with at most this many nodes
   int shor_select_kb = 1048576;    // OMC_SHOR_SELECT_KB: violated-minor selection streams (no materialised keys) when 16 B per candidate exceed this many KiB; 0 = always materialise
   int streams = 4;                 // OMC_STREAMS: <= 1 serialises a solve on one stream
@@ -96,6 +97,7 @@ static const Knob OMC_KNOBS[] = {
   {"OMC_NO_GRAPH", &Tuning::no_graph, nullptr},              {"OMC_NO_SUBSPACE", &Tuning::no_subspace, nullptr},
   {"OMC_NO_WS_SPLIT", &Tuning::no_ws_split, nullptr},        {"OMC_SEGV_TRACE", &Tuning::segv_trace, nullptr},
   {"OMC_SHOR_EXPLICIT", &Tuning::shor_explicit, nullptr},    {"OMC_SHOR_NO_SUBSPACE", &Tuning::shor_no_subspace, nullptr},
+  {"OMC_CONE_MULTI_MIN", nullptr, &Tuning::cone_multi_min},
   {"OMC_GRAPH_MAX", nullptr, &Tuning::graph_max},            {"OMC_SHOR_SELECT_KB", nullptr, &Tuning::shor_select_kb},
   {"OMC_STREAMS", nullptr, &Tuning::streams},
   {"OMC_SUB_DEBUG", nullptr, &Tuning::sub_debug},            {"OMC_SUB_QMAX", nullptr, &Tuning::sub_qmax},
@@ -144,6 +146,8 @@ struct omc_instance {
   DevBuf bslotlist, bgap, bvotes, blamDX, bXsC, bsubSC, bsubIC;
   DevBuf bsubz, bscal, bbx, bint, bcp, bcone, bglob, bXout, bThout, bXin, bMbuf, bVrow, bXs, bsubS, bsubI;
   long long sub_tot[8] = {0};
+  DevBuf bmwstat, sbigmw, pjM, pjV, pjW, pjS, pjD, pjI;      // sweep statistics of the multi-workgroup eigen-kernels (base workspace, Shor view) ; buffers of omc_psd_project_batch
+  long long mw_tot[5] = {0};      // omc_last_cone_multi_stats
   OmcWS ws{};
   omc_relax_params params{};
   bool staged = false;
@@ -499,6 +503,11 @@ static int put_descriptors(const OmcWS& w, const NodePack& pk, int B, size_t row
 
 // fixed parameters of the eigen-kernels and the column kernel (OmcWS fields)
 static constexpr int MAX_SWEEPS = 30;          // sweep cap of the warm-started Jacobi kernel (k_cone_ws)
+// Sweep budget of the next multi-workgroup calls of a view (omc_relax_solve reads the counts at a certificate check).  interval_max: most
+// sweeps of a call since the last check, 0 = no call in that interval.  Warm calls: what the last interval needed + 2.  After an interval
+// without a call the next one is a fall-back from a basis that has gone stale by an unknown amount (on a warm-started solve not even the
+// first calls were cold): the full bound -- the launches of the sweeps not needed leave at once.  Exported for the tests.
+int omc_cone_multi_budget(int interval_max) { return interval_max > 0 ? std::min(MAX_SWEEPS, interval_max + 2) : MAX_SWEEPS; }
 static constexpr int CP_SERIES = 6;            // Neumann-series order of k_colprox_pair's finish
 static constexpr int CP_MAXPASS = 60;          // cap on the secular passes of k_colprox_pair
 static constexpr int SUB_GUARD = 2;            // Ritz values of the tracked block that must stay negative
@@ -722,7 +731,9 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   w.rbi = h->brbi.as<int>(); w.rbj = h->brbj.as<int>(); w.rcoef = h->brcoef.as<double>(); w.rrhs = h->brrhs.as<double>(); w.cutx = h->bcutx.as<double>();
   if ((rc_ = put_descriptors(w, pk, B, sN, 0, L, cut_x, h->stream))) return rc_;
   // LDS / scratch decisions: one planner (omc_layout.h), the slabs allocated from the strides it reports
-  w.geo = omc_plan_geometry(n, w.np16, k, rmax, Rmax, h->cmax, h->tun.global_nolds);
+  w.geo = omc_plan_geometry(n, w.np16, k, rmax, Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
+  ENS(h->bmwstat, sB * 4 * sizeof(int)); HIPCHK(hipMemsetAsync(h->bmwstat.p, 0, sB * 4 * sizeof(int), h->stream));
+  w.mw_stat = h->bmwstat.as<int>(); w.mw_budget = MAX_SWEEPS; w.ev_out = nullptr;
   if (w.geo.cp_scratch_stride) { ENS(h->bcp, sB * m * w.geo.cp_scratch_stride * 8); w.cp_scratch = h->bcp.as<double>(); }
   if (w.geo.ws.slab_stride) { ENS(h->bcone, sB * w.geo.ws.slab_stride * 8); w.cone_scratch = h->bcone.as<double>(); }
   if (w.geo.glob.slab_stride) { ENS(h->bglob, sB * w.geo.glob.slab_stride * 8); w.glob_scratch = h->bglob.as<double>(); }
@@ -885,6 +896,31 @@ int omc_relax_solve(omc_instance* h) {
   // The full eigen-kernel runs the slots that have no tracked block (or are backing off) -- a handful per launch, each a long single-workgroup
   // job, known before the iteration starts (ws_first) -- on a stream of its own beside k_cone_sub; what k_cone_sub then could not do (a failed
   // call, ~1 in 30 000) is a second, almost empty launch behind both.  One launch after k_cone_sub made every iteration wait for the sum.
+  // Multi-workgroup eigen-kernels (geo.mw): a call is a sequence of launches whose sweep budget the host fixes when it enqueues them.  The
+  // budget is the full bound while a slot may be on its first call (cold start), else the most sweeps a call needed since the last check + 2
+  // (read at the check, where the host synchronises anyway).  An interval without a call (the tracked block served every slot) says nothing
+  // about the next one, a fall-back from a basis that has gone stale: omc_cone_multi_budget then gives the full bound again.
+  // [0] base cone, [1] big cone of Shor mode; the certificate launches keep the bound.
+  const bool mw_any = w.geo.mw || (shor && h->wbig.geo.mw);
+  int mw_budget[2] = {MAX_SWEEPS, MAX_SWEEPS};
+  for (int q = 0; q < 5; ++q) h->mw_tot[q] = 0;
+  auto mw_collect = [&]() -> int {      // statistics since the last call of this function -> totals and the next budgets
+    if (!mw_any) return 0;
+    std::vector<int> st(4 * (size_t)S);
+    for (int v = 0; v < 2; ++v) {
+      const OmcWS& wv = v ? h->wbig : w;
+      if (!(v ? shor && wv.geo.mw : wv.geo.mw)) continue;
+      HIPCHK(hipMemcpyAsync(st.data(), wv.mw_stat, sizeof(int) * st.size(), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      HIPCHK(hipMemsetAsync(wv.mw_stat, 0, sizeof(int) * st.size(), s));
+      int mx = 0;
+      for (int b = 0; b < S; ++b) { h->mw_tot[0] += st[4 * b]; h->mw_tot[2] += st[4 * b + 2]; mx = std::max(mx, st[4 * b + 3]); }
+      if (mx) h->mw_tot[1] = mx;      // an interval without a call keeps the last figure
+      h->mw_tot[3] = std::max<long long>(h->mw_tot[3], mx);
+      mw_budget[v] = omc_cone_multi_budget(mx);
+    }
+    return 0;
+  };
   const bool split = multi && !tun.no_ws_split && w.sub_enable && w.geo.ws_lpp && w.ws_first;
   auto body = [&](const OmcWS& wg, bool timed, bool with_aa, bool capturing) -> int {
     hipEvent_t* const ev = capturing ? h->gevc : h->gev;
@@ -899,9 +935,10 @@ int omc_relax_solve(omc_instance* h) {
       OmcWS wb = h->wbig; wb.nB = wg.nB; wb.slot_list = wg.slot_list;
       if (w.sub_enable) MAYBE_TIMED(sm, OMC_KERNEL_CONESUB, gact, omc_launch_cone_sub(&wg, sm));
       if (wb.sub_enable) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, 0, omc_launch_cone_sub(&wb, sb));
-      if (wb.geo.ws_lpp) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone_ws(&wb, sb));
+      wb.mw_budget = mw_budget[1];
+      if (wb.geo.ws_lpp || wb.geo.mw) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone_ws(&wb, sb));
       else MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone(&wb, CONE_BIG, sb));
-      if (w.geo.ws_lpp) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
+      if (w.geo.ws_lpp || w.geo.mw) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
       else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, sm));
       MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
       MAYBE_TIMED(sc, OMC_KERNEL_SHOR_MINORS, gact, { omc_shor_launch_minor_pre(&sw, sc); omc_shor_launch_vkeys(&sw, sc); });
@@ -929,7 +966,7 @@ int omc_relax_solve(omc_instance* h) {
       OmcWS wB = wg; wB.ws_phase = 2;
       MAYBE_TIMED(sm, OMC_KERNEL_CONE, 0, omc_launch_cone_ws(&wB, sm));
     }
-    else if (w.geo.ws_lpp) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
+    else if (w.geo.ws_lpp || w.geo.mw) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
     else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, sm));
     if (!split) MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
     if (multi) {
@@ -948,6 +985,7 @@ int omc_relax_solve(omc_instance* h) {
     if (!ninit2) return 0;
     int rc = push_flags(init2, fin2); if (rc) return rc;
     TIMED(OMC_KERNEL_SETUP, ninit2, omc_launch_setup(&w, s));
+    mw_budget[0] = mw_budget[1] = MAX_SWEEPS;
     recount();
     rc = push_list(); if (rc) return rc;
     wait_main = true;
@@ -974,9 +1012,9 @@ int omc_relax_solve(omc_instance* h) {
     // per-kernel HIP-event timing brackets every launch of a sampled iteration (two event records per kernel: ~25 us of queue bubbles per
     // iteration at small batches); OMC_TIMING_STRIDE=s samples every s-th iteration (averages per launch are over the sampled launches), 0 = none
     const bool sampled = tun.timing_stride > 0 && (it % tun.timing_stride) == 0;
-    const bool use_graph = multi && nlist <= graph_max && !tun.no_graph && !(sampled && tun.timing_stride > 1);
+    const bool use_graph = multi && nlist <= graph_max && !tun.no_graph && !(sampled && tun.timing_stride > 1) && !mw_any;      // hundreds of launches per call: eager
     if (gact > 0) {
-      OmcWS wg = w; wg.slot_list = h->bslotlist.as<int>(); wg.nB = nlist;
+      OmcWS wg = w; wg.slot_list = h->bslotlist.as<int>(); wg.nB = nlist; wg.mw_budget = mw_budget[0];
       if (multi && wait_main) HIPCHK(hipStreamWaitEvent(sm, h->ev_main, 0));
       if (use_graph) {
         if (gexec_n != nlist) {      // (re)capture: one graph without and one with the acceleration kernel at its end
@@ -1019,7 +1057,7 @@ int omc_relax_solve(omc_instance* h) {
         OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, s);
         omc_launch_check_final(&w, timed_out ? OMC_ST_TIME : 0, 1, s);
       } else {
-        if (w.geo.ws_lpp) { OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, s); }
+        if (w.geo.ws_lpp || w.geo.mw) { OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, s); }
         else omc_launch_cone(&w, CONE_EVALS, s);
         omc_launch_check_final(&w, timed_out ? OMC_ST_TIME : 0, 2, s);      // per-slot iteration cap is applied on the device
       }
@@ -1028,6 +1066,7 @@ int omc_relax_solve(omc_instance* h) {
     });
     HIPCHK(hipMemcpyAsync(done.data(), w.done, sizeof(int) * S, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    { int rc = mw_collect(); if (rc) return rc; }
     finish_events(h);      // every timed launch of the interval has joined s (the side streams join sm before k_global, sm joins s at a check)
     Btot = h->Btot_live.load();
     if (P.first_wins) {   // the first certified node ends the batch (penalty autotune): everything still running is harvested as it stands
@@ -1082,13 +1121,14 @@ int omc_relax_solve(omc_instance* h) {
       }
       rc = push_flags(init, fin); if (rc) return rc;      // synchronises the stream: the harvest kernels have written the per-node outputs
       { std::lock_guard<std::mutex> lk(h->done_mu); h->done_q.insert(h->done_q.end(), harvested_ids.begin(), harvested_ids.end()); }
-      if (ninit) { if (shor) omc_shor_launch_setup(&sw, s); TIMED(OMC_KERNEL_SETUP, ninit, omc_launch_setup(&w, s)); }
+      if (ninit) { if (shor) omc_shor_launch_setup(&sw, s); TIMED(OMC_KERNEL_SETUP, ninit, omc_launch_setup(&w, s)); mw_budget[0] = mw_budget[1] = MAX_SWEEPS; }
     }
     recount();
     if (nfin || nnew) { int rc = push_list(); if (rc) return rc; }
     if (next < Btot && !timed_out && nactive < S) { int rc = refill_idle(); if (rc) return rc; }      // appended nodes for slots that had gone idle
     if (timed_out) { int rc = close_unslotted(OMC_ST_TIME); if (rc) return rc; }
   }
+  { int rc = mw_collect(); if (rc) return rc; }
   {
     std::vector<int> sw(S);
     HIPCHK(hipMemcpyAsync(sw.data(), w.sweeps, sizeof(int) * S, hipMemcpyDeviceToHost, s));
@@ -1536,7 +1576,9 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   wb.n = N; wb.np16 = NPb; wb.Mbuf = sh.MbufB; wb.Vrow = sh.VrowB; wb.vvalid = sh.vvalidB; wb.fro2 = sh.fro2B; wb.W1 = sh.P0;
   wb.sub_enable = 0; wb.cert_enable = 0; wb.ws_mode = 0; wb.clip_hi = 1e300; wb.sub_debug = 0; wb.ws_first = nullptr; wb.ws_phase = 0;
   // the view's own geometry (only the eigen-kernels are launched through it)
-  wb.geo = omc_plan_geometry(N, NPb, wb.k, wb.rmax, wb.Rmax, h->cmax, h->tun.global_nolds);
+  wb.geo = omc_plan_geometry(N, NPb, wb.k, wb.rmax, wb.Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
+  ENS(h->sbigmw, sB * 4 * sizeof(int)); HIPCHK(hipMemsetAsync(h->sbigmw.p, 0, sB * 4 * sizeof(int), s));
+  wb.mw_stat = h->sbigmw.as<int>();
   if (wb.geo.ws.slab_stride) { ENS(h->sbigscr, sB * wb.geo.ws.slab_stride * 8); wb.cone_scratch = h->sbigscr.as<double>(); }
   // the big cone's input has a handful of positive eigenvalues once the iterate has settled (measured: 2 - 5 of n + m): the tracked-subspace
   // kernel of the base engine follows them; the warm-started full kernel seeds the block and is the fall-back
@@ -1698,6 +1740,110 @@ int omc_left_singular_batch(omc_instance* h, int B, const double* X, double* U_o
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
   h->staged = false;
+  return 0;
+}
+
+// Spectral clip of B symmetric matrices of order N by the eigen-kernels of the relaxation, on their own (OMC.jl:1554-1556 are the cones they
+// serve).  A private view of the workspace (n = N, its own Mbuf / Vrow / W1 / slab) goes through omc_launch_cone_ws / omc_launch_cone: no
+// second copy of a kernel.  The kernels clip at 0 from below: lo must be 0.  Where k_cone_ws does not exist (orders 129 - 144, above 1024)
+// the single-workgroup path is the cold kernel k_cone, which returns P only.
+int omc_psd_project_batch(omc_instance* h, int B, int N, const double* M, double lo, double hi, int algo, const double* V0, double* P,
+                          double* evals, double* V) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
+  if (!M || !P) return fail(OMC_ERR_ARGUMENT, "M / P is NULL");
+  if (B < 1) return fail(OMC_ERR_ARGUMENT, "B must be positive");
+  if (N < 2) return fail(OMC_ERR_ARGUMENT, "N must be at least 2");
+  if (!(lo <= hi)) return fail(OMC_ERR_ARGUMENT, "lo must not exceed hi");
+  if (algo < 0 || algo > 2) return fail(OMC_ERR_ARGUMENT, "algo must be 0, 1 or 2");
+  if (lo != 0.0) return fail(OMC_ERR_UNSUPPORTED, "omc_psd_project_batch: the eigen-kernels clip at 0 from below, lo must be 0");
+  if (N > MW_MAX_ORDER) return fail(OMC_ERR_UNSUPPORTED, "omc_psd_project_batch: order above 4096");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t sB = (size_t)B, NP = (size_t)((N + 15) & ~15);
+  OmcWS w;
+  memset(&w, 0, sizeof(w));
+  w.nB = w.B = w.Btot = B; w.n = N; w.np16 = (int)NP; w.k = 1; w.max_sweeps = MAX_SWEEPS; w.mw_budget = MAX_SWEEPS;
+  w.clip_hi = hi < 1e300 ? hi : 1e300;
+  w.geo = omc_plan_geometry(N, (int)NP, 1, 1, 1, 1, 0, algo == 1 ? MW_MAX_ORDER + 1 : h->tun.cone_multi_min);
+  if (algo == 2 && !w.geo.mw) geom_set_mw(w.geo, N);
+  const bool cold = !w.geo.mw && !w.geo.ws_lpp;      // no k_cone_ws at this order (129 .. 144, above 1024): the cold kernel k_cone, as in a relaxation
+  if (cold && (evals || V)) return fail(OMC_ERR_UNSUPPORTED, "omc_psd_project_batch: the cold single-workgroup kernel (orders 129 - 144 and above 1024) returns P only");
+  ENS(h->pjM, sB * NP * NP * 8); ENS(h->pjV, sB * NP * NP * 8); ENS(h->pjW, sB * N * N * 8);
+  ENS(h->pjD, sB * (1 + NP) * 8); ENS(h->pjI, sB * 7 * sizeof(int));
+  if (w.geo.ws.slab_stride) { ENS(h->pjS, sB * w.geo.ws.slab_stride * 8); w.cone_scratch = h->pjS.as<double>(); }
+  w.Mbuf = h->pjM.as<double>(); w.Vrow = h->pjV.as<double>(); w.W1 = h->pjW.as<double>();
+  w.fro2 = h->pjD.as<double>(); w.ev_out = h->pjD.as<double>() + sB;
+  int* ip = h->pjI.as<int>();
+  w.done = ip; w.vvalid = ip + sB; w.sweeps = ip + 2 * sB; w.mw_stat = ip + 3 * sB;
+  // symmetrised, zero-padded input, its squared Frobenius norm, the starting basis as the row-major Vrow
+  std::vector<double> hM(sB * NP * NP, 0.0), hV(V0 ? sB * NP * NP : 0, 0.0), hf(sB, 0.0);
+  for (size_t b = 0; b < sB; ++b) {
+    const double* Mb = M + b * N * N; double* Mo = hM.data() + b * NP * NP;
+    double f2 = 0.0;
+    for (int j = 0; j < N; ++j)
+      for (int i = 0; i < N; ++i) { const double v = 0.5 * (Mb[(size_t)j * N + i] + Mb[(size_t)i * N + j]); Mo[(size_t)j * NP + i] = v; f2 += v * v; }
+    hf[b] = f2;
+    if (V0)
+      for (int t = 0; t < N; ++t)
+        for (int kk = 0; kk < N; ++kk) hV[b * NP * NP + (size_t)kk * NP + t] = V0[b * N * N + (size_t)t * N + kk];
+  }
+  std::vector<int> hi_(sB * 7, 0);
+  if (V0) for (size_t b = 0; b < sB; ++b) hi_[sB + b] = 1;
+  HIPCHK(hipMemcpyAsync(w.Mbuf, hM.data(), hM.size() * 8, hipMemcpyHostToDevice, s));
+  if (V0) HIPCHK(hipMemcpyAsync(w.Vrow, hV.data(), hV.size() * 8, hipMemcpyHostToDevice, s));
+  else HIPCHK(hipMemsetAsync(w.Vrow, 0, sB * NP * NP * 8, s));
+  HIPCHK(hipMemcpyAsync(w.fro2, hf.data(), sB * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(ip, hi_.data(), hi_.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  hipEvent_t e0 = nullptr, e1 = nullptr;      // device time of the projection alone (uploads and downloads outside)
+  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+  struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
+  HIPCHK(hipEventRecord(e0, s));
+  if (cold) omc_launch_cone(&w, CONE_BIG, s); else omc_launch_cone_ws(&w, s);
+  HIPCHK(hipEventRecord(e1, s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(P, w.W1, sB * N * N * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(hi_.data(), ip, hi_.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  std::vector<double> lam;
+  if (evals || V) {
+    hV.resize(sB * NP * NP);
+    HIPCHK(hipMemcpyAsync(hV.data(), w.Vrow, hV.size() * 8, hipMemcpyDeviceToHost, s));
+    if (w.geo.mw) { lam.resize(sB * NP); HIPCHK(hipMemcpyAsync(lam.data(), w.ev_out, lam.size() * 8, hipMemcpyDeviceToHost, s)); }
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  // sweep statistics of this call (omc_last_cone_multi_stats): calls, most sweeps of a matrix, exhausted budgets, the same maximum
+  h->mw_tot[0] = B; h->mw_tot[1] = 0; h->mw_tot[2] = 0;
+  for (size_t b = 0; b < sB; ++b) {
+    h->mw_tot[1] = std::max<long long>(h->mw_tot[1], hi_[2 * sB + b]);
+    if (w.geo.mw) h->mw_tot[2] += hi_[3 * sB + 4 * b + 2];
+  }
+  h->mw_tot[3] = h->mw_tot[1];
+  { float msv = 0.f; HIPCHK(hipEventElapsedTime(&msv, e0, e1)); h->mw_tot[4] = (long long)(1000.0 * msv); }
+  if (evals || V) {      // ascending eigenvalues, V permuted with them (the kernels leave the columns in no particular order)
+    std::vector<double> lb(N); std::vector<int> perm(N);
+    for (size_t b = 0; b < sB; ++b) {
+      const double* Vr = hV.data() + b * NP * NP; const double* Mo = hM.data() + b * NP * NP;
+      if (w.geo.mw) for (int t = 0; t < N; ++t) lb[t] = lam[b * NP + t];
+      else {      // k_cone_ws keeps its eigenvalues in LDS: Rayleigh quotients of the returned eigenvectors
+        for (int t = 0; t < N; ++t) {
+          double q = 0.0;
+          for (int j = 0; j < N; ++j) { const double vj = Vr[(size_t)j * NP + t]; double a = 0.0; for (int i = 0; i < N; ++i) a += Mo[(size_t)j * NP + i] * Vr[(size_t)i * NP + t]; q += a * vj; }
+          lb[t] = q;
+        }
+      }
+      for (int t = 0; t < N; ++t) perm[t] = t;
+      std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return lb[x] < lb[y]; });
+      for (int t = 0; t < N; ++t) {
+        if (evals) evals[b * N + t] = lb[perm[t]];
+        if (V) for (int kk = 0; kk < N; ++kk) V[b * N * N + (size_t)t * N + kk] = Vr[(size_t)kk * NP + perm[t]];
+      }
+    }
+  }
+  return 0;
+}
+
+int omc_last_cone_multi_stats(omc_instance* h, int64_t* out) {
+  if (!h || !out) return fail(OMC_ERR_ARGUMENT, "NULL argument");
+  for (int q = 0; q < 5; ++q) out[q] = h->mw_tot[q];
   return 0;
 }
 

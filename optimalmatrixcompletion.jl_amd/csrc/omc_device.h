@@ -103,6 +103,10 @@ struct OmcWS {
   // warm start from a parent's final state (omc_state_pool_create / omc_relax_set_warm): per-node pool indices (-1: cold / not saved)
   const int *load_from, *save_to;      // Btot each, or NULL
   double *pY, *pD1, *pD3, *pU, *palpha, *psval, *pXs, *ptheta, *pscal;   // pool: strides n*n, n*n, n*n, n*k, nnz, m, np16*16, 16, 4 (rho, sub_on, -, -)
+  // multi-workgroup eigen-kernels (geo.mw, omc_cone_mw.hip): sweeps enqueued per call; per slot calls, sweeps of the last call, calls that
+  // used up their budget without meeting the stop rule, most sweeps of a call since the host last cleared it; eigenvalues of the last
+  // projection in column order (B * np16; NULL: not wanted)
+  int mw_budget; int* mw_stat; double* ev_out;
   int* sub_stat;          // B * 8: calls, power steps, failures (fall back to the full decomposition), seeds, failures by cause (too many positive Ritz values, step cap, Cholesky), Rayleigh-Ritz passes
   // rows
   int* R;                 // B
@@ -151,6 +155,7 @@ void omc_launch_cone(const OmcWS* w, int mode, hipStream_t s);
 void omc_launch_global(const OmcWS* w, hipStream_t s);
 void omc_launch_small(const OmcWS* w, int mode, hipStream_t s);
 void omc_launch_cone_ws(const OmcWS* w, hipStream_t s);
+void omc_launch_cone_mw(const OmcWS* w, hipStream_t s);      /* omc_cone_mw.hip: what omc_launch_cone_ws does when w->geo.mw is set */
 void omc_launch_cone_sub(const OmcWS* w, hipStream_t s);
 void omc_launch_check_zero(const OmcWS* w, hipStream_t s);
 void omc_launch_check_build(const OmcWS* w, hipStream_t s);

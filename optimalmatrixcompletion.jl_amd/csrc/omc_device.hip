@@ -495,17 +495,6 @@ __global__ void __launch_bounds__(256) k_colprox(OmcWS w, int mode) {
 #define JROWS 20  // rows cached in registers per lane
 #define WS_JROWS 32  // same for the warm-started kernel's run-time-bound variant (n <= 16 * 32 = 512)
 
-__device__ __forceinline__ void rr_pair(int step, int t, int Np, int& p, int& q) {
-  // round-robin tournament on Np (even) players: step in [0,Np-1), t in [0,Np/2)
-  const int M1 = Np - 1;
-  if (t == 0) { p = step; q = Np - 1; }
-  else {
-    p = step + t; if (p >= M1) p -= M1;          // step < M1, t < M1: one conditional subtraction replaces the modulo
-    q = step - t; if (q < 0) q += M1;
-  }
-  if (p > q) { int tmp = p; p = q; q = tmp; }
-}
-
 // One-sided Jacobi with cached squared column norms (only the cross product needs a reduction), DPP reductions,
 // rotations applied from registers, one barrier per step.  nrm2: Np doubles (LDS).  Returns the sweeps done.
 template <int LPP>
@@ -2808,6 +2797,7 @@ void omc_launch_cone(const OmcWS* w, int mode, hipStream_t s) {
   else hipLaunchKernelGGL(k_cone<false>, dim3(w->nB), dim3(512), 0, s, *w, mode);
 }
 void omc_launch_cone_ws(const OmcWS* w, hipStream_t s) {
+  if (w->geo.mw) { omc_launch_cone_mw(w, s); return; }      // omc_cone_mw.hip: the same projection as a sequence of multi-workgroup launches
   const int lpp = w->geo.ws_lpp, rpl2 = w->geo.ws_rpl2;
   if (w->geo.ws.use_lds) {
     if (lpp == 16) launch_ws_lds<16>(w, s);

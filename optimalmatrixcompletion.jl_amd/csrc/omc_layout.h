@@ -41,6 +41,19 @@ OMC_HD WsGeometry ws_geometry(int N) {
   }
   return {rpl <= 32 ? lpp : 0, rpl, ld, use_lds, ws_bytes(N, ld)};
 }
+// ---- multi-workgroup eigen-kernels (omc_cone_mw.hip), per-slot global slab: G (Ncp columns of ld doubles; columns padded to whole block
+// pairs, rows to 16), squared norms ev, eigenvalues lam, weights wgt (Ncp each), selection sel (Ncp ints), the largest squared relative
+// cross product of each sweep smax (MW_MAXSW 64-bit words), head (base, then nsel and nkeep as ints) ---------------------------------------
+#define MW_B 16         // columns per block: one v_mfma_f64_16x16x4_f64 tile, a 32 x 32 Gram matrix per pair
+#define MW_MAXSW 32     // sweep slots of smax: the sweep budget of a call never exceeds it
+#define MW_MIN_ORDER 145   // below, k_cone_ws holds G in LDS: the multi-workgroup path is never planned there
+#define MW_MAX_ORDER 4096
+struct MwLayout { int ld, Ncp, nb; size_t ev, lam, wgt, sel, smax, head, bytes; };
+OMC_HD MwLayout mw_layout(int N) {
+  const int NP = (N + 15) & ~15, Ncp = (N + 2 * MW_B - 1) & ~(2 * MW_B - 1), ld = NP + 4;
+  const size_t ev = (size_t)Ncp * ld, sel = ev + 3 * (size_t)Ncp, smax = sel + Ncp / 2, head = smax + MW_MAXSW;
+  return {ld, Ncp, Ncp / MW_B, ev, ev + Ncp, ev + 2 * (size_t)Ncp, sel, smax, head, (head + 4) * 8};
+}
 // ---- k_cone_sub: X, then Z (SUBP x LD each; Z in a global slab beyond order 512), 4 partial 16 x 16 products (Cs), Gram / Cholesky /
 // Ritz rotation (Hs, 16 x 17), Jacobi work (Gj, 16 x 17), Ritz values (th), squared norms (evj), red (32), wgt (16), sel (16 ints) ------
 struct SubLayout { int LD, zglob; size_t Za, Cs, Hs, Gj, th, evj, red, wgt, sel, bytes; };
@@ -95,9 +108,17 @@ struct OmcGeom {
   int ws_lpp, ws_rpl2, ws_ld;             // k_cone_ws: lanes per pair (0: order beyond the kernel), rows per lane / 2, leading dimension of G
   int cp_lds_c, cp_lds_doubles, cp_keepB; // k_colprox: columns up to cp_lds_c rows in LDS (cp_lds_doubles per wave); cp_keepB = 0: dense columns, B is gathered again instead of kept
   size_t cp_scratch_stride, sub_lds;      // k_colprox slab per wave (B*m waves), 0 when every column fits the LDS ; dynamic LDS of k_cone_sub
+  int mw; MwLayout mwl;                   // 1: omc_launch_cone_ws takes the multi-workgroup kernels (their slab layout; it shares cone_scratch and its stride)
 };
-// n, np16: order of the cone matrix and its padding to 16 (the Shor view of the big cone passes n + m); cmax: longest column
-OMC_HD OmcGeom omc_plan_geometry(int n, int np16, int k, int rmax, int Rmax, int cmax, int global_nolds) {
+// switch a planned geometry to the multi-workgroup eigen-kernels at order n: the shared slab grows to their need (a multiple of 4 doubles: 32-byte rows)
+OMC_HD void geom_set_mw(OmcGeom& g, int n) {
+  g.mw = 1; g.mwl = mw_layout(n);
+  size_t st = g.mwl.bytes / 8 + 8; if (st < g.ws.slab_stride) st = g.ws.slab_stride;
+  g.cone.slab_stride = g.ws.slab_stride = (st + 3) & ~(size_t)3;
+}
+// n, np16: order of the cone matrix and its padding to 16 (the Shor view of the big cone passes n + m); cmax: longest column;
+// cone_multi_min: orders from this value on (and never below MW_MIN_ORDER) take the multi-workgroup eigen-kernels
+OMC_HD OmcGeom omc_plan_geometry(int n, int np16, int k, int rmax, int Rmax, int cmax, int global_nolds, int cone_multi_min) {
   OmcGeom g;
   const WsGeometry wg = ws_geometry(n);
   g.cone = plan_block(cone_bytes(n), cone_bytes(n) <= OMC_MAX_DYN_LDS);
@@ -111,6 +132,8 @@ OMC_HD OmcGeom omc_plan_geometry(int n, int np16, int k, int rmax, int Rmax, int
   g.cp_lds_c = cmax < 64 ? cmax : 64; g.cp_keepB = g.cp_lds_c <= 40 ? 1 : 0;
   g.cp_lds_doubles = cp_reg_layout(g.cp_lds_c, g.cp_keepB).doubles;
   g.cp_scratch_stride = cmax > g.cp_lds_c ? cp_body_layout(cmax).doubles : 0;
+  g.mw = 0; g.mwl = MwLayout{};
+  if (n >= MW_MIN_ORDER && !wg.use_lds && n >= cone_multi_min && n <= MW_MAX_ORDER) geom_set_mw(g, n);
   return g;
 }
 #endif

@@ -66,6 +66,17 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   return s;
 }
 
+__device__ __forceinline__ void rr_pair(int step, int t, int Np, int& p, int& q) {
+  // round-robin tournament on Np (even) players: step in [0,Np-1), t in [0,Np/2)
+  const int M1 = Np - 1;
+  if (t == 0) { p = step; q = Np - 1; }
+  else {
+    p = step + t; if (p >= M1) p -= M1;          // step < M1, t < M1: one conditional subtraction replaces the modulo
+    q = step - t; if (q < 0) q += M1;
+  }
+  if (p > q) { int tmp = p; p = q; q = tmp; }
+}
+
 #define TRI(r, q) ((size_t)(r) * ((r) + 1) / 2 + (q))
 #define WAVE_SYNC()                                      \
   do {                                                   \
