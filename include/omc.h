@@ -142,13 +142,41 @@ int omc_set_node_rho_scales(omc_instance* h, int B, const double* rho_scale);
 int omc_relax_solve(omc_instance* h);
 /* ---- warm start from the parent's state (an addition of the engine; the reference cold-starts every model, OMC.jl:1482) ----------------------
  * A child is its parent plus one cut.  omc_state_pool_create reserves `capacity` final states on the device (about 24 n^2 + 8 (n k + |Omega| + m
- * + 16 n) bytes each: 0.27 MB at 100 x 100).  omc_relax_set_warm applies to the NEXT omc_relax_stage / omc_relax_batch with the same B and is
- * consumed by it: node b starts from pool entry load_from[b] (-1 or NULL: cold start) and its final state is stored in entry save_to[b]
- * (-1 or NULL: not stored).  The caller owns the numbering (e.g. a ring).  A warm node keeps its own base penalty (the parent's scaled
- * duals are rescaled), inherits Y, the duals of the two full cones, the column multipliers and the tracked block of the cone; the result is the
- * same convex program's optimum (same certificate), reached in fewer iterations.  Not available in Shor mode. */
+ * + 16 n) bytes each: 0.27 MB at 100 x 100); it empties the pool and drops a Shor extension reserved earlier.  omc_relax_set_warm applies to
+ * the NEXT omc_relax_stage / omc_relax_batch (or omc_relax_stage_shor / omc_relax_batch_shor, see below) with the same B and is consumed by
+ * it: node b starts from pool entry load_from[b] (-1 or NULL: cold start) and its final state is stored in entry save_to[b] (-1 or NULL: not
+ * stored).  The caller owns the numbering (e.g. a ring).  A warm node keeps its own base penalty (the parent's scaled duals are rescaled),
+ * inherits Y, the duals of the two full cones, the column multipliers and the tracked block of the cone; the result is the same convex
+ * program's optimum (same certificate), reached in fewer iterations.  An entry saved during a solve can be loaded by a later stage (or by
+ * a node appended later), not by a node of the same staged batch.
+ *
+ * Shor mode.  omc_state_pool_reserve_shor(h, nq_max), called after omc_state_pool_create, extends every entry by the Shor state of a node
+ * with at most nq_max minors: X, W, the multipliers of the paraboloids and of the order-(n+m) cone, Theta, and per minor the 15 duals of its
+ * order-5 block and its five lifted values -- 8 (3 n m + m^2 + (n + m)^2 + 2 m + 20 nq_max) bytes per entry plus a 32-byte header (per-minor
+ * arrays are stored with stride nq_max).  Calling it again reallocates and invalidates every entry; OMC_ERR_ARGUMENT without a pool or for
+ * nq_max < 0; when the device cannot hold it the HIP out-of-memory code is returned and the pool stays as it was.  With the reservation the
+ * next omc_relax_stage_shor / omc_relax_batch_shor honours omc_relax_set_warm (rank k = 1); without it the indices are ignored.  Rank k > 1
+ * batches never use them (neither those the base engine serves nor those of the knob OMC_SHOR_EXPLICIT).
+ * The library keeps, per entry, which mode saved it and a signature of the node's lists; the signature is set when the saving node is
+ * harvested (a node that never finishes leaves the entry as it was).  At stage time load_from[b] is treated as -1 when the entry is empty,
+ * was saved by the other mode (also in omc_relax_stage and omc_relax_append: a base node never starts from a Shor-mode state), holds more
+ * than nq_max minors, or fails omc_shor_warm_compat against node b's lists; save_to[b] is treated as -1 when node b has more than nq_max
+ * minors.  A node that loads starts from the parent's X, W, Theta and multipliers (rescaled to its own penalty); the blocks of minors the
+ * parent did not have start with zero duals and rank-one lifted values from X; the eigen-state of the order-(n+m) cone starts cold.
+ *   omc_shor_warm_compat      pure host function (no handle, no device): 1 for identical (minor list, SOC list) pairs, 2 when the parent's
+ *                             minor list is a strict prefix of the child's and both SOC lists are the complement shorthand (n_soc = -1),
+ *                             0 otherwise.  Lists in the wire format of omc_relax_stage_shor.
+ *   omc_last_shor_warm_stats  out[4] of the last staged Shor batch: nodes loaded with an identical list, loaded through a prefix, loads
+ *                             refused, states saved (counted as the nodes are harvested).
+ *   omc_state_pool_fetch_shor the point of a Shor-mode entry, unscaled: *nq minors, X (n*m), Theta (m*m), V (5 per minor, as
+ *                             omc_relax_fetch_shor_V); NULL pointers are skipped; OMC_ERR_ARGUMENT for an empty or base-mode entry. */
 int omc_state_pool_create(omc_instance* h, int capacity);
+int omc_state_pool_reserve_shor(omc_instance* h, int64_t nq_max);
 int omc_relax_set_warm(omc_instance* h, int B, const int* load_from, const int* save_to);
+int omc_shor_warm_compat(int64_t n_parent, const int64_t* parent_idx, int64_t n_soc_parent, const int64_t* parent_soc, int64_t n_child,
+                         const int64_t* child_idx, int64_t n_soc_child, const int64_t* child_soc);
+int omc_last_shor_warm_stats(omc_instance* h, int64_t out[4]);
+int omc_state_pool_fetch_shor(omc_instance* h, int entry, int64_t* nq, double* X, double* Theta, double* V);
 /* Asynchronous form of omc_relax_solve: submit returns at once (the solve runs on a worker thread of the library), poll reports
  * progress (running flag, nodes harvested so far, nodes staged), wait joins and returns the solve's return code (message via
  * omc_last_error on the waiting thread).  The reference's loop is serial (OMC.jl:700-719); with this the host can prepare the next

@@ -18,6 +18,7 @@ EXPORTS = [
     "omc_last_kernel_stats", "omc_last_solver_info", "omc_last_subspace_stats", "omc_set_node_rho_scales", "omc_left_singular_batch", "omc_psd_project_batch", "omc_last_cone_multi_stats", "omc_cone_multi_budget", "omc_relax_reserve", "omc_relax_append", "omc_relax_fetch_done", "omc_relax_hold", "omc_debug_stamps", "omc_tuning_set", "omc_tuning_reload_env", "omc_debug_residuals", "omc_debug_diag", "omc_debug_aa",
     "omc_shor_count", "omc_shor_indexes", "omc_violated_shor_minors", "omc_shor_last_stats", "omc_shor_last_select_stats",
     "omc_relax_stage_shor", "omc_relax_fetch_shor", "omc_relax_batch_shor", "omc_set_shor_penalties", "omc_set_shor_keep_V", "omc_relax_fetch_shor_V", "omc_last_shor_subspace_stats", "omc_state_pool_create", "omc_relax_set_warm",
+    "omc_state_pool_reserve_shor", "omc_shor_warm_compat", "omc_last_shor_warm_stats", "omc_state_pool_fetch_shor",
     "omc_altmin_master_objectives", "omc_comm_unique_id", "omc_comm_init", "omc_allreduce_bounds", "omc_bcast_incumbent", "omc_allgather_records", "omc_comm_destroy",
 ]
 
@@ -69,6 +70,10 @@ def load():
     lib.omc_last_shor_subspace_stats.argtypes = [vp, vp]
     lib.omc_state_pool_create.argtypes = [vp, C.c_int]
     lib.omc_relax_set_warm.argtypes = [vp, C.c_int, vp, vp]
+    lib.omc_state_pool_reserve_shor.argtypes = [vp, C.c_int64]
+    lib.omc_shor_warm_compat.argtypes = [C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp]
+    lib.omc_last_shor_warm_stats.argtypes = [vp, vp]
+    lib.omc_state_pool_fetch_shor.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.omc_relax_submit.argtypes = [vp]
     lib.omc_relax_poll.argtypes = [vp, vp, vp, vp]
     lib.omc_relax_wait.argtypes = [vp]

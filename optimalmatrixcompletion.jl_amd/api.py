@@ -149,14 +149,44 @@ class Engine:
         _lib.check(self._lib.omc_state_pool_create(self._h, int(capacity)))
         self.pool_capacity = int(capacity)
 
+    def state_pool_reserve_shor(self, nq_max):
+        """Extend every pool entry by the Shor state of a node with at most nq_max minors (omc_state_pool_reserve_shor; after
+        state_pool_create).  From then on stage_shor honours load_from / save_to."""
+        _lib.check(self._lib.omc_state_pool_reserve_shor(self._h, int(nq_max)))
+        self.pool_shor_nq_max = int(nq_max)
+
+    @staticmethod
+    def shor_state_bytes(n, m, nq_max):
+        """Bytes the Shor extension adds to one pool entry (the formula of include/omc.h)."""
+        return 8 * (3 * n * m + m * m + (n + m) ** 2 + 2 * m + 20 * int(nq_max)) + 32
+
+    def shor_warm_stats(self):
+        """Warm-start accounting of the last staged Shor batch (omc_last_shor_warm_stats)."""
+        o = np.zeros(4, np.int64)
+        _lib.check(self._lib.omc_last_shor_warm_stats(self._h, _lib.ptr(o)))
+        return dict(loaded_identical=int(o[0]), loaded_prefix=int(o[1]), refused=int(o[2]), saved=int(o[3]))
+
+    def state_pool_fetch_shor(self, entry):
+        """The point a Shor-mode pool entry holds, unscaled (omc_state_pool_fetch_shor): dict(nq, X (n, m), Theta (m, m), V (nq, 5))."""
+        n, m = self.n, self.m
+        nq = np.zeros(1, np.int64)
+        _lib.check(self._lib.omc_state_pool_fetch_shor(self._h, int(entry), _lib.ptr(nq), None, None, None))
+        X = np.zeros(n * m); Th = np.zeros(m * m); V = np.zeros((max(int(nq[0]), 1), 5))
+        _lib.check(self._lib.omc_state_pool_fetch_shor(self._h, int(entry), _lib.ptr(nq), _lib.ptr(X), _lib.ptr(Th), _lib.ptr(V)))
+        return dict(nq=int(nq[0]), X=X.reshape((n, m), order="F"), Theta=Th.reshape((m, m), order="F"), V=V[:int(nq[0])])
+
+    def _set_warm(self, B, load_from, save_to):
+        if load_from is None and save_to is None:
+            return
+        lf = None if load_from is None else np.ascontiguousarray(np.asarray(load_from, dtype=np.int32))
+        sv = None if save_to is None else np.ascontiguousarray(np.asarray(save_to, dtype=np.int32))
+        if (lf is not None and lf.shape != (B,)) or (sv is not None and sv.shape != (B,)):
+            raise ValueError("load_from / save_to must hold one pool index per node")
+        _lib.check(self._lib.omc_relax_set_warm(self._h, B, _lib.ptr(lf), _lib.ptr(sv)))
+
     def stage(self, nodes, disjunctive_cuts_type="linear", params=None, U_lower=None, U_upper=None, rho_scales=None, load_from=None, save_to=None):
         n, k = self.n, self.k
-        if load_from is not None or save_to is not None:
-            lf = None if load_from is None else np.ascontiguousarray(np.asarray(load_from, dtype=np.int32))
-            sv = None if save_to is None else np.ascontiguousarray(np.asarray(save_to, dtype=np.int32))
-            if (lf is not None and lf.shape != (len(nodes),)) or (sv is not None and sv.shape != (len(nodes),)):
-                raise ValueError("load_from / save_to must hold one pool index per node")
-            _lib.check(self._lib.omc_relax_set_warm(self._h, len(nodes), _lib.ptr(lf), _lib.ptr(sv)))
+        self._set_warm(len(nodes), load_from, save_to)
         if rho_scales is not None:
             rs = np.ascontiguousarray(np.asarray(rho_scales, dtype=np.float64))
             if rs.shape != (len(nodes),):
@@ -175,14 +205,17 @@ class Engine:
                                              _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(lo), _lib.ptr(hi)))
         self._B = B
 
-    def stage_shor(self, nodes, shor_info, disjunctive_cuts_type="linear", params=None, U_lower=None, U_upper=None, penalties=None, keep_V=False):
+    def stage_shor(self, nodes, shor_info, disjunctive_cuts_type="linear", params=None, U_lower=None, U_upper=None, penalties=None, keep_V=False,
+                   load_from=None, save_to=None):
         """Stage a batch with add_Shor_valid_inequalities = true (OMC.jl:747-754 with node.Shor_info).  shor_info[b] =
         (constraints_indexes, SOC_constraints_indexes): 1-based (i1, i2, j1, j2) tuples and 1-based (i, j) pairs as the reference
         holds them (OMC.jl:37-40); SOC_constraints_indexes = None means "every coordinate outside the minors" (what the reference's
-        driver always builds, OMC.jl:656-673, 2508-2517)."""
+        driver always builds, OMC.jl:656-673, 2508-2517).  load_from / save_to: pool entries as in stage(); honoured once
+        state_pool_reserve_shor has been called (rank 1), ignored otherwise; shor_warm_stats() tells what the library did with them."""
         n, k = self.n, self.k
         if len(shor_info) != len(nodes):
             raise ValueError("one Shor_info per node")
+        self._set_warm(len(nodes), load_from, save_to)
         _lib.check(self._lib.omc_set_shor_keep_V(self._h, 1 if keep_V else 0))
         self._nqmax = max([len(np.asarray(mi).reshape(-1, 4)) for (mi, _) in shor_info] + [1])
         if penalties is not None:
@@ -314,7 +347,8 @@ class Engine:
         if add_Shor_valid_inequalities:
             if shor_info is None:
                 raise ValueError("add_Shor_valid_inequalities = true needs node.Shor_info (OMC.jl:1508)")
-            self.stage_shor(nodes, shor_info, disjunctive_cuts_type, params, U_lower, U_upper, shor_penalties, keep_V=(want_V and self.k == 1))
+            self.stage_shor(nodes, shor_info, disjunctive_cuts_type, params, U_lower, U_upper, shor_penalties, keep_V=(want_V and self.k == 1),
+                            load_from=load_from, save_to=save_to)
             self.solve()
             out = self.fetch(want_Y, want_X, want_Theta)
             for r, Wb in zip(out, self.fetch_shor()):

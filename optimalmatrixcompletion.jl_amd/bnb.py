@@ -191,7 +191,7 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
                      add_Shor_valid_inequalities_fraction=1.0, add_Shor_valid_inequalities_iterative=False,
                      max_update_Shor_indices_probability=1.0, min_update_Shor_indices_probability=0.1,
                      update_Shor_indices_probability_decay_rate=1.1, update_Shor_indices_n_minors=100, shor_params=None,
-                     warm_start=True, warm_pool_bytes=6 << 30):
+                     warm_start=True, warm_pool_bytes=6 << 30, shor_warm_start=False, shor_warm_depth=32):
     """Behavioural counterpart of the reference driver for use_disjunctive_cuts = true, no Shor, one altmin run at the
     root (altmin_root_n_iters = 1).  Differences, all deliberate: (1) up to `batch` nodes are popped per round in the
     reference's selection order and relaxed in ONE GPU batch (batch=1 reproduces the serial order); (2) the node bound
@@ -207,6 +207,10 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
     adds, with probability p(depth), the update_Shor_indices_n_minors most violated minors of its X (generate_violated_Shor_minors on
     the device) to the list its children inherit.  The SOC list is always "every coordinate outside the minors" (OMC.jl:656-665, 2508-2517).  (5) A master-feasible node updates the incumbent with
     evaluate_objective of the rank-k projection of its X, a certified value, instead of the relaxation objective (OMC.jl:818-828).
+    shor_warm_start (rank 1, one rank; off by default): Shor nodes start from their parent's final state through the same ring of pool
+    entries as the base branch (Engine.state_pool_reserve_shor); the pool is sized from warm_pool_bytes for lists of the root's length plus
+    shor_warm_depth updates of update_Shor_indices_n_minors minors, and a node whose list has outgrown that starts cold and is not saved
+    (counter shor_warm_outgrown).  counters["warm_started"] counts the loads the library accepted.
     Returns (solution, instance) dicts with the reference's key names where they apply (OMC.jl:604-621, 391-454)."""
     import heapq
     import time
@@ -297,6 +301,17 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
             engine.state_pool_create(pool_cap)
         else:
             pool_cap = 0
+    shor_nq_max = 0
+    if shor and shor_warm_start and k == 1 and world_size == 1 and hasattr(engine, "state_pool_reserve_shor"):
+        nnz = int(np.count_nonzero(indices)); np16 = (n + 15) // 16 * 16
+        shor_nq_max = len(root_minors) + (int(shor_warm_depth) * int(update_Shor_indices_n_minors) if add_Shor_valid_inequalities_iterative else 0)
+        state_bytes = 8 * (3 * n * n + n * k + nnz + m + 16 * np16 + 20) + engine.shor_state_bytes(n, m, shor_nq_max)
+        pool_cap = int(max(0, min(1 << 17, warm_pool_bytes // state_bytes)))
+        if pool_cap >= 2:
+            engine.state_pool_create(pool_cap)
+            engine.state_pool_reserve_shor(shor_nq_max)
+        else:
+            pool_cap = 0
     # ---- tree ------------------------------------------------------------------------------------------------
     nodes = {1: dict(cuts=[], LB=-math.inf, depth=0, parent=0)}
     if shor:
@@ -361,25 +376,38 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
             t0 = time.time()
             mine = todo[rank::world_size] if world_size > 1 else todo                        # round-robin in queue order
             need = [(nid, nd) for nid, nd in mine if nid not in precomputed]
-            if shor:
-                fresh = engine.matrix_completion_SDP_relaxation([nd["cuts"] for _, nd in need], disjunctive_cuts_type, params=PS, want_X=True,
-                                                                add_Shor_valid_inequalities=True,
-                                                                shor_info=[(nd["shor"], None) for _, nd in need]) if need else []
-            elif pool_cap and need:
+            if pool_cap and need:
                 lf = []; sv = []
-                for nid, nd in need:
+                fits = [not shor or len(nd["shor"]) <= shor_nq_max for _, nd in need]          # a Shor list that has outgrown the pool: cold, not saved
+                for (nid, nd), ok in zip(need, fits):
                     ps = nd.get("pstate")          # (rank, pool entry, parent id): valid while the ring has not re-used the entry
-                    lf.append(ps[1] if (ps is not None and ps[0] == rank and pool_owner.get(ps[1]) == ps[2]) else -1)
+                    lf.append(ps[1] if (ok and ps is not None and ps[0] == rank and pool_owner.get(ps[1]) == ps[2]) else -1)
                 busy = set(v for v in lf if v >= 0)          # entries this batch still reads: a slot may be set up after another one has been harvested
-                for nid, nd in need:
+                for (nid, nd), ok in zip(need, fits):
+                    if not ok:
+                        sv.append(-1); counters["shor_warm_outgrown"] = counters.get("shor_warm_outgrown", 0) + 1
+                        continue
                     while pool_next in busy and len(busy) < pool_cap:
                         pool_next = (pool_next + 1) % pool_cap
                     sv.append(pool_next); pool_owner[pool_next] = nid; pool_next = (pool_next + 1) % pool_cap
-                counters["warm_started"] = counters.get("warm_started", 0) + sum(1 for v in lf if v >= 0)
-                fresh = engine.matrix_completion_SDP_relaxation([nd["cuts"] for _, nd in need], disjunctive_cuts_type, params=P, want_X=True,
-                                                                load_from=lf, save_to=sv)
+                if shor:
+                    fresh = engine.matrix_completion_SDP_relaxation([nd["cuts"] for _, nd in need], disjunctive_cuts_type, params=PS, want_X=True,
+                                                                    add_Shor_valid_inequalities=True, shor_info=[(nd["shor"], None) for _, nd in need],
+                                                                    load_from=lf, save_to=sv)
+                    ws = engine.shor_warm_stats()
+                    counters["warm_started"] = counters.get("warm_started", 0) + ws["loaded_identical"] + ws["loaded_prefix"]
+                    counters["shor_warm_refused"] = counters.get("shor_warm_refused", 0) + ws["refused"]
+                else:
+                    counters["warm_started"] = counters.get("warm_started", 0) + sum(1 for v in lf if v >= 0)
+                    fresh = engine.matrix_completion_SDP_relaxation([nd["cuts"] for _, nd in need], disjunctive_cuts_type, params=P, want_X=True,
+                                                                    load_from=lf, save_to=sv)
                 for (nid, nd), s_ in zip(need, sv):
-                    nd["state"] = (rank, s_, nid)
+                    if s_ >= 0:
+                        nd["state"] = (rank, s_, nid)
+            elif shor:
+                fresh = engine.matrix_completion_SDP_relaxation([nd["cuts"] for _, nd in need], disjunctive_cuts_type, params=PS, want_X=True,
+                                                                add_Shor_valid_inequalities=True,
+                                                                shor_info=[(nd["shor"], None) for _, nd in need]) if need else []
             else:
                 fresh = engine.matrix_completion_SDP_relaxation([nd["cuts"] for _, nd in need], disjunctive_cuts_type, params=P,
                                                                 want_X=True) if need else []

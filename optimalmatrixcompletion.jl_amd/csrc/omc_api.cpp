@@ -175,6 +175,14 @@ struct omc_instance {
   long long big_sub_tot[8] = {0};
   // warm-start pool (omc_state_pool_create / omc_relax_set_warm)
   int pool_cap = 0; DevBuf pY, pD1, pD3, pU, palpha, psval, pXs, ptheta, pscal, bwarmL, bwarmS; std::vector<int> warm_load, warm_save;
+  // Shor extension of the pool (omc_state_pool_reserve_shor) and the host's signature of every entry: which mode saved it and for which lists.
+  // A signature is written when the node that saves is harvested (solve thread) and read at stage / append time (caller's thread): sig_mu.
+  struct PoolSig { int kind = 0; int64_t nq = 0, nsoc = 0; uint64_t hlist = 0, hsoc = 0; };      // kind: 0 empty, 1 base, 2 Shor
+  bool pool_shor = false; int64_t pool_nqmax = 0; DevBuf pShor, pShorHdr, sloadpart;
+  std::vector<PoolSig> pool_sig, node_sig; std::mutex sig_mu;
+  std::vector<int> save_host;      // per node of the staged batch: the entry its final state goes to (-1: none), as the device sees it
+  bool shor_warm = false;          // set by omc_relax_stage_shor for the omc_relax_stage call it makes: the indices have passed its filter
+  int64_t shor_warm_stats[4] = {0, 0, 0, 0};      // omc_last_shor_warm_stats
   // kernel stats
   int64_t launches[OMC_KERNEL_NCLASS] = {0}; double ms[OMC_KERNEL_NCLASS] = {0}; int64_t units[OMC_KERNEL_NCLASS] = {0};
   size_t nnz_rows() const { return row_idx.size(); }
@@ -715,7 +723,15 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
     if (h->warm_load.size() != (size_t)B) h->warm_load.clear();
     if (h->warm_save.size() != (size_t)B) h->warm_save.clear();
   }
-  if (h->pool_cap > 0 && !shor && (h->warm_load.size() == sN || h->warm_save.size() == sN)) {
+  const bool warm_ok = !shor || h->shor_warm;
+  h->shor_warm = false;
+  h->save_host.assign(sN, -1);
+  if (h->pool_cap > 0 && !shor && h->warm_load.size() == sN) {      // entries saved by a Shor solve do not hold what the base engine loads (alpha, sval)
+    std::lock_guard<std::mutex> lk(h->sig_mu);
+    for (int& e : h->warm_load) if (e >= 0 && (size_t)e < h->pool_sig.size() && h->pool_sig[e].kind == 2) e = -1;
+  }
+  if (h->pool_cap > 0 && warm_ok && (h->warm_load.size() == sN || h->warm_save.size() == sN)) {
+    if (h->warm_save.size() == sN) h->save_host = h->warm_save;
     if (h->warm_load.size() == sN) { if ((rc_ = upload(h->bwarmL, h->warm_load.data(), sizeof(int) * sN, h->stream))) return rc_; w.load_from = h->bwarmL.as<int>(); }
     if (h->warm_save.size() == sN) { if ((rc_ = upload(h->bwarmS, h->warm_save.data(), sizeof(int) * sN, h->stream))) return rc_; w.save_to = h->bwarmS.as<int>(); }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -784,6 +800,91 @@ int omc_state_pool_create(omc_instance* h, int capacity) {
     ENS(h->psval, c * (size_t)h->m * 8); ENS(h->pXs, c * np16 * 16 * 8); ENS(h->ptheta, c * 16 * 8); ENS(h->pscal, c * 4 * 8);
   }
   h->pool_cap = capacity;
+  { std::lock_guard<std::mutex> lk(h->sig_mu); h->pool_sig.assign(c, omc_instance::PoolSig{}); }
+  h->pool_shor = false; h->pool_nqmax = 0;      // the extension is sized per entry: reserve it again for the new capacity
+  return 0;
+}
+
+static uint64_t fnv1a(const void* p, size_t bytes, uint64_t hsh) {
+  const uint8_t* c = (const uint8_t*)p;
+  for (size_t e = 0; e < bytes; ++e) { hsh ^= c[e]; hsh *= 1099511628211ull; }
+  return hsh;
+}
+static constexpr uint64_t FNV_SEED = 1469598103934665603ull;
+
+// The one rule for starting a Shor node from a saved Shor state: 1 = identical (minor list, SOC list) pairs, 2 = the parent's minor list is a
+// strict prefix of the child's and both SOC lists are the complement shorthand, 0 = no transfer.  same_head: the child's first n_parent tuples
+// are the parent's list; same_soc: the SOC lists are equal (only asked when the lengths agree).
+static int shor_warm_rule(int64_t n_parent, int64_t n_soc_parent, int64_t n_child, int64_t n_soc_child, bool same_head, bool same_soc) {
+  if (n_parent < 0 || n_child < 0 || n_parent > n_child || !same_head) return 0;
+  if (n_parent == n_child) return (n_soc_parent == n_soc_child && same_soc) ? 1 : 0;
+  return (n_soc_parent == -1 && n_soc_child == -1) ? 2 : 0;
+}
+
+int omc_shor_warm_compat(int64_t n_parent, const int64_t* parent_idx, int64_t n_soc_parent, const int64_t* parent_soc, int64_t n_child,
+                         const int64_t* child_idx, int64_t n_soc_child, const int64_t* child_soc) {
+  if (n_parent < 0 || n_child < 0 || n_parent > n_child) return 0;
+  if ((n_parent > 0 && !parent_idx) || (n_child > 0 && !child_idx)) return 0;
+  if ((n_soc_parent > 0 && !parent_soc) || (n_soc_child > 0 && !child_soc)) return 0;
+  const bool same_head = n_parent == 0 || memcmp(parent_idx, child_idx, 32 * (size_t)n_parent) == 0;
+  const bool same_soc = n_soc_parent == n_soc_child && (n_soc_parent <= 0 || memcmp(parent_soc, child_soc, 16 * (size_t)n_soc_parent) == 0);
+  return shor_warm_rule(n_parent, n_soc_parent, n_child, n_soc_child, same_head, same_soc);
+}
+
+int omc_state_pool_reserve_shor(omc_instance* h, int64_t nq_max) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
+  if (h->pool_cap <= 0) return fail(OMC_ERR_ARGUMENT, "omc_state_pool_reserve_shor: no state pool (omc_state_pool_create)");
+  if (nq_max < 0 || nq_max >= (1ll << 28)) return fail(OMC_ERR_ARGUMENT, "omc_state_pool_reserve_shor: nq_max out of range");
+  if (h->worker_running.load()) return fail(OMC_ERR_ARGUMENT, "omc_state_pool_reserve_shor: a solve is running");
+  HIPCHK(hipSetDevice(h->device));
+  const ShorPoolLayout L = shor_pool_layout(h->n, h->m, (int)nq_max);
+  DevBuf nb, nh;      // allocated beside the old buffers: a failure leaves the pool as it was
+  { int r_ = nb.ensure((size_t)h->pool_cap * L.stride * 8); if (r_) return r_; }
+  { int r_ = nh.ensure((size_t)h->pool_cap * 4 * sizeof(long long)); if (r_) return r_; }
+  HIPCHK(hipMemsetAsync(nh.p, 0, (size_t)h->pool_cap * 4 * sizeof(long long), h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  std::swap(h->pShor.p, nb.p); std::swap(h->pShor.cap, nb.cap);
+  std::swap(h->pShorHdr.p, nh.p); std::swap(h->pShorHdr.cap, nh.cap);
+  { std::lock_guard<std::mutex> lk(h->sig_mu); h->pool_sig.assign((size_t)h->pool_cap, omc_instance::PoolSig{}); }      // every entry is invalid now
+  h->pool_shor = true; h->pool_nqmax = nq_max;
+  return 0;
+}
+
+int omc_last_shor_warm_stats(omc_instance* h, int64_t out[4]) {
+  if (!h || !out) return fail(OMC_ERR_ARGUMENT, "NULL argument");
+  for (int q = 0; q < 4; ++q) out[q] = h->shor_warm_stats[q];
+  return 0;
+}
+
+// scale of the Shor splitting: the program is homogeneous of degree 2 in A (oracle: shor_scale)
+static double shor_scale(const omc_instance* h) {
+  return sqrt(((double)h->nnz / ((double)h->n * h->m)) * (double)std::min(h->n, h->m) / std::max(h->sumA2, 1e-300));
+}
+
+int omc_state_pool_fetch_shor(omc_instance* h, int entry, int64_t* nq, double* X, double* Theta, double* V) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
+  if (!h->pool_shor || entry < 0 || entry >= h->pool_cap) return fail(OMC_ERR_ARGUMENT, "omc_state_pool_fetch_shor: no such entry (omc_state_pool_reserve_shor)");
+  if (h->worker_running.load()) return fail(OMC_ERR_ARGUMENT, "omc_state_pool_fetch_shor: a solve is running");
+  { std::lock_guard<std::mutex> lk(h->sig_mu);
+    if (h->pool_sig[entry].kind != 2) return fail(OMC_ERR_ARGUMENT, "omc_state_pool_fetch_shor: the entry is empty or was saved by a base-mode solve"); }
+  HIPCHK(hipSetDevice(h->device));
+  const size_t n = h->n, m = h->m, pnq = (size_t)h->pool_nqmax;
+  const ShorPoolLayout L = shor_pool_layout(h->n, h->m, (int)pnq);
+  const double* E = h->pShor.as<double>() + (size_t)entry * L.stride;
+  long long hd[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(hd, h->pShorHdr.as<long long>() + (size_t)entry * 4, sizeof(hd), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const size_t q = (size_t)std::max<long long>(0, std::min<long long>(hd[0], (long long)pnq));
+  if (nq) *nq = (int64_t)q;
+  const double isc = 1.0 / shor_scale(h), is2 = isc * isc;
+  if (X) { HIPCHK(hipMemcpyAsync(X, E + L.X, 8 * n * m, hipMemcpyDeviceToHost, h->stream)); }
+  if (Theta) { HIPCHK(hipMemcpyAsync(Theta, E + L.Th, 8 * m * m, hipMemcpyDeviceToHost, h->stream)); }
+  std::vector<double> Vs;
+  if (V && q) { Vs.resize(5 * q); for (int c = 0; c < 5; ++c) HIPCHK(hipMemcpyAsync(Vs.data() + c * q, E + L.V + c * pnq, 8 * q, hipMemcpyDeviceToHost, h->stream)); }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (X) for (size_t e = 0; e < n * m; ++e) X[e] *= isc;
+  if (Theta) for (size_t e = 0; e < m * m; ++e) Theta[e] *= is2;
+  if (V) for (size_t t = 0; t < q; ++t) for (int c = 0; c < 5; ++c) V[t * 5 + c] = Vs[c * q + t] * is2;
   return 0;
 }
 
@@ -1103,6 +1204,7 @@ int omc_relax_solve(omc_instance* h) {
       int rc = push_flags(init, fin); if (rc) return rc;
       TIMED(OMC_KERNEL_HARVEST, nfin, {
         if (w.save_to) omc_launch_state_save(&w, s);                              // warm-start pool: before the recovery overwrites the iterate U = Q Vt
+        if (shor) omc_shor_launch_state_save(&sw, s);                             // its Shor extension (no-op without indices)
         omc_launch_small(&w, SMALL_RECOVER, s);   // a U with U U' <= Y and the same Q'U
         if (w.sep_done) omc_launch_sep_sub(&w, s);                                // separation vector from the tracked block where there is one
         omc_launch_cone(&w, CONE_SEP, s);           // separation vector (OMC.jl:2466-2477)
@@ -1120,6 +1222,15 @@ int omc_relax_solve(omc_instance* h) {
         else node_of[b] = -1;
       }
       rc = push_flags(init, fin); if (rc) return rc;      // synchronises the stream: the harvest kernels have written the per-node outputs
+      if (w.save_to) {      // the entries these nodes saved to hold their state from here on (push_flags has synchronised the stream)
+        std::lock_guard<std::mutex> lk(h->sig_mu);
+        for (int id : harvested_ids) {
+          const int sv = (size_t)id < h->save_host.size() ? h->save_host[id] : -1;
+          if (sv < 0 || (size_t)sv >= h->pool_sig.size()) continue;
+          if (shor) { h->pool_sig[sv] = h->node_sig[id]; ++h->shor_warm_stats[3]; }
+          else { h->pool_sig[sv] = omc_instance::PoolSig{}; h->pool_sig[sv].kind = 1; }
+        }
+      }
       { std::lock_guard<std::mutex> lk(h->done_mu); h->done_q.insert(h->done_q.end(), harvested_ids.begin(), harvested_ids.end()); }
       if (ninit) { if (shor) omc_shor_launch_setup(&sw, s); TIMED(OMC_KERNEL_SETUP, ninit, omc_launch_setup(&w, s)); mw_budget[0] = mw_budget[1] = MAX_SWEEPS; }
     }
@@ -1195,8 +1306,17 @@ int omc_relax_append(omc_instance* h, int B2, const int* L, const double* cut_x,
   { int rc = put_descriptors(w, pk, B2, B2, f, L, cut_x, as); if (rc) return rc; }
   std::vector<double> hrho(B2, w.rho);
   HIPCHK(hipMemcpyAsync(const_cast<double*>(w.rho_node) + f, hrho.data(), 8 * (size_t)B2, hipMemcpyHostToDevice, as));
-  if (load_from) HIPCHK(hipMemcpyAsync(const_cast<int*>(w.load_from) + f, load_from, sizeof(int) * B2, hipMemcpyHostToDevice, as));
-  if (save_to) HIPCHK(hipMemcpyAsync(const_cast<int*>(w.save_to) + f, save_to, sizeof(int) * B2, hipMemcpyHostToDevice, as));
+  std::vector<int> lfv;
+  if (load_from) {      // as at stage time: no base start from an entry that a Shor solve saved
+    lfv.assign(load_from, load_from + B2);
+    std::lock_guard<std::mutex> lk2(h->sig_mu);
+    for (int& e : lfv) if (e >= 0 && (size_t)e < h->pool_sig.size() && h->pool_sig[e].kind == 2) e = -1;
+    HIPCHK(hipMemcpyAsync(const_cast<int*>(w.load_from) + f, lfv.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
+  }
+  if (save_to) {
+    HIPCHK(hipMemcpyAsync(const_cast<int*>(w.save_to) + f, save_to, sizeof(int) * B2, hipMemcpyHostToDevice, as));
+    for (int b = 0; b < B2; ++b) h->save_host[f + b] = save_to[b];      // sized for node_cap at stage time; read by the solve only below Btot_live
+  }
   HIPCHK(hipStreamSynchronize(as));
   h->Btot_live.store(first + B2); h->Btot = first + B2;
   if (!h->worker_running.load()) h->ws.Btot = first + B2;      // no solve in flight: the staged batch simply grew
@@ -1377,7 +1497,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   }
   if (so[B] > 0 && !shor_idx) return fail(OMC_ERR_ARGUMENT, "shor_idx is NULL but n_shor > 0");
   if (co[B] > 0 && !soc_idx) return fail(OMC_ERR_ARGUMENT, "soc_idx is NULL but n_soc > 0");
-  auto fnv = [](const void* p, size_t bytes, uint64_t hsh) { const uint8_t* c = (const uint8_t*)p; for (size_t e = 0; e < bytes; ++e) { hsh ^= c[e]; hsh *= 1099511628211ull; } return hsh; };
+  auto fnv = fnv1a;
   std::unordered_map<uint64_t, std::vector<int>> byhash;      // hash -> group ids
   std::vector<int> rep;                                        // representative node of each group
   std::vector<int> node_group(B);
@@ -1480,12 +1600,45 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
     bool all_free = true;
     for (int g = 0; g < NG && all_free; ++g) for (int j = 0; j < m; ++j) if (gh[g].ctype[j] != 0) { all_free = false; break; }
     if (all_free && !h->tun.shor_explicit) {
+      h->warm_load.clear(); h->warm_save.clear();      // warm-start indices are not honoured on this path (include/omc.h)
       int rc0 = omc_relax_stage(h, B, params, cut_type, L, cut_x, cut_Uhat, cut_dir, U_lower, U_upper);
       if (rc0) return rc0;
       h->shor_via_base = true;
       h->shor_slackrow = gh[0].slackrow;      // first unobserved row of every column (a property of the mask: the same for every list)
       return 0;
     }
+  }
+  // ---- warm start: the indices of omc_relax_set_warm pass the host's filter, so that the kernels see a plain "warm or cold" per node ------
+  for (int q = 0; q < 4; ++q) h->shor_warm_stats[q] = 0;
+  h->shor_warm = false;
+  std::vector<uint64_t> list_hash(NG);
+  for (int g = 0; g < NG; ++g) list_hash[g] = fnv(shor_idx + 4 * so[rep[g]], 32 * (size_t)n_shor[rep[g]], FNV_SEED);
+  if (h->pool_cap > 0 && h->pool_shor && h->k == 1 && (h->warm_load.size() == (size_t)B || h->warm_save.size() == (size_t)B)) {
+    h->node_sig.assign(B, omc_instance::PoolSig{});
+    for (int b = 0; b < B; ++b) {
+      omc_instance::PoolSig& sg = h->node_sig[b];
+      sg.kind = 2; sg.nq = n_shor[b]; sg.nsoc = n_soc[b]; sg.hlist = list_hash[node_group[b]];
+      sg.hsoc = n_soc[b] > 0 ? fnv(soc_idx + 2 * co[b], 16 * (size_t)n_soc[b], FNV_SEED) : 0;
+    }
+    std::lock_guard<std::mutex> lk(h->sig_mu);
+    if (h->warm_load.size() == (size_t)B)
+      for (int b = 0; b < B; ++b) {
+        int& e = h->warm_load[b];
+        if (e < 0) continue;
+        const omc_instance::PoolSig& pe = h->pool_sig[e];
+        const omc_instance::PoolSig& sg = h->node_sig[b];
+        int how = 0;      // empty, saved by the base engine, larger than the reservation, or not related by shor_warm_rule: cold start
+        if (pe.kind == 2 && pe.nq <= h->pool_nqmax && pe.nq <= sg.nq) {
+          const bool same_head = pe.hlist == (pe.nq == sg.nq ? sg.hlist : fnv(shor_idx + 4 * so[b], 32 * (size_t)pe.nq, FNV_SEED));
+          how = shor_warm_rule(pe.nq, pe.nsoc, sg.nq, sg.nsoc, same_head, pe.nsoc == sg.nsoc && pe.hsoc == sg.hsoc);
+        }
+        if (how == 0) { e = -1; ++h->shor_warm_stats[2]; } else ++h->shor_warm_stats[how - 1];
+      }
+    if (h->warm_save.size() == (size_t)B)
+      for (int b = 0; b < B; ++b) if (h->warm_save[b] >= 0 && n_shor[b] > h->pool_nqmax) h->warm_save[b] = -1;      // no room for this list
+    h->shor_warm = true;
+  } else {
+    h->warm_load.clear(); h->warm_save.clear();      // no reservation (or rank k > 1): ignored
   }
   // ---- base staging (rows, small cone, clip, certificate machinery) with the Shor flag ----------------------------------------------
   h->shor_req = true;
@@ -1507,7 +1660,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
       size_t o = G.off_int;
       const int* base = h->sgInts.as<int>();
       auto put = [&](const std::vector<int>& v) { const int* dp = base + o; if (!v.empty()) memcpy(&hi[o], v.data(), v.size() * sizeof(int)); o += v.size(); return dp; };
-      gd[g].nq = G.nq; gd[g].nv1 = G.nv1; gd[g].nv2 = G.nv2; gd[g].pad = 0;
+      gd[g].nq = G.nq; gd[g].nv1 = G.nv1; gd[g].nv2 = G.nv2; gd[g].pad = 0; gd[g].hash = list_hash[g];
       // the weight of the order-5 blocks on an entry of X / W is r4 x (blocks that hold it): r4 follows the mean multiplicity 4 nq / (n m)
       // (measured: 20 at 12 x 14 with 152 minors, 5 at 100 x 100 with 38 813, 1.2 at 200 x 200 with 632 732 certify fastest)
       gd[g].r4 = (h->shor_r4 > 0.0) ? h->shor_r4 : std::min(40.0, std::max(0.25, 75.0 * (double)n * (double)m / (4.0 * (double)std::max(G.nq, 1))));
@@ -1524,7 +1677,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
     HIPCHK(hipStreamSynchronize(s));          // the host vectors die with this block
   }
   // ---- scaling: the program is homogeneous of degree 2 in A (oracle: shor_scale) -------------------------------------------------------
-  const double sc = sqrt(((double)h->nnz / ((double)n * m)) * (double)std::min(n, m) / std::max(h->sumA2, 1e-300));
+  const double sc = shor_scale(h);
   {
     std::vector<double> Ah((size_t)n * m);
     for (size_t e = 0; e < Ah.size(); ++e) Ah[e] = h->A[e] * sc;
@@ -1568,6 +1721,12 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   sh.objcol = w.objcol; sh.c0col = w.c0col; sh.lamDX = w.lamDX;
   sh.oX = h->soX.as<double>(); sh.oW = h->soW.as<double>(); sh.oTh = h->soTh.as<double>();
   sh.oV = nullptr;
+  if (w.load_from || w.save_to) {      // indices that passed the filter above: the Shor extension of the pool beside the base entries
+    const ShorPoolLayout PL = shor_pool_layout(n, m, (int)h->pool_nqmax);
+    sh.load_from = w.load_from; sh.save_to = w.save_to; sh.pscal = w.pscal; sh.pY = w.pY; sh.rho_node = w.rho_node;
+    sh.pS = h->pShor.as<double>(); sh.pShdr = h->pShorHdr.as<long long>(); sh.pstride = PL.stride; sh.pnq = (int)h->pool_nqmax;
+    ENS(h->sloadpart, sB * NPb * 2 * 8); sh.loadpart = h->sloadpart.as<double>();
+  }
   if (h->shor_keep_V) { ENS(h->soV, sN * 5 * nq1 * 8); HIPCHK(hipMemsetAsync(h->soV.p, 0, sN * 5 * nq1 * 8, s)); sh.oV = h->soV.as<double>(); }
   // ---- base workspace in Shor mode, and the view through which its eigen-kernels project the order-(n+m) cone -------------------------
   w.shor = 1; w.shN = N; w.shP0 = sh.P0; w.shD0 = sh.D0; w.inv_s2 = 1.0 / (sc * sc);

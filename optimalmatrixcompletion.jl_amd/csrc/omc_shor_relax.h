@@ -15,6 +15,7 @@
 // index structure of one Shor list (shared by every node that carries the same list: the reference's static mode gives all nodes one list)
 struct ShorGroupDev {
   int nq, nv1, nv2, pad;
+  unsigned long long hash;   // FNV-1a of the list's tuples (the host's signature of a pool entry; written to the entry's header by k_shor_state_save)
   double r4;            // penalty of this list's order-5 blocks relative to rho (auto: 75 n m / (4 nq), clamped to [0.25, 40])
   const int* mi;        // 4 * nq: i1, i2, j1, j2 (0-based), SoA: mi[c * nq + q]
   const int* kid;       // 4 * nq: key ids of V1[i1,(j1,j2)], V1[i2,(j1,j2)], V2[(i1,i2),j1], V2[(i1,i2),j2], SoA
@@ -49,7 +50,25 @@ struct ShWS {
   double *objcol, *c0col, *lamDX;               // base certificate inputs (S*m, S*m, S*m*n)
   double *oX, *oW, *oTh;                        // Btot * (n*m, n*m, m*m)
   double* oV;                                   // Btot * 5 * nqmax (NULL: not kept): V1a, V1b, V2a, V2b, V3 per minor
+  // warm start (omc_state_pool_reserve_shor): NULL / 0 when the batch carries no pool indices.  The host has already replaced every index
+  // that may not be used by -1, so a node is simply warm (load_from >= 0) or cold.
+  const int *load_from, *save_to;               // Btot: pool entries
+  const double *pscal, *pY, *rho_node;          // base pool: penalty of the saved state (pscal[4 e]) and its Y ; base penalty per node
+  double* pS; long long* pShdr;                 // pool_cap * pstride doubles (layout: shor_pool_*) ; pool_cap * 4: nq, list hash, 0, 0
+  size_t pstride; int pnq;                      // doubles per entry ; minors an entry has room for (stride of its per-minor arrays)
+  double* loadpart;                             // S * NPb * 2: per-column sums of the rebuilt big-cone input (k_shor_state_load)
 };
+
+// Shor extension of a pool entry, in doubles: X, W (completed: X^2 off the minors), D5x | Theta | D0 | D5t, nu5 | Tq (15 per minor, SoA with
+// stride pnq) | the five lifted values of every minor (SoA with stride pnq).  3 n m + m^2 + (n + m)^2 + 2 m + 20 pnq in all.
+struct ShorPoolLayout { size_t X, W, D5x, Th, D0, D5t, nu5, Tq, V, stride; };
+static inline __host__ __device__ ShorPoolLayout shor_pool_layout(int n, int m, int pnq) {
+  ShorPoolLayout L;
+  const size_t nm = (size_t)n * m, N = (size_t)n + m;
+  L.X = 0; L.W = nm; L.D5x = 2 * nm; L.Th = 3 * nm; L.D0 = L.Th + (size_t)m * m; L.D5t = L.D0 + N * N; L.nu5 = L.D5t + m;
+  L.Tq = L.nu5 + m; L.V = L.Tq + (size_t)15 * pnq; L.stride = L.V + (size_t)5 * pnq;
+  return L;
+}
 
 #ifdef __cplusplus
 extern "C" {
@@ -63,6 +82,7 @@ void omc_shor_launch_reduce(const ShWS* w, hipStream_t s);
 void omc_shor_launch_check(const ShWS* w, hipStream_t s);
 void omc_shor_launch_rescale(const ShWS* w, hipStream_t s);
 void omc_shor_launch_harvest(const ShWS* w, hipStream_t s);
+void omc_shor_launch_state_save(const ShWS* w, hipStream_t s);
 #ifdef __cplusplus
 }
 #endif

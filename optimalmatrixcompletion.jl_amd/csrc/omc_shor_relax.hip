@@ -109,6 +109,7 @@ __device__ __forceinline__ double fro_weight(int e) { return (e == 0 || e == 2 |
 __global__ void __launch_bounds__(SH_T) k_shor_setup(ShWS w, double y0) {
   const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
   if (!w.init[b]) return;
+  if (w.load_from && w.load_from[w.node_of[b]] >= 0) return;      // warm: k_shor_state_load has filled the slot
   const int n = w.n, m = w.m, N = w.N, NP = w.NPb;
   const size_t nm = (size_t)n * m;
   for (size_t e = tid; e < nm; e += T) { w.X[b * nm + e] = 0.0; w.W[b * nm + e] = 0.0; w.D5x[b * nm + e] = 0.0; w.P5x[b * nm + e] = 0.0; }
@@ -643,8 +644,171 @@ __global__ void __launch_bounds__(SH_T) k_shor_harvest(ShWS w) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// warm start: the final Shor state of a node in a pool entry, and a child's start from it.  Both kernels run on
+// grids of (blocks x slots) whose blocks return at the filter; plain grid-stride copies, no atomics, sums in a fixed order.
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Final state of the slots flagged fin whose node names an entry (next to the base k_state_save, which keeps Y, U, the duals of the two
+// base cones and the penalty).  Tq holds the duals of the order-5 blocks here (k_shor_minor_post).  The lifted variables are stored as
+// values per minor, not per key: key numbering belongs to a list.  W is completed by X^2 off the minors, so that a child whose list adds
+// coordinates finds a sensible value there without knowing the parent's classes.
+__global__ void __launch_bounds__(SH_T) k_shor_state_save(ShWS w) {
+  const int b = blockIdx.y;
+  if (!w.fin[b]) return;
+  const int nb = w.node_of[b];
+  const int sv = w.save_to[nb];
+  if (sv < 0) return;
+  const ShorGroupDev G = w.groups[w.node_group[nb]];
+  const int nq = G.nq, pnq = w.pnq;
+  if (nq > pnq) return;                                   // the host does not ask for it (omc_relax_stage_shor)
+  const int n = w.n, m = w.m, N = w.N;
+  const size_t nm = (size_t)n * m, g0 = (size_t)blockIdx.x * SH_T + threadIdx.x, gs = (size_t)gridDim.x * SH_T;
+  const ShorPoolLayout L = shor_pool_layout(n, m, pnq);
+  double* E = w.pS + (size_t)sv * w.pstride;
+  const double* X = w.X + b * nm; const double* W = w.W + b * nm;
+  for (size_t e = g0; e < nm; e += gs) {
+    const double x = X[e];
+    E[L.X + e] = x; E[L.W + e] = (G.eclass[e] == 2) ? W[e] : x * x; E[L.D5x + e] = w.D5x[b * nm + e];
+  }
+  for (size_t e = g0; e < (size_t)m * m; e += gs) E[L.Th + e] = w.Th[(size_t)b * m * m + e];
+  for (size_t e = g0; e < (size_t)N * N; e += gs) E[L.D0 + e] = w.D0[(size_t)b * N * N + e];
+  for (size_t e = g0; e < (size_t)m; e += gs) { E[L.D5t + e] = w.D5t[(size_t)b * m + e]; E[L.nu5 + e] = w.nu5[(size_t)b * m + e]; }
+  const double* Tq = w.Tq + (size_t)b * 15 * w.nqmax;
+  for (size_t t = g0; t < (size_t)15 * nq; t += gs) { const size_t e = t / nq, q = t % nq; E[L.Tq + e * pnq + q] = Tq[e * w.nqmax + q]; }
+  const double* V1 = w.V1 + (size_t)b * w.nv1max; const double* V2 = w.V2 + (size_t)b * w.nv2max; const double* V3 = w.V3 + (size_t)b * w.nqmax;
+  for (size_t t = g0; t < (size_t)5 * nq; t += gs) {
+    const size_t c = t / nq, q = t % nq;
+    E[L.V + c * pnq + q] = (c < 2) ? V1[G.kid[c * nq + q]] : (c < 4) ? V2[G.kid[c * nq + q]] : V3[q];
+  }
+  if (g0 == 0) { long long* hd = w.pShdr + (size_t)sv * 4; hd[0] = nq; hd[1] = (long long)G.hash; hd[2] = 0; hd[3] = 0; }
+}
+
+// Start of the slots that received a node with load_from >= 0 (runs before k_shor_setup, which leaves them alone, and before the base
+// k_setup, which loads Y, U and the duals of the base cones from the same entry and clears the init flag).  Everything is read from the
+// pool, nothing from what another block of this launch writes.
+//   X, W, Theta copied; D0, D5x, D5t and the duals of the order-5 blocks times fw = rho_parent / rho_child (the factor k_setup applies
+//   to D1 / D3: the multipliers rho D are unchanged; the child keeps its own base penalty); minors beyond the parent's list: zero duals;
+//   every key of the child's list: the saved value of its first member that the parent had, else the rank-one value from X (V3: the
+//   mean of the minor's two products) -- one writer per key;
+//   the big cone's next input [Y X; X' Theta] - D0 with its zero padding, one column per block pass, and its per-column sums
+//   (k_shor_state_load_fin adds them in a fixed order); P0, Pq, Nq, P5x, VrowB zero.
+__global__ void __launch_bounds__(SH_T) k_shor_state_load(ShWS w) {
+  __shared__ double red[32];
+  const int b = blockIdx.y;
+  if (!w.init[b]) return;
+  const int nb = w.node_of[b];
+  const int lf = w.load_from[nb];
+  if (lf < 0) return;
+  const ShorGroupDev G = w.groups[w.node_group[nb]];
+  const int n = w.n, m = w.m, N = w.N, NP = w.NPb, pnq = w.pnq, nq = G.nq;
+  int nqp = (int)w.pShdr[(size_t)lf * 4];                  // minors of the saved list: a prefix of this node's (the host checked)
+  nqp = nqp < 0 ? 0 : nqp > nq ? nq : nqp; nqp = nqp > pnq ? pnq : nqp;
+  const size_t nm = (size_t)n * m, g0 = (size_t)blockIdx.x * SH_T + threadIdx.x, gs = (size_t)gridDim.x * SH_T;
+  const ShorPoolLayout L = shor_pool_layout(n, m, pnq);
+  const double* E = w.pS + (size_t)lf * w.pstride;
+  const double* pX = E + L.X;
+  const double fw = w.pscal[(size_t)lf * 4] / w.rho_node[nb];
+  for (size_t e = g0; e < nm; e += gs) {
+    w.X[b * nm + e] = pX[e]; w.W[b * nm + e] = E[L.W + e]; w.D5x[b * nm + e] = E[L.D5x + e] * fw; w.P5x[b * nm + e] = 0.0;
+  }
+  for (size_t e = g0; e < (size_t)m * m; e += gs) w.Th[(size_t)b * m * m + e] = E[L.Th + e];
+  for (size_t e = g0; e < (size_t)m; e += gs) { w.D5t[(size_t)b * m + e] = E[L.D5t + e] * fw; w.nu5[(size_t)b * m + e] = E[L.nu5 + e]; }
+  for (size_t e = g0; e < (size_t)N * N; e += gs) { w.D0[(size_t)b * N * N + e] = E[L.D0 + e] * fw; w.P0[(size_t)b * N * N + e] = 0.0; }
+  for (size_t e = g0; e < (size_t)NP * NP; e += gs) w.VrowB[(size_t)b * NP * NP + e] = 0.0;
+  for (size_t t = g0; t < (size_t)15 * w.nqmax; t += gs) {
+    const size_t e = t / w.nqmax, q = t % w.nqmax;
+    w.Tq[(size_t)b * 15 * w.nqmax + t] = (q < (size_t)nqp) ? E[L.Tq + e * pnq + q] * fw : 0.0;
+    w.Pq[(size_t)b * 15 * w.nqmax + t] = 0.0; w.Nq[(size_t)b * 15 * w.nqmax + t] = 0.0;
+  }
+  // lifted variables, one thread per key of THIS node's list
+  for (size_t t = g0; t < (size_t)G.nv1; t += gs) {
+    const int p0 = G.v1ptr[t], p1 = G.v1ptr[t + 1];
+    int p = p0;
+    while (p < p1 && (G.v1ent[p] >> 1) >= nqp) ++p;
+    double v;
+    if (p < p1) { const int ent = G.v1ent[p]; v = E[L.V + (size_t)(ent & 1) * pnq + (ent >> 1)]; }
+    else {
+      const int ent = G.v1ent[p0], q = ent >> 1;
+      const int i = G.mi[(ent & 1) * nq + q], j1 = G.mi[2 * nq + q], j2 = G.mi[3 * nq + q];
+      v = pX[(size_t)j1 * n + i] * pX[(size_t)j2 * n + i];
+    }
+    w.V1[(size_t)b * w.nv1max + t] = v;
+  }
+  for (size_t t = g0; t < (size_t)G.nv2; t += gs) {
+    const int p0 = G.v2ptr[t], p1 = G.v2ptr[t + 1];
+    int p = p0;
+    while (p < p1 && (G.v2ent[p] >> 1) >= nqp) ++p;
+    double v;
+    if (p < p1) { const int ent = G.v2ent[p]; v = E[L.V + (size_t)(2 + (ent & 1)) * pnq + (ent >> 1)]; }
+    else {
+      const int ent = G.v2ent[p0], q = ent >> 1;
+      const int i1 = G.mi[q], i2 = G.mi[nq + q], j = G.mi[(2 + (ent & 1)) * nq + q];
+      v = pX[(size_t)j * n + i1] * pX[(size_t)j * n + i2];
+    }
+    w.V2[(size_t)b * w.nv2max + t] = v;
+  }
+  for (size_t q = g0; q < (size_t)w.nqmax; q += gs) {
+    double v = 0.0;
+    if (q < (size_t)nqp) v = E[L.V + (size_t)4 * pnq + q];
+    else if (q < (size_t)nq) {
+      const int i1 = G.mi[q], i2 = G.mi[nq + q], j1 = G.mi[2 * nq + q], j2 = G.mi[3 * nq + q];
+      v = 0.5 * (pX[(size_t)j1 * n + i1] * pX[(size_t)j2 * n + i2] + pX[(size_t)j2 * n + i1] * pX[(size_t)j1 * n + i2]);
+    }
+    w.V3[(size_t)b * w.nqmax + q] = v;
+  }
+  // next input of the big cone, column by column (the sums of a column do not depend on the grid)
+  const double* pY = w.pY + (size_t)lf * n * n;
+  for (int jj = blockIdx.x; jj < NP; jj += gridDim.x) {
+    double fr2 = 0.0, tr1 = 0.0;
+    for (int i = threadIdx.x; i < NP; i += SH_T) {
+      double mv = 0.0;
+      if (i < N && jj < N) {
+        double g;
+        if (i < n && jj < n) g = pY[(size_t)jj * n + i];
+        else if (i < n) g = pX[(size_t)(jj - n) * n + i];
+        else if (jj < n) g = pX[(size_t)(i - n) * n + jj];
+        else g = E[L.Th + (size_t)(jj - n) * m + (i - n)];
+        mv = g - E[L.D0 + (size_t)jj * N + i] * fw;
+        fr2 += mv * mv;
+        if (i == jj) tr1 += mv;
+      }
+      w.MbufB[(size_t)b * NP * NP + (size_t)jj * NP + i] = mv;
+    }
+    fr2 = block_sum(fr2, red);
+    tr1 = block_sum(tr1, red);
+    if (threadIdx.x == 0) { w.loadpart[((size_t)b * NP + jj) * 2] = fr2; w.loadpart[((size_t)b * NP + jj) * 2 + 1] = tr1; }
+  }
+}
+
+// sums of the loaded slots in a fixed order; the big cone's eigen-state starts cold (only the first projection of a node pays for that)
+__global__ void __launch_bounds__(SH_T) k_shor_state_load_fin(ShWS w) {
+  __shared__ double red[32];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (!w.init[b]) return;
+  if (w.load_from[w.node_of[b]] < 0) return;
+  double f = 0.0, tr = 0.0;
+  for (int j = tid; j < w.N; j += SH_T) { f += w.loadpart[((size_t)b * w.NPb + j) * 2]; tr += w.loadpart[((size_t)b * w.NPb + j) * 2 + 1]; }
+  f = block_sum(f, red); tr = block_sum(tr, red);
+  if (tid == 0) {
+    w.fro2B[b] = f; w.trB[b] = tr; w.vvalidB[b] = 0;
+    if (w.sub_onB) { w.sub_onB[b] = 0; w.cone_doneB[b] = 0; w.sub_waitB[b] = 0; w.sub_nfailB[b] = 0; }
+  }
+}
+
+// blocks per slot of the two state kernels: enough for the largest array of an entry at four elements per thread
+static int shor_state_blocks(const ShWS* w) {
+  const size_t big = (size_t)15 * (size_t)(w->nqmax > 0 ? w->nqmax : 1), nn = (size_t)w->NPb * w->NPb;
+  const size_t el = big > nn ? big : nn;
+  const size_t g = (el + (size_t)SH_T * 4 - 1) / ((size_t)SH_T * 4);
+  return (int)(g < 1 ? 1 : g > 4096 ? 4096 : g);
+}
+
 extern "C" {
 void omc_shor_launch_setup(const ShWS* w, hipStream_t s) {
+  if (w->load_from) {
+    hipLaunchKernelGGL(k_shor_state_load, dim3(shor_state_blocks(w), w->S), dim3(SH_T), 0, s, *w);
+    hipLaunchKernelGGL(k_shor_state_load_fin, dim3(w->S), dim3(SH_T), 0, s, *w);
+  }
   hipLaunchKernelGGL(k_shor_setup, dim3(w->S), dim3(SH_T), 0, s, *w, (double)w->k / (double)w->n);      // Y0 = (k / n) I
 }
 void omc_shor_launch_minor_pre(const ShWS* w, hipStream_t s) {
@@ -668,5 +832,8 @@ void omc_shor_launch_check(const ShWS* w, hipStream_t s) {
   hipLaunchKernelGGL(k_shor_chk_cols, dim3(w->m, w->S), dim3(SH_T), 0, s, *w);
 }
 void omc_shor_launch_rescale(const ShWS* w, hipStream_t s) { hipLaunchKernelGGL(k_shor_rescale, dim3(w->S), dim3(SH_T), 0, s, *w); }
+void omc_shor_launch_state_save(const ShWS* w, hipStream_t s) {
+  if (w->save_to) hipLaunchKernelGGL(k_shor_state_save, dim3(shor_state_blocks(w), w->S), dim3(SH_T), 0, s, *w);
+}
 void omc_shor_launch_harvest(const ShWS* w, hipStream_t s) { hipLaunchKernelGGL(k_shor_harvest, dim3(w->m, w->S), dim3(SH_T), 0, s, *w); }
 }
