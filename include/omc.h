@@ -358,6 +358,21 @@ int omc_comm_destroy(omc_instance* h);
 #define OMC_KERNEL_NCLASS 14      /* OMC_KERNEL_CHECK = eigenvalues of the Lagrangian matrix + decisions */
 /* info[8]: solve seconds, total Jacobi sweeps of k_cone, rho, r_max, LDS flags (cone, global, small), R_max */
 int omc_last_solver_info(omc_instance* h, double* info);
+/* Workgroups per CU that the HIP runtime reports (hipOccupancyMaxActiveBlocksPerMultiprocessor) for the iteration kernels, at the block
+ * size and the dynamic LDS of the geometry last staged on this instance (error before the first stage).  out[OMC_RES_N]; -1 = the kernel is
+ * not launched at this geometry.  A residency lost to registers or LDS shows here, not only in a profile.  No counterpart in the reference. */
+#define OMC_RES_CONE_SUB 0        /* k_cone_sub<0>: the cone block */
+#define OMC_RES_CONE_SUB_CERT 1   /* k_cone_sub<1>: certificate estimator */
+#define OMC_RES_CONE_SUB_SEP 2    /* k_cone_sub<2>: separation vector */
+#define OMC_RES_GLOBAL 3          /* k_global, LDS or L2-resident variant as planned */
+#define OMC_RES_SMALL 4           /* k_small, likewise */
+#define OMC_RES_COLPROX_PAIR 5
+#define OMC_RES_COLPROX_WIDE 6
+#define OMC_RES_COLPROX 7         /* one column per wave */
+#define OMC_RES_CONE_WS 8         /* the k_cone_ws variant in use */
+#define OMC_RES_CONE 9            /* k_cone (cold Jacobi) */
+#define OMC_RES_N 10
+int omc_kernel_residency(omc_instance* h, int* out);
 /* out[8] of the last omc_relax_solve: calls of k_cone_sub, its power steps, calls that fell back to the full eigendecomposition,
  * seedings of the tracked subspace by the full kernel, fall-backs by cause (more than 12 positive Ritz values, step cap, Cholesky
  * breakdown), Rayleigh-Ritz passes */

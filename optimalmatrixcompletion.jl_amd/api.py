@@ -29,6 +29,9 @@ BREAKPOINTS = {"smallest_1_eigvec": 1, "smallest_2_eigvec": 2}
 STATUS_NAMES = {0: "OPTIMAL", 1: "SLOW_PROGRESS", 2: "TIME_LIMIT", 3: "INFEASIBLE"}
 KERNEL_CLASSES = ["colprox", "cone", "global", "check", "setup", "small", "accel", "cone_sub", "check_col", "check_build", "harvest",
                   "shor_bigcone", "shor_minors", "shor_cols"]
+# order of omc_kernel_residency's output (OMC_RES_* in include/omc.h)
+RESIDENCY_KERNELS = ["k_cone_sub<0>", "k_cone_sub<1>", "k_cone_sub<2>", "k_global", "k_small", "k_colprox_pair", "k_colprox_wide", "k_colprox",
+                     "k_cone_ws", "k_cone"]
 
 
 def default_params(**kw) -> RelaxParams:
@@ -382,6 +385,13 @@ class Engine:
         _lib.check(self._lib.omc_last_shor_subspace_stats(self._h, _lib.ptr(out)))
         return dict(calls=int(out[0]), power_steps=int(out[1]), fallbacks=int(out[2]), seeds=int(out[3]), fail_positive=int(out[4]),
                     fail_steps=int(out[5]), fail_cholesky=int(out[6]), ritz_passes=int(out[7]))
+
+    def kernel_residency(self):
+        """Workgroups per CU that the HIP runtime reports for the iteration kernels at the geometry last staged (block size and dynamic
+        LDS as launched); -1 for a kernel that geometry does not launch.  Read-only: solver_info() keeps its shape."""
+        out = np.zeros(len(RESIDENCY_KERNELS), np.int32)
+        _lib.check(self._lib.omc_kernel_residency(self._h, _lib.ptr(out)))
+        return {nm: int(v) for nm, v in zip(RESIDENCY_KERNELS, out)}
 
     def solver_info(self):
         info = np.zeros(8)

@@ -2663,6 +2663,14 @@ int omc_last_subspace_stats(omc_instance* h, int64_t* out) {
   return 0;
 }
 
+int omc_kernel_residency(omc_instance* h, int* out) {
+  if (!h || !out) return fail(OMC_ERR_ARGUMENT, "NULL argument");
+  if (!h->ws.geo.sub_lds) return fail(OMC_ERR_ARGUMENT, "omc_kernel_residency: nothing staged yet (the geometry is planned by omc_relax_stage)");
+  HIPCHK(hipSetDevice(h->device));
+  omc_query_residency(&h->ws, out);
+  return 0;
+}
+
 int omc_last_kernel_stats(omc_instance* h, int64_t* launches, double* ms, int64_t* units) {
   if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
   for (int c = 0; c < OMC_KERNEL_NCLASS; ++c) {

@@ -337,3 +337,10 @@ extern "C" void omc_launch_colprox_sweep(const OmcWS* w, hipStream_t s) {
     hipLaunchKernelGGL(k_colprox_wide, dim3((ww + wpb - 1) / wpb), dim3(wpb * 64), (size_t)wpb * CPP_LDS_DOUBLES * sizeof(double), s, *w);
   }
 }
+
+extern "C" void omc_colprox_sweep_residency(int* pair, int* wide) {
+  const int wpb = 4;
+  const size_t lds = (size_t)wpb * CPP_LDS_DOUBLES * sizeof(double);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(pair, (const void*)k_colprox_pair, wpb * 64, lds) != hipSuccess) *pair = -1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(wide, (const void*)k_colprox_wide, wpb * 64, lds) != hipSuccess) *wide = -1;
+}

@@ -171,6 +171,8 @@ void omc_launch_make_Theta(const OmcWS* w, const double* X, double* Th, hipStrea
 void omc_launch_eval_objective(int B, int n, int m, double gamma, const double* A, const uint8_t* mask, const double* X,
                                double* out, hipStream_t s);
 int omc_set_max_lds(void);
+void omc_query_residency(const OmcWS* w, int* out /* OMC_RES_N */);      /* workgroups per CU of the iteration kernels at w->geo (omc_kernel_residency) */
+void omc_colprox_sweep_residency(int* pair, int* wide);                /* omc_colprox.hip: k_colprox_pair, k_colprox_wide as omc_launch_colprox_sweep launches them */
 void omc_launch_gram_XXt(const OmcWS* w, const double* X, int B, hipStream_t s);
 void omc_launch_colprox_sweep(const OmcWS* w, hipStream_t s);      /* omc_colprox.hip */
 #ifdef __cplusplus

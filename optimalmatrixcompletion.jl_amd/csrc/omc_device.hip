@@ -16,6 +16,7 @@
 #include <type_traits>
 #include <stdint.h>
 #include "omc_device.h"
+#include "omc.h"
 
 #include "omc_wave.h"
 
@@ -1196,8 +1197,11 @@ __global__ void __launch_bounds__(TPB) k_cone_ws(OmcWS w) {
 //     hides outside the block); otherwise more steps, and after sub_qmax steps the slot falls back to the full kernel.
 // The shift s centres the untracked spectrum [lo, theta_min]; lo comes from the first two moments of M (trace and Frobenius
 // norm, written by k_global) by Samuelson's inequality, so it is a rigorous bound, not a guess.
-// One 256-thread workgroup per slot, ~38 KB of LDS: four workgroups per CU.  The full kernel (k_cone_ws) seeds X from its
-// eigenvectors whenever it finds at most SUBP - sub_guard positive eigenvalues.
+// One 256-thread workgroup per slot, ~42 KB of LDS at order 100 (sub_layout).  Registers, not LDS, set the residency: the kernel needs
+// ~240 VGPRs, and __launch_bounds__(256, 2) keeps it inside the 256 of two waves per SIMD = two workgroups per CU (without the second
+// argument the compiler takes the 512-register budget of one wave per SIMD, parks values in AGPRs and halves the residency; three or
+// more workgroups spill).  The full kernel (k_cone_ws) seeds X from its eigenvectors whenever it finds at most SUBP - sub_guard
+// positive eigenvalues.
 // ---------------------------------------------------------------------------------------------------------
 
 // MODE 0: the cone block (above).  MODE 1: the certificate -- the k most negative eigenvalues of the Lagrangian matrix Mchk (k_check_build)
@@ -1205,7 +1209,7 @@ __global__ void __launch_bounds__(TPB) k_cone_ws(OmcWS w) {
 // result is an ESTIMATE of the dual bound (optimistic by the square of the residual): k_check_final uses it for its decisions and every
 // node that is about to finish gets the rigorous eigendecomposition (k_cone_ws, ws_mode = 1) before anything is reported (w.confirm).
 template <int MODE>
-__global__ void __launch_bounds__(256) k_cone_sub(OmcWS w) {
+__global__ void __launch_bounds__(256, 2) k_cone_sub(OmcWS w) {
   extern __shared__ double smem[];
   __shared__ int s_flag, s_nsel, s_cond;
   __shared__ double s_shift, s_cs[SUBP];
@@ -1246,40 +1250,46 @@ __global__ void __launch_bounds__(256) k_cone_sub(OmcWS w) {
   __syncthreads();
 
   // Z (+ s X) = M X for the row tiles of this wave (up to three, computed together: independent accumulators and twelve loads in
-  // flight per lane); operands: M from L2 (symmetric: column k of M is row k), X from LDS
-  auto mul_MX = [&](double shift) {
+  // flight per lane); operands: M from L2 (symmetric: column k of M is row k; 32-bit offsets from the slot's wave-uniform base: one
+  // address register per load instead of two), X from LDS.  X -> Z, or back: Z -> X (LDS only: the source stays an LDS address for the
+  // compiler -- through a generic pointer its reads in the K loop become flat loads that queue behind the prefetches of M).  scaled:
+  // column j of the result is multiplied by s_cs[j] in the tile store (the rescale between the power steps of a chunk: the same
+  // product of the same two values as a pass of its own).
+  auto mul_MX = [&](double shift, bool back, bool scaled) {
+    const double* Xi = Xa + (back ? L.Za : 0);
+    double* Zo = back ? Xa : Za;
     for (int tb = 0; tb < nt; tb += 12) {      // 12 row tiles per pass (NP <= 192: one pass)
       const int b0 = tb + wv;
       if (b0 >= nt) break;
       const int t0 = b0, t1 = (b0 + 4 < nt) ? b0 + 4 : b0, t2 = (b0 + 8 < nt) ? b0 + 8 : b0;     // invalid tiles alias tile t0 (results dropped)
       const bool v1 = b0 + 4 < nt, v2 = b0 + 8 < nt;
       double4v acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = acc0, acc2 = acc0;
-      const double* M0 = Mb + (t0 << 4) + li;
-      const double* M1 = Mb + (t1 << 4) + li;
-      const double* M2 = Mb + (t2 << 4) + li;
-      const double* Xb = Xa + (size_t)li * LD;
+      const unsigned m0 = (t0 << 4) + li, m1 = (t1 << 4) + li, m2 = (t2 << 4) + li;
+      const double* Xb = Xi + (size_t)li * LD;
       double a0[4], a1[4], a2[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) { const size_t o = (size_t)(4 * u + lk) * NP; a0[u] = M0[o]; a1[u] = M1[o]; a2[u] = M2[o]; }
+      for (int u = 0; u < 4; ++u) { const unsigned o = (unsigned)(4 * u + lk) * (unsigned)NP; a0[u] = Mb[m0 + o]; a1[u] = Mb[m1 + o]; a2[u] = Mb[m2 + o]; }
       for (int k0 = 0; k0 < NP; k0 += 16) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const double x0 = sgn * a0[u], x1 = sgn * a1[u], x2 = sgn * a2[u], bv = Xb[k0 + 4 * u + lk];
           int kn = k0 + 16 + 4 * u + lk;
           kn = (kn < NP) ? kn : kn - NP;               // wrapped prefetch of the last chunk is never used
-          const size_t o = (size_t)kn * NP;
-          a0[u] = M0[o]; a1[u] = M1[o]; a2[u] = M2[o];
+          const unsigned o = (unsigned)kn * (unsigned)NP;
+          a0[u] = Mb[m0 + o]; a1[u] = Mb[m1 + o]; a2[u] = Mb[m2 + o];
           acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0, bv, acc0, 0, 0, 0);
           acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1, bv, acc1, 0, 0, 0);
           if (nt > 8) acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(x2, bv, acc2, 0, 0, 0);
         }
       }
+      const double cs = scaled ? s_cs[li] : 1.0;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const size_t a = (size_t)li * LD + lk + 4 * r;
-        Za[a + (t0 << 4)] = acc0[r] + shift * Xa[a + (t0 << 4)];
-        if (v1) Za[a + (t1 << 4)] = acc1[r] + shift * Xa[a + (t1 << 4)];
-        if (v2) Za[a + (t2 << 4)] = acc2[r] + shift * Xa[a + (t2 << 4)];
+        const double z0 = acc0[r] + shift * Xi[a + (t0 << 4)];
+        Zo[a + (t0 << 4)] = scaled ? cs * z0 : z0;
+        if (v1) { const double z1 = acc1[r] + shift * Xi[a + (t1 << 4)]; Zo[a + (t1 << 4)] = scaled ? cs * z1 : z1; }
+        if (v2) { const double z2 = acc2[r] + shift * Xi[a + (t2 << 4)]; Zo[a + (t2 << 4)] = scaled ? cs * z2 : z2; }
       }
     }
   };
@@ -1336,15 +1346,23 @@ __global__ void __launch_bounds__(256) k_cone_sub(OmcWS w) {
     const double shift = s_shift;
     SUBSTAMP(1);
     for (int c = 0; c < chunk && !fail && !skip_steps; ++c) {
-      mul_MX(shift);
+      // inside a chunk the block is only rescaled: the span after `chunk` steps is the same, and the condition of the block grows by
+      // at most (largest / smallest shifted Ritz value)^chunk, which the orthonormalisation at the end of the chunk absorbs (it is
+      // repeated once when its pivots say the block had become ill-conditioned).  The steps alternate between the two buffers, the
+      // rescale in the tile store: X -> Z, Z -> X, ... with the last step of the chunk X -> Z (the orthonormalisation reads Z), so a
+      // step is backward when an odd number of steps follows it.  A first step that would have to be backward (even chunk) and the
+      // Z slab in global memory (orders beyond 512) keep the copy: forward, then X <- s_cs Z as a pass of its own.
+      // MODE 1 keeps the copy as well: it runs only where Z is in the global slab (cert_enable: orders beyond 512).
+      const bool inner = MODE != 2 && c + 1 < chunk, pp = MODE == 0 && !L.zglob, back = inner && pp && c > 0 && ((chunk - 1 - c) & 1);
+      const bool copy = inner && !back && (!pp || ((chunk - 1 - c) & 1));
+      mul_MX(shift, back, inner && !copy);
       __syncthreads();
       SUBSTAMP(2);
-      if (MODE != 2 && c + 1 < chunk) {
-        // inside a chunk the block is only rescaled: the span after `chunk` steps is the same, and the condition of the block grows by
-        // at most (largest / smallest shifted Ritz value)^chunk, which the orthonormalisation at the end of the chunk absorbs (it is
-        // repeated once when its pivots say the block had become ill-conditioned)
-        for (int e = tid; e < SUBP * NP; e += T) { const int j = e / NP, r = e - j * NP; Xa[(size_t)j * LD + r] = s_cs[j] * Za[(size_t)j * LD + r]; }
-        __syncthreads();
+      if (inner) {
+        if (copy) {
+          for (int e = tid; e < SUBP * NP; e += T) { const int j = e / NP, r = e - j * NP; Xa[(size_t)j * LD + r] = s_cs[j] * Za[(size_t)j * LD + r]; }
+          __syncthreads();
+        }
         SUBSTAMP(5);
         ++steps;
         continue;
@@ -1416,7 +1434,7 @@ __global__ void __launch_bounds__(256) k_cone_sub(OmcWS w) {
     if (fail) break;
     skip_steps = false;
     // ---- Rayleigh-Ritz ------------------------------------------------------------------------------------------------------
-    mul_MX(0.0);
+    mul_MX(0.0, false, false);
     __syncthreads();
     gram(Xa, Za);
     SUBSTAMP(6);
@@ -2772,6 +2790,22 @@ static void launch_ws_lds(const OmcWS* w, hipStream_t s) {
     default: hipLaunchKernelGGL((k_cone_ws<LPP, true, 0>), dim3(w->nB), dim3(512), lds_bytes, s, *w); break;
   }
 }
+// omc_query_residency: what the runtime grants a kernel at a block size and dynamic LDS; the k_cone_ws variant launch_ws_lds<LPP> picks
+static int residency_of(const void* kern, int threads, size_t lds) {
+  int nb = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, lds) == hipSuccess ? nb : -1;
+}
+template <int LPP>
+static const void* ws_lds_kernel(int rpl2) {
+  switch (rpl2) {
+    case 4: return (const void*)k_cone_ws<LPP, true, 4>;
+    case 5: return (const void*)k_cone_ws<LPP, true, 5>;
+    case 6: return (const void*)k_cone_ws<LPP, true, 6>;
+    case 7: return (const void*)k_cone_ws<LPP, true, 7>;
+    case 8: return (const void*)k_cone_ws<LPP, true, 8>;
+    default: return (const void*)k_cone_ws<LPP, true, 0>;
+  }
+}
 // Y[b] = X[b] X[b]' (both triangles) for B matrices X of size n x m (column-major), on the matrix cores: the Gram matrix whose k dominant eigenvectors
 // are svd(X).U[:, 1:k] (OMC.jl:524, 564, 921: the rank-k rounding of an incumbent)
 __global__ void __launch_bounds__(256) k_gram_XXt(OmcWS w, const double* X) {
@@ -2864,5 +2898,29 @@ int omc_set_max_lds(void) {
   if (e3 != hipSuccess) return 3000 + (int)e3;
   if (e4 != hipSuccess) return 4000 + (int)e4;
   return 0;
+}
+// Workgroups per CU that the HIP runtime grants each iteration kernel at the block size and dynamic LDS the launchers above use for this
+// workspace (registers, static and dynamic LDS, wave slots: whichever is the tightest).  out[OMC_RES_N]; -1 = the query failed or the
+// kernel is not launched at this geometry (k_cone_ws with the multi-workgroup kernels or beyond its orders).
+void omc_query_residency(const OmcWS* w, int* out) {
+  const OmcGeom& g = w->geo;
+  out[OMC_RES_CONE_SUB] = residency_of((const void*)k_cone_sub<0>, 256, g.sub_lds);
+  out[OMC_RES_CONE_SUB_CERT] = residency_of((const void*)k_cone_sub<1>, 256, g.sub_lds);
+  out[OMC_RES_CONE_SUB_SEP] = residency_of((const void*)k_cone_sub<2>, 256, g.sub_lds);
+  out[OMC_RES_GLOBAL] = g.glob.use_lds ? residency_of((const void*)k_global<true>, 512, g.glob.lds_bytes) : residency_of((const void*)k_global<false>, 512, 0);
+  out[OMC_RES_SMALL] = g.small.use_lds ? residency_of((const void*)k_small<true>, 256, g.small.lds_bytes) : residency_of((const void*)k_small<false>, 256, 0);
+  omc_colprox_sweep_residency(&out[OMC_RES_COLPROX_PAIR], &out[OMC_RES_COLPROX_WIDE]);
+  out[OMC_RES_COLPROX] = residency_of((const void*)k_colprox, 256, (size_t)4 * g.cp_lds_doubles * sizeof(double));
+  out[OMC_RES_CONE] = g.cone.use_lds ? residency_of((const void*)k_cone<true>, 512, g.cone.lds_bytes) : residency_of((const void*)k_cone<false>, 512, 0);
+  // k_cone_ws: the variant omc_launch_cone_ws takes
+  const int lpp = g.ws_lpp, rpl2 = g.ws_rpl2;
+  int ws = -1;      // multi-workgroup kernels, or an order beyond the kernel
+  if (g.mw || !lpp) ;
+  else if (g.ws.use_lds) ws = residency_of(lpp == 16 ? ws_lds_kernel<16>(rpl2) : lpp == 8 ? ws_lds_kernel<8>(rpl2) : ws_lds_kernel<4>(rpl2), 512, g.ws.lds_bytes);
+  else if (lpp == 64) ws = rpl2 == 8 ? residency_of((const void*)k_cone_ws<64, false, 8, 1024>, 1024, 0) : residency_of((const void*)k_cone_ws<64, false, 0, 1024>, 1024, 0);
+  else if (rpl2 == 7 && !w->cone_512) ws = residency_of((const void*)k_cone_ws<16, false, 7, 1024>, 1024, 0);
+  else if (rpl2 == 8 && !w->cone_512) ws = residency_of((const void*)k_cone_ws<16, false, 8, 1024>, 1024, 0);
+  else ws = residency_of((const void*)k_cone_ws<16, false, 0>, 512, 0);
+  out[OMC_RES_CONE_WS] = ws;
 }
 }
