@@ -166,7 +166,8 @@ int omc_relax_solve(omc_instance* h);
  *   omc_shor_warm_compat      pure host function (no handle, no device): 1 for identical (minor list, SOC list) pairs, 2 when the parent's
  *                             minor list is a strict prefix of the child's and both SOC lists are the complement shorthand (n_soc = -1),
  *                             0 otherwise.  Lists in the wire format of omc_relax_stage_shor.
- *   omc_last_shor_warm_stats  out[4] of the last staged Shor batch: nodes loaded with an identical list, loaded through a prefix, loads
+ *   omc_last_shor_warm_stats  out[4] of the last staged Shor batch, nodes appended to it included (omc_relax_append_shor applies the same
+ *                             filter and adds to the counts): nodes loaded with an identical list, loaded through a prefix, loads
  *                             refused, states saved (counted as the nodes are harvested).
  *   omc_state_pool_fetch_shor the point of a Shor-mode entry, unscaled: *nq minors, X (n*m), Theta (m*m), V (5 per minor, as
  *                             omc_relax_fetch_shor_V); NULL pointers are skipped; OMC_ERR_ARGUMENT for an empty or base-mode entry. */
@@ -190,7 +191,7 @@ int omc_relax_submit(omc_instance* h);
  * omc_relax_stage (load_from / save_to: warm-start pool entries as in omc_relax_set_warm, or NULL): before the solve starts, or while a
  * submitted solve is running -- the loop hands them to free slots at its next check -- and is refused once that solve has ended (the end is
  * decided under the same lock, so a node is either relaxed or refused, never lost).  Results: omc_relax_fetch returns every node, appended
- * ones behind the staged ones in the order they were appended.  Not available in Shor mode. */
+ * ones behind the staged ones in the order they were appended.  A Shor batch takes omc_relax_append_shor instead (below). */
 /* omc_relax_fetch_done: results of the nodes finished since the last call, in the order they finished -- callable while the submitted solve is
  * running (the other half of a queue-driven host loop: OMC.jl:700-719 pops, relaxes and pushes the children of one node at a time).
  * node_ids[i] indexes the staged + appended nodes; per node: U (n*k), lambda_min (2), breakpoint_x (n), Y (n*n) as in omc_relax_fetch (NULL: skipped). */
@@ -244,6 +245,35 @@ int omc_relax_batch_shor(omc_instance* h, int B, const omc_relax_params* params,
 /* penalties of the Shor-mode splitting, in the scaled variables (defaults 0.05, 0 = automatic per list: 75 n m / (4 n_shor) clamped to
  * [0.25, 40], 2; params->rho_scale multiplies rho) */
 int omc_set_shor_penalties(omc_instance* h, double rho, double r4, double r5);
+/* Appending nodes to a staged or RUNNING Shor batch (rank k = 1): the Shor form of omc_relax_reserve / omc_relax_append / omc_relax_fetch_done.
+ *   omc_relax_reserve_shor(h, nq_max, extra_lists)  with omc_relax_reserve(h, extra_nodes, max_cuts) applies to the NEXT omc_relax_stage_shor and is
+ *       consumed by it: the per-slot strides become nqmax = max(staged, nq_max) minors and max(staged, 2 nqmax) V1 / V2 keys, the group table
+ *       gets extra_lists more entries, the per-node outputs (X, W, Theta, V when kept) are sized for staged + extra_nodes nodes.  Device memory
+ *       on top of the staged batch: extra_lists x (4 (20 nq_max + n m + m + 3) + align16(n m + m) + 80) bytes of index room, 8 (2 n m + m^2
+ *       + 5 nqmax [V kept]) bytes per extra node, and per slot 368 bytes per minor of stride (V3 and the three 15-entry arrays of the
+ *       order-5 blocks) and 16 bytes per V1 / V2 key of stride, beyond what the staged lists need.
+ *       Negative arguments: OMC_ERR_ARGUMENT.  Without this call a Shor batch is staged exactly as before (omc_relax_reserve alone gives room
+ *       for nodes that carry a list the batch already knows).
+ *   omc_relax_append_shor  adds B nodes in the wire format of omc_relax_stage_shor (default U bounds; load_from / save_to as in
+ *       omc_relax_append, or NULL) before the solve or while a submitted solve runs; same lock and end-of-batch decision as omc_relax_append,
+ *       so a node is either relaxed or refused.  A node whose (minor list, SOC list) pair the batch already knows -- staged or appended --
+ *       shares that list's index structure and uses no list capacity (the reference's static mode needs extra_lists = 0); a new list takes one
+ *       of the extra_lists.  Warm-start indices pass the filter of omc_relax_stage_shor and are counted into omc_last_shor_warm_stats, which
+ *       accumulates over the batch.  Refused with OMC_ERR_ARGUMENT and a message naming the limit: nothing staged or the batch is not in Shor
+ *       mode (omc_relax_append in turn refuses Shor batches); the solve has ended; beyond the node capacity; more cuts than reserved; a new list
+ *       longer than nqmax; a new list when the list capacity is used up; warm-start indices without a pool that has its Shor extension; the
+ *       argument errors of omc_relax_stage_shor.  Rank k > 1: OMC_ERR_UNSUPPORTED (a batch the base engine serves takes omc_relax_append).
+ *       A refused call leaves the batch as it was.  Not recycled: the group of a list stays for the life of the batch.
+ *   omc_relax_fetch_done_shor  X (n*m), W (n*m), Theta (m*m) per id, for node ids that omc_relax_fetch_done has already returned, while the
+ *       solve runs (NULL pointers are skipped): the values omc_relax_fetch / omc_relax_fetch_shor give for the node after the solve.  An id out
+ *       of range or not yet returned: OMC_ERR_ARGUMENT.
+ * After the solve omc_relax_fetch, omc_relax_fetch_shor and omc_relax_fetch_shor_V (stride 5 nqmax) return every node, appended ones behind the
+ * staged ones. */
+int omc_relax_reserve_shor(omc_instance* h, int64_t nq_max, int extra_lists);
+int omc_relax_append_shor(omc_instance* h, int B, const int* L, const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir,
+                          const int64_t* n_shor, const int64_t* shor_idx, const int64_t* n_soc, const int64_t* soc_idx,
+                          const int* load_from, const int* save_to);
+int omc_relax_fetch_done_shor(omc_instance* h, int n_ids, const int* node_ids, double* X, double* W, double* Theta);
 
 /* ---- alternating_minimization (OMC.jl:1979-2279), disjunctive mode, B problems at once, rank k <= 4 --------
  * U_initial n*k per problem; cuts as above (only the per-cut bounds on v = U'x are imposed, OMC.jl:2047-2093);

@@ -5,6 +5,8 @@ backed by the HIP library.  Reference = /root/reference/src/OptimalMatrixComplet
     .matrix_completion_SDP_relaxation(nodes, ...) OMC.jl:1431-1943, a batch of nodes; with `shor_info` = one (constraints_indexes,
                                                   SOC_constraints_indexes) pair per node (BBNodeShorInfo, OMC.jl:37-40) the Shor-mode program
                                                   (add_Shor_valid_inequalities = true, rank 1)
+    .reserve / .append / .fetch_done / .hold      nodes pushed into a staged or running batch as their parents finish (the queue of OMC.jl:700-719);
+    .reserve_shor / .append_shor / .fetch_done_shor   the same for a Shor-mode batch (rank 1)
     .matrix_completion_master_feasible(Y, U)      OMC.jl:1261-1277
     .breakpoint_vectors(Y, U, breakpoints)        OMC.jl:2466-2477
     .evaluate_objective(X)                        OMC.jl:2330-2359
@@ -62,6 +64,24 @@ def _pack_cuts(nodes, n, k, cut_type):
                 cd[t, j] = DIR_CODES[d] if isinstance(d, str) else int(d)
             t += 1
     return L, cx, cU, cd
+
+
+def _pack_shor(shor_info):
+    """Wire format of omc_relax_stage_shor / omc_relax_append_shor: (n_shor, shor_idx, n_soc, soc_idx) of one (constraints_indexes,
+    SOC_constraints_indexes) pair per node; SOC_constraints_indexes = None is sent as n_soc = -1."""
+    B = len(shor_info)
+    nsh = np.zeros(B, np.int64); nso = np.zeros(B, np.int64); sh_parts = []; so_parts = []
+    for b, (minors, soc) in enumerate(shor_info):
+        mq = np.asarray(minors, np.int64).reshape(-1, 4)
+        nsh[b] = len(mq); sh_parts.append(mq)
+        if soc is None:
+            nso[b] = -1
+        else:
+            sq = np.asarray(soc, np.int64).reshape(-1, 2)
+            nso[b] = len(sq); so_parts.append(sq)
+    shi = np.ascontiguousarray(np.concatenate(sh_parts)) if sh_parts and sum(len(a) for a in sh_parts) else np.zeros((1, 4), np.int64)
+    soi = np.ascontiguousarray(np.concatenate(so_parts)) if so_parts and sum(len(a) for a in so_parts) else np.zeros((1, 2), np.int64)
+    return nsh, nso, shi, soi
 
 
 def shor_rank_k_extension(k, X, W, minors):
@@ -220,7 +240,8 @@ class Engine:
             raise ValueError("one Shor_info per node")
         self._set_warm(len(nodes), load_from, save_to)
         _lib.check(self._lib.omc_set_shor_keep_V(self._h, 1 if keep_V else 0))
-        self._nqmax = max([len(np.asarray(mi).reshape(-1, 4)) for (mi, _) in shor_info] + [1])
+        self._nqmax = max([len(np.asarray(mi).reshape(-1, 4)) for (mi, _) in shor_info] + [1, getattr(self, "_reserved_nq", 0)])      # reserve_shor: consumed below
+        self._reserved_nq = 0
         if penalties is not None:
             _lib.check(self._lib.omc_set_shor_penalties(self._h, float(penalties[0]), float(penalties[1]), float(penalties[2])))
         L, cx, cU, cd = _pack_cuts(nodes, n, k, disjunctive_cuts_type)
@@ -231,17 +252,7 @@ class Engine:
             lo = np.ascontiguousarray(np.stack([np.asfortranarray(u).ravel(order="F") for u in U_lower]))
         if U_upper is not None:
             hi = np.ascontiguousarray(np.stack([np.asfortranarray(u).ravel(order="F") for u in U_upper]))
-        nsh = np.zeros(B, np.int64); nso = np.zeros(B, np.int64); sh_parts = []; so_parts = []
-        for b, (minors, soc) in enumerate(shor_info):
-            mq = np.asarray(minors, np.int64).reshape(-1, 4)
-            nsh[b] = len(mq); sh_parts.append(mq)
-            if soc is None:
-                nso[b] = -1
-            else:
-                sq = np.asarray(soc, np.int64).reshape(-1, 2)
-                nso[b] = len(sq); so_parts.append(sq)
-        shi = np.ascontiguousarray(np.concatenate(sh_parts)) if sh_parts and sum(len(a) for a in sh_parts) else np.zeros((1, 4), np.int64)
-        soi = np.ascontiguousarray(np.concatenate(so_parts)) if so_parts and sum(len(a) for a in so_parts) else np.zeros((1, 2), np.int64)
+        nsh, nso, shi, soi = _pack_shor(shor_info)
         self._keep = (L, cx, cU, cd, lo, hi, p, nsh, nso, shi, soi)
         _lib.check(self._lib.omc_relax_stage_shor(self._h, B, C.byref(p), CUT_TYPES[disjunctive_cuts_type], _lib.ptr(L), _lib.ptr(cx),
                                                   _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(nsh), _lib.ptr(shi),
@@ -276,6 +287,47 @@ class Engine:
             raise ValueError("load_from / save_to must hold one pool index per node")
         _lib.check(self._lib.omc_relax_append(self._h, len(nodes), _lib.ptr(L), _lib.ptr(cx), _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(lf), _lib.ptr(sv)))
         self._B += len(nodes)
+
+    def reserve_shor(self, nq_max, extra_lists):
+        """With reserve(): room in the NEXT stage_shor batch for appended nodes whose lists hold at most nq_max minors, extra_lists of them
+        lists the batch does not know yet (omc_relax_reserve_shor).  A node that carries a list the batch knows needs no list room."""
+        _lib.check(self._lib.omc_relax_reserve_shor(self._h, int(nq_max), int(extra_lists)))
+        self._reserved_nq = int(nq_max)
+
+    def append_shor(self, nodes, shor_info, disjunctive_cuts_type="linear", load_from=None, save_to=None):
+        """Add Shor nodes to the staged Shor batch -- also while a submitted solve is running (omc_relax_append_shor).  shor_info as in
+        stage_shor; load_from / save_to as in append().  Raises OmcError when the library refuses (solve ended, a capacity of reserve() /
+        reserve_shor() used up, ...): the batch is then as it was."""
+        n, k = self.n, self.k
+        if len(shor_info) != len(nodes):
+            raise ValueError("one Shor_info per node")
+        L, cx, cU, cd = _pack_cuts(nodes, n, k, disjunctive_cuts_type)
+        lf = None if load_from is None else np.ascontiguousarray(np.asarray(load_from, dtype=np.int32))
+        sv = None if save_to is None else np.ascontiguousarray(np.asarray(save_to, dtype=np.int32))
+        if (lf is not None and lf.shape != (len(nodes),)) or (sv is not None and sv.shape != (len(nodes),)):
+            raise ValueError("load_from / save_to must hold one pool index per node")
+        nsh, nso, shi, soi = _pack_shor(shor_info)
+        _lib.check(self._lib.omc_relax_append_shor(self._h, len(nodes), _lib.ptr(L), _lib.ptr(cx), _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(nsh),
+                                                   _lib.ptr(shi), _lib.ptr(nso), _lib.ptr(soi), _lib.ptr(lf), _lib.ptr(sv)))
+        self._B += len(nodes)
+
+    def fetch_done_shor(self, ids, want_W=False, want_Theta=False):
+        """X (and W, Theta on request) of nodes that fetch_done() has already returned, while the solve runs (omc_relax_fetch_done_shor):
+        one dict per id, the matrices that fetch() / fetch_shor() give for the node after the solve."""
+        n, m = self.n, self.m
+        idv = np.ascontiguousarray(np.asarray(list(ids), dtype=np.int32))
+        c = len(idv)
+        X = np.zeros((max(c, 1), n * m)); W = np.zeros((max(c, 1), n * m)) if want_W else None; Th = np.zeros((max(c, 1), m * m)) if want_Theta else None
+        _lib.check(self._lib.omc_relax_fetch_done_shor(self._h, c, _lib.ptr(idv), _lib.ptr(X), _lib.ptr(W), _lib.ptr(Th)))
+        out = []
+        for i in range(c):
+            d = dict(node=int(idv[i]), X=X[i].reshape((n, m), order="F"))
+            if want_W:
+                d["W"] = W[i].reshape((n, m), order="F")
+            if want_Theta:
+                d["Theta"] = Th[i].reshape((m, m), order="F")
+            out.append(d)
+        return out
 
     def hold(self, on=True):
         """Keep the submitted solve open when it runs dry (omc_relax_hold): it waits for append() until hold(False)."""

@@ -13,6 +13,8 @@ import itertools
 
 import numpy as np
 
+from .shor_lists import ShorLists
+
 DIRECTIONS_OF = {  # OMC.jl:2481-2491
     "linear": ["left", "right"],
     "linear2": ["left", "middle", "right"],
@@ -231,17 +233,10 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
     if shor:
         if world_size != 1:
             raise NotImplementedError("Shor mode of the driver counterpart runs on one rank (the violated-minor update needs the node's X)")
-        if not 0.0 <= add_Shor_valid_inequalities_fraction <= 1.0:
-            raise ValueError("Argument `add_Shor_valid_inequalities_fraction` out of bounds [0.0, 1.0].")          # OMC.jl:256-263
-        if add_Shor_valid_inequalities_iterative:
-            if not 0.0 <= max_update_Shor_indices_probability <= 1.0:
-                raise ValueError("Argument `max_update_Shor_indices_probability` out of bounds [0.0, 1.0].")       # OMC.jl:297-303
-            if not 0.0 < min_update_Shor_indices_probability < 1.0:
-                raise ValueError("Argument `min_update_Shor_indices_probability` out of bounds (0.0, 1.0).")       # OMC.jl:304-310
-            if not 1.0 < update_Shor_indices_probability_decay_rate:
-                raise ValueError("Argument `update_Shor_indices_probability_decay_rate` out of bounds (1.0, inf).")   # OMC.jl:311-317
-            if not 1 <= update_Shor_indices_n_minors:
-                raise ValueError("Argument `update_Shor_indices_n_minors` out of bounds [1.0, inf).")              # OMC.jl:318-324
+        # the list bookkeeping (range checks of OMC.jl:256-263, 297-324 included) is shared with the queue-driven driver
+        lists = ShorLists(shor_classes, add_Shor_valid_inequalities_fraction, add_Shor_valid_inequalities_iterative,
+                          max_update_Shor_indices_probability, min_update_Shor_indices_probability,
+                          update_Shor_indices_probability_decay_rate, update_Shor_indices_n_minors)
     start = time.time()
     counters = dict(nodes_explored=0, nodes_total=1, nodes_dominated=0, nodes_relax_infeasible=0, nodes_relax_feasible=0,
                     nodes_relax_feasible_pruned=0, nodes_master_feasible=0, nodes_master_feasible_improvement=0,
@@ -283,14 +278,7 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
     if shor:
         # 1e-5 is the tolerance SURVEY 8c states for the Shor configurations; the splitting needs a few thousand iterations per node
         PS = shor_params or default_params(rho_scale=1.0, breakpoints=BREAKPOINTS[disjunctive_cuts_breakpoints], eps_gap=1e-5, max_iters=8000)
-        if add_Shor_valid_inequalities_iterative:
-            root_minors = np.zeros((0, 4), np.int64)                                       # OMC.jl:670-674
-        else:
-            root_minors = np.asarray(engine.generate_rank1_matrix_completion_Shor_constraints_indexes(shor_classes), np.int64).reshape(-1, 4)
-            if add_Shor_valid_inequalities_fraction < 1.0:                                 # randsubseq, OMC.jl:652-655
-                root_minors = root_minors[rng.random(len(root_minors)) < add_Shor_valid_inequalities_fraction]
-        shor_decay_depth = (math.log(max_update_Shor_indices_probability / min_update_Shor_indices_probability, update_Shor_indices_probability_decay_rate)
-                            if add_Shor_valid_inequalities_iterative else 0.0)
+        root_minors = lists.root(engine, rng)
     # ---- warm-start pool: ring of final states on the device, entry -> id of the node that owns it --------------------------------
     pool_cap = 0; pool_next = 0; pool_owner = {}
     if warm_start and not shor and hasattr(engine, "state_pool_create"):
@@ -304,7 +292,7 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
     shor_nq_max = 0
     if shor and shor_warm_start and k == 1 and world_size == 1 and hasattr(engine, "state_pool_reserve_shor"):
         nnz = int(np.count_nonzero(indices)); np16 = (n + 15) // 16 * 16
-        shor_nq_max = len(root_minors) + (int(shor_warm_depth) * int(update_Shor_indices_n_minors) if add_Shor_valid_inequalities_iterative else 0)
+        shor_nq_max = lists.pool_nq_max(root_minors, shor_warm_depth)
         state_bytes = 8 * (3 * n * n + n * k + nnz + m + 16 * np16 + 20) + engine.shor_state_bytes(n, m, shor_nq_max)
         pool_cap = int(max(0, min(1 << 17, warm_pool_bytes // state_bytes)))
         if pool_cap >= 2:
@@ -483,18 +471,8 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
                 r = dict(breakpoint_vec=row[6:6 + n].copy(), U=row[6 + n:].reshape((n, k), order="F").copy())
                 kids = make_children(nd["cuts"], r, disjunctive_cuts_type, k)
                 child_shor = nd.get("shor")
-                if shor and add_Shor_valid_inequalities_iterative:                          # OMC.jl:956-967, 2495-2518
-                    pu = (min_update_Shor_indices_probability if nd["depth"] > shor_decay_depth
-                          else max_update_Shor_indices_probability / (update_Shor_indices_probability_decay_rate ** nd["depth"]))
-                    if rng.random() < pu:
-                        # OMC.jl:2497 passes reshape(X, (1, n, m)) whatever k is: the score is the minor of X itself (also what the k > 1 extension
-                        # Xt_1 = X, Xt_t = 0 gives); the device routine takes (k, n, m)
-                        X3 = np.zeros((k, n, m)); X3[0] = local[nid]["X"]
-                        new = engine.generate_violated_Shor_minors(X3, shor_classes, [tuple(t) for t in child_shor.tolist()],
-                                                                   int(update_Shor_indices_n_minors))
-                        add = np.asarray([t for _, t in new], np.int64).reshape(-1, 4)
-                        child_shor = np.concatenate([child_shor, add]) if len(add) else child_shor     # union (2504-2507): `new` excludes the existing ones
-                        counters["shor_updates"] = counters.get("shor_updates", 0) + 1
+                if shor:                                                                    # OMC.jl:956-967, 2495-2518
+                    child_shor = lists.child(engine, child_shor, nd["depth"], lambda: local[nid]["X"], rng, k, counters)
                 for cuts in kids:
                     counters["nodes_total"] += 1
                     cid = counters["nodes_total"]

@@ -5,9 +5,17 @@
 creates the children exactly as the reference's loop does for one node (OMC.jl:765-1031), and pushes the best open nodes into the
 running solve (omc_relax_append) so that the slots never drain while the queue holds work.  Same selection rule (best-first on the
 parent's bound), same altmin coin (OMC.jl:856-870), same certified bounds as `bnb.branch_and_bound`; what differs is only WHEN a node
-is relaxed relative to its cousins (several hundred nodes are in flight, as with batch > 1 there).  Rank one process, disjunctive cuts
-only (the Shor lists and the multi-rank exchange stay with the round-based driver).  A second handle of the same instance serves
-altmin, rounding and the objective scans while the first one is busy with the solve.
+is relaxed relative to its cousins (several hundred nodes are in flight, as with batch > 1 there).  One process (the multi-rank
+exchange stays with the round-based driver).  A second handle of the same instance serves altmin, rounding, the objective scans and the
+violated-minor scans while the first one is busy with the solve.
+
+With add_Shor_valid_inequalities (rank 1; the keywords, defaults and range checks of `bnb.branch_and_bound`) every node carries
+node.Shor_info (OMC.jl:37-40): the open solve is staged with stage_shor behind reserve / reserve_shor, children go in through
+append_shor and inherit their parent's list; in iterative mode a split node that wins the coin of OMC.jl:956-967 fetches its X
+(fetch_done_shor) and its children carry the list extended by the most violated minors -- a list the running batch does not know
+yet, which takes one of the reserved lists.  The list bookkeeping is shor_lists.ShorLists, shared with the round-based driver.  When the
+node capacity, the cut depth, the list length or the list capacity of the running solve is used up the driver lets it drain and stages
+the next one.
 """
 from __future__ import annotations
 
@@ -17,7 +25,8 @@ import time
 
 import numpy as np
 
-from .bnb import make_children, autotune_rho_scale, compute_gap, left_singular
+from .bnb import make_children, autotune_rho_scale, compute_gap, left_singular, rank_k_projection
+from .shor_lists import ShorLists
 
 
 def _incumbent_from_U(engine2, A, indices, U, gamma):
@@ -39,10 +48,24 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                                disjunctive_cuts_breakpoints="smallest_1_eigvec", rho_scale=None, altmin_flag=True,
                                max_altmin_probability=1.0, min_altmin_probability=0.005, altmin_probability_decay_rate=1.1,
                                slots=1024, in_flight_target=None, capacity=1 << 15, depth_reserve=8, seed=0, accel=1,
-                               warm_pool_bytes=6 << 30, verbose=False):
+                               warm_pool_bytes=6 << 30, verbose=False,
+                               add_Shor_valid_inequalities=False, Shor_valid_inequalities_noisy_rank1_num_entries_present=(1, 2, 3, 4),
+                               add_Shor_valid_inequalities_fraction=1.0, add_Shor_valid_inequalities_iterative=False,
+                               max_update_Shor_indices_probability=1.0, min_update_Shor_indices_probability=0.1,
+                               update_Shor_indices_probability_decay_rate=1.1, update_Shor_indices_n_minors=100, shor_params=None,
+                               shor_warm_start=False, shor_warm_depth=32, shor_list_capacity=1024):
+    """Queue-driven branch and bound (module docstring).  The Shor keywords are those of bnb.branch_and_bound; shor_list_capacity is the
+    number of lists new to a running solve that one epoch reserves room for (iterative mode; the static mode needs none)."""
     from .api import default_params, BREAKPOINTS, Engine
     from .data import compute_MSE
     n, m, k = engine.n, engine.m, engine.k
+    shor = bool(add_Shor_valid_inequalities)
+    if shor:
+        if k > 1:
+            raise NotImplementedError("Shor mode of the queue-driven driver is rank 1 (omc_relax_append_shor); rank k > 1 runs in bnb.branch_and_bound")
+        lists = ShorLists(Shor_valid_inequalities_noisy_rank1_num_entries_present, add_Shor_valid_inequalities_fraction,
+                          add_Shor_valid_inequalities_iterative, max_update_Shor_indices_probability, min_update_Shor_indices_probability,
+                          update_Shor_indices_probability_decay_rate, update_Shor_indices_n_minors)
     A = np.asarray(A, float); indices = np.asarray(indices, bool)
     rng = np.random.default_rng(seed)
     start = time.time()
@@ -64,20 +87,36 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
     ub = float(engine2.evaluate_objective(X0))
     solution.update(objective_initial=ub, X_initial=X0, objective=ub, X=X0, U=left_singular(engine2, X0, k))
     # ---- penalty scale and root relaxation (the winner of the autotune batch IS the root relaxation) --------------------------
+    if shor and rho_scale is None:
+        rho_scale = 1.0                      # the Shor splitting has its own (scaled) penalties: no autotune
     if rho_scale is None:
         rho_scale, _, root = autotune_rho_scale(engine, disjunctive_cuts_type, return_result=True, breakpoints=BREAKPOINTS[disjunctive_cuts_breakpoints])
     else:
         root = None
     P = default_params(rho_scale=float(rho_scale), breakpoints=BREAKPOINTS[disjunctive_cuts_breakpoints], accel=int(accel), slots=int(slots))
+    root_minors = None
+    if shor:
+        # as bnb.branch_and_bound: 1e-5 is the tolerance SURVEY 8c states for the Shor configurations
+        P = shor_params or default_params(rho_scale=1.0, breakpoints=BREAKPOINTS[disjunctive_cuts_breakpoints], eps_gap=1e-5, max_iters=8000)
+        P.slots = int(slots)
+        root_minors = lists.root(engine, rng)
+        root = engine.matrix_completion_SDP_relaxation([[]], disjunctive_cuts_type, params=P, want_X=True, add_Shor_valid_inequalities=True,
+                                                       shor_info=[(root_minors, None)])[0]
     if root is None:
         root = engine.matrix_completion_SDP_relaxation([[]], disjunctive_cuts_type, params=P, want_X=False)[0]
     # ---- warm-start pool: a ring much longer than the in-flight window, entry -> node that owns it -----------------------------
     nnz = int(np.count_nonzero(indices)); np16 = (n + 15) // 16 * 16
     state_bytes = 8 * (3 * n * n + n * k + nnz + m + 16 * np16 + 20)
     target = int(in_flight_target or 2 * slots)
-    pool_cap = int(max(0, min(1 << 16, warm_pool_bytes // state_bytes)))
+    shor_nq_max = 0
+    if shor:
+        shor_nq_max = lists.pool_nq_max(root_minors, shor_warm_depth)
+        state_bytes += engine.shor_state_bytes(n, m, shor_nq_max)
+    pool_cap = int(max(0, min(1 << 16, warm_pool_bytes // state_bytes))) if (not shor or shor_warm_start) else 0
     if pool_cap >= 8 * target:
         engine.state_pool_create(pool_cap)
+        if shor:
+            engine.state_pool_reserve_shor(shor_nq_max)
     else:
         pool_cap = 0
     pool_next = 0; pool_owner = {}
@@ -98,6 +137,10 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
             for nid in [i for i, nd in nodes.items() if nd["LB"] > ub]:       # prune dominated nodes (OMC.jl:1220-1244)
                 del nodes[nid]
 
+    def node_X(o):
+        """X of a finished Shor node: the root's result carries it, a node of the running solve is fetched (fetch_done_shor)."""
+        return o["X"] if "X" in o else engine.fetch_done_shor([o["node"]])[0]["X"]
+
     def process(nid, nd, o):
         """One node's share of OMC.jl:765-1031."""
         nonlocal lb
@@ -106,6 +149,8 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
             counters["nodes_relax_infeasible"] += 1
             return
         counters["nodes_relax_feasible"] += 1
+        if shor and len(nd["shor"]):
+            counters["shor_nodes_with_minors"] = counters.get("shor_nodes_with_minors", 0) + 1
         bound = o["dual_bound"]
         if nid == 1:
             lb = bound
@@ -114,7 +159,11 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
             return
         if o["status_code"] == 0 and o["lambda_min"][0] >= -1e-6:
             counters["nodes_master_feasible"] += 1
-            val, Xk = _incumbent_from_U(engine2, A, indices, o["U"], engine.gamma)
+            if shor:                         # as bnb.branch_and_bound: the master objective of the rank-k projection of the node's X
+                Xk, _ = rank_k_projection(node_X(o), k, engine2)
+                val = float(engine2.evaluate_objective(Xk))
+            else:
+                val, Xk = _incumbent_from_U(engine2, A, indices, o["U"], engine.gamma)
             consider(val, Xk, "master")
             return
         counters["nodes_relax_feasible_split"] += 1
@@ -123,10 +172,15 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
             if rng.random() < p:
                 counters["nodes_relax_feasible_split_altmin"] += 1
                 pending_altmin.append((o["Y"], nd["cuts"]))
+        child_shor = None
+        if shor:                             # OMC.jl:956-967, 2495-2518; the scan runs on the second handle
+            child_shor = lists.child(engine2, nd["shor"], nd["depth"], lambda: node_X(o), rng, k, counters)
         for cuts in make_children(nd["cuts"], o, disjunctive_cuts_type, k):
             counters["nodes_total"] += 1
             cid = counters["nodes_total"]
             nodes[cid] = dict(cuts=cuts, LB=bound, depth=nd["depth"] + 1, pstate=nd.get("state"))
+            if shor:
+                nodes[cid]["shor"] = child_shor
             heapq.heappush(heap, (bound, cid))
 
     def run_altmin(force=False):
@@ -142,7 +196,9 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
             consider(best["master_objective"], best["U"] @ best["V"], "altmin")
         t_altmin += time.time() - t0
 
-    def pop_best(limit, depth_cap):
+    def pop_best(limit, depth_cap, nq_cap=None, known=None, list_room=0):
+        """The best open nodes the running (or next) solve can take: at most `limit`, none deeper than the reserved cut depth; in Shor mode
+        none whose list is longer than nq_cap, and at most list_room lists the solve does not know yet (known: id of a list -> the list)."""
         out = []
         while heap and len(out) < limit:
             _, nid = heap[0]
@@ -152,6 +208,14 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                 heapq.heappop(heap); del nodes[nid]; counters["nodes_dominated"] += 1; continue
             if nodes[nid]["depth"] > depth_cap:
                 break
+            if shor and nq_cap is not None:
+                lst = nodes[nid]["shor"]
+                if len(lst) > nq_cap:
+                    break
+                if id(lst) not in known:
+                    if list_room <= 0:
+                        break
+                    list_room -= 1; known[id(lst)] = lst
             heapq.heappop(heap)
             out.append((nid, nodes.pop(nid)))
         return out
@@ -161,17 +225,22 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
         if not pool_cap:
             return None, None
         lf = []; sv = []
-        for nid, nd in batch:
+        fits = [not shor or len(nd["shor"]) <= shor_nq_max for _, nd in batch]      # a Shor list that has outgrown the pool: cold, not saved
+        for (nid, nd), fit in zip(batch, fits):
             ps = nd.get("pstate")
-            ok = ps is not None and pool_owner.get(ps[0]) == ps[1]
+            ok = fit and ps is not None and pool_owner.get(ps[0]) == ps[1]
             lf.append(ps[0] if ok else -1)
-            counters["warm_started"] += 1 if ok else 0
-        for nid, nd in batch:
+            if not shor:                     # Shor mode counts the loads the library accepted (shor_warm_stats, at the end of an epoch)
+                counters["warm_started"] += 1 if ok else 0
+        for (nid, nd), fit in zip(batch, fits):
+            if not fit:
+                sv.append(-1); counters["shor_warm_outgrown"] = counters.get("shor_warm_outgrown", 0) + 1
+                continue
             sv.append(pool_next); pool_owner[pool_next] = nid; nd["state"] = (pool_next, nid); pool_next = (pool_next + 1) % pool_cap
         return lf, sv
 
     # root: already relaxed; its state is not in the pool (children of the root start cold)
-    process(1, dict(cuts=[], LB=-math.inf, depth=0), dict(root, Y=root.get("Y")) if root.get("Y") is not None else root)
+    process(1, dict(cuts=[], LB=-math.inf, depth=0, shor=root_minors), dict(root, Y=root.get("Y")) if root.get("Y") is not None else root)
     run_altmin(force=True)
     now_gap = compute_gap(lb, ub)
     run_log = [(counters["nodes_explored"], counters["nodes_total"], len(nodes), lb, ub, now_gap, time.time() - start)]
@@ -189,13 +258,25 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
         counters["epochs"] += 1
         best = [nid for _, nid in heapq.nsmallest(slots, heap) if nid in nodes]          # the nodes this epoch starts with decide the cut depth it reserves
         depth_cap = (max(nodes[nid]["depth"] for nid in best) if best else 0) + depth_reserve
-        first = pop_best(slots, depth_cap)
+        nq_cap = None; known = {}; list_cap = 0
+        if shor:
+            # the staged lists are free; an epoch of the iterative mode reserves room for lists depth_reserve updates longer than the longest
+            # it starts with and for shor_list_capacity lists that the updates of its split nodes will create
+            nq_cap = max([len(nodes[nid]["shor"]) for nid in best] + [0]) + (depth_reserve * lists.n_minors if lists.iterative else 0)
+            list_cap = int(shor_list_capacity) if lists.iterative else 0
+        first = pop_best(slots, depth_cap, nq_cap, known, len(best) + 1)
         if not first:
             break
+        n_staged_lists = len(known)
         lf, sv = warm_indices(first)
         P.time_limit = max(1.0, time_limit - (time.time() - start))
         engine.reserve(capacity, depth_cap)
-        engine.stage([nd["cuts"] for _, nd in first], disjunctive_cuts_type, P, load_from=lf, save_to=sv)
+        if shor:
+            engine.reserve_shor(nq_cap, list_cap)
+            engine.stage_shor([nd["cuts"] for _, nd in first], [(nd["shor"], None) for _, nd in first], disjunctive_cuts_type, P,
+                              load_from=lf, save_to=sv)
+        else:
+            engine.stage([nd["cuts"] for _, nd in first], disjunctive_cuts_type, P, load_from=lf, save_to=sv)
         engine.hold(True)
         t_epoch = time.time()
         engine.submit()
@@ -220,12 +301,19 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                 break
             if not stop_push and len(in_flight) < target:
                 room = min(target - len(in_flight), capacity - (sent - len(first)))
-                push = pop_best(room, depth_cap) if room > 0 else []
+                snapshot = dict(known) if shor else None
+                push = pop_best(room, depth_cap, nq_cap, known, n_staged_lists + list_cap - len(known)) if room > 0 else []
                 if push:
                     lf, sv = warm_indices(push)
                     try:
-                        engine.append([nd["cuts"] for _, nd in push], disjunctive_cuts_type, load_from=lf, save_to=sv)
+                        if shor:
+                            engine.append_shor([nd["cuts"] for _, nd in push], [(nd["shor"], None) for _, nd in push], disjunctive_cuts_type,
+                                               load_from=lf, save_to=sv)
+                        else:
+                            engine.append([nd["cuts"] for _, nd in push], disjunctive_cuts_type, load_from=lf, save_to=sv)
                     except Exception:                              # the solve ended on its time limit between our checks: back into the queue
+                        if shor:
+                            known.clear(); known.update(snapshot)
                         for nid, nd in push:
                             nodes[nid] = nd; heapq.heappush(heap, (nd["LB"], nid))
                         stop_push = True
@@ -234,7 +322,7 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                         in_flight[sent + q] = item
                     sent += len(push)
                 elif room <= 0 or (heap and nodes):
-                    stop_push = True            # capacity used up, or the best open node lies below the reserved depth: drain and stage a new solve
+                    stop_push = True            # capacity used up, or the best open node lies below the reserved depth (Shor: carries a list too long, or a new list when none is left): drain and stage a new solve
             if stop_push and not in_flight:
                 break
             if not got:
@@ -247,6 +335,10 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                 process(nid, nd, o)
         for nid, nd in in_flight.values():              # (none unless the time limit struck) -- back into the queue
             nodes[nid] = nd; heapq.heappush(heap, (nd["LB"], nid))
+        if shor and pool_cap:
+            ws = engine.shor_warm_stats()    # accumulated over the staged and the appended nodes of this solve
+            counters["warm_started"] += ws["loaded_identical"] + ws["loaded_prefix"]
+            counters["shor_warm_refused"] = counters.get("shor_warm_refused", 0) + ws["refused"]
         relax_seconds += time.time() - t_epoch
         run_altmin(force=True)
         v = open_lb({})

@@ -173,6 +173,13 @@ struct omc_instance {
   DevBuf sgInts, sgBytes, sgGroups, sgNodeGroup, sAh, sX, sW, sTh, sV1, sV2, sV3, sD0, sP0, sMbufB, sVrowB, sTq, sPq, sNq, sD5x, sD5t, snu5, sP5x,
       scolpart, sminpart, sminpart2, sfroB, svvB, se1, se2, soX, soW, soTh, sbigscr, sXsB, ssubSB, ssubIB;
   long long big_sub_tot[8] = {0};
+  // appending Shor nodes (omc_relax_reserve_shor, omc_relax_append_shor): the reservation of the NEXT omc_relax_stage_shor, and for the life of the
+  // staged batch the lists it knows (staged or appended; hash -> groups, with a host copy of every list to tell equal hashes apart), the group
+  // table's capacity and how much of the two index arenas is in use.  Written at stage time and under append_mu.
+  struct ShorListKey { int64_t nq = 0, nsoc = 0; uint64_t hlist = 0; std::vector<int64_t> idx, soc; };
+  int64_t reserve_shor_nq = 0; int reserve_shor_lists = 0; bool reserve_shor_set = false;
+  std::unordered_map<uint64_t, std::vector<int>> sh_byhash; std::vector<ShorListKey> sh_lists;
+  int sh_group_cap = 0; size_t sh_int_used = 0, sh_int_cap = 0, sh_byte_used = 0, sh_byte_cap = 0;
   // warm-start pool (omc_state_pool_create / omc_relax_set_warm)
   int pool_cap = 0; DevBuf pY, pD1, pD3, pU, palpha, psval, pXs, ptheta, pscal, bwarmL, bwarmS; std::vector<int> warm_load, warm_save;
   // Shor extension of the pool (omc_state_pool_reserve_shor) and the host's signature of every entry: which mode saved it and for which lists.
@@ -550,7 +557,7 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   { int rcp = pack_nodes(h, P, cut_type, B, L, cut_x, cut_Uhat, cut_dir, U_lower, U_upper, pk); if (rcp) return rcp; }
   int Rmax = pk.Rmax, rmax = pk.rmax, Lmax = pk.Lmax;
   // omc_relax_reserve: room for nodes appended later (default U bounds, at most reserve_cuts cuts each)
-  const int extra_nodes = shor ? 0 : h->reserve_nodes, extra_cuts = shor ? 0 : h->reserve_cuts;
+  const int extra_nodes = h->reserve_nodes, extra_cuts = h->reserve_cuts;
   h->reserve_nodes = 0; h->reserve_cuts = 0;
   if (extra_nodes > 0) {
     Lmax = std::max(Lmax, extra_cuts);
@@ -715,7 +722,7 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   }
   // warm-start indices of this batch (consumed: they belong to this stage call only)
   w.load_from = nullptr; w.save_to = nullptr;
-  if (h->pool_cap > 0 && !shor && extra_nodes > 0) {      // appended nodes may name pool entries: both index arrays exist, -1 where nothing was given
+  if (h->pool_cap > 0 && (!shor || h->shor_warm) && extra_nodes > 0) {      // appended nodes may name pool entries: both index arrays exist, -1 where nothing was given
     if (h->warm_load.size() != (size_t)B) h->warm_load.assign(B, -1);
     if (h->warm_save.size() != (size_t)B) h->warm_save.assign(B, -1);
     h->warm_load.resize(sN, -1); h->warm_save.resize(sN, -1);
@@ -914,7 +921,7 @@ int omc_relax_solve(omc_instance* h) {
   auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->stream;
   const int S = w.B; int Btot = h->Btot_live.load();      // nodes staged so far: omc_relax_append may add more while this loop runs (re-read at every check)
-  struct CloseGuard { omc_instance* h; ~CloseGuard() { std::lock_guard<std::mutex> lk(h->append_mu); h->append_closed = true; h->ws.Btot = h->Btot_live.load(); h->Btot = h->ws.Btot; } } close_guard{h};
+  struct CloseGuard { omc_instance* h; ~CloseGuard() { std::lock_guard<std::mutex> lk(h->append_mu); h->append_closed = true; h->ws.Btot = h->Btot_live.load(); h->Btot = h->ws.Btot; if (h->shor_on) h->sh.Btot = h->ws.Btot; } } close_guard{h};
   // slot bookkeeping on the host: node of each slot (-1 = idle), next pending node
   std::vector<int> node_of(S), flags(3 * (size_t)S), done(S, 0);
   for (int b = 0; b < S; ++b) node_of[b] = (b < Btot) ? b : -1;      // with omc_relax_reserve there may be more slots than nodes staged so far: the others start idle
@@ -1085,6 +1092,7 @@ int omc_relax_solve(omc_instance* h) {
     for (int b = 0; b < S && next < Btot; ++b) if (node_of[b] < 0) { node_of[b] = next++; init2[b] = 1; parked[b] = 0; ++ninit2; }
     if (!ninit2) return 0;
     int rc = push_flags(init2, fin2); if (rc) return rc;
+    if (shor) omc_shor_launch_setup(&sw, s);       // as at the start and at a harvest: the Shor state of the slot, before the base setup clears the init flags
     TIMED(OMC_KERNEL_SETUP, ninit2, omc_launch_setup(&w, s));
     mw_budget[0] = mw_budget[1] = MAX_SWEEPS;
     recount();
@@ -1284,7 +1292,7 @@ int omc_relax_append(omc_instance* h, int B2, const int* L, const double* cut_x,
                      const int* load_from, const int* save_to) {
   if (!h || !h->staged) return fail(OMC_ERR_ARGUMENT, "omc_relax_append: nothing staged");
   if (B2 <= 0) return fail(OMC_ERR_ARGUMENT, "B must be positive");
-  if (h->shor_on) return fail(OMC_ERR_UNSUPPORTED, "omc_relax_append: not available in Shor mode");
+  if (h->shor_on) return fail(OMC_ERR_UNSUPPORTED, "omc_relax_append: the staged batch is in Shor mode (omc_relax_append_shor)");
   HIPCHK(hipSetDevice(h->device));
   std::lock_guard<std::mutex> lk(h->append_mu);
   if (h->append_closed) return fail(OMC_ERR_ARGUMENT, "omc_relax_append: the solve of this batch has ended (stage a new batch)");
@@ -1458,9 +1466,12 @@ int omc_set_shor_penalties(omc_instance* h, double rho, double r4, double r5) {
 namespace {
 struct ShorGroupHost {
   int nq = 0, nv1 = 0, nv2 = 0;
+  uint64_t hash = 0; double r4 = 0.0;      // FNV-1a of the list's tuples ; penalty of its order-5 blocks relative to rho
   std::vector<int> mi, kid, cptr, cent, v1ptr, v1ent, v2ptr, v2ent, slackrow;
   std::vector<uint8_t> eclass, ctype;
   size_t off_int = 0, off_byte = 0;       // offsets into the concatenated device buffers
+  size_t ints() const { return mi.size() + kid.size() + cptr.size() + cent.size() + v1ptr.size() + v1ent.size() + v2ptr.size() + v2ent.size() + slackrow.size(); }
+  size_t bytes() const { return (eclass.size() + ctype.size() + 15) & ~(size_t)15; }
 };
 // keys sorted, ids assigned in sorted order (as numpy.unique does in the oracle); members in increasing (minor, position) order
 static void build_keys(const std::vector<uint64_t>& keyA, const std::vector<uint64_t>& keyB, int nq, int& nkeys, int* kidA, int* kidB,
@@ -1478,7 +1489,163 @@ static void build_keys(const std::vector<uint64_t>& keyA, const std::vector<uint
   }
   ptr.push_back((int)all.size());
 }
+
+// wire format of a batch of Shor lists: lengths checked, offsets of every node's tuples / pairs in the concatenated arrays
+static int shor_list_offsets(int B, const int64_t* n_shor, const int64_t* shor_idx, const int64_t* n_soc, const int64_t* soc_idx,
+                             std::vector<size_t>& so, std::vector<size_t>& co) {
+  so.assign(B + 1, 0); co.assign(B + 1, 0);
+  for (int b = 0; b < B; ++b) {
+    if (n_shor[b] < 0 || n_soc[b] < -1) return fail(OMC_ERR_ARGUMENT, "negative list length");
+    if (n_shor[b] >= (1ll << 28)) return fail(OMC_ERR_UNSUPPORTED, "Shor mode: more than 2^28 minors in one node");
+    so[b + 1] = so[b] + (size_t)n_shor[b]; co[b + 1] = co[b] + (size_t)(n_soc[b] > 0 ? n_soc[b] : 0);
+  }
+  if (so[B] > 0 && !shor_idx) return fail(OMC_ERR_ARGUMENT, "shor_idx is NULL but n_shor > 0");
+  if (co[B] > 0 && !soc_idx) return fail(OMC_ERR_ARGUMENT, "soc_idx is NULL but n_soc > 0");
+  return 0;
+}
+
+// identity of a (minor list, SOC list) pair among the lists a batch knows: hash of both lists, then the lists themselves
+using ShorListKey = omc_instance::ShorListKey;
+static uint64_t shor_pair_hash(int64_t nq, const int64_t* idx, int64_t nsoc, const int64_t* soc) {
+  uint64_t hv = FNV_SEED;
+  hv = fnv1a(&nq, 8, hv); hv = fnv1a(&nsoc, 8, hv);
+  hv = fnv1a(idx, 32 * (size_t)nq, hv);
+  if (nsoc > 0) hv = fnv1a(soc, 16 * (size_t)nsoc, hv);
+  return hv;
+}
+static int find_shor_list(const std::unordered_map<uint64_t, std::vector<int>>& byhash, const std::vector<ShorListKey>& lists, uint64_t hv,
+                          int64_t nq, const int64_t* idx, int64_t nsoc, const int64_t* soc) {
+  auto it = byhash.find(hv);
+  if (it == byhash.end()) return -1;
+  for (int g : it->second) {
+    const ShorListKey& K = lists[g];
+    if (K.nq == nq && K.nsoc == nsoc && (nq == 0 || memcmp(K.idx.data(), idx, 32 * (size_t)nq) == 0) &&
+        (nsoc <= 0 || memcmp(K.soc.data(), soc, 16 * (size_t)nsoc) == 0)) return g;
+  }
+  return -1;
+}
+static void add_shor_list(std::unordered_map<uint64_t, std::vector<int>>& byhash, std::vector<ShorListKey>& lists, uint64_t hv,
+                          int64_t nq, const int64_t* idx, int64_t nsoc, const int64_t* soc) {
+  ShorListKey K;
+  K.nq = nq; K.nsoc = nsoc; K.hlist = fnv1a(idx, 32 * (size_t)nq, FNV_SEED);
+  if (nq > 0) K.idx.assign(idx, idx + 4 * (size_t)nq);
+  if (nsoc > 0) K.soc.assign(soc, soc + 2 * (size_t)nsoc);
+  byhash[hv].push_back((int)lists.size());
+  lists.push_back(std::move(K));
+}
+
+// One (minor list, SOC list) pair -> the index structure its nodes share (validation, keys, coordinate CSR, entry classes, column types, slack
+// rows, block penalty, list hash).  The one builder: omc_relax_stage_shor and omc_relax_append_shor both come through here.
+static int build_shor_group(const omc_instance* h, int64_t nq64, const int64_t* idx, int64_t nsoc, const int64_t* soc, ShorGroupHost& G) {
+  const int n = h->n, m = h->m;
+  const int nq = (int)nq64;
+  G.nq = nq;
+  G.hash = fnv1a(idx, 32 * (size_t)nq, FNV_SEED);
+  G.mi.resize((size_t)4 * nq); G.kid.resize((size_t)4 * nq);
+  std::vector<uint64_t> enc(nq), k1a(nq), k1b(nq), k2a(nq), k2b(nq);
+  std::vector<int> cnt((size_t)n * m + 1, 0);
+  for (int q = 0; q < nq; ++q) {
+    const int64_t* t = idx + 4 * (size_t)q;
+    const int64_t i1 = t[0] - 1, i2 = t[1] - 1, j1 = t[2] - 1, j2 = t[3] - 1;
+    if (!(0 <= i1 && i1 < i2 && i2 < n && 0 <= j1 && j1 < j2 && j2 < m))
+      return fail(OMC_ERR_ARGUMENT, "Shor minors must satisfy 1 <= i1 < i2 <= n, 1 <= j1 < j2 <= m (OMC.jl:2556-2603)");
+    G.mi[q] = (int)i1; G.mi[(size_t)nq + q] = (int)i2; G.mi[(size_t)2 * nq + q] = (int)j1; G.mi[(size_t)3 * nq + q] = (int)j2;
+    enc[q] = (((uint64_t)i1 * n + (uint64_t)i2) * m + (uint64_t)j1) * m + (uint64_t)j2;
+    k1a[q] = ((uint64_t)i1 * m + j1) * m + j2; k1b[q] = ((uint64_t)i2 * m + j1) * m + j2;      // V1[i,(j1,j2)]
+    k2a[q] = ((uint64_t)i1 * n + i2) * m + j1; k2b[q] = ((uint64_t)i1 * n + i2) * m + j2;      // V2[(i1,i2),j]
+    ++cnt[(size_t)j1 * n + i1]; ++cnt[(size_t)j2 * n + i1]; ++cnt[(size_t)j1 * n + i2]; ++cnt[(size_t)j2 * n + i2];
+  }
+  { std::vector<uint64_t> se = enc; std::sort(se.begin(), se.end()); if (std::adjacent_find(se.begin(), se.end()) != se.end()) return fail(OMC_ERR_ARGUMENT, "duplicate Shor minor in a node's list"); }
+  build_keys(k1a, k1b, nq, G.nv1, G.kid.data(), G.kid.data() + nq, G.v1ptr, G.v1ent);
+  build_keys(k2a, k2b, nq, G.nv2, G.kid.data() + (size_t)2 * nq, G.kid.data() + (size_t)3 * nq, G.v2ptr, G.v2ent);
+  // coordinate CSR: members in increasing (minor, position) order
+  G.cptr.assign((size_t)n * m + 1, 0);
+  for (size_t e = 0; e < (size_t)n * m; ++e) G.cptr[e + 1] = G.cptr[e] + cnt[e];
+  G.cent.resize((size_t)4 * nq);
+  { std::vector<int> fill(G.cptr.begin(), G.cptr.end() - 1);
+    for (int q = 0; q < nq; ++q) {
+      const int i1 = G.mi[q], i2 = G.mi[(size_t)nq + q], j1 = G.mi[(size_t)2 * nq + q], j2 = G.mi[(size_t)3 * nq + q];
+      const size_t ce[4] = {(size_t)j1 * n + i1, (size_t)j2 * n + i1, (size_t)j1 * n + i2, (size_t)j2 * n + i2};
+      for (int p = 0; p < 4; ++p) G.cent[fill[ce[p]]++] = 4 * q + p;
+    } }
+  // entry classes, column types, slack rows
+  G.eclass.assign((size_t)n * m, 0);
+  if (nsoc < 0) { for (size_t e = 0; e < (size_t)n * m; ++e) G.eclass[e] = 1; }
+  else for (int64_t c = 0; c < nsoc; ++c) {
+    const int64_t i = soc[2 * c] - 1, j = soc[2 * c + 1] - 1;
+    if (!(0 <= i && i < n && 0 <= j && j < m)) return fail(OMC_ERR_ARGUMENT, "SOC coordinate out of range");
+    G.eclass[(size_t)j * n + i] = 1;
+  }
+  for (size_t e = 0; e < (size_t)n * m; ++e) if (cnt[e] > 0) G.eclass[e] = 2;      // W >= X^2 is implied by the order-5 block there
+  G.ctype.assign(m, 2); G.slackrow.assign(m, -1);
+  for (int j = 0; j < m; ++j) {
+    int first_nonC = -1, first_unobs = -1;
+    for (int i = 0; i < n; ++i) {
+      if (G.eclass[(size_t)j * n + i] == 2) continue;
+      if (first_nonC < 0) first_nonC = i;
+      if (first_unobs < 0 && !h->mask[(size_t)j * n + i]) first_unobs = i;
+    }
+    if (first_unobs >= 0) { G.ctype[j] = 0; G.slackrow[j] = first_unobs; }
+    else if (first_nonC >= 0) { G.ctype[j] = 1; G.slackrow[j] = first_nonC; }
+  }
+  if (h->k > 1) {
+    // Reference quirk Q5 (oracle/omc_oracle_shor.py header): in the rank k > 1 form (OMC.jl:1526-1551, 1780-1827) the slack that H
+    // cancels in W = sum Wt + 2 sum H makes every per-layer order-5 block satisfiable, so the minors do not constrain (X, W); what remains of them
+    // is W >= X^2 on their coordinates (implied by the order-(k+1) block).  The program solved is therefore the one without order-5 blocks and
+    // with those coordinates on the SOC list; the lifted variables Xt, Wt, H, V of the result are an explicit extension (host side: api.py).
+    for (size_t e = 0; e < (size_t)n * m; ++e) if (G.eclass[e] == 2) G.eclass[e] = 1;
+    for (int j = 0; j < m; ++j) {
+      int first_unobs = -1;
+      for (int i = 0; i < n; ++i) if (!h->mask[(size_t)j * n + i]) { first_unobs = i; break; }
+      if (first_unobs >= 0) { G.ctype[j] = 0; G.slackrow[j] = first_unobs; } else { G.ctype[j] = 1; G.slackrow[j] = 0; }
+    }
+    G.nq = 0; G.nv1 = 0; G.nv2 = 0;
+    G.mi.clear(); G.kid.clear(); G.cent.clear(); G.v1ent.clear(); G.v2ent.clear();
+    G.cptr.assign((size_t)n * m + 1, 0); G.v1ptr.assign(1, 0); G.v2ptr.assign(1, 0);
+  }
+  // the weight of the order-5 blocks on an entry of X / W is r4 x (blocks that hold it): r4 follows the mean multiplicity 4 nq / (n m)
+  // (measured: 20 at 12 x 14 with 152 minors, 5 at 100 x 100 with 38 813, 1.2 at 200 x 200 with 632 732 certify fastest)
+  G.r4 = (h->shor_r4 > 0.0) ? h->shor_r4 : std::min(40.0, std::max(0.25, 75.0 * (double)n * (double)m / (4.0 * (double)std::max(G.nq, 1))));
+  return 0;
+}
+
+// image of a group in the two index arenas: hi / hb are host images whose element 0 lands at dev_int / dev_byte on the device; the group's
+// own offsets (off_int, off_byte) are relative to them
+static void pack_shor_group(const ShorGroupHost& G, int* hi, uint8_t* hb, const int* dev_int, const uint8_t* dev_byte, ShorGroupDev& d) {
+  size_t o = G.off_int;
+  auto put = [&](const std::vector<int>& v) { const int* dp = dev_int + o; if (!v.empty()) memcpy(hi + o, v.data(), v.size() * sizeof(int)); o += v.size(); return dp; };
+  d.nq = G.nq; d.nv1 = G.nv1; d.nv2 = G.nv2; d.pad = 0; d.hash = G.hash; d.r4 = G.r4;
+  d.mi = put(G.mi); d.kid = put(G.kid); d.cptr = put(G.cptr); d.cent = put(G.cent);
+  d.v1ptr = put(G.v1ptr); d.v1ent = put(G.v1ent); d.v2ptr = put(G.v2ptr); d.v2ent = put(G.v2ent); d.slackrow = put(G.slackrow);
+  memcpy(hb + G.off_byte, G.eclass.data(), G.eclass.size());
+  memcpy(hb + G.off_byte + G.eclass.size(), G.ctype.data(), G.ctype.size());
+  d.eclass = dev_byte + G.off_byte; d.ctype = d.eclass + G.eclass.size();
+}
+
+// The host's filter of one node's warm-start indices (omc_relax_stage_shor and omc_relax_append_shor; the caller holds sig_mu): a load index that
+// may not be used -- empty entry, saved by the base engine, larger than the reservation, not related by shor_warm_rule -- becomes -1 and is
+// counted as refused; a save index of a list the reservation has no room for becomes -1.
+static void shor_warm_filter(omc_instance* h, const omc_instance::PoolSig& sg, const int64_t* idx, int* load, int* save) {
+  if (load && *load >= 0) {
+    const omc_instance::PoolSig& pe = h->pool_sig[*load];
+    int how = 0;
+    if (pe.kind == 2 && pe.nq <= h->pool_nqmax && pe.nq <= sg.nq) {
+      const bool same_head = pe.hlist == (pe.nq == sg.nq ? sg.hlist : fnv1a(idx, 32 * (size_t)pe.nq, FNV_SEED));
+      how = shor_warm_rule(pe.nq, pe.nsoc, sg.nq, sg.nsoc, same_head, pe.nsoc == sg.nsoc && pe.hsoc == sg.hsoc);
+    }
+    if (how == 0) { *load = -1; ++h->shor_warm_stats[2]; } else ++h->shor_warm_stats[how - 1];
+  }
+  if (save && *save >= 0 && sg.nq > h->pool_nqmax) *save = -1;
+}
 }  // namespace
+
+int omc_relax_reserve_shor(omc_instance* h, int64_t nq_max, int extra_lists) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
+  if (nq_max < 0 || extra_lists < 0) return fail(OMC_ERR_ARGUMENT, "omc_relax_reserve_shor: negative argument");
+  if (nq_max >= (1ll << 28)) return fail(OMC_ERR_ARGUMENT, "omc_relax_reserve_shor: nq_max out of range");
+  h->reserve_shor_nq = nq_max; h->reserve_shor_lists = extra_lists; h->reserve_shor_set = true;
+  return 0;
+}
 
 int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params, int cut_type, const int* L, const double* cut_x,
                          const double* cut_Uhat, const int8_t* cut_dir, const double* U_lower, const double* U_upper,
@@ -1489,30 +1656,17 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   const int n = h->n, m = h->m;
   if ((long long)n * m >= (1ll << 30)) return fail(OMC_ERR_UNSUPPORTED, "Shor mode: n * m too large for the 32-bit index structures");
   // ---- group the nodes by identical lists ------------------------------------------------------------------------------------------
-  std::vector<size_t> so(B + 1, 0), co(B + 1, 0);
-  for (int b = 0; b < B; ++b) {
-    if (n_shor[b] < 0 || n_soc[b] < -1) return fail(OMC_ERR_ARGUMENT, "negative list length");
-    if (n_shor[b] >= (1ll << 28)) return fail(OMC_ERR_UNSUPPORTED, "Shor mode: more than 2^28 minors in one node");
-    so[b + 1] = so[b] + (size_t)n_shor[b]; co[b + 1] = co[b] + (size_t)(n_soc[b] > 0 ? n_soc[b] : 0);
-  }
-  if (so[B] > 0 && !shor_idx) return fail(OMC_ERR_ARGUMENT, "shor_idx is NULL but n_shor > 0");
-  if (co[B] > 0 && !soc_idx) return fail(OMC_ERR_ARGUMENT, "soc_idx is NULL but n_soc > 0");
-  auto fnv = fnv1a;
+  std::vector<size_t> so, co;
+  { int rc0 = shor_list_offsets(B, n_shor, shor_idx, n_soc, soc_idx, so, co); if (rc0) return rc0; }
   std::unordered_map<uint64_t, std::vector<int>> byhash;      // hash -> group ids
+  std::vector<ShorListKey> lists;                               // the list of each group (kept in the handle for the life of the batch)
   std::vector<int> rep;                                        // representative node of each group
   std::vector<int> node_group(B);
   for (int b = 0; b < B; ++b) {
-    uint64_t hv = 1469598103934665603ull;
-    hv = fnv(&n_shor[b], 8, hv); hv = fnv(&n_soc[b], 8, hv);
-    hv = fnv(shor_idx + 4 * so[b], 32 * (size_t)n_shor[b], hv);
-    if (n_soc[b] > 0) hv = fnv(soc_idx + 2 * co[b], 16 * (size_t)n_soc[b], hv);
-    int gid = -1;
-    for (int g : byhash[hv]) {
-      const int r = rep[g];
-      if (n_shor[r] == n_shor[b] && n_soc[r] == n_soc[b] && memcmp(shor_idx + 4 * so[r], shor_idx + 4 * so[b], 32 * (size_t)n_shor[b]) == 0 &&
-          (n_soc[b] <= 0 || memcmp(soc_idx + 2 * co[r], soc_idx + 2 * co[b], 16 * (size_t)n_soc[b]) == 0)) { gid = g; break; }
-    }
-    if (gid < 0) { gid = (int)rep.size(); rep.push_back(b); byhash[hv].push_back(gid); }
+    const int64_t* ib = shor_idx + 4 * so[b]; const int64_t* sb = soc_idx + 2 * co[b];
+    const uint64_t hv = shor_pair_hash(n_shor[b], ib, n_soc[b], sb);
+    int gid = find_shor_list(byhash, lists, hv, n_shor[b], ib, n_soc[b], sb);
+    if (gid < 0) { gid = (int)rep.size(); rep.push_back(b); add_shor_list(byhash, lists, hv, n_shor[b], ib, n_soc[b], sb); }
     node_group[b] = gid;
   }
   const int NG = (int)rep.size();
@@ -1522,77 +1676,14 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   for (int g = 0; g < NG; ++g) {
     ShorGroupHost& G = gh[g];
     const int b = rep[g];
-    const int nq = (int)n_shor[b];
-    G.nq = nq;
-    G.mi.resize((size_t)4 * nq); G.kid.resize((size_t)4 * nq);
-    std::vector<uint64_t> enc(nq), k1a(nq), k1b(nq), k2a(nq), k2b(nq);
-    std::vector<int> cnt((size_t)n * m + 1, 0);
-    for (int q = 0; q < nq; ++q) {
-      const int64_t* t = shor_idx + 4 * (so[b] + q);
-      const int64_t i1 = t[0] - 1, i2 = t[1] - 1, j1 = t[2] - 1, j2 = t[3] - 1;
-      if (!(0 <= i1 && i1 < i2 && i2 < n && 0 <= j1 && j1 < j2 && j2 < m))
-        return fail(OMC_ERR_ARGUMENT, "Shor minors must satisfy 1 <= i1 < i2 <= n, 1 <= j1 < j2 <= m (OMC.jl:2556-2603)");
-      G.mi[q] = (int)i1; G.mi[(size_t)nq + q] = (int)i2; G.mi[(size_t)2 * nq + q] = (int)j1; G.mi[(size_t)3 * nq + q] = (int)j2;
-      enc[q] = (((uint64_t)i1 * n + (uint64_t)i2) * m + (uint64_t)j1) * m + (uint64_t)j2;
-      k1a[q] = ((uint64_t)i1 * m + j1) * m + j2; k1b[q] = ((uint64_t)i2 * m + j1) * m + j2;      // V1[i,(j1,j2)]
-      k2a[q] = ((uint64_t)i1 * n + i2) * m + j1; k2b[q] = ((uint64_t)i1 * n + i2) * m + j2;      // V2[(i1,i2),j]
-      ++cnt[(size_t)j1 * n + i1]; ++cnt[(size_t)j2 * n + i1]; ++cnt[(size_t)j1 * n + i2]; ++cnt[(size_t)j2 * n + i2];
-    }
-    { std::vector<uint64_t> se = enc; std::sort(se.begin(), se.end()); if (std::adjacent_find(se.begin(), se.end()) != se.end()) return fail(OMC_ERR_ARGUMENT, "duplicate Shor minor in a node's list"); }
-    build_keys(k1a, k1b, nq, G.nv1, G.kid.data(), G.kid.data() + nq, G.v1ptr, G.v1ent);
-    build_keys(k2a, k2b, nq, G.nv2, G.kid.data() + (size_t)2 * nq, G.kid.data() + (size_t)3 * nq, G.v2ptr, G.v2ent);
-    // coordinate CSR: members in increasing (minor, position) order
-    G.cptr.assign((size_t)n * m + 1, 0);
-    for (size_t e = 0; e < (size_t)n * m; ++e) G.cptr[e + 1] = G.cptr[e] + cnt[e];
-    G.cent.resize((size_t)4 * nq);
-    { std::vector<int> fill(G.cptr.begin(), G.cptr.end() - 1);
-      for (int q = 0; q < nq; ++q) {
-        const int i1 = G.mi[q], i2 = G.mi[(size_t)nq + q], j1 = G.mi[(size_t)2 * nq + q], j2 = G.mi[(size_t)3 * nq + q];
-        const size_t ce[4] = {(size_t)j1 * n + i1, (size_t)j2 * n + i1, (size_t)j1 * n + i2, (size_t)j2 * n + i2};
-        for (int p = 0; p < 4; ++p) G.cent[fill[ce[p]]++] = 4 * q + p;
-      } }
-    // entry classes, column types, slack rows
-    G.eclass.assign((size_t)n * m, 0);
-    if (n_soc[b] < 0) { for (size_t e = 0; e < (size_t)n * m; ++e) G.eclass[e] = 1; }
-    else for (int64_t c = 0; c < n_soc[b]; ++c) {
-      const int64_t i = soc_idx[2 * (co[b] + c)] - 1, j = soc_idx[2 * (co[b] + c) + 1] - 1;
-      if (!(0 <= i && i < n && 0 <= j && j < m)) return fail(OMC_ERR_ARGUMENT, "SOC coordinate out of range");
-      G.eclass[(size_t)j * n + i] = 1;
-    }
-    for (size_t e = 0; e < (size_t)n * m; ++e) if (cnt[e] > 0) G.eclass[e] = 2;      // W >= X^2 is implied by the order-5 block there
-    G.ctype.assign(m, 2); G.slackrow.assign(m, -1);
-    for (int j = 0; j < m; ++j) {
-      int first_nonC = -1, first_unobs = -1;
-      for (int i = 0; i < n; ++i) {
-        if (G.eclass[(size_t)j * n + i] == 2) continue;
-        if (first_nonC < 0) first_nonC = i;
-        if (first_unobs < 0 && !h->mask[(size_t)j * n + i]) first_unobs = i;
-      }
-      if (first_unobs >= 0) { G.ctype[j] = 0; G.slackrow[j] = first_unobs; }
-      else if (first_nonC >= 0) { G.ctype[j] = 1; G.slackrow[j] = first_nonC; }
-    }
-    if (h->k > 1) {
-      // Reference quirk Q5 (oracle/omc_oracle_shor.py header): in the rank k > 1 form (OMC.jl:1526-1551, 1780-1827) the slack that H
-      // cancels in W = sum Wt + 2 sum H makes every per-layer order-5 block satisfiable, so the minors do not constrain (X, W); what remains of them
-      // is W >= X^2 on their coordinates (implied by the order-(k+1) block).  The program solved is therefore the one without order-5 blocks and
-      // with those coordinates on the SOC list; the lifted variables Xt, Wt, H, V of the result are an explicit extension (host side: api.py).
-      for (size_t e = 0; e < (size_t)n * m; ++e) if (G.eclass[e] == 2) G.eclass[e] = 1;
-      for (int j = 0; j < m; ++j) {
-        int first_unobs = -1;
-        for (int i = 0; i < n; ++i) if (!h->mask[(size_t)j * n + i]) { first_unobs = i; break; }
-        if (first_unobs >= 0) { G.ctype[j] = 0; G.slackrow[j] = first_unobs; } else { G.ctype[j] = 1; G.slackrow[j] = 0; }
-      }
-      G.nq = 0; G.nv1 = 0; G.nv2 = 0;
-      G.mi.clear(); G.kid.clear(); G.cent.clear(); G.v1ent.clear(); G.v2ent.clear();
-      G.cptr.assign((size_t)n * m + 1, 0); G.v1ptr.assign(1, 0); G.v2ptr.assign(1, 0);
-    }
+    { int rc0 = build_shor_group(h, n_shor[b], shor_idx + 4 * so[b], n_soc[b], soc_idx + 2 * co[b], G); if (rc0) return rc0; }
     nqmax = std::max(nqmax, G.nq); nv1max = std::max(nv1max, G.nv1); nv2max = std::max(nv2max, G.nv2);
-    G.off_int = tot_int;
-    tot_int += G.mi.size() + G.kid.size() + G.cptr.size() + G.cent.size() + G.v1ptr.size() + G.v1ent.size() + G.v2ptr.size() + G.v2ent.size() + G.slackrow.size();
-    G.off_byte = tot_byte;
-    tot_byte += G.eclass.size() + G.ctype.size();
-    tot_byte = (tot_byte + 15) & ~(size_t)15;
+    G.off_int = tot_int; tot_int += G.ints();
+    G.off_byte = tot_byte; tot_byte += G.bytes();
   }
+  // omc_relax_reserve_shor: consumed by this call
+  const bool res_set = h->reserve_shor_set; const int64_t res_nq = res_set ? h->reserve_shor_nq : 0; const int res_lists = res_set ? h->reserve_shor_lists : 0;
+  h->reserve_shor_set = false; h->reserve_shor_nq = 0; h->reserve_shor_lists = 0;
   // ---- rank k > 1 with an unobserved entry in every column: the program without order-5 blocks IS the base relaxation (theta_j >= x_j' Y^+ x_j
   // implies theta_j >= ||x_j||^2 because Y <= I, and the slack of Theta_jj = sum_i W_ij sits on an unobserved entry at no cost): the base engine
   // solves it (no order-(n+m) cone), omc_relax_fetch_shor completes W = X^2 + slack from its (X, Theta).
@@ -1609,33 +1700,20 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
     }
   }
   // ---- warm start: the indices of omc_relax_set_warm pass the host's filter, so that the kernels see a plain "warm or cold" per node ------
+  // With omc_relax_reserve and a pool both index arrays exist (omc_relax_stage fills what was not given with -1): appended nodes may name entries.
   for (int q = 0; q < 4; ++q) h->shor_warm_stats[q] = 0;
   h->shor_warm = false;
-  std::vector<uint64_t> list_hash(NG);
-  for (int g = 0; g < NG; ++g) list_hash[g] = fnv(shor_idx + 4 * so[rep[g]], 32 * (size_t)n_shor[rep[g]], FNV_SEED);
-  if (h->pool_cap > 0 && h->pool_shor && h->k == 1 && (h->warm_load.size() == (size_t)B || h->warm_save.size() == (size_t)B)) {
-    h->node_sig.assign(B, omc_instance::PoolSig{});
+  const int extra_nodes = h->reserve_nodes;      // consumed by omc_relax_stage below
+  if (h->pool_cap > 0 && h->pool_shor && h->k == 1 && (h->warm_load.size() == (size_t)B || h->warm_save.size() == (size_t)B || extra_nodes > 0)) {
+    std::lock_guard<std::mutex> lk(h->sig_mu);
+    h->node_sig.assign((size_t)B + (size_t)extra_nodes, omc_instance::PoolSig{});
     for (int b = 0; b < B; ++b) {
       omc_instance::PoolSig& sg = h->node_sig[b];
-      sg.kind = 2; sg.nq = n_shor[b]; sg.nsoc = n_soc[b]; sg.hlist = list_hash[node_group[b]];
-      sg.hsoc = n_soc[b] > 0 ? fnv(soc_idx + 2 * co[b], 16 * (size_t)n_soc[b], FNV_SEED) : 0;
+      sg.kind = 2; sg.nq = n_shor[b]; sg.nsoc = n_soc[b]; sg.hlist = gh[node_group[b]].hash;
+      sg.hsoc = n_soc[b] > 0 ? fnv1a(soc_idx + 2 * co[b], 16 * (size_t)n_soc[b], FNV_SEED) : 0;
+      shor_warm_filter(h, sg, shor_idx + 4 * so[b], h->warm_load.size() == (size_t)B ? &h->warm_load[b] : nullptr,
+                       h->warm_save.size() == (size_t)B ? &h->warm_save[b] : nullptr);
     }
-    std::lock_guard<std::mutex> lk(h->sig_mu);
-    if (h->warm_load.size() == (size_t)B)
-      for (int b = 0; b < B; ++b) {
-        int& e = h->warm_load[b];
-        if (e < 0) continue;
-        const omc_instance::PoolSig& pe = h->pool_sig[e];
-        const omc_instance::PoolSig& sg = h->node_sig[b];
-        int how = 0;      // empty, saved by the base engine, larger than the reservation, or not related by shor_warm_rule: cold start
-        if (pe.kind == 2 && pe.nq <= h->pool_nqmax && pe.nq <= sg.nq) {
-          const bool same_head = pe.hlist == (pe.nq == sg.nq ? sg.hlist : fnv(shor_idx + 4 * so[b], 32 * (size_t)pe.nq, FNV_SEED));
-          how = shor_warm_rule(pe.nq, pe.nsoc, sg.nq, sg.nsoc, same_head, pe.nsoc == sg.nsoc && pe.hsoc == sg.hsoc);
-        }
-        if (how == 0) { e = -1; ++h->shor_warm_stats[2]; } else ++h->shor_warm_stats[how - 1];
-      }
-    if (h->warm_save.size() == (size_t)B)
-      for (int b = 0; b < B; ++b) if (h->warm_save[b] >= 0 && n_shor[b] > h->pool_nqmax) h->warm_save[b] = -1;      // no room for this list
     h->shor_warm = true;
   } else {
     h->warm_load.clear(); h->warm_save.clear();      // no reservation (or rank k > 1): ignored
@@ -1649,33 +1727,30 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   OmcWS& w = h->ws;
   const int S = w.B, N = n + m;
   hipStream_t s = h->stream;
+  // ---- strides and capacities: the staged lists, or what omc_relax_reserve_shor asked for (a minor has two V1 and two V2 keys: nv <= 2 nq) ----
+  if (res_set) {
+    nqmax = (int)std::max<int64_t>(nqmax, res_nq);
+    nv1max = std::max(nv1max, 2 * nqmax); nv2max = std::max(nv2max, 2 * nqmax);
+  }
+  const size_t int_cap = tot_int + (size_t)res_lists * ((size_t)20 * (size_t)res_nq + (size_t)n * m + (size_t)m + 3);
+  const size_t byte_cap = tot_byte + (size_t)res_lists * ((((size_t)n * m + (size_t)m) + 15) & ~(size_t)15);
   // ---- upload the index structures ------------------------------------------------------------------------------------------------
   {
     std::vector<int> hi(tot_int ? tot_int : 1); std::vector<uint8_t> hb(tot_byte ? tot_byte : 16, 0);
-    if ((rc = h->sgInts.ensure(hi.size() * sizeof(int)))) return rc;
-    if ((rc = h->sgBytes.ensure(hb.size()))) return rc;
+    if ((rc = h->sgInts.ensure(std::max(int_cap, hi.size()) * sizeof(int)))) return rc;
+    if ((rc = h->sgBytes.ensure(std::max(byte_cap, hb.size())))) return rc;
+    if ((rc = h->sgGroups.ensure(sizeof(ShorGroupDev) * ((size_t)NG + (size_t)res_lists)))) return rc;
+    if ((rc = h->sgNodeGroup.ensure(sizeof(int) * (size_t)h->node_cap))) return rc;
     std::vector<ShorGroupDev> gd(NG);
-    for (int g = 0; g < NG; ++g) {
-      ShorGroupHost& G = gh[g];
-      size_t o = G.off_int;
-      const int* base = h->sgInts.as<int>();
-      auto put = [&](const std::vector<int>& v) { const int* dp = base + o; if (!v.empty()) memcpy(&hi[o], v.data(), v.size() * sizeof(int)); o += v.size(); return dp; };
-      gd[g].nq = G.nq; gd[g].nv1 = G.nv1; gd[g].nv2 = G.nv2; gd[g].pad = 0; gd[g].hash = list_hash[g];
-      // the weight of the order-5 blocks on an entry of X / W is r4 x (blocks that hold it): r4 follows the mean multiplicity 4 nq / (n m)
-      // (measured: 20 at 12 x 14 with 152 minors, 5 at 100 x 100 with 38 813, 1.2 at 200 x 200 with 632 732 certify fastest)
-      gd[g].r4 = (h->shor_r4 > 0.0) ? h->shor_r4 : std::min(40.0, std::max(0.25, 75.0 * (double)n * (double)m / (4.0 * (double)std::max(G.nq, 1))));
-      gd[g].mi = put(G.mi); gd[g].kid = put(G.kid); gd[g].cptr = put(G.cptr); gd[g].cent = put(G.cent);
-      gd[g].v1ptr = put(G.v1ptr); gd[g].v1ent = put(G.v1ent); gd[g].v2ptr = put(G.v2ptr); gd[g].v2ent = put(G.v2ent); gd[g].slackrow = put(G.slackrow);
-      memcpy(&hb[G.off_byte], G.eclass.data(), G.eclass.size());
-      memcpy(&hb[G.off_byte + G.eclass.size()], G.ctype.data(), G.ctype.size());
-      gd[g].eclass = h->sgBytes.as<uint8_t>() + G.off_byte; gd[g].ctype = gd[g].eclass + G.eclass.size();
-    }
+    for (int g = 0; g < NG; ++g) pack_shor_group(gh[g], hi.data(), hb.data(), h->sgInts.as<int>(), h->sgBytes.as<uint8_t>(), gd[g]);
     HIPCHK(hipMemcpyAsync(h->sgInts.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(h->sgBytes.p, hb.data(), hb.size(), hipMemcpyHostToDevice, s));
-    if ((rc = upload(h->sgGroups, gd.data(), sizeof(ShorGroupDev) * NG, s))) return rc;
-    if ((rc = upload(h->sgNodeGroup, node_group.data(), sizeof(int) * B, s))) return rc;
+    HIPCHK(hipMemcpyAsync(h->sgGroups.p, gd.data(), sizeof(ShorGroupDev) * NG, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->sgNodeGroup.p, node_group.data(), sizeof(int) * B, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));          // the host vectors die with this block
   }
+  h->sh_byhash = std::move(byhash); h->sh_lists = std::move(lists);
+  h->sh_group_cap = NG + res_lists; h->sh_int_used = tot_int; h->sh_int_cap = int_cap; h->sh_byte_used = tot_byte; h->sh_byte_cap = byte_cap;
   // ---- scaling: the program is homogeneous of degree 2 in A (oracle: shor_scale) -------------------------------------------------------
   const double sc = shor_scale(h);
   {
@@ -1687,7 +1762,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   // ---- state ---------------------------------------------------------------------------------------------------------------------------
   ShWS& sh = h->sh;
   memset(&sh, 0, sizeof(sh));
-  const size_t sB = (size_t)S, sN = (size_t)B, nm = (size_t)n * m;
+  const size_t sB = (size_t)S, sN = (size_t)h->node_cap, nm = (size_t)n * m;      // per-node outputs: room for the appended nodes too
   const int NPb = (N + 15) & ~15;
   const int nmb = std::max(1, (nqmax + 255) / 256);
   const size_t nq1 = (size_t)std::max(nqmax, 1), nv11 = (size_t)std::max(nv1max, 1), nv21 = (size_t)std::max(nv2max, 1);
@@ -1817,6 +1892,148 @@ int omc_relax_batch_shor(omc_instance* h, int B, const omc_relax_params* params,
   rc = omc_relax_fetch(h, objective, dual_bound, status, iters, Y, U, X, Theta, lambda_min, breakpoint_x, solve_time);
   if (rc) return rc;
   return omc_relax_fetch_shor(h, W);
+}
+
+// ---- appending Shor nodes to a staged / running Shor batch (rank 1) ---------------------------------------------------------------------
+// The Shor form of omc_relax_append: same lock, same end-of-batch decision, descriptors first and the counter last.  A node whose lists the
+// batch already knows (staged or appended) shares that group; a new list is built by build_shor_group and written into the room that
+// omc_relax_reserve_shor reserved in the index arenas and the group table, behind everything the running kernels can reach (they find a list
+// through node_group of a node below Btot_live).  Every refusal is decided before anything is written: a refused call leaves the batch as it was.
+int omc_relax_append_shor(omc_instance* h, int B2, const int* L, const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir,
+                          const int64_t* n_shor, const int64_t* shor_idx, const int64_t* n_soc, const int64_t* soc_idx,
+                          const int* load_from, const int* save_to) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
+  if (h->k > 1) return fail(OMC_ERR_UNSUPPORTED, "omc_relax_append_shor: rank k > 1 is not supported (a batch served by the base engine takes omc_relax_append)");
+  if (!h->staged) return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: nothing staged");
+  if (!h->shor_on) return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: the staged batch is not in Shor mode (omc_relax_append)");
+  if (B2 <= 0) return fail(OMC_ERR_ARGUMENT, "B must be positive");
+  if (!n_shor || !n_soc) return fail(OMC_ERR_ARGUMENT, "n_shor / n_soc is NULL");
+  HIPCHK(hipSetDevice(h->device));
+  std::lock_guard<std::mutex> lk(h->append_mu);
+  if (h->append_closed) return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: the solve of this batch has ended (stage a new batch)");
+  const OmcWS& w = h->ws;
+  const ShWS& sh = h->sh;
+  const int first = h->Btot_live.load();
+  if (first + B2 > h->node_cap) return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: beyond the node capacity given to omc_relax_reserve");
+  NodePack pk;
+  { int rcp = pack_nodes(h, h->params, h->staged_cut_type, B2, L, cut_x, cut_Uhat, cut_dir, nullptr, nullptr, pk); if (rcp) return rcp; }
+  if (pk.Rmax > w.Rmax || pk.rmax > w.rmax || pk.Lmax > w.Lmax) return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a node has more cuts than omc_relax_reserve allowed for");
+  if ((load_from || save_to) && !(w.load_from && w.save_to))
+    return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: warm-start indices need a state pool with its Shor extension (omc_state_pool_reserve_shor) before the batch was staged");
+  for (int b = 0; b < B2; ++b) {
+    if (load_from && load_from[b] >= h->pool_cap) return fail(OMC_ERR_ARGUMENT, "load_from index beyond the pool");
+    if (save_to && save_to[b] >= h->pool_cap) return fail(OMC_ERR_ARGUMENT, "save_to index beyond the pool");
+  }
+  // ---- lists: known ones share their group, new ones are built (and may still be refused) --------------------------------------------------
+  std::vector<size_t> so, co;
+  { int rc0 = shor_list_offsets(B2, n_shor, shor_idx, n_soc, soc_idx, so, co); if (rc0) return rc0; }
+  const int NG0 = (int)h->sh_lists.size();
+  std::unordered_map<uint64_t, std::vector<int>> nhash; std::vector<ShorListKey> nlists; std::vector<uint64_t> nhv;      // lists new with this call
+  std::vector<ShorGroupHost> gh;
+  std::vector<int> node_group(B2);
+  size_t add_int = 0, add_byte = 0;
+  for (int b = 0; b < B2; ++b) {
+    const int64_t* ib = shor_idx + 4 * so[b]; const int64_t* sb = soc_idx + 2 * co[b];
+    const uint64_t hv = shor_pair_hash(n_shor[b], ib, n_soc[b], sb);
+    int gid = find_shor_list(h->sh_byhash, h->sh_lists, hv, n_shor[b], ib, n_soc[b], sb);
+    if (gid < 0) {
+      const int g2 = find_shor_list(nhash, nlists, hv, n_shor[b], ib, n_soc[b], sb);
+      if (g2 >= 0) gid = NG0 + g2;
+    }
+    if (gid < 0) {
+      if (n_shor[b] > sh.nqmax)
+        return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a list has " + std::to_string(n_shor[b]) + " minors, the batch has room for " + std::to_string(sh.nqmax) + " per node (nq_max of omc_relax_reserve_shor)");
+      if (NG0 + (int)nlists.size() >= h->sh_group_cap)
+        return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a new list, and the list capacity of the batch (" + std::to_string(h->sh_group_cap) + " lists: staged + extra_lists of omc_relax_reserve_shor) is used up");
+      gh.emplace_back();
+      ShorGroupHost& G = gh.back();
+      { int rc0 = build_shor_group(h, n_shor[b], ib, n_soc[b], sb, G); if (rc0) return rc0; }
+      G.off_int = add_int; add_int += G.ints();
+      G.off_byte = add_byte; add_byte += G.bytes();
+      if (G.nv1 > sh.nv1max || G.nv2 > sh.nv2max || h->sh_int_used + add_int > h->sh_int_cap || h->sh_byte_used + add_byte > h->sh_byte_cap)
+        return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a new list does not fit the index room reserved by omc_relax_reserve_shor (list capacity used up)");
+      gid = NG0 + (int)nlists.size();
+      add_shor_list(nhash, nlists, hv, n_shor[b], ib, n_soc[b], sb);
+      nhv.push_back(hv);
+    }
+    node_group[b] = gid;
+  }
+  // ---- warm start: the filter of stage time; node_sig lets the harvest sign the entry an appended node saves to ---------------------------
+  std::vector<int> lfv, svv;
+  if (w.load_from && w.save_to) {
+    lfv.assign(B2, -1); svv.assign(B2, -1);
+    if (load_from) lfv.assign(load_from, load_from + B2);
+    if (save_to) svv.assign(save_to, save_to + B2);
+    std::lock_guard<std::mutex> lk2(h->sig_mu);
+    for (int b = 0; b < B2; ++b) {
+      omc_instance::PoolSig sg;
+      sg.kind = 2; sg.nq = n_shor[b]; sg.nsoc = n_soc[b];
+      sg.hlist = node_group[b] < NG0 ? h->sh_lists[node_group[b]].hlist : nlists[node_group[b] - NG0].hlist;
+      sg.hsoc = n_soc[b] > 0 ? fnv1a(soc_idx + 2 * co[b], 16 * (size_t)n_soc[b], FNV_SEED) : 0;
+      shor_warm_filter(h, sg, shor_idx + 4 * so[b], &lfv[b], &svv[b]);
+      h->node_sig[(size_t)first + b] = sg;      // sized for node_cap at stage time; read by the solve only below Btot_live
+    }
+  }
+  // ---- write: new groups, then the descriptors of the nodes, all on the append stream; the counter moves last -----------------------------
+  if (!h->append_stream) HIPCHK(hipStreamCreateWithFlags(&h->append_stream, hipStreamNonBlocking));
+  hipStream_t as = h->append_stream;
+  const size_t f = (size_t)first;
+  std::vector<int> hi(add_int ? add_int : 1); std::vector<uint8_t> hb(add_byte ? add_byte : 16, 0);
+  std::vector<ShorGroupDev> gd(gh.size());
+  if (!gh.empty()) {
+    const int* dint = h->sgInts.as<int>() + h->sh_int_used; const uint8_t* dbyte = h->sgBytes.as<uint8_t>() + h->sh_byte_used;
+    for (size_t g = 0; g < gh.size(); ++g) pack_shor_group(gh[g], hi.data(), hb.data(), dint, dbyte, gd[g]);
+    HIPCHK(hipMemcpyAsync(const_cast<int*>(dint), hi.data(), add_int * sizeof(int), hipMemcpyHostToDevice, as));
+    HIPCHK(hipMemcpyAsync(const_cast<uint8_t*>(dbyte), hb.data(), add_byte, hipMemcpyHostToDevice, as));
+    HIPCHK(hipMemcpyAsync(h->sgGroups.as<ShorGroupDev>() + NG0, gd.data(), sizeof(ShorGroupDev) * gd.size(), hipMemcpyHostToDevice, as));
+  }
+  HIPCHK(hipMemcpyAsync(h->sgNodeGroup.as<int>() + f, node_group.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
+  { int rc = put_descriptors(w, pk, B2, B2, f, L, cut_x, as); if (rc) return rc; }
+  std::vector<double> hrho(B2, w.rho);
+  HIPCHK(hipMemcpyAsync(const_cast<double*>(w.rho_node) + f, hrho.data(), 8 * (size_t)B2, hipMemcpyHostToDevice, as));
+  if (!lfv.empty()) {
+    HIPCHK(hipMemcpyAsync(const_cast<int*>(w.load_from) + f, lfv.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
+    HIPCHK(hipMemcpyAsync(const_cast<int*>(w.save_to) + f, svv.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
+    for (int b = 0; b < B2; ++b) h->save_host[f + b] = svv[b];
+  }
+  HIPCHK(hipStreamSynchronize(as));
+  for (size_t g = 0; g < nlists.size(); ++g) {
+    h->sh_byhash[nhv[g]].push_back((int)h->sh_lists.size());
+    h->sh_lists.push_back(std::move(nlists[g]));
+  }
+  h->sh_int_used += add_int; h->sh_byte_used += add_byte;
+  h->Btot_live.store(first + B2); h->Btot = first + B2;
+  if (!h->worker_running.load()) { h->ws.Btot = first + B2; h->sh.Btot = first + B2; }      // no solve in flight: the staged batch simply grew (a running solve sets both when it ends)
+  return 0;
+}
+
+// X, W, Theta of nodes that omc_relax_fetch_done has already returned, copied from the per-node outputs on the fetch stream while the solve
+// runs (the harvest wrote them before the id was queued).  The values omc_relax_fetch / omc_relax_fetch_shor give after the solve.
+int omc_relax_fetch_done_shor(omc_instance* h, int n_ids, const int* node_ids, double* X, double* W, double* Theta) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
+  if (!h->staged || !h->shor_on) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_done_shor: no Shor-mode batch staged");
+  if (n_ids < 0 || (n_ids > 0 && !node_ids)) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_done_shor: bad arguments");
+  if (n_ids == 0) return 0;
+  {
+    std::lock_guard<std::mutex> lk(h->done_mu);
+    std::vector<char> seen((size_t)std::max(h->node_cap, 1), 0);
+    for (size_t i = 0; i < h->done_read; ++i) if ((size_t)h->done_q[i] < seen.size()) seen[h->done_q[i]] = 1;
+    for (int i = 0; i < n_ids; ++i)
+      if (node_ids[i] < 0 || (size_t)node_ids[i] >= seen.size() || !seen[node_ids[i]])
+        return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_done_shor: node " + std::to_string(node_ids[i]) + " is out of range or has not been returned by omc_relax_fetch_done");
+  }
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->fetch_stream) HIPCHK(hipStreamCreateWithFlags(&h->fetch_stream, hipStreamNonBlocking));
+  hipStream_t fs = h->fetch_stream;
+  const size_t nm = (size_t)h->n * h->m, mm = (size_t)h->m * h->m;
+  for (int i = 0; i < n_ids; ++i) {
+    const size_t nb = (size_t)node_ids[i];
+    if (X) HIPCHK(hipMemcpyAsync(X + i * nm, h->sh.oX + nb * nm, 8 * nm, hipMemcpyDeviceToHost, fs));
+    if (W) HIPCHK(hipMemcpyAsync(W + i * nm, h->sh.oW + nb * nm, 8 * nm, hipMemcpyDeviceToHost, fs));
+    if (Theta) HIPCHK(hipMemcpyAsync(Theta + i * mm, h->sh.oTh + nb * mm, 8 * mm, hipMemcpyDeviceToHost, fs));
+  }
+  HIPCHK(hipStreamSynchronize(fs));
+  return 0;
 }
 
 int omc_evaluate_objective(omc_instance* h, int B, const double* X, double* objective) {
