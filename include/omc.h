@@ -275,10 +275,14 @@ int omc_relax_append_shor(omc_instance* h, int B, const int* L, const double* cu
                           const int* load_from, const int* save_to);
 int omc_relax_fetch_done_shor(omc_instance* h, int n_ids, const int* node_ids, double* X, double* W, double* Theta);
 
-/* ---- alternating_minimization (OMC.jl:1979-2279), disjunctive mode, B problems at once, rank k <= 4 --------
+/* ---- alternating_minimization (OMC.jl:1979-2279), disjunctive mode, B problems at once, rank k <= 8 --------
  * U_initial n*k per problem; cuts as above (only the per-cut bounds on v = U'x are imposed, OMC.jl:2047-2093);
  * k > 1 adds the pair cones ||U_j1 +- U_j2|| <= sqrt 2 of OMC.jl:2029-2045.
- * Outputs: U n*k, V k*m, converged, n_iters, objectives (max_iters doubles per problem, NaN padded).     */
+ * Outputs: U n*k, V k*m, converged, n_iters, objectives (max_iters doubles per problem, NaN padded).
+ * time_limit (seconds, OMC.jl:1999-2003, 2186-2189): <= 0 solves nothing (n_iters 0).  A positive limit is checked on the device's clock
+ * at the top of every iteration, per problem; the first iteration always runs.  A problem stopped by the clock returns converged 0, n_iters =
+ * iterations completed, U and V of the last completed iteration and every objective recorded.  Not enforced where the device does not
+ * report its clock rate, and for limits that are not finite.                                                */
 int omc_altmin_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q1, const int* L,
                      const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir, const double* U_initial,
                      double eps, int max_iters, double time_limit, double* U, double* V, int* converged,
@@ -287,6 +291,11 @@ int omc_altmin_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q
 /* evaluate_objective(U * V) of the LAST omc_altmin_batch call (OMC.jl:920 `X_local = U * V`, 925-927), computed on the device from the
  * factors inside the altmin kernel: the driver compares it with the incumbent without forming X; X is built for the winner only. */
 int omc_altmin_master_objectives(omc_instance* h, int B, double* objective);
+/* The launch plan of omc_altmin_batch for problems of size n x m, rank k with at most max_cuts cuts per problem, computed on the host (no
+ * device call, no handle).  nolds != 0: as under OMC_ALTMIN_NOLDS=1.  out[4] = kernel variant (1: rank 1, 2: ranks 2 - 4, 3: ranks 5 - 8),
+ * dynamic LDS bytes of the launch (0 with the slab), bytes of global slab per problem (0 with LDS), rows of model_U per problem (Rmax).
+ * OMC_ERR_UNSUPPORTED for k > 8, OMC_ERR_ARGUMENT for sizes that are not positive. */
+int omc_altmin_plan(int n, int m, int k, int max_cuts, int nolds, int64_t* out);
 
 /* ---- evaluate_objective (OMC.jl:2330-2359) for B matrices X (n*m each) --------------------------------- */
 int omc_evaluate_objective(omc_instance* h, int B, const double* X, double* objective);

@@ -20,7 +20,7 @@ EXPORTS = [
     "omc_relax_stage_shor", "omc_relax_fetch_shor", "omc_relax_batch_shor", "omc_set_shor_penalties", "omc_set_shor_keep_V", "omc_relax_fetch_shor_V", "omc_last_shor_subspace_stats", "omc_state_pool_create", "omc_relax_set_warm",
     "omc_state_pool_reserve_shor", "omc_shor_warm_compat", "omc_last_shor_warm_stats", "omc_state_pool_fetch_shor",
     "omc_relax_reserve_shor", "omc_relax_append_shor", "omc_relax_fetch_done_shor",
-    "omc_altmin_master_objectives", "omc_comm_unique_id", "omc_comm_init", "omc_allreduce_bounds", "omc_bcast_incumbent", "omc_allgather_records", "omc_comm_destroy",
+    "omc_altmin_master_objectives", "omc_altmin_plan", "omc_comm_unique_id", "omc_comm_init", "omc_allreduce_bounds", "omc_bcast_incumbent", "omc_allgather_records", "omc_comm_destroy",
 ]
 
 
@@ -113,6 +113,7 @@ def load():
     lib.omc_shor_last_stats.argtypes = [vp, vp, vp]
     lib.omc_shor_last_select_stats.argtypes = [vp, vp]
     lib.omc_altmin_master_objectives.argtypes = [vp, C.c_int, vp]
+    lib.omc_altmin_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.omc_comm_unique_id.argtypes = [vp]
     lib.omc_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
     lib.omc_allreduce_bounds.argtypes = [vp, vp, vp, vp]

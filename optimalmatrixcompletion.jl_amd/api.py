@@ -577,6 +577,13 @@ class Engine:
                      solve_time=float(tm[b]), n_iters=int(ni[b]), max_iters=max_iters, objectives=list(obj[b, :ni[b] - (0 if cv[b] or ni[b] == 0 or not np.isnan(obj[b, ni[b] - 1]) else 1)]),
                      master_objective=float(mo[b])) for b in range(B)]
 
+    def altmin_plan(self, max_cuts=0, nolds=False):
+        """Launch plan of alternating_minimization for this instance with at most max_cuts cuts per problem (omc_altmin_plan, host only):
+        kernel variant (1: rank 1, 2: ranks 2 - 4, 3: ranks 5 - 8), dynamic LDS bytes, bytes of global slab per problem, rows of model_U."""
+        out = np.zeros(4, np.int64)
+        _lib.check(self._lib.omc_altmin_plan(self.n, self.m, self.k, int(max_cuts), int(bool(nolds)), _lib.ptr(out)))
+        return dict(variant=int(out[0]), lds_bytes=int(out[1]), slab_bytes=int(out[2]), Rmax=int(out[3]))
+
     # ---- objective -------------------------------------------------------------------------------------
     # ---- Shor minors (OMC.jl:2545-2640) ------------------------------------------------------------------------
     def shor_count(self, num_entries_present_list):

@@ -225,8 +225,6 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
     if node_selection not in ("breadthfirst", "bestfirst", "depthfirst", "bestfirst_depthfirst"):
         raise ValueError("Invalid input for node selection.")                              # OMC.jl:233-238
     n, m, k = engine.n, engine.m, engine.k
-    if engine.k > 4 and altmin_flag:
-        raise NotImplementedError("GPU altmin supports rank k <= 4; pass altmin_flag=False beyond that")
     rng = np.random.default_rng(seed)                                                      # OMC.jl:333 (Random.seed!(0))
     shor = bool(add_Shor_valid_inequalities)
     shor_classes = [int(c) for c in Shor_valid_inequalities_noisy_rank1_num_entries_present]
@@ -252,7 +250,7 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
         # batch, the best objective wins
         sc = float(np.abs(U0).max())
         starts = [U0] + [U0 + sc * rng.standard_normal((n, k)) for _ in range(max(int(altmin_root_n_iters), 1) - 1)]
-        ams = engine.alternating_minimization(starts, [[] for _ in starts], disjunctive_cuts_type)
+        ams = engine.alternating_minimization(starts, [[] for _ in starts], disjunctive_cuts_type, time_limit=time_limit)      # OMC.jl:545
         best = min(ams, key=lambda a: a["master_objective"])          # evaluate_objective(U V) from the factors, on the device
         X0 = best["U"] @ best["V"]
     else:
@@ -446,7 +444,7 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
                 if chosen:
                     t0 = time.time()
                     Ur = engine.round_Y([local[nid]["Y"] for nid, _ in chosen])              # OMC.jl:873
-                    ams = engine.alternating_minimization(Ur, [nd["cuts"] for _, nd in chosen], disjunctive_cuts_type)
+                    ams = engine.alternating_minimization(Ur, [nd["cuts"] for _, nd in chosen], disjunctive_cuts_type, time_limit=time_limit)      # OMC.jl:880, 888
                     # master objective of U V from the factors, on the device (OMC.jl:919-927): X is formed for the best one only
                     conv = [a for a in ams if a["converged"]]
                     if conv:

@@ -80,7 +80,7 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
     U0 = left_singular(engine2, A0, k)
     solution = {}
     if altmin_flag:
-        am = engine2.alternating_minimization([U0], [[]], disjunctive_cuts_type)[0]
+        am = engine2.alternating_minimization([U0], [[]], disjunctive_cuts_type, time_limit=time_limit)[0]      # OMC.jl:545
         X0 = am["U"] @ am["V"]
     else:
         X0 = U0 @ (U0.T @ A0)
@@ -190,7 +190,7 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
         t0 = time.time()
         batch = pending_altmin[:64]; del pending_altmin[:64]
         Ur = engine2.round_Y([y for y, _ in batch])                                           # OMC.jl:873
-        ams = [a for a in engine2.alternating_minimization(Ur, [c for _, c in batch], disjunctive_cuts_type) if a["converged"]]
+        ams = [a for a in engine2.alternating_minimization(Ur, [c for _, c in batch], disjunctive_cuts_type, time_limit=time_limit) if a["converged"]]      # OMC.jl:880, 888
         if ams:
             best = min(ams, key=lambda a: a["master_objective"])
             consider(best["master_objective"], best["U"] @ best["V"], "altmin")

@@ -20,6 +20,7 @@ struct AltminWS {
   double* G;               // B*Rmax*Rmax scratch
   double* scratch; size_t scratch_stride;   // per-problem global slab that replaces the dynamic LDS when the problem does not fit it (NULL: LDS)
   size_t lds_bytes;        // dynamic LDS of the launch (0 with the slab); stride and bytes from altmin_plan (omc_layout.h)
+  long long tl_ticks;      // time_limit in ticks of the device's constant-rate clock (wall_clock64); 0: no limit
 };
 
 #ifdef __cplusplus

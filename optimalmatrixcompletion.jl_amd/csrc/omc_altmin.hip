@@ -22,6 +22,18 @@ __device__ __forceinline__ double am_row_entry(const AltminWS& w, int b, int r, 
   return cf * w.cutx[((size_t)b * w.Lmax + w.rcut[(size_t)b * w.Rmax + r]) * w.n + i];
 }
 
+// time_limit of alternating_minimization (OMC.jl:1999-2003, 2186-2189) inside the launch: thread 0 stamps the device's constant-rate clock right
+// before the loop and reads it again at the top of every iteration; its verdict goes through LDS, so the whole workgroup leaves together.
+// The first iteration runs for any positive limit (the stamp is taken right before its check; `done == 0` makes that unconditional, so U and V
+// always hold a completed iteration).
+__device__ __forceinline__ long long am_clock_start(const AltminWS& w, int tid) { return (w.tl_ticks && tid == 0) ? (long long)wall_clock64() : 0; }
+__device__ __forceinline__ bool am_out_of_time(const AltminWS& w, int tid, long long t_start, int done, int* s_late) {
+  if (!w.tl_ticks || done == 0) return false;      // no limit, or nothing completed yet: same for every thread
+  if (tid == 0) *s_late = ((long long)wall_clock64() - t_start >= w.tl_ticks) ? 1 : 0;
+  __syncthreads();
+  return *s_late != 0;                // rewritten only at the top of the next iteration, workgroup barriers later
+}
+
 #define AM_MAX_DOUBLINGS 64      // bracket search of the ball multiplier (theta <= 2^64 max|g|: beyond that model_U is infeasible)
 #define AM_FEAS_TOL 1e-6         // largest row violation / excess of ||u||^2 - 1 accepted from a U-step (the oracle uses the same)
 __device__ __forceinline__ double block_max(double v, double* red) {
@@ -43,7 +55,7 @@ __global__ void __launch_bounds__(256) k_altmin(AltminWS w) {
   __shared__ double s_Gp[NNQP_GP_DOUBLES];
   __shared__ double s_sv[NNQP_PMAX], s_tmp[NNQP_PMAX];
   __shared__ int s_pl[NNQP_PMAX];
-  __shared__ int s_stop, s_ov;
+  __shared__ int s_stop, s_ov, s_late;
   const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
   const int n = w.n, m = w.m, R = w.R[b];
   const Altmin1Layout L = altmin1_layout(n, m, w.Rmax);
@@ -58,7 +70,9 @@ __global__ void __launch_bounds__(256) k_altmin(AltminWS w) {
   __syncthreads();
   double objective_current = 1e10;   // OMC.jl:2012
   int counter = 0, converged = 0, failed = 0;
+  const long long t_start = am_clock_start(w, tid);
   while (counter < w.max_iters) {
+    if (am_out_of_time(w, tid, t_start, counter, &s_late)) break;      // OMC.jl:2186-2189: counter < max_iters && elapsed < time_limit
     ++counter;
     // ---- V-step ------------------------------------------------------------------------------------------
     double uu = 0.0;
@@ -179,7 +193,7 @@ __global__ void __launch_bounds__(256) k_altmin(AltminWS w) {
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Rank k > 1 (k <= 4).  model_U has k^2 quadratic constraints sum_i (w_c' u_i)^2 <= r_c: the k unit balls (OMC.jl:2164-2171) and,
+// Rank 2 <= k <= 4 (ranks 5 .. 8: k_altmin_w below, same algorithm).  model_U has k^2 quadratic constraints sum_i (w_c' u_i)^2 <= r_c: the k unit balls (OMC.jl:2164-2171) and,
 // per pair of columns, ||U_j1 +- U_j2||^2 <= 2 (OMC.jl:2029-2045).  Their multipliers theta_c >= 0 shift every row Hessian by
 // the same k x k matrix S(theta) = 2 sum_c theta_c w_c w_c'; for fixed theta the problem is the row-separable QP with linear
 // rows of the rank-1 case (active-set NNQP on the Gram matrix C H(theta)^-1 C').  Outer: projected Newton on the concave dual
@@ -228,7 +242,7 @@ __global__ void __launch_bounds__(256) k_altmin_k(AltminWS w) {
   __shared__ int s_pl[NNQP_PMAX];
   __shared__ double s_th[AK_QMAX], s_th2[AK_QMAX], s_q[AK_QMAX], s_qt[AK_QMAX], s_W[AK_QMAX * AK_KMAX], s_rad[AK_QMAX];
   __shared__ double s_J[AK_QMAX * AK_QMAX], s_P[AK_QMAX * AK_QMAX], s_L[AK_QMAX * AK_QMAX], s_step[AK_QMAX];
-  __shared__ int s_act[AK_QMAX], s_nact, s_flag, s_stop, s_ov;
+  __shared__ int s_act[AK_QMAX], s_nact, s_flag, s_stop, s_ov, s_late;
   const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
   const int n = w.n, m = w.m, k = w.k, kk = k * k, mq = k * k, R = w.R[b];
   const AltminKLayout L = altmink_layout(n, m, k, w.Rmax);
@@ -352,7 +366,9 @@ __global__ void __launch_bounds__(256) k_altmin_k(AltminWS w) {
 
   double objective_current = 1e10;   // OMC.jl:2012
   int counter = 0, converged = 0, failed = 0;
+  const long long t_start = am_clock_start(w, tid);
   while (counter < w.max_iters) {
+    if (am_out_of_time(w, tid, t_start, counter, &s_late)) break;      // OMC.jl:2186-2189: counter < max_iters && elapsed < time_limit
     ++counter;
     // ---- V-step (model_V, OMC.jl:2192-2209): (sum_{i in O_j} u_i u_i' + U'U / gamma) v_j = sum_{i in O_j} A_ij u_i ---------
     double utu[AK_KMAX][AK_KMAX];
@@ -559,12 +575,368 @@ __global__ void __launch_bounds__(256) k_altmin_k(AltminWS w) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Ranks 5 <= k <= 8 (k_altmin_w): the algorithm of k_altmin_k, organised without per-thread k x k or k^2 arrays.
+//   * every k x k solve (H_i + S(theta) per row i, the normal equations per column j) belongs to a group of 8 lanes: lane a holds row a of
+//     the matrix in 8 registers, Gauss-Jordan with in-group shuffles (the steps of ak_inv, same pivot test), 32 matrices per pass of the workgroup;
+//   * the k^2 constraint values come from the k x k Gram matrix U'U: ball j = G_jj - 1, pair (a, b, +-) = G_aa + G_bb +- 2 G_ab - 2;
+//   * multiplier vectors, Jacobian, model matrix and Cholesky factor of the dual Newton method live in the working block (altminw_layout,
+//     leading dimension k^2); the damped Cholesky and its two triangular solves run on wave 0 (wave_cholesky / wave_chol_solve);
+//   * scalar decisions (Newton residual, ascent test, damping) are taken by thread 0, published through LDS and read after a barrier.
+// ---------------------------------------------------------------------------------------------------------------------
+#define AW_KMAX ALTMIN_KMAX
+#define AW_QMAX (AW_KMAX * AW_KMAX)
+
+// in-place Gauss-Jordan inverse of a symmetric positive definite matrix spread over 8 lanes (lane a = row a; rows and columns >= k are the
+// identity); false, for the whole group, if a pivot is not positive
+__device__ __forceinline__ bool aw_inv8(double (&row)[AW_KMAX], int k, int a) {
+  bool ok = true;
+#pragma unroll
+  for (int p = 0; p < AW_KMAX; ++p) {
+    if (p >= k) continue;                            // k is the same in every thread
+    const double piv = __shfl(row[p], p, AW_KMAX);
+    if (!(piv > 0.0)) ok = false;
+    const double d = 1.0 / piv;
+    if (a == p) {
+      row[p] = 1.0;
+#pragma unroll
+      for (int c = 0; c < AW_KMAX; ++c) row[c] *= d;
+    }
+    double pr[AW_KMAX];
+#pragma unroll
+    for (int c = 0; c < AW_KMAX; ++c) pr[c] = __shfl(row[c], p, AW_KMAX);
+    if (a != p) {
+      const double f = row[p];
+      row[p] = 0.0;
+#pragma unroll
+      for (int c = 0; c < AW_KMAX; ++c) row[c] -= f * pr[c];
+    }
+  }
+  return ok;
+}
+
+// out[a * AW_KMAX + c] = scale * sum_t x[t * k + a] x[t * k + c] (both triangles): one wave per pair a <= c; ends with a workgroup barrier
+__device__ __forceinline__ void aw_gram(const double* x, int cnt, int k, double scale, double* out) {
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  const int np = k * (k + 1) / 2;
+  for (int p = wv; p < np; p += nw) {                // wave-uniform
+    int a = 0, rest = p;
+    while (rest >= k - a) { rest -= k - a; ++a; }
+    const int c = a + rest;
+    double acc = 0.0;
+    for (int t = lane; t < cnt; t += WAVE) acc += x[(size_t)t * k + a] * x[(size_t)t * k + c];
+    acc = wave_sum(acc) * scale;
+    if (lane == 0) { out[a * AW_KMAX + c] = acc; out[c * AW_KMAX + a] = acc; }
+  }
+  __syncthreads();
+}
+
+__global__ void __launch_bounds__(256) k_altmin_w(AltminWS w) {
+  extern __shared__ double sm_lds[];
+  double* sm = w.scratch ? w.scratch + (size_t)blockIdx.x * w.scratch_stride : sm_lds;
+  __shared__ double red[32];
+  __shared__ double s_Gp[NNQP_GP_DOUBLES];
+  __shared__ double s_sv[NNQP_PMAX], s_tmp[NNQP_PMAX];
+  __shared__ int s_pl[NNQP_PMAX];
+  __shared__ double s_S[AW_QMAX], s_Gu[AW_QMAX], s_Gv[AW_QMAX], s_sg[AW_QMAX];      // S(theta), Gram matrices (k x k in 8 x 8), sign of a pair constraint
+  __shared__ int s_j1[AW_QMAX], s_j2[AW_QMAX];                                      // columns of a constraint (s_j2 = -1: ball)
+  __shared__ double s_res, s_dv, s_pv, s_lm, s_scale;                               // Newton scalars, owned by thread 0
+  __shared__ int s_nact, s_flag, s_stop, s_ov, s_late;
+  const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+  const int n = w.n, m = w.m, k = w.k, kk = k * k, mq = k * k, R = w.R[b];
+  const int grp = tid >> 3, ga = tid & 7, NG = T >> 3;      // 8-lane group of the k x k solves, row held by this lane
+  const int gac = ga < k ? ga : 0;                          // clamped row: padding lanes load in range and discard
+  const AltminWLayout L = altminw_layout(n, m, k, w.Rmax);
+  double* u = sm;                 // n*k, row i at u + i*k  (accepted iterate)
+  double* ut = sm + L.ut;         // candidate of the last evaluation
+  double *u0 = sm + L.u0, *g = sm + L.g;
+  double *H = sm + L.H, *Hinv = sm + L.Hinv;      // n*k*k each
+  double* v = sm + L.v;           // k*m, column j at v + j*k
+  double *cvec = sm + L.cvec, *mu = sm + L.mu;
+  double *th = sm + L.th, *th2 = sm + L.th2, *q = sm + L.q, *qt = sm + L.qt, *step = sm + L.step, *tmpv = sm + L.tmp;
+  int* act = (int*)(sm + L.act);
+  double *J = sm + L.J, *P = sm + L.P, *Lc = sm + L.Lc;
+  double* G = w.G + (size_t)b * w.Rmax * w.Rmax;
+  double* objs = w.objectives + (size_t)b * w.max_iters;
+  for (int e = tid; e < n * k; e += T) { const int i = e % n, a = e / n; u[i * k + a] = w.U0[(size_t)b * n * k + e]; }   // input is column-major n x k
+  for (int r = tid; r < w.Rmax; r += T) mu[r] = 0.0;
+  for (int t = tid; t < w.max_iters; t += T) objs[t] = __longlong_as_double(0x7ff8000000000000LL);
+  if (tid == 0) {   // quadratic constraints: balls, then (+, -) per pair  (quadratic_constraint_vectors in the oracle)
+    int c = 0;
+    for (int j = 0; j < k; ++j) { s_j1[c] = j; s_j2[c] = -1; s_sg[c] = 0.0; ++c; }
+    for (int j1 = 0; j1 < k - 1; ++j1)
+      for (int j2 = j1 + 1; j2 < k; ++j2)
+        for (int sg = 0; sg < 2; ++sg) { s_j1[c] = j1; s_j2[c] = j2; s_sg[c] = sg ? -1.0 : 1.0; ++c; }
+  }
+  __syncthreads();
+  // ---- one evaluation of the inner problem for multipliers tha: candidate ut, constraint values qout, primal quadratic value
+  auto evaluate = [&](const double* tha, double* qout) -> double {
+    if (tid < AW_QMAX) {      // S(theta) = 2 sum_c theta_c w_c w_c'
+      const int a = tid >> 3, c2 = tid & 7;
+      double acc = 0.0;
+      for (int c = 0; c < mq; ++c) {
+        const int j1 = s_j1[c], j2 = s_j2[c];
+        const double wa = (a == j1) ? 1.0 : (a == j2) ? s_sg[c] : 0.0, wc = (c2 == j1) ? 1.0 : (c2 == j2) ? s_sg[c] : 0.0;
+        acc += 2.0 * tha[c] * wa * wc;
+      }
+      s_S[tid] = acc;
+    }
+    __syncthreads();
+    for (int i0 = 0; i0 < n; i0 += NG) {      // (H_i + S)^-1 and u0_i = (H_i + S)^-1 g_i, one row i per 8-lane group
+      const int i = i0 + grp; const bool valid = i < n; const int ic = valid ? i : n - 1;
+      double row[AW_KMAX];
+#pragma unroll
+      for (int c = 0; c < AW_KMAX; ++c) {
+        const double hv = H[ic * kk + gac * k + (c < k ? c : 0)] + s_S[gac * AW_KMAX + c];
+        row[c] = (ga < k && c < k) ? hv : ((ga == c) ? 1.0 : 0.0);
+      }
+      aw_inv8(row, k, ga);
+      const double gv = g[ic * k + gac];
+      double acc = 0.0;
+#pragma unroll
+      for (int c = 0; c < AW_KMAX; ++c) { const double gc = __shfl(gv, c, AW_KMAX); if (c < k) acc += row[c] * gc; }
+      if (valid && ga < k) {
+#pragma unroll
+        for (int c = 0; c < AW_KMAX; ++c) if (c < k) Hinv[i * kk + ga * k + c] = row[c];
+        u0[i * k + ga] = acc;
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < R * R; e += T) {
+      const int r1 = e / R, r2 = e - r1 * R;
+      if (r2 < r1) continue;
+      const int j1 = w.rbj[(size_t)b * w.Rmax + r1], j2 = w.rbj[(size_t)b * w.Rmax + r2];
+      double acc = 0.0;
+      for (int i = 0; i < n; ++i) { const double x1 = ak_row_x(w, b, r1, i); if (x1 != 0.0) acc += x1 * ak_row_x(w, b, r2, i) * Hinv[i * kk + j1 * k + j2]; }
+      G[(size_t)r1 * w.Rmax + r2] = acc; G[(size_t)r2 * w.Rmax + r1] = acc;
+    }
+    for (int r = tid; r < R; r += T) {
+      const int j = w.rbj[(size_t)b * w.Rmax + r];
+      double acc = 0.0;
+      for (int i = 0; i < n; ++i) acc += ak_row_x(w, b, r, i) * u0[i * k + j];
+      cvec[r] = acc - w.rrhs[(size_t)b * w.Rmax + r];
+    }
+    __syncthreads();
+    if (R > 0 && tid < 64) { const int ov = wave_nnqp(G, w.Rmax, cvec, mu, R, s_Gp, s_sv, s_tmp, s_pl, tid); if (tid == 0 && ov) s_ov = 1; }
+    __syncthreads();
+    for (int e = tid; e < n * k; e += T) {      // ut = u0 - sum_r mu_r x_r(i) Hinv_i[:, j_r]
+      const int i = e / k, a = e - i * k;
+      double ui = u0[e];
+      for (int r = 0; r < R; ++r) {
+        const double mv = mu[r];
+        if (mv == 0.0) continue;
+        const double x = ak_row_x(w, b, r, i);
+        if (x == 0.0) continue;
+        ui -= mv * x * Hinv[i * kk + a * k + w.rbj[(size_t)b * w.Rmax + r]];
+      }
+      ut[e] = ui;
+    }
+    __syncthreads();
+    double pv = 0.0;
+    for (int e = tid; e < n * k; e += T) {
+      const int i = e / k, a = e - i * k;
+      double hu = 0.0;
+      for (int c2 = 0; c2 < k; ++c2) hu += H[i * kk + a * k + c2] * ut[i * k + c2];
+      pv += ut[e] * (0.5 * hu - g[e]);
+    }
+    pv = block_sum(pv, red);
+    aw_gram(ut, n, k, 1.0, s_Gu);
+    if (tid < mq) {
+      const int j1 = s_j1[tid], j2 = s_j2[tid];
+      qout[tid] = (j2 < 0) ? s_Gu[j1 * AW_KMAX + j1] - 1.0
+                           : s_Gu[j1 * AW_KMAX + j1] + s_Gu[j2 * AW_KMAX + j2] + s_sg[tid] * 2.0 * s_Gu[j1 * AW_KMAX + j2] - 2.0;
+    }
+    __syncthreads();
+    return pv;
+  };
+  // thread 0 only
+  auto kkt_res = [&](const double* tha, const double* qa) { double r_ = 0.0; for (int c = 0; c < mq; ++c) r_ = fmax(r_, fabs(fmin(tha[c], -qa[c]))); return r_; };
+  auto dotq = [&](const double* tha, const double* qa) { double r_ = 0.0; for (int c = 0; c < mq; ++c) r_ += tha[c] * qa[c]; return r_; };
+
+  double objective_current = 1e10;   // OMC.jl:2012
+  int counter = 0, converged = 0, failed = 0;
+  const long long t_start = am_clock_start(w, tid);
+  while (counter < w.max_iters) {
+    if (am_out_of_time(w, tid, t_start, counter, &s_late)) break;      // OMC.jl:2186-2189: counter < max_iters && elapsed < time_limit
+    ++counter;
+    // ---- V-step (model_V, OMC.jl:2192-2209): (sum_{i in O_j} u_i u_i' + U'U / gamma) v_j = sum_{i in O_j} A_ij u_i ---------
+    aw_gram(u, n, k, 1.0 / w.gamma, s_Gu);
+    for (int j0 = 0; j0 < m; j0 += NG) {
+      const int j = j0 + grp; const bool valid = j < m; const int jc = valid ? j : m - 1;
+      double row[AW_KMAX], rhs = 0.0;
+#pragma unroll
+      for (int c = 0; c < AW_KMAX; ++c) row[c] = (ga < k && c < k) ? s_Gu[ga * AW_KMAX + c] : ((ga == c) ? 1.0 : 0.0);
+      for (int p = w.col_ptr[jc]; p < w.col_ptr[jc + 1]; ++p) {
+        const int i = w.col_idx[p]; const double av = w.col_val[p];
+        const double ua = u[i * k + gac];
+        rhs += av * ua;
+#pragma unroll
+        for (int c = 0; c < AW_KMAX; ++c) { const double uc = u[i * k + (c < k ? c : 0)]; if (ga < k && c < k) row[c] += ua * uc; }
+      }
+      const bool ok = aw_inv8(row, k, ga);
+      double acc = 0.0;
+#pragma unroll
+      for (int c = 0; c < AW_KMAX; ++c) { const double rc = __shfl(rhs, c, AW_KMAX); if (c < k) acc += row[c] * rc; }
+      if (valid && ga < k) v[j * k + ga] = ok ? acc : 0.0;
+    }
+    __syncthreads();
+    // ---- U-step quantities: H_i = sum_{j in O_i} v_j v_j' + V V' / gamma, g_i = sum_{j in O_i} A_ij v_j --------------------------
+    aw_gram(v, m, k, 1.0 / w.gamma, s_Gv);
+    for (int i0 = 0; i0 < n; i0 += NG) {
+      const int i = i0 + grp;
+      if (i >= n || ga >= k) continue;       // no cross-lane traffic in this loop
+      double hh[AW_KMAX], gg = 0.0;
+#pragma unroll
+      for (int c = 0; c < AW_KMAX; ++c) hh[c] = s_Gv[ga * AW_KMAX + c];
+      for (int p = w.row_ptr[i]; p < w.row_ptr[i + 1]; ++p) {
+        const int j = w.row_idx[p]; const double av = w.row_val[p];
+        const double va = v[j * k + ga];
+        gg += av * va;
+#pragma unroll
+        for (int c = 0; c < AW_KMAX; ++c) if (c < k) hh[c] += va * v[j * k + c];
+      }
+      g[i * k + ga] = gg;
+#pragma unroll
+      for (int c = 0; c < AW_KMAX; ++c) if (c < k) H[i * kk + ga * k + c] = hh[c];
+    }
+    if (tid < mq) th[tid] = 0.0;
+    if (tid == 0) s_ov = 0;
+    __syncthreads();
+    // ---- U-step: projected Newton on the dual ------------------------------------------------------------------------------
+    {
+      const double pv0 = evaluate(th, q);
+      for (int e = tid; e < n * k; e += T) u[e] = ut[e];
+      if (tid == 0) { s_pv = pv0; s_dv = pv0 + dotq(th, q); s_res = kkt_res(th, q); s_lm = 1e-10; }
+      __syncthreads();
+    }
+    for (int nit = 0; nit < 60; ++nit) {
+      if (!(s_res > 1e-12)) break;           // written by thread 0 before the last barrier; the next write is barriers away
+      if (tid == 0) { int na = 0; for (int c = 0; c < mq; ++c) if (th[c] > 0.0 || q[c] > 0.0) act[na++] = c; s_nact = na; }
+      __syncthreads();
+      const int na = s_nact;
+      for (int a = 0; a < na; ++a) {         // forward-difference Jacobian of q over the active set, column a
+        const int c = act[a];
+        const double dl = 1e-7 * fmax(1.0, th[c]);
+        if (tid < mq) th2[tid] = th[tid] + ((tid == c) ? dl : 0.0);
+        __syncthreads();
+        evaluate(th2, qt);
+        if (tid < na) J[tid * mq + a] = (qt[act[tid]] - q[act[tid]]) / dl;
+        __syncthreads();
+      }
+      for (int e = tid; e < na * na; e += T) { const int a = e / na, a2 = e - a * na; P[a * mq + a2] = -0.5 * (J[a * mq + a2] + J[a2 * mq + a]); }
+      __syncthreads();
+      if (tid == 0) { double tr = 0.0; for (int a = 0; a < na; ++a) tr += P[a * mq + a]; s_scale = fmax(tr, 1e-300) / na; }
+      __syncthreads();
+      int accepted = 0;
+      for (int tr_ = 0; tr_ < 40; ++tr_) {
+        if (tid < WAVE) {   // wave 0: (P + lm scale I) step = q_act by Cholesky; candidate multipliers
+          const double damp = s_lm * s_scale;
+          for (int e = tid; e < na * na; e += WAVE) { const int a = e / na, a2 = e - a * na; if (a2 <= a) Lc[TRI(a, a2)] = P[a * mq + a2] + ((a == a2) ? damp : 0.0); }
+          WAVE_SYNC();
+          const bool ok = wave_cholesky(Lc, na, tid);
+          if (ok) {
+            for (int i = tid; i < na; i += WAVE) tmpv[i] = q[act[i]];
+            WAVE_SYNC();
+            wave_chol_solve(Lc, na, tmpv, step, tid);
+            for (int c = tid; c < mq; c += WAVE) th2[c] = th[c];
+            WAVE_SYNC();
+            for (int i = tid; i < na; i += WAVE) th2[act[i]] = fmax(th[act[i]] + step[i], 0.0);
+          }
+          if (tid == 0) { s_flag = ok ? 1 : 0; if (!ok) s_lm *= 10.0; }
+        }
+        __syncthreads();
+        if (!s_flag) { __syncthreads(); continue; }
+        const double pvn = evaluate(th2, qt);
+        if (tid == 0) {
+          const double dv = s_dv, res = s_res;
+          const double dn = pvn + dotq(th2, qt), rn = kkt_res(th2, qt);
+          double lin = 0.0;
+          for (int c = 0; c < mq; ++c) lin += q[c] * (th2[c] - th[c]);
+          const bool ok2 = (dn >= dv + 1e-4 * lin - 1e-14 * fmax(1.0, fabs(dv))) && (dn > dv || rn < res);
+          if (ok2) { s_res = rn; s_dv = dn; s_pv = pvn; s_lm = fmax(s_lm * 0.1, 1e-12); }
+          else s_lm *= 10.0;
+          s_stop = ok2 ? 1 : 0;
+        }
+        __syncthreads();
+        accepted = s_stop;
+        if (accepted) {
+          if (tid < mq) { th[tid] = th2[tid]; q[tid] = qt[tid]; }
+          for (int e = tid; e < n * k; e += T) u[e] = ut[e];
+        }
+        __syncthreads();
+        if (accepted) break;
+      }
+      if (!accepted) break;
+    }
+    // ---- did model_U have a solution?  (OMC.jl:2231, 2263-2265: a failed solve ends the loop with converged = false) ---------
+    {
+      double viol = 0.0;
+      for (int r = tid; r < R; r += T) {
+        const int j = w.rbj[(size_t)b * w.Rmax + r];
+        double acc = 0.0;
+        for (int i = 0; i < n; ++i) acc += ak_row_x(w, b, r, i) * u[i * k + j];
+        viol = fmax(viol, acc - w.rrhs[(size_t)b * w.Rmax + r]);
+      }
+      for (int c = tid; c < mq; c += T) viol = fmax(viol, q[c]);
+      viol = block_max(viol, red);
+      // s_ov is sticky over the evaluations of this U-step: a rejected trial may have set it, so it is only trusted together with a violation
+      const bool bad = !(viol <= AM_FEAS_TOL) || (s_ov && viol > 1e-9);
+      __syncthreads();
+      if (bad) { failed = 1; break; }
+    }
+    // ---- objective of model_U (OMC.jl:2232) and the convergence rules (2234-2245, quirk Q3) ---------------------------------
+    const double objective_new = s_pv + 0.5 * w.sumA2;
+    if (tid == 0) {
+      objs[counter - 1] = objective_new;
+      int conv = 0;
+      const double diff = fabs((objective_new - objective_current) / objective_current);
+      if (diff < w.eps) conv = 1;
+      else if (counter > 5) {
+        conv = 1;
+        for (int i2 = 0; i2 < 5; ++i2) if (!(objs[counter - 1 - i2] > objs[counter - 6])) conv = 0;
+      }
+      s_stop = conv;
+    }
+    __syncthreads();
+    converged = s_stop;
+    __syncthreads();
+    if (converged) break;
+    objective_current = objective_new;
+  }
+  __syncthreads();
+  for (int e = tid; e < n * k; e += T) { const int i = e % n, a = e / n; w.U[(size_t)b * n * k + e] = u[i * k + a]; }
+  for (int e = tid; e < k * m; e += T) w.V[(size_t)b * k * m + e] = v[e];      // k x m column-major = v[j*k + a]
+  if (tid == 0) { w.converged[b] = failed ? 0 : converged; w.n_iters[b] = counter; }
+  {   // evaluate_objective(U V) from the factors: masked fit over the CSR rows + tr((U'U)(V V')) / (2 gamma)
+    double fit = 0.0;
+    for (int i = tid; i < n; i += T) {
+      for (int p = w.row_ptr[i]; p < w.row_ptr[i + 1]; ++p) {
+        const int j = w.row_idx[p];
+        double x = 0.0;
+        for (int a = 0; a < k; ++a) x += u[i * k + a] * v[j * k + a];
+        const double d = x - w.row_val[p]; fit += d * d;
+      }
+    }
+    fit = block_sum(fit, red);
+    aw_gram(u, n, k, 1.0, s_Gu);
+    aw_gram(v, m, k, 1.0, s_Gv);
+    if (tid == 0) {
+      double reg = 0.0;
+      for (int a = 0; a < k; ++a) for (int c2 = 0; c2 < k; ++c2) reg += s_Gu[a * AW_KMAX + c2] * s_Gv[a * AW_KMAX + c2];
+      w.mobj[b] = 0.5 * fit + reg / (2.0 * w.gamma);
+    }
+  }
+}
+
 extern "C" void omc_launch_altmin(const AltminWS* w, hipStream_t s) {      // rank-1 or rank-k kernel, launch bytes from the descriptor (altmin_plan)
-  if (w->k == 1) hipLaunchKernelGGL(k_altmin, dim3(w->B), dim3(256), w->lds_bytes, s, *w);
-  else hipLaunchKernelGGL(k_altmin_k, dim3(w->B), dim3(256), w->lds_bytes, s, *w);
+  const int var = altmin_variant(w->k);
+  if (var == 1) hipLaunchKernelGGL(k_altmin, dim3(w->B), dim3(256), w->lds_bytes, s, *w);
+  else if (var == 2) hipLaunchKernelGGL(k_altmin_k, dim3(w->B), dim3(256), w->lds_bytes, s, *w);
+  else hipLaunchKernelGGL(k_altmin_w, dim3(w->B), dim3(256), w->lds_bytes, s, *w);
 }
 extern "C" int omc_altmin_set_lds(void) {
   // k_altmin_k holds ~20 KB of static LDS (Newton scratch, NNQP): its dynamic budget is 128 KB
   if (hipFuncSetAttribute((const void*)k_altmin_k, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) (void)hipGetLastError();
+  if (hipFuncSetAttribute((const void*)k_altmin_w, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) (void)hipGetLastError();      // ~21 KB static
   return (int)hipFuncSetAttribute((const void*)k_altmin, hipFuncAttributeMaxDynamicSharedMemorySize, OMC_MAX_DYN_LDS - 8 * 1024);   // ~18 KB static (NNQP scratch)
 }

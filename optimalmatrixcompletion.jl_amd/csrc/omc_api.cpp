@@ -159,6 +159,7 @@ struct omc_instance {
   std::atomic<int> hold{0};      // omc_relax_hold: a solve that has run dry waits for omc_relax_append instead of ending
   std::vector<int> done_q; size_t done_read = 0; std::mutex done_mu; hipStream_t fetch_stream = nullptr;      // nodes harvested so far, in harvest order (omc_relax_fetch_done)
   void* comm = nullptr; int comm_rank = 0, comm_world = 1; DevBuf bcomm, amobj; int amobj_B = 0;
+  int wall_khz = 0;      // rate of the device's constant clock (wall_clock64) for the time_limit of omc_altmin_batch; 0: unknown, the limit is not enforced inside a launch
   std::vector<double> rho_scale_per_node; DevBuf brho, brhon, blamD, bslotint, boY, boU, boal, bobx, boscal, boint;
   int Btot = 0;
   // Shor minors (a10 / a11): row bitsets and per-pair popcounts, built at the first call
@@ -243,6 +244,7 @@ int omc_instance_create(int n, int m, int k, const double* A, const uint8_t* mas
   if (h->tun.segv_trace) { signal(SIGSEGV, omc_segv_trace); signal(SIGABRT, omc_segv_trace); }
   struct Guard { omc_instance*& p; ~Guard() { if (p) omc_instance_destroy(p); } } guard{h};     // every early return below frees the handle
   h->n = n; h->m = m; h->k = k; h->gamma = gamma; h->device = device;
+  { int khz = 0; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) h->wall_khz = khz; else (void)hipGetLastError(); }
   h->A.assign(A, A + (size_t)n * m);
   h->mask.resize((size_t)n * m);
   for (size_t e = 0; e < (size_t)n * m; ++e) h->mask[e] = mask[e] ? 1 : 0;
@@ -2231,7 +2233,7 @@ int omc_altmin_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q
   if (B <= 0 || max_iters <= 0) return fail(OMC_ERR_ARGUMENT, "B and max_iters must be positive");
   if (cut_type != OMC_CUT_LINEAR && cut_type != OMC_CUT_LINEAR2 && cut_type != OMC_CUT_LINEAR3)
     return fail(OMC_ERR_INVALID_ENUM, "Invalid input for disjunctive cuts type (OMC.jl:1456-1462)");
-  if (!(time_limit > 0.0)) {      // OMC.jl:2186-2189: the loop condition fails at once -- nothing is solved (a launch runs <= max_iters iterations in milliseconds, so this is the only case in which the limit can bind)
+  if (!(time_limit > 0.0)) {      // OMC.jl:2186-2189: the loop condition fails at once -- nothing is solved (a positive limit is checked inside the launch, at the top of every iteration)
     const size_t nk = (size_t)h->n * h->k, mk = (size_t)h->m * h->k;
     for (int b = 0; b < B; ++b) { if (converged) converged[b] = 0; if (n_iters) n_iters[b] = 0; if (solve_time) solve_time[b] = 0.0; }
     memset(U, 0, sizeof(double) * nk * B); memset(V, 0, sizeof(double) * mk * B);
@@ -2242,7 +2244,7 @@ int omc_altmin_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q
   if (B <= 0 || max_iters <= 0) return fail(OMC_ERR_ARGUMENT, "B and max_iters must be positive");
   if (cut_type != OMC_CUT_LINEAR && cut_type != OMC_CUT_LINEAR2 && cut_type != OMC_CUT_LINEAR3)
     return fail(OMC_ERR_INVALID_ENUM, "Invalid input for disjunctive cuts type (OMC.jl:1456-1462)");
-  if (h->k > 4) return fail(OMC_ERR_UNSUPPORTED, "omc_altmin_batch: rank k > 4 is not supported");
+  if (h->k > ALTMIN_KMAX) return fail(OMC_ERR_UNSUPPORTED, "omc_altmin_batch: rank k > 8 is not supported");
   HIPCHK(hipSetDevice(h->device));
   const int n = h->n, m = h->m, k = h->k;
   auto t0 = std::chrono::steady_clock::now();
@@ -2302,6 +2304,10 @@ int omc_altmin_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q
   AltminWS w{};
   w.B = B; w.n = n; w.m = m; w.k = k; w.Rmax = Rmax; w.Lmax = Lmax; w.max_iters = max_iters;
   w.gamma = h->gamma; w.eps = eps; w.sumA2 = h->sumA2;
+  {   // time_limit in clock ticks (at least 1); 0 = no limit: clock rate unknown, or a value that is not finite or does not fit
+    const double ticks = time_limit * 1000.0 * (double)h->wall_khz;
+    w.tl_ticks = (h->wall_khz > 0 && std::isfinite(ticks) && ticks < 4.0e18) ? std::max<long long>(1, (long long)ticks) : 0;
+  }
   w.col_ptr = h->dcol_ptr.as<int>(); w.col_idx = h->dcol_idx.as<int>(); w.col_val = h->dcol_val.as<double>();
   w.row_ptr = h->drow_ptr.as<int>(); w.row_idx = h->drow_idx.as<int>(); w.row_val = h->drow_val.as<double>();
   w.R = h->aR.as<int>(); w.rkind = h->arkind.as<int>(); w.rcut = h->arcut.as<int>(); w.rbi = h->arbi.as<int>(); w.rbj = h->arbj.as<int>();
@@ -2322,6 +2328,16 @@ int omc_altmin_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q
   HIPCHK(hipGetLastError());
   const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   if (solve_time) for (int b = 0; b < B; ++b) solve_time[b] = el;
+  return 0;
+}
+
+int omc_altmin_plan(int n, int m, int k, int max_cuts, int nolds, int64_t* out) {
+  if (!out) return fail(OMC_ERR_ARGUMENT, "out is NULL");
+  if (n <= 0 || m <= 0 || k <= 0) return fail(OMC_ERR_ARGUMENT, "n, m and k must be positive");
+  if (k > ALTMIN_KMAX) return fail(OMC_ERR_UNSUPPORTED, "omc_altmin_plan: rank k > 8 is not supported");
+  const int Rmax = k * (k + 1) / 2 + 2 * k * std::max(1, max_cuts);      // as omc_altmin_batch sizes the rows of model_U
+  const KernelPlan ap = altmin_plan(n, m, k, Rmax, nolds != 0);
+  out[0] = altmin_variant(k); out[1] = (int64_t)ap.lds_bytes; out[2] = (int64_t)ap.slab_stride * 8; out[3] = Rmax;
   return 0;
 }
 

@@ -95,13 +95,25 @@ OMC_HD AltminKLayout altmink_layout(int n, int m, int k, int Rmax) {
   const size_t nk = (size_t)n * k, H = 4 * nk, v = H + 2 * nk * k, cvec = v + (size_t)k * m;
   return {nk, 2 * nk, 3 * nk, H, H + nk * k, v, cvec, cvec + Rmax, (cvec + 2 * Rmax + 8) * 8};
 }
+// k_altmin_w (ranks 5 .. 8): the state of k_altmin_k, then the multiplier vectors of the dual Newton method (th, th2, q, qt, step, tmp: mq = k^2
+// doubles each; act: mq ints), its Jacobian J and model matrix P (mq x mq, leading dimension mq) and the packed Cholesky factor Lc (mq (mq + 1) / 2)
+struct AltminWLayout { size_t ut, u0, g, H, Hinv, v, cvec, mu, th, th2, q, qt, step, tmp, act, J, P, Lc, bytes; };
+OMC_HD AltminWLayout altminw_layout(int n, int m, int k, int Rmax) {
+  const size_t nk = (size_t)n * k, mq = (size_t)k * k, H = 4 * nk, v = H + 2 * nk * k, cvec = v + (size_t)k * m, th = cvec + 2 * Rmax, J = th + 7 * mq, Lc = J + 2 * mq * mq;
+  return {nk, 2 * nk, 3 * nk, H, H + nk * k, v, cvec, cvec + Rmax, th, th + mq, th + 2 * mq, th + 3 * mq, th + 4 * mq, th + 5 * mq, th + 6 * mq, J, J + mq * mq, Lc,
+          (Lc + mq * (mq + 1) / 2 + 8) * 8};
+}
 // ---- launch decisions ---------------------------------------------------------------------------------------------------------------------
 struct KernelPlan { int use_lds; size_t lds_bytes, slab_stride; };      // launch bytes (0 with the slab) ; slab stride in doubles (0 with LDS)
 OMC_HD KernelPlan plan_block(size_t bytes, bool fits) { return {fits ? 1 : 0, fits ? bytes : 0, fits ? 0 : bytes / 8 + 8}; }
-// altmin: 8 KB of headroom under the kernel's dynamic budget (omc_altmin_set_lds; k_altmin_k holds ~25 KB of static LDS)
+// altmin: kernel variant by rank (1: k_altmin, 2: k_altmin_k, 3: k_altmin_w); 8 KB of headroom under the kernel's dynamic budget
+// (omc_altmin_set_lds; k_altmin_k holds ~25 KB of static LDS, k_altmin_w ~21 KB: NNQP scratch, k x k work matrices, constraint tables)
+#define ALTMIN_KMAX 8
+OMC_HD int altmin_variant(int k) { return k == 1 ? 1 : (k <= 4 ? 2 : 3); }
 OMC_HD KernelPlan altmin_plan(int n, int m, int k, int Rmax, int nolds) {
-  const size_t bytes = (k == 1) ? altmin1_layout(n, m, Rmax).bytes : altmink_layout(n, m, k, Rmax).bytes;
-  return plan_block(bytes, bytes + 8 * 1024 <= ((k == 1) ? (size_t)OMC_MAX_DYN_LDS - 8 * 1024 : (size_t)128 * 1024) && !nolds);
+  const int var = altmin_variant(k);
+  const size_t bytes = (var == 1) ? altmin1_layout(n, m, Rmax).bytes : (var == 2) ? altmink_layout(n, m, k, Rmax).bytes : altminw_layout(n, m, k, Rmax).bytes;
+  return plan_block(bytes, bytes + 8 * 1024 <= ((var == 1) ? (size_t)OMC_MAX_DYN_LDS - 8 * 1024 : (size_t)128 * 1024) && !nolds);
 }
 struct OmcGeom {
   KernelPlan cone, ws, glob, small;       // cone and ws share one slab (cone_scratch) and its stride
