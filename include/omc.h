@@ -433,8 +433,28 @@ int omc_debug_diag(omc_instance* h, double* out);
 int omc_debug_aa(omc_instance* h, int* accepted, int* rejected);
 /* last primal / dual ADMM residuals of every node of the staged batch (diagnostics) */
 int omc_debug_residuals(omc_instance* h, double* rp, double* rd);
+/* ms of OMC_KERNEL_SETUP is the time of k_setup and of k_setup_gram (the rows' Gram matrix, which k_setup formed itself before it became a
+ * kernel of its own beside the harvest): the work the class always timed.  launches and units count k_setup only. */
 int omc_last_kernel_stats(omc_instance* h, int64_t* launches /*NCLASS*/, double* ms /*NCLASS*/,
                           int64_t* units /*NCLASS*/);
+/* Host time of the last omc_relax_solve between its iterations (steady_clock on the solving thread), by piece: milliseconds and how often the
+ * piece ran.  A check: the wait for its kernels and the done flags, the bookkeeping up to the decision what to harvest, the new slot list, the
+ * drain of the timing events (after the next iteration has been enqueued).  A harvest: the first flags upload, enqueueing its kernels, the wait
+ * for them with the second upload, the pool / queue bookkeeping, enqueueing the setup.  The last two are whole events: from the end of a check's
+ * wait to the next iteration's enqueue (without / with a harvest).  No counterpart in the reference. */
+#define OMC_HOST_CHECK_WAIT 0
+#define OMC_HOST_CHECK_SCAN 1
+#define OMC_HOST_LIST 2
+#define OMC_HOST_EVENT_DRAIN 3
+#define OMC_HOST_HARVEST_FLAGS 4
+#define OMC_HOST_HARVEST_ENQUEUE 5
+#define OMC_HOST_HARVEST_WAIT 6
+#define OMC_HOST_HARVEST_BOOK 7
+#define OMC_HOST_SETUP_ENQUEUE 8
+#define OMC_HOST_CHECK_TOTAL 9
+#define OMC_HOST_HARVEST_TOTAL 10
+#define OMC_HOST_NPHASE 11
+int omc_last_host_phases(omc_instance* h, double* ms /*NPHASE*/, int64_t* count /*NPHASE*/);
 
 #ifdef __cplusplus
 }

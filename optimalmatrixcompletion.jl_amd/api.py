@@ -31,6 +31,9 @@ BREAKPOINTS = {"smallest_1_eigvec": 1, "smallest_2_eigvec": 2}
 STATUS_NAMES = {0: "OPTIMAL", 1: "SLOW_PROGRESS", 2: "TIME_LIMIT", 3: "INFEASIBLE"}
 KERNEL_CLASSES = ["colprox", "cone", "global", "check", "setup", "small", "accel", "cone_sub", "check_col", "check_build", "harvest",
                   "shor_bigcone", "shor_minors", "shor_cols"]
+# omc_last_host_phases, in the order of OMC_HOST_* (include/omc.h)
+HOST_PHASES = ["check_wait", "check_scan", "list", "event_drain", "harvest_flags", "harvest_enqueue", "harvest_wait", "harvest_book",
+               "setup_enqueue", "check_total", "harvest_total"]
 # order of omc_kernel_residency's output (OMC_RES_* in include/omc.h)
 RESIDENCY_KERNELS = ["k_cone_sub<0>", "k_cone_sub<1>", "k_cone_sub<2>", "k_global", "k_small", "k_colprox_pair", "k_colprox_wide", "k_colprox",
                      "k_cone_ws", "k_cone"]
@@ -420,9 +423,19 @@ class Engine:
         return self.fetch(want_Y, want_X, want_Theta)
 
     def kernel_stats(self):
+        """Launches, units and HIP-event milliseconds per kernel class of the last solve.  The ms of "setup" covers k_setup and k_setup_gram
+        (the Gram matrix k_setup used to form itself); its launches and units count k_setup only."""
         nc = len(KERNEL_CLASSES); la = np.zeros(nc, np.int64); ms = np.zeros(nc); un = np.zeros(nc, np.int64)
         _lib.check(self._lib.omc_last_kernel_stats(self._h, _lib.ptr(la), _lib.ptr(ms), _lib.ptr(un)))
         return {KERNEL_CLASSES[i]: dict(launches=int(la[i]), ms=float(ms[i]), units=int(un[i])) for i in range(nc)}
+
+    def host_phases(self):
+        """Host time of the last solve between its iterations, by piece (omc_last_host_phases): {piece: dict(ms, count)}."""
+        if not hasattr(self._lib, "omc_last_host_phases"):
+            raise OmcError(-100, "this build of the library has no omc_last_host_phases")
+        ms = np.zeros(len(HOST_PHASES)); cnt = np.zeros(len(HOST_PHASES), np.int64)
+        _lib.check(self._lib.omc_last_host_phases(self._h, _lib.ptr(ms), _lib.ptr(cnt)))
+        return {HOST_PHASES[i]: dict(ms=float(ms[i]), count=int(cnt[i])) for i in range(len(HOST_PHASES))}
 
     def subspace_stats(self):
         """k_cone_sub accounting of the last solve: calls, power steps, fall-backs to the full eigendecomposition, seedings."""

@@ -64,6 +64,25 @@ struct DevBuf {
   template <class T> T* as() { return (T*)p; }
 };
 
+// page-locked host memory: copies from and to it are asynchronous, so the host may go on while one is in flight
+struct PinBuf {
+  void* p = nullptr; size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { if (p) (void)hipHostFree(p); }
+  int ensure(size_t bytes) {
+    if (bytes <= cap) return 0;
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) { g_err = std::string("hipHostMalloc: ") + hipGetErrorString(e); return (int)e; }
+    cap = bytes;
+    return 0;
+  }
+  template <class T> T* as() { return (T*)p; }
+};
+
 // Tuning knobs.  The environment is read in ONE place -- tuning_from_env, called by omc_instance_create and by omc_tuning_reload_env -- and a
 // caller that does not want its environment to matter sets the knobs through omc_tuning_set; nothing else in the library calls getenv
 // (behaviour of the shipped library depended on the caller's environment at every solve, one knob even per iteration).
@@ -73,14 +92,17 @@ struct Tuning {
   bool colprox_no_xcd = false;     // OMC_COLPROX_NO_XCD: no XCD-local placement of the column workgroups
   bool cone_512 = false;           // OMC_CONE_512: 512-thread form of the full eigen-kernel at large orders
   bool dense_proj = false;         // OMC_DENSE_PROJ: dense W1 and the Yp store instead of the factored projections
+  bool host_phases = false;        // OMC_HOST_PHASES: every solve prints its host time between the iterations (omc_last_host_phases) to stderr when it ends
   bool global_nolds = false;       // OMC_GLOBAL_NOLDS: k_global's target in its L2-resident scratch instead of LDS
   bool no_colprox_pair = false;    // OMC_NO_COLPROX_PAIR: k_colprox for every column
   bool no_graph = false;           // OMC_NO_GRAPH: no hipGraph replay of the iteration body
   bool no_subspace = false;        // OMC_NO_SUBSPACE: no tracked subspace (k_cone_sub) for the cone block
   bool no_ws_split = false;        // OMC_NO_WS_SPLIT: the full eigen-kernel as one launch after k_cone_sub
   bool segv_trace = false;         // OMC_SEGV_TRACE: print the native frames of a crashing thread
+  bool setup_gram_inline = false;  // OMC_SETUP_GRAM_INLINE: k_setup forms the rows' Gram matrix itself (one workgroup per slot) instead of k_setup_gram
   bool shor_explicit = false;      // OMC_SHOR_EXPLICIT: rank k > 1 Shor batches by the Shor engine even where the base engine would serve them
   bool shor_no_subspace = false;   // OMC_SHOR_NO_SUBSPACE: no tracked subspace for the order-(n+m) cone of Shor mode
+  int check_xs = 16;               // OMC_CHECK_XS: cut vectors of the rows with a nonzero multiplier that k_check_build stages in LDS (the rest is read from global memory)
   int cone_multi_min = 1025;       // OMC_CONE_MULTI_MIN: cone orders from this value on (never below 145) take the multi-workgroup eigen-kernels; the default is where only the cold kernel existed
   int graph_max = 16;              // OMC_GRAPH_MAX: hipGraph replay for batches staged with at most this many nodes
   int shor_select_kb = 1048576;    // OMC_SHOR_SELECT_KB: violated-minor selection streams (no materialised keys) when 16 B per candidate exceed this many KiB; 0 = always materialise
@@ -93,11 +115,13 @@ struct Knob { const char* name; bool Tuning::*flag; int Tuning::*num; };
 static const Knob OMC_KNOBS[] = {
   {"OMC_ALTMIN_NOLDS", &Tuning::altmin_nolds, nullptr},      {"OMC_COLPROX_NO_XCD", &Tuning::colprox_no_xcd, nullptr},
   {"OMC_CONE_512", &Tuning::cone_512, nullptr},              {"OMC_DENSE_PROJ", &Tuning::dense_proj, nullptr},
-  {"OMC_GLOBAL_NOLDS", &Tuning::global_nolds, nullptr},      {"OMC_NO_COLPROX_PAIR", &Tuning::no_colprox_pair, nullptr},
+  {"OMC_GLOBAL_NOLDS", &Tuning::global_nolds, nullptr},      {"OMC_HOST_PHASES", &Tuning::host_phases, nullptr},
+  {"OMC_NO_COLPROX_PAIR", &Tuning::no_colprox_pair, nullptr},
   {"OMC_NO_GRAPH", &Tuning::no_graph, nullptr},              {"OMC_NO_SUBSPACE", &Tuning::no_subspace, nullptr},
   {"OMC_NO_WS_SPLIT", &Tuning::no_ws_split, nullptr},        {"OMC_SEGV_TRACE", &Tuning::segv_trace, nullptr},
+  {"OMC_SETUP_GRAM_INLINE", &Tuning::setup_gram_inline, nullptr},
   {"OMC_SHOR_EXPLICIT", &Tuning::shor_explicit, nullptr},    {"OMC_SHOR_NO_SUBSPACE", &Tuning::shor_no_subspace, nullptr},
-  {"OMC_CONE_MULTI_MIN", nullptr, &Tuning::cone_multi_min},
+  {"OMC_CHECK_XS", nullptr, &Tuning::check_xs},              {"OMC_CONE_MULTI_MIN", nullptr, &Tuning::cone_multi_min},
   {"OMC_GRAPH_MAX", nullptr, &Tuning::graph_max},            {"OMC_SHOR_SELECT_KB", nullptr, &Tuning::shor_select_kb},
   {"OMC_STREAMS", nullptr, &Tuning::streams},
   {"OMC_SUB_DEBUG", nullptr, &Tuning::sub_debug},            {"OMC_SUB_QMAX", nullptr, &Tuning::sub_qmax},
@@ -136,6 +160,13 @@ struct omc_instance {
   hipEvent_t gev[5] = {};
   hipEvent_t gevc[5] = {};      // the same fork / join events for bodies recorded under stream capture: an event is never used both inside a captured graph and eagerly
   hipEvent_t ev_main = nullptr;
+  // between the iterations (check, harvest, refill): page-locked images of the slot flags and of the slot list, two of each so that the host
+  // writes one while the copy of the other may still be in flight (ev_up: recorded behind each copy, waited for before the image is rewritten),
+  // of the done flags, and of the (slot, node) jobs of k_setup_gram with their device copy; ev_gram marks that kernel's end on its stream
+  PinBuf pin_flags[2], pin_list[2], pin_done, pin_jobs; DevBuf bgramjobs;
+  hipEvent_t ev_up[4] = {}; bool ev_up_rec[4] = {}; hipEvent_t ev_gram = nullptr; bool ev_gram_rec = false;
+  // host time of the last solve between the iterations, by piece (omc_last_host_phases): milliseconds and events
+  double host_ms[OMC_HOST_NPHASE] = {0}; int64_t host_cnt[OMC_HOST_NPHASE] = {0};
   DevBuf dA, dmask, dcol_ptr, dcol_idx, dcol_val, dNcnt, dwY, dsolo, dwide;
   int nwide = 0;      // columns outside the pairs with at most 64 observed rows (k_colprox_wide)
   int nsolo = 0;      // columns that k_colprox_pair leaves to k_colprox (more than 32 observed rows, unpaired last column)
@@ -194,8 +225,10 @@ struct omc_instance {
   // kernel stats
   int64_t launches[OMC_KERNEL_NCLASS] = {0}; double ms[OMC_KERNEL_NCLASS] = {0}; int64_t units[OMC_KERNEL_NCLASS] = {0};
   size_t nnz_rows() const { return row_idx.size(); }
-  std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
-  std::vector<int> ev_class;
+  // timing events: two pools that swap at a check, so that the pool of the interval that has just ended is read (finish_events) after the
+  // next iteration has been enqueued while the launches of that iteration record into the other one
+  std::vector<hipEvent_t> ev_pool[2]; size_t ev_used[2] = {0, 0}; int ev_cur = 0;
+  std::vector<int> ev_class[2];
 };
 
 extern "C" {
@@ -321,7 +354,9 @@ void omc_instance_destroy(omc_instance* h) {
   (void)hipSetDevice(h->device);
   (void)omc_comm_destroy(h);
   for (hipStream_t q : {h->stream, h->gs[0], h->gs[1], h->gs[2], h->append_stream, h->fetch_stream}) if (q) (void)hipStreamDestroy(q);
-  for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
+  for (int q = 0; q < 2; ++q) for (hipEvent_t e : h->ev_pool[q]) (void)hipEventDestroy(e);
+  for (hipEvent_t e : h->ev_up) if (e) (void)hipEventDestroy(e);
+  if (h->ev_gram) (void)hipEventDestroy(h->ev_gram);
   for (int q = 0; q < 5; ++q) for (hipEvent_t e : {h->gev[q], h->gevc[q]}) if (e) (void)hipEventDestroy(e);
   if (h->ev_main) (void)hipEventDestroy(h->ev_main);
   delete h;      // the device buffers free themselves
@@ -353,23 +388,35 @@ static int cut_piece(int cut_type, int dir, double vhat, int q1, double* lo, dou
 // Per-kernel timing: a pair of pool events brackets a launch; the pool is drained by finish_events.  If an event cannot be created, or one of
 // the two records fails, the launch runs (and is counted) untimed.
 static bool next_event_pair(omc_instance* h) {
-  while (h->ev_pool.size() < h->ev_used + 2) {
+  std::vector<hipEvent_t>& pool = h->ev_pool[h->ev_cur];
+  while (pool.size() < h->ev_used[h->ev_cur] + 2) {
     hipEvent_t e;
     if (hipEventCreate(&e) != hipSuccess) return false;
-    h->ev_pool.push_back(e);
+    pool.push_back(e);
   }
   return true;
 }
 #define TIMED_ON(strm, cls, units_, call)                                                                     \
   do {                                                                                                        \
-    const bool t0_ = next_event_pair(h) && hipEventRecord(h->ev_pool[h->ev_used], strm) == hipSuccess;        \
+    const int pc_ = h->ev_cur;                                                                                \
+    const bool t0_ = next_event_pair(h) && hipEventRecord(h->ev_pool[pc_][h->ev_used[pc_]], strm) == hipSuccess; \
     call;                                                                                                     \
-    if (t0_ && hipEventRecord(h->ev_pool[h->ev_used + 1], strm) == hipSuccess) {                              \
-      h->ev_used += 2; h->ev_class.push_back(cls);                                                            \
+    if (t0_ && hipEventRecord(h->ev_pool[pc_][h->ev_used[pc_] + 1], strm) == hipSuccess) {                    \
+      h->ev_used[pc_] += 2; h->ev_class[pc_].push_back(cls);                                                  \
     }                                                                                                         \
     h->launches[cls] += 1; h->units[cls] += (units_);                                                         \
   } while (0)
 #define TIMED(cls, units_, call) TIMED_ON(h->stream, cls, units_, call)
+// a launch timed into class `cls` that is not one of the class's launches (k_setup_gram: ms of the setup class, see omc_last_kernel_stats)
+#define TIMED_UNCOUNTED_ON(strm, cls, call)                                                                   \
+  do {                                                                                                        \
+    const int pc_ = h->ev_cur;                                                                                \
+    const bool t0_ = next_event_pair(h) && hipEventRecord(h->ev_pool[pc_][h->ev_used[pc_]], strm) == hipSuccess; \
+    call;                                                                                                     \
+    if (t0_ && hipEventRecord(h->ev_pool[pc_][h->ev_used[pc_] + 1], strm) == hipSuccess) {                    \
+      h->ev_used[pc_] += 2; h->ev_class[pc_].push_back(cls);                                                  \
+    }                                                                                                         \
+  } while (0)
 
 // rows (OMC.jl:1558-1685) and row subspace of a set of nodes, on the host: shared by omc_relax_stage and omc_relax_append
 struct NodePack {
@@ -780,12 +827,12 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   return 0;
 }
 
-static int finish_events(omc_instance* h) {
-  for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
+static int finish_events(omc_instance* h, int pool) {      // every launch the pool has timed must have completed
+  for (size_t i = 0; i + 1 < h->ev_used[pool]; i += 2) {
     float msv = 0.f;
-    if (hipEventElapsedTime(&msv, h->ev_pool[i], h->ev_pool[i + 1]) == hipSuccess) h->ms[h->ev_class[i / 2]] += msv;
+    if (hipEventElapsedTime(&msv, h->ev_pool[pool][i], h->ev_pool[pool][i + 1]) == hipSuccess) h->ms[h->ev_class[pool][i / 2]] += msv;
   }
-  h->ev_used = 0; h->ev_class.clear();
+  h->ev_used[pool] = 0; h->ev_class[pool].clear();
   return 0;
 }
 
@@ -919,33 +966,46 @@ int omc_relax_solve(omc_instance* h) {
   const omc_relax_params& P = h->params;
   const Tuning tun = h->tun;      // copied once: omc_tuning_set may run on the caller's thread while a submitted solve runs on the worker
   for (int c = 0; c < OMC_KERNEL_NCLASS; ++c) { h->launches[c] = 0; h->ms[c] = 0; h->units[c] = 0; }
-  h->ev_used = 0; h->ev_class.clear();
+  for (int q = 0; q < 2; ++q) { h->ev_used[q] = 0; h->ev_class[q].clear(); }
+  h->ev_cur = 0;
+  for (int q = 0; q < OMC_HOST_NPHASE; ++q) { h->host_ms[q] = 0; h->host_cnt[q] = 0; }
   auto t0 = std::chrono::steady_clock::now();
   hipStream_t s = h->stream;
+  // host stamps between the iterations (omc_last_host_phases): stamp(q) charges the time since the previous stamp to piece q
+  auto t_last = t0;
+  auto stamp_begin = [&]() { t_last = std::chrono::steady_clock::now(); };
+  auto stamp = [&](int q) { const auto t = std::chrono::steady_clock::now(); h->host_ms[q] += std::chrono::duration<double, std::milli>(t - t_last).count(); h->host_cnt[q] += 1; t_last = t; };
   const int S = w.B; int Btot = h->Btot_live.load();      // nodes staged so far: omc_relax_append may add more while this loop runs (re-read at every check)
   struct CloseGuard { omc_instance* h; ~CloseGuard() { std::lock_guard<std::mutex> lk(h->append_mu); h->append_closed = true; h->ws.Btot = h->Btot_live.load(); h->Btot = h->ws.Btot; if (h->shor_on) h->sh.Btot = h->ws.Btot; } } close_guard{h};
   // slot bookkeeping on the host: node of each slot (-1 = idle), next pending node
-  std::vector<int> node_of(S), flags(3 * (size_t)S), done(S, 0);
+  std::vector<int> node_of(S);
   for (int b = 0; b < S; ++b) node_of[b] = (b < Btot) ? b : -1;      // with omc_relax_reserve there may be more slots than nodes staged so far: the others start idle
   int next = std::min(S, Btot), harvested = 0, nactive = next;
-  auto push_flags = [&](const std::vector<int>& init, const std::vector<int>& fin) -> int {
-    for (int b = 0; b < S; ++b) { flags[b] = node_of[b] < 0 ? 0 : node_of[b]; flags[S + b] = init[b]; flags[2 * (size_t)S + b] = fin[b]; }
-    HIPCHK(hipMemcpyAsync(w.node_of, flags.data(), sizeof(int) * flags.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));                  // `flags` is rewritten by the next push
+  // Page-locked images (see omc_instance): an upload returns at once, and an image is rewritten only after the copy that last read it has
+  // completed (its event; two images alternate, so that wait is over long before it is asked for)
+  for (int q = 0; q < 2; ++q) { int rc = h->pin_flags[q].ensure(sizeof(int) * 3 * (size_t)S); if (rc) return rc; rc = h->pin_list[q].ensure(sizeof(int) * (size_t)S); if (rc) return rc; }
+  { int rc = h->pin_done.ensure(sizeof(int) * (size_t)S); if (rc) return rc; rc = h->pin_jobs.ensure(sizeof(int) * 2 * (size_t)S); if (rc) return rc; rc = h->bgramjobs.ensure(sizeof(int) * 2 * (size_t)S); if (rc) return rc; }
+  for (int q = 0; q < 4; ++q) { if (!h->ev_up[q]) HIPCHK(hipEventCreateWithFlags(&h->ev_up[q], hipEventDisableTiming)); h->ev_up_rec[q] = false; }
+  if (!h->ev_gram) HIPCHK(hipEventCreateWithFlags(&h->ev_gram, hipEventDisableTiming));
+  h->ev_gram_rec = false;
+  int* const done = h->pin_done.as<int>();
+  for (int b = 0; b < S; ++b) done[b] = 0;
+  int flags_cur = 0, list_cur = 0;
+  auto image_free = [&](int q) -> int {      // q: 0, 1 flags; 2, 3 slot list
+    if (h->ev_up_rec[q]) { HIPCHK(hipEventSynchronize(h->ev_up[q])); h->ev_up_rec[q] = false; }
     return 0;
   };
-  {
-    std::vector<int> init(S, 1), fin(S, 0);
-    for (int b = 0; b < S; ++b) { init[b] = node_of[b] >= 0 ? 1 : 0; done[b] = node_of[b] >= 0 ? 0 : 1; }
-    int rc = push_flags(init, fin); if (rc) return rc;
-    if (nactive < S) { HIPCHK(hipMemcpyAsync(w.done, done.data(), sizeof(int) * S, hipMemcpyHostToDevice, s)); HIPCHK(hipStreamSynchronize(s)); }      // idle slots are skipped by every kernel
-  }
-  const bool shor = h->shor_on;
-  const ShWS& sw = h->sh;
-  if (shor) omc_shor_launch_setup(&sw, s);       // before the base setup, which clears the init flags
-  TIMED(OMC_KERNEL_SETUP, S, omc_launch_setup(&w, s));
-  int it = 0;
-  const int check = std::max(1, P.check_every);
+  // sync: the caller needs the stream drained behind the upload (the harvest kernels' outputs); nothing else waits for a flags upload
+  auto push_flags = [&](const std::vector<int>& init, const std::vector<int>& fin, bool sync) -> int {
+    const int q = flags_cur; flags_cur ^= 1;
+    { int rc = image_free(q); if (rc) return rc; }
+    int* flags = h->pin_flags[q].as<int>();
+    for (int b = 0; b < S; ++b) { flags[b] = node_of[b] < 0 ? 0 : node_of[b]; flags[S + b] = init[b]; flags[2 * (size_t)S + b] = fin[b]; }
+    HIPCHK(hipMemcpyAsync(w.node_of, flags, sizeof(int) * 3 * (size_t)S, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(h->ev_up[q], s)); h->ev_up_rec[q] = true;
+    if (sync) HIPCHK(hipStreamSynchronize(s));
+    return 0;
+  };
   // Streams.  Inside an iteration the three blocks are independent of each other (columns: Y, Yp, alpha -> alpha, Lambda;
   // cone: Y - D1 -> W1; small cone: Y, D3, V -> E3, W3*): a main stream (cone, then the global step) and two side streams
   // (columns, small cone) forked and joined by events, so that the latency-bound column waves and the small workgroups
@@ -958,16 +1018,56 @@ int omc_relax_solve(omc_instance* h) {
     HIPCHK(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
   }
   const hipStream_t sm = multi ? h->gs[0] : s, sb = multi ? h->gs[1] : s, sc = multi ? h->gs[2] : s;
+  // The Gram matrix of the rows of every node that is about to get a slot (k_setup_gram): G depends on the node's descriptor only and nothing
+  // but k_setup and k_global touches it, so it is formed on the column stream -- idle between a check and the next iteration -- beside the
+  // harvest kernels of the slot's previous node, and joined to the main stream behind k_setup (gram_join), ahead of the next k_global.
+  // jobs: (slot, node) pairs in pin_jobs.  Its time goes to the setup class; it is not a launch of that class.
+  h->ws.setup_gram_inline = tun.setup_gram_inline ? 1 : 0;
+  h->ws.check_xs = std::min(std::max(0, tun.check_xs), CB_XS);      // at most CB_XS doubles are staged: more vectors than that never fit
+  int* const jobs = h->pin_jobs.as<int>();
+  auto gram_launch = [&](int njobs) -> int {
+    if (tun.setup_gram_inline || njobs <= 0) return 0;
+    HIPCHK(hipMemcpyAsync(h->bgramjobs.p, jobs, sizeof(int) * 2 * (size_t)njobs, hipMemcpyHostToDevice, sb));
+    for (int q = 0; q < njobs; ++q)      // the host builds the list: a job outside the slots or the nodes is a bookkeeping error, not something to skip
+      if (jobs[2 * q] < 0 || jobs[2 * q] >= S || jobs[2 * q + 1] < 0 || jobs[2 * q + 1] >= Btot) return fail(OMC_ERR_ARGUMENT, "omc_relax_solve: k_setup_gram job outside the slots / nodes");
+    TIMED_UNCOUNTED_ON(sb, OMC_KERNEL_SETUP, omc_launch_setup_gram(&w, h->bgramjobs.as<int>(), njobs, Btot, sb));
+    HIPCHK(hipEventRecord(h->ev_gram, sb)); h->ev_gram_rec = true;
+    return 0;
+  };
+  auto gram_jobs_free = [&]() -> int {      // before pin_jobs is rewritten
+    if (h->ev_gram_rec) { HIPCHK(hipEventSynchronize(h->ev_gram)); h->ev_gram_rec = false; }
+    return 0;
+  };
+  auto gram_join = [&]() -> int {
+    if (h->ev_gram_rec && sb != s) HIPCHK(hipStreamWaitEvent(s, h->ev_gram, 0));
+    return 0;
+  };
+  std::vector<int> init(S, 0), fin(S, 0), init2(S, 0), fin2(S, 0), harvested_ids;      // scratch of a check / a harvest / refill_idle
+  {
+    int nj = 0;
+    for (int b = 0; b < S; ++b) { init[b] = node_of[b] >= 0 ? 1 : 0; done[b] = node_of[b] >= 0 ? 0 : 1; if (node_of[b] >= 0) { jobs[2 * nj] = b; jobs[2 * nj + 1] = node_of[b]; ++nj; } }
+    int rc = gram_launch(nj); if (rc) return rc;
+    rc = push_flags(init, fin, false); if (rc) return rc;
+    if (nactive < S) { HIPCHK(hipMemcpyAsync(w.done, done, sizeof(int) * S, hipMemcpyHostToDevice, s)); HIPCHK(hipStreamSynchronize(s)); }      // idle slots are skipped by every kernel
+  }
+  const bool shor = h->shor_on;
+  const ShWS& sw = h->sh;
+  if (shor) omc_shor_launch_setup(&sw, s);       // before the base setup, which clears the init flags
+  TIMED(OMC_KERNEL_SETUP, S, omc_launch_setup(&w, s));
+  { int rc = gram_join(); if (rc) return rc; }
+  int it = 0;
+  const int check = std::max(1, P.check_every);
   // compact list of the slots that hold a running node: the per-iteration kernels launch over it (rebuilt when slots finish or are refilled)
   std::vector<char> parked(S, 0);      // finished, waiting for the next harvest
   int check_index = 0;
-  std::vector<int> alist(S);
   int nlist = 0;
   auto push_list = [&]() -> int {
+    const int q = list_cur; list_cur ^= 1;
+    { int rc = image_free(2 + q); if (rc) return rc; }
+    int* alist = h->pin_list[q].as<int>();
     nlist = 0;
     for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && !parked[b]) alist[nlist++] = b;
-    if (nlist) HIPCHK(hipMemcpyAsync(h->bslotlist.p, alist.data(), sizeof(int) * nlist, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if (nlist) { HIPCHK(hipMemcpyAsync(h->bslotlist.p, alist, sizeof(int) * nlist, hipMemcpyHostToDevice, s)); HIPCHK(hipEventRecord(h->ev_up[2 + q], s)); h->ev_up_rec[2 + q] = true; }
     return 0;
   };
   { int rc = push_list(); if (rc) return rc; }
@@ -992,6 +1092,7 @@ int omc_relax_solve(omc_instance* h) {
   };
   bool timed_out = false;
   h->total_sweeps = 0;
+  int drain_pool = -1;       // timing-event pool that waits to be read (finish_events): filled up to the last check, read after the next iteration is enqueued
   bool wait_main = true;     // the iteration streams must wait for the work queued on the main stream (setup, checks, refills)
   // Small batches are launch-bound (batch 1: ~190 us of launches, event records and waits around ~115 us of kernels per iteration):
   // the body of an iteration (fork, three concurrent blocks, join, global step) is captured once into a hipGraph and replayed.  Per-kernel
@@ -1089,13 +1190,17 @@ int omc_relax_solve(omc_instance* h) {
   };
   // nodes appended while every slot was idle (or while the loop was about to end): hand them to idle slots
   auto refill_idle = [&]() -> int {
-    std::vector<int> init2(S, 0), fin2(S, 0);
+    if (next >= Btot) return 0;
+    std::fill(init2.begin(), init2.end(), 0); std::fill(fin2.begin(), fin2.end(), 0);
+    int rc = gram_jobs_free(); if (rc) return rc;
     int ninit2 = 0;
-    for (int b = 0; b < S && next < Btot; ++b) if (node_of[b] < 0) { node_of[b] = next++; init2[b] = 1; parked[b] = 0; ++ninit2; }
+    for (int b = 0; b < S && next < Btot; ++b) if (node_of[b] < 0) { jobs[2 * ninit2] = b; jobs[2 * ninit2 + 1] = next; node_of[b] = next++; init2[b] = 1; parked[b] = 0; ++ninit2; }
     if (!ninit2) return 0;
-    int rc = push_flags(init2, fin2); if (rc) return rc;
+    rc = gram_launch(ninit2); if (rc) return rc;
+    rc = push_flags(init2, fin2, false); if (rc) return rc;
     if (shor) omc_shor_launch_setup(&sw, s);       // as at the start and at a harvest: the Shor state of the slot, before the base setup clears the init flags
     TIMED(OMC_KERNEL_SETUP, ninit2, omc_launch_setup(&w, s));
+    rc = gram_join(); if (rc) return rc;
     mw_budget[0] = mw_budget[1] = MAX_SWEEPS;
     recount();
     rc = push_list(); if (rc) return rc;
@@ -1152,6 +1257,9 @@ int omc_relax_solve(omc_instance* h) {
       if (multi && is_check) { HIPCHK(hipEventRecord(h->gev[3], sm)); HIPCHK(hipStreamWaitEvent(s, h->gev[3], 0)); }
     }
     wait_main = false;
+    if (drain_pool >= 0) {      // the timing events of the interval before the last check, now that the device has the next iteration to run
+      stamp_begin(); finish_events(h, drain_pool); drain_pool = -1; stamp(OMC_HOST_EVENT_DRAIN);
+    }
     if (!is_check) continue;
     wait_main = true;
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1175,10 +1283,16 @@ int omc_relax_solve(omc_instance* h) {
       if (w.bump_max > 0) { if (shor) omc_shor_launch_rescale(&sw, s); omc_launch_rho_rescale(&w, s); }
       if (w.accel) omc_launch_aa(&w, s);      // after the certificate (computed on an image of the map), skips finished slots
     });
-    HIPCHK(hipMemcpyAsync(done.data(), w.done, sizeof(int) * S, hipMemcpyDeviceToHost, s));
+    stamp_begin();
+    HIPCHK(hipMemcpyAsync(done, w.done, sizeof(int) * S, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    stamp(OMC_HOST_CHECK_WAIT);
+    const auto t_check = t_last;
     { int rc = mw_collect(); if (rc) return rc; }
-    finish_events(h);      // every timed launch of the interval has joined s (the side streams join sm before k_global, sm joins s at a check)
+    // every timed launch of the interval has joined s (the side streams join sm before k_global, sm joins s at a check) and so has completed:
+    // its pool is read once the next iteration is enqueued; what is launched from here on records into the other pool, which is empty
+    if (drain_pool >= 0) { finish_events(h, drain_pool); drain_pool = -1; }
+    drain_pool = h->ev_cur; h->ev_cur ^= 1;
     Btot = h->Btot_live.load();
     if (P.first_wins) {   // the first certified node ends the batch (penalty autotune): everything still running is harvested as it stands
       std::vector<int> stv(S);
@@ -1188,7 +1302,7 @@ int omc_relax_solve(omc_instance* h) {
       for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && done[b] && stv[b] == OMC_ST_OPTIMAL) won = true;
       if (won) {
         for (int b = 0; b < S; ++b) done[b] = 1;
-        HIPCHK(hipMemcpyAsync(w.done, done.data(), sizeof(int) * S, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(w.done, done, sizeof(int) * S, hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
         int rc = close_unslotted(OMC_ST_SLOW); if (rc) return rc;
       }
@@ -1198,7 +1312,7 @@ int omc_relax_solve(omc_instance* h) {
     // iterations in the full eigendecomposition, the straggler of every launch it is part of, and each harvest is 1 - 3 ms of few-workgroup
     // kernels on the main stream -- batching them halves the launches that carry young slots.  A finished slot waits (done = 1, skipped
     // by every kernel and left out of the slot list) for at most REFILL_EVERY - 1 check intervals.
-    std::vector<int> init(S, 0), fin(S, 0);
+    std::fill(init.begin(), init.end(), 0); std::fill(fin.begin(), fin.end(), 0);
     int nfin = 0, nlive = 0, nnew = 0;
     for (int b = 0; b < S; ++b) {
       if (node_of[b] < 0) continue;
@@ -1210,8 +1324,15 @@ int omc_relax_solve(omc_instance* h) {
     const bool harvest_now = nfin > 0 && (nlive == 0 || (next < Btot ? (check_index % REFILL_EVERY == 0 || nlive < 256) : (check_index % (4 * REFILL_EVERY) == 0)));
     if (harvest_now) for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && done[b]) { fin[b] = 1; parked[b] = 0; }
     if (!harvest_now) nfin = 0;
+    stamp(OMC_HOST_CHECK_SCAN);
     if (nfin) {
-      int rc = push_flags(init, fin); if (rc) return rc;
+      // which pending node goes to which finished slot is known now (ascending slots take ascending nodes, as the loop below hands them out)
+      int rc = gram_jobs_free(); if (rc) return rc;
+      int nj = 0;
+      if (!timed_out) for (int b = 0, nx = next; b < S && nx < Btot; ++b) if (fin[b]) { jobs[2 * nj] = b; jobs[2 * nj + 1] = nx++; ++nj; }
+      rc = gram_launch(nj); if (rc) return rc;
+      rc = push_flags(init, fin, false); if (rc) return rc;
+      stamp(OMC_HOST_HARVEST_FLAGS);
       TIMED(OMC_KERNEL_HARVEST, nfin, {
         if (w.save_to) omc_launch_state_save(&w, s);                              // warm-start pool: before the recovery overwrites the iterate U = Q Vt
         if (shor) omc_shor_launch_state_save(&sw, s);                             // its Shor extension (no-op without indices)
@@ -1221,9 +1342,10 @@ int omc_relax_solve(omc_instance* h) {
         omc_launch_harvest(&w, s);
         if (shor) omc_shor_launch_harvest(&sw, s);
       });
+      stamp(OMC_HOST_HARVEST_ENQUEUE);
       harvested += nfin; h->nodes_done.store(harvested);
       int ninit = 0;
-      std::vector<int> harvested_ids;
+      harvested_ids.clear();
       for (int b = 0; b < S; ++b) {
         if (!fin[b]) continue;
         fin[b] = 0;
@@ -1231,7 +1353,8 @@ int omc_relax_solve(omc_instance* h) {
         if (next < Btot && !timed_out) { node_of[b] = next++; init[b] = 1; ++ninit; }
         else node_of[b] = -1;
       }
-      rc = push_flags(init, fin); if (rc) return rc;      // synchronises the stream: the harvest kernels have written the per-node outputs
+      rc = push_flags(init, fin, true); if (rc) return rc;      // synchronises the stream: the harvest kernels have written the per-node outputs
+      stamp(OMC_HOST_HARVEST_WAIT);
       if (w.save_to) {      // the entries these nodes saved to hold their state from here on (push_flags has synchronised the stream)
         std::lock_guard<std::mutex> lk(h->sig_mu);
         for (int id : harvested_ids) {
@@ -1242,12 +1365,19 @@ int omc_relax_solve(omc_instance* h) {
         }
       }
       { std::lock_guard<std::mutex> lk(h->done_mu); h->done_q.insert(h->done_q.end(), harvested_ids.begin(), harvested_ids.end()); }
+      stamp(OMC_HOST_HARVEST_BOOK);
       if (ninit) { if (shor) omc_shor_launch_setup(&sw, s); TIMED(OMC_KERNEL_SETUP, ninit, omc_launch_setup(&w, s)); mw_budget[0] = mw_budget[1] = MAX_SWEEPS; }
+      rc = gram_join(); if (rc) return rc;
+      stamp(OMC_HOST_SETUP_ENQUEUE);
     }
     recount();
-    if (nfin || nnew) { int rc = push_list(); if (rc) return rc; }
+    if (nfin || nnew) { int rc = push_list(); if (rc) return rc; stamp(OMC_HOST_LIST); }
     if (next < Btot && !timed_out && nactive < S) { int rc = refill_idle(); if (rc) return rc; }      // appended nodes for slots that had gone idle
     if (timed_out) { int rc = close_unslotted(OMC_ST_TIME); if (rc) return rc; }
+    {
+      const int q = nfin ? OMC_HOST_HARVEST_TOTAL : OMC_HOST_CHECK_TOTAL;
+      h->host_ms[q] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_check).count(); h->host_cnt[q] += 1;
+    }
   }
   { int rc = mw_collect(); if (rc) return rc; }
   {
@@ -1271,9 +1401,16 @@ int omc_relax_solve(omc_instance* h) {
     HIPCHK(hipMemsetAsync(h->wbig.sub_stat, 0, sizeof(int) * ss.size(), s));
   }
   HIPCHK(hipGetLastError());
-  finish_events(h);
+  if (drain_pool >= 0) finish_events(h, drain_pool);      // the older pool first: the sums are formed in launch order
+  finish_events(h, h->ev_cur);
   h->last_solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   h->last_iters_total = it;
+  if (tun.host_phases) {
+    static const char* const nm[OMC_HOST_NPHASE] = {"check_wait", "check_scan", "list", "event_drain", "harvest_flags", "harvest_enqueue", "harvest_wait", "harvest_book", "setup_enqueue", "check_total", "harvest_total"};
+    fprintf(stderr, "omc host phases (solve %.1f ms, %d iterations):", 1e3 * h->last_solve_seconds, it);
+    for (int q = 0; q < OMC_HOST_NPHASE; ++q) fprintf(stderr, " %s %.3f ms / %lld", nm[q], h->host_ms[q], (long long)h->host_cnt[q]);
+    fprintf(stderr, "\n");
+  }
   (void)harvested;
   return 0;
 }
@@ -2729,6 +2866,12 @@ int omc_debug_aa(omc_instance* h, int* accepted, int* rejected) {
 int omc_debug_diag(omc_instance* h, double* out /* 8 * slots */) {
   if (!h || !out || !h->ws.stamps) return fail(OMC_ERR_ARGUMENT, "no diagnostics");
   HIPCHK(hipMemcpy(out, h->ws.stamps + 32, 8 * 8 * (size_t)h->ws.B, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int omc_last_host_phases(omc_instance* h, double* ms, int64_t* count) {
+  if (!h || !ms || !count) return fail(OMC_ERR_ARGUMENT, "NULL argument");
+  for (int q = 0; q < OMC_HOST_NPHASE; ++q) { ms[q] = h->host_ms[q]; count[q] = h->host_cnt[q]; }
   return 0;
 }
 

@@ -71,6 +71,7 @@ struct OmcWS {
   double* sval;           // m
   double *objcol, *c0col; // m: per-column terms of the exact objective / Fenchel constant (k_colprox mode 1 -> k_check_build)
   double* Mchk;           // n*n
+  int check_xs;           // cut vectors k_check_build stages in LDS (OMC_CHECK_XS, 0 = none: every listed cut row reads global memory)
   double *Mbuf, *Vrow;    // np16*np16: next cone input Y - D1 (zero padded) ; eigenvectors of the last projection, row-major
   double* fro2;           // B: ||Mbuf||_F^2
   int* vvalid;            // B: Vrow holds eigenvectors
@@ -115,6 +116,7 @@ struct OmcWS {
   double* rrhs;           // B*Rmax
   double* cutx;           // B*Lmax*n
   double* G;              // B*Rmax*Rmax
+  int setup_gram_inline;  // 1 (OMC_SETUP_GRAM_INLINE): k_setup forms G itself, pair after pair; 0: k_setup_gram has formed it before k_setup runs
   double* lam;            // B*Rmax
   // scalars per node
   double *obj, *objout, *objprev, *lbprev, *lb, *c0, *evsum, *cpen, *cst, *rp, *rd, *lmin;  // B (lmin 2B)
@@ -150,6 +152,7 @@ struct OmcWS {
 extern "C" {
 #endif
 void omc_launch_setup(const OmcWS* w, hipStream_t s);
+void omc_launch_setup_gram(const OmcWS* w, const int* jobs, int njobs, int nnodes, hipStream_t s);      /* G of the (slot, node) pairs in jobs[2 * njobs] (device), nodes below nnodes */
 void omc_launch_colprox(const OmcWS* w, int mode, hipStream_t s);
 void omc_launch_cone(const OmcWS* w, int mode, hipStream_t s);
 void omc_launch_global(const OmcWS* w, hipStream_t s);

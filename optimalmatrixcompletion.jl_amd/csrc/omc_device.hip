@@ -62,6 +62,38 @@ __device__ __forceinline__ double rowU_entry(const OmcWS& w, int nb, int r, int 
   return w.cutx[((size_t)nb * w.Lmax + l) * w.n + i] * w.rcoef[((size_t)nb * w.Rmax + r) * w.k + j];
 }
 
+// one entry of the Gram matrix (and its mirror image): the whole workgroup reduces the pair (r, s) of node nb's rows; G is the slot's matrix
+__device__ __forceinline__ void gram_pair(const OmcWS& w, int nb, int r, int s, double* G, double* red) {
+  const int n = w.n, k = w.k, tid = threadIdx.x, T = blockDim.x;
+  const int kr = w.rkind[(size_t)nb * w.Rmax + r], ks = w.rkind[(size_t)nb * w.Rmax + s];
+  double acc = 0.0;
+  const bool yr = (kr == ROW_TRACE || kr == ROW_CUT), ys = (ks == ROW_TRACE || ks == ROW_CUT);
+  if (yr && ys) {
+    const double* xr = (kr == ROW_CUT) ? w.cutx + ((size_t)nb * w.Lmax + w.rcut[(size_t)nb * w.Rmax + r]) * n : nullptr;
+    const double* xs = (ks == ROW_CUT) ? w.cutx + ((size_t)nb * w.Lmax + w.rcut[(size_t)nb * w.Rmax + s]) * n : nullptr;
+    if (!xr && !xs) {
+      for (int i = tid; i < n; i += T) acc += 1.0 / w.wY1[(size_t)i * n + i];
+    } else if (!xr || !xs) {
+      const double* x = xr ? xr : xs;
+      for (int i = tid; i < n; i += T) acc += x[i] * x[i] / w.wY1[(size_t)i * n + i];
+    } else {
+      for (int e = tid; e < n * n; e += T) {
+        int i = e % n, j = e / n;
+        acc += xr[i] * xr[j] * xs[i] * xs[j] / w.wY1[e];
+      }
+    }
+  }
+  if (kr != ROW_TRACE && ks != ROW_TRACE) {
+    for (int e = tid; e < n * k; e += T) {
+      int i = e % n, j = e / n;
+      double a = rowU_entry(w, nb, r, i, j);
+      if (a != 0.0) acc += a * rowU_entry(w, nb, s, i, j) * 0.5;
+    }
+  }
+  double tot = block_sum(acc, red);
+  if (tid == 0) { G[(size_t)r * w.Rmax + s] = tot; G[(size_t)s * w.Rmax + r] = tot; }
+}
+
 __global__ void k_setup(OmcWS w) {
   if (!w.init[blockIdx.x]) return;                 // only slots that received a new node
   const int nb = w.node_of[blockIdx.x];
@@ -156,39 +188,36 @@ __global__ void k_setup(OmcWS w) {
     w.done[b] = 0; w.rowov[b] = 0; w.gap_prev[b] = 1e300; w.gap_rate[b] = 1.0; w.slow_votes[b] = 0; w.status[b] = OMC_ST_SLOW; w.iters[b] = 0; w.stall[b] = 0; w.nbump[b] = 0; w.lastbump[b] = 0; w.bfac[b] = 1.0;
     w.obj[b] = 1e300; w.objout[b] = 1e300; w.objprev[b] = 1e300; w.lbprev[b] = -1e300; w.lb[b] = -1e300; w.rp[b] = 1e300; w.rd[b] = 1e300;
   }
-  // Gram matrix for rho = 1
+  // Gram matrix for rho = 1: k_setup_gram has written it (one workgroup per chunk of row pairs, beside the harvest); setup_gram_inline = 1
+  // (OMC_SETUP_GRAM_INLINE) walks the pairs here, one after the other, as before
+  if (w.setup_gram_inline) {
+    double* G = w.G + (size_t)b * w.Rmax * w.Rmax;
+    for (int r = 0; r < R; ++r)
+      for (int s = r; s < R; ++s) gram_pair(w, nb, r, s, G, red);
+  }
+}
+
+// The Gram matrix of k_setup on a grid of its own: workgroup (c, q) reduces the row pairs [c * GRAM_CHUNK, (c + 1) * GRAM_CHUNK) of job q =
+// (slot, node) with gram_pair, i.e. with the 256 threads, the strides, the order of terms and the block_sum of the serial walk: G comes out bit
+// for bit the same.  The jobs come from the host, which knows which pending node goes to which slot before the slot is harvested (node_of is
+// not read: it still names the node that is leaving).  Pair numbering and chunks: gram_pair_of, GRAM_CHUNK (omc_layout.h).
+__global__ void __launch_bounds__(256) k_setup_gram(OmcWS w, const int* jobs, int njobs, int nnodes) {
+  const int q = blockIdx.y;
+  if (q >= njobs) return;
+  const int b = jobs[2 * q], nb = jobs[2 * q + 1];
+  if (b < 0 || b >= w.B || nb < 0 || nb >= nnodes) return;      // never taken: the host refuses such a list before the launch (omc_relax_solve); kept so that no list can write out of bounds.  nnodes: the nodes staged or appended so far (w.Btot is the count at stage time)
+  const int R = w.R[nb];
+  const int npairs = gram_npairs(R);
+  int p = blockIdx.x * GRAM_CHUNK;
+  if (p >= npairs) return;
+  const int pend = (p + GRAM_CHUNK < npairs) ? p + GRAM_CHUNK : npairs;
+  __shared__ double red[32];
   double* G = w.G + (size_t)b * w.Rmax * w.Rmax;
-  for (int r = 0; r < R; ++r) {
-    const int kr = w.rkind[(size_t)nb * w.Rmax + r];
-    for (int s = r; s < R; ++s) {
-      const int ks = w.rkind[(size_t)nb * w.Rmax + s];
-      double acc = 0.0;
-      const bool yr = (kr == ROW_TRACE || kr == ROW_CUT), ys = (ks == ROW_TRACE || ks == ROW_CUT);
-      if (yr && ys) {
-        const double* xr = (kr == ROW_CUT) ? w.cutx + ((size_t)nb * w.Lmax + w.rcut[(size_t)nb * w.Rmax + r]) * n : nullptr;
-        const double* xs = (ks == ROW_CUT) ? w.cutx + ((size_t)nb * w.Lmax + w.rcut[(size_t)nb * w.Rmax + s]) * n : nullptr;
-        if (!xr && !xs) {
-          for (int i = tid; i < n; i += T) acc += 1.0 / w.wY1[(size_t)i * n + i];
-        } else if (!xr || !xs) {
-          const double* x = xr ? xr : xs;
-          for (int i = tid; i < n; i += T) acc += x[i] * x[i] / w.wY1[(size_t)i * n + i];
-        } else {
-          for (int e = tid; e < n * n; e += T) {
-            int i = e % n, j = e / n;
-            acc += xr[i] * xr[j] * xs[i] * xs[j] / w.wY1[e];
-          }
-        }
-      }
-      if (kr != ROW_TRACE && ks != ROW_TRACE) {
-        for (int e = tid; e < n * k; e += T) {
-          int i = e % n, j = e / n;
-          double a = rowU_entry(w, nb, r, i, j);
-          if (a != 0.0) acc += a * rowU_entry(w, nb, s, i, j) * 0.5;
-        }
-      }
-      double tot = block_sum(acc, red);
-      if (tid == 0) { G[(size_t)r * w.Rmax + s] = tot; G[(size_t)s * w.Rmax + r] = tot; }
-    }
+  int r, s;
+  gram_pair_of(p, R, &r, &s);
+  for (; p < pend; ++p) {
+    gram_pair(w, nb, r, s, G, red);
+    gram_pair_next(R, &r, &s);
   }
 }
 
@@ -2331,8 +2360,16 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
 //   (k_cone CONE_EVALS then fills evsum)
 //   k_check_final : lb = c0 + evsum - cpen + cst ; stop tests (gap, infeasibility, stall)
 // ---------------------------------------------------------------------------------------------------------
+// The rows that contribute are those with a nonzero multiplier, a handful of the R rows of a deep node and none at a cold start: wave 0 lists
+// them once, in ascending order (ballot), the cut rows among them a second time with their vector's index, and the first cut vectors are staged
+// in LDS; an entry then adds the terms of the listed rows in that same order, so Mchk and cU are what the walk over all R rows gives, bit for
+// bit.  CB_LIST bounds the lists (a node with more rows takes the walk); w.check_xs vectors (OMC_CHECK_XS), at most CB_XS doubles, are staged and
+// the listed cut rows beyond them read their vectors from global memory.
+#define CB_LIST 256
 __global__ void __launch_bounds__(512) k_check_build(OmcWS w) {
   __shared__ double red[32];
+  __shared__ int s_arow[CB_LIST], s_ccut[CB_LIST], s_na, s_nc;
+  __shared__ double s_alam[CB_LIST], s_clam[CB_LIST], s_xs[CB_XS];
   const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
   if (w.done[b]) return;
   const int nb = w.node_of[b];
@@ -2344,29 +2381,74 @@ __global__ void __launch_bounds__(512) k_check_build(OmcWS w) {
   const double* Q = w.Qb + (size_t)nb * n * rm;
   const double rho = w.rho_b[b], g = w.gamma;
   double* cU = w.chk_scratch + (size_t)b * n * k;
+  const bool listed = R <= CB_LIST;
+  if (listed && tid < WAVE) {
+    int na = 0, nc = 0;
+    const unsigned long long below = (1ull << tid) - 1ull;
+    for (int r0 = 0; r0 < R; r0 += WAVE) {
+      const int rr = r0 + tid;
+      const double lv = rr < R ? lam[rr] : 0.0;
+      const bool act = lv != 0.0;
+      const bool cut = act && w.rkind[(size_t)nb * w.Rmax + rr] == ROW_CUT;
+      const unsigned long long ma = __ballot(act), mc = __ballot(cut);
+      if (act) { const int pos = na + __popcll(ma & below); s_arow[pos] = rr; s_alam[pos] = lv; }
+      if (cut) { const int pos = nc + __popcll(mc & below); s_ccut[pos] = w.rcut[(size_t)nb * w.Rmax + rr]; s_clam[pos] = lv; }
+      na += __popcll(ma); nc += __popcll(mc);
+    }
+    if (tid == 0) { s_na = na; s_nc = nc; }
+  }
   {   // exact objective and Fenchel constant: per-column terms of k_colprox (mode 1) added in a fixed order (no atomics: run-to-run identical)
     double so = 0.0, sc = 0.0;
     for (int j = tid; j < m; j += T) { so += w.objcol[(size_t)b * m + j]; sc += w.c0col[(size_t)b * m + j]; }
-    so = block_sum(so, red); sc = block_sum(sc, red);
+    so = block_sum(so, red); sc = block_sum(sc, red);      // its barriers publish the lists
     if (tid == 0) { w.obj[b] = so; w.c0[b] = sc; }
   }
-  for (int e = tid; e < n * n; e += T) {
-    int i = e % n, j = e / n;
-    double v = -rho * E3[e];
-    for (int rr = 0; rr < R; ++rr) {
-      double lv = lam[rr];
-      if (lv != 0.0 && w.rkind[(size_t)nb * w.Rmax + rr] == ROW_CUT) {
-        const double* x = cutx + (size_t)w.rcut[(size_t)nb * w.Rmax + rr] * n;
+  if (listed) {
+    const int na = s_na, nc = s_nc;
+    const int cap = (w.check_xs * n <= CB_XS) ? w.check_xs : CB_XS / n;
+    const int ncs = nc < cap ? nc : cap;      // cut vectors staged in LDS
+    for (int e = tid; e < ncs * n; e += T) { const int c = e / n, i = e - c * n; s_xs[e] = cutx[(size_t)s_ccut[c] * n + i]; }
+    __syncthreads();
+    for (int e = tid; e < n * n; e += T) {
+      int i = e % n, j = e / n;
+      double v = -rho * E3[e];
+      for (int a = 0; a < ncs; ++a) {
+        const double lv = s_clam[a];
+        const double* x = s_xs + a * n;
         v += lv * x[i] * x[j];
       }
+      for (int a = ncs; a < nc; ++a) {
+        const double lv = s_clam[a];
+        const double* x = cutx + (size_t)s_ccut[a] * n;
+        v += lv * x[i] * x[j];
+      }
+      M[e] = v;
     }
-    M[e] = v;
-  }
-  for (int e = tid; e < n * k; e += T) {
-    int i = e % n, j = e / n;
-    double cu = 0.0;
-    for (int rr = 0; rr < R; ++rr) { double lv = lam[rr]; if (lv != 0.0) cu += lv * rowU_entry(w, nb, rr, i, j); }
-    cU[e] = cu;
+    for (int e = tid; e < n * k; e += T) {
+      int i = e % n, j = e / n;
+      double cu = 0.0;
+      for (int a = 0; a < na; ++a) { double lv = s_alam[a]; cu += lv * rowU_entry(w, nb, s_arow[a], i, j); }
+      cU[e] = cu;
+    }
+  } else {
+    for (int e = tid; e < n * n; e += T) {
+      int i = e % n, j = e / n;
+      double v = -rho * E3[e];
+      for (int rr = 0; rr < R; ++rr) {
+        double lv = lam[rr];
+        if (lv != 0.0 && w.rkind[(size_t)nb * w.Rmax + rr] == ROW_CUT) {
+          const double* x = cutx + (size_t)w.rcut[(size_t)nb * w.Rmax + rr] * n;
+          v += lv * x[i] * x[j];
+        }
+      }
+      M[e] = v;
+    }
+    for (int e = tid; e < n * k; e += T) {
+      int i = e % n, j = e / n;
+      double cu = 0.0;
+      for (int rr = 0; rr < R; ++rr) { double lv = lam[rr]; if (lv != 0.0) cu += lv * rowU_entry(w, nb, rr, i, j); }
+      cU[e] = cu;
+    }
   }
   __syncthreads();
   const double* al = w.alphaX + (size_t)b * w.nnz;
@@ -2816,6 +2898,14 @@ __global__ void __launch_bounds__(256) k_gram_XXt(OmcWS w, const double* X) {
 extern "C" {
 void omc_launch_gram_XXt(const OmcWS* w, const double* X, int B, hipStream_t s) { hipLaunchKernelGGL(k_gram_XXt, dim3(B), dim3(256), 0, s, *w, X); }
 void omc_launch_setup(const OmcWS* w, hipStream_t s) { hipLaunchKernelGGL(k_setup, dim3(w->B), dim3(256), 0, s, *w); }
+void omc_launch_setup_gram(const OmcWS* w, const int* jobs, int njobs, int nnodes, hipStream_t s) {
+  const int chunks = gram_chunks(w->Rmax);
+  if (njobs <= 0 || chunks <= 0) return;
+  for (int q0 = 0; q0 < njobs; q0 += 65535) {      // grid.y is limited to 65535
+    const int nq = njobs - q0 < 65535 ? njobs - q0 : 65535;
+    hipLaunchKernelGGL(k_setup_gram, dim3(chunks, nq), dim3(256), 0, s, *w, jobs + 2 * (size_t)q0, nq, nnodes);
+  }
+}
 void omc_launch_colprox(const OmcWS* w, int mode, hipStream_t s) {
   const int wpb = 4;
   if (mode == 0 && w->cp_pair) {

@@ -41,6 +41,18 @@ OMC_HD WsGeometry ws_geometry(int N) {
   }
   return {rpl <= 32 ? lpp : 0, rpl, ld, use_lds, ws_bytes(N, ld)};
 }
+// ---- k_setup_gram: the R (R + 1) / 2 pairs (r, s), r <= s, of a node's R rows numbered row by row -- (0,0), (0,1), .., (0,R-1), (1,1), .. --
+// and cut into chunks of GRAM_CHUNK consecutive pairs, one workgroup each ------------------------------------------------------------------
+#define GRAM_CHUNK 8
+#define CB_XS 4096   // doubles of cut vectors that k_check_build stages in LDS (the host clamps OMC_CHECK_XS to it)
+OMC_HD int gram_npairs(int R) { return R * (R + 1) / 2; }
+OMC_HD int gram_chunks(int R) { return (gram_npairs(R) + GRAM_CHUNK - 1) / GRAM_CHUNK; }
+OMC_HD void gram_pair_of(int p, int R, int* r, int* s) {      // p < gram_npairs(R)
+  int rr = 0;
+  while (p >= R - rr) { p -= R - rr; ++rr; }
+  *r = rr; *s = rr + p;
+}
+OMC_HD void gram_pair_next(int R, int* r, int* s) { if (++*s == R) { ++*r; *s = *r; } }
 // ---- multi-workgroup eigen-kernels (omc_cone_mw.hip), per-slot global slab: G (Ncp columns of ld doubles; columns padded to whole block
 // pairs, rows to 16), squared norms ev, eigenvalues lam, weights wgt (Ncp each), selection sel (Ncp ints), the largest squared relative
 // cross product of each sweep smax (MW_MAXSW 64-bit words), head (base, then nsel and nkeep as ints) ---------------------------------------
