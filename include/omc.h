@@ -322,6 +322,25 @@ int omc_left_singular_batch(omc_instance* h, int B, const double* X, double* U_o
  * (orders 129 - 144 and above 1024). */
 int omc_psd_project_batch(omc_instance* h, int B, int N, const double* M, double lo, double hi, int algo,
                           const double* V0, double* P, double* evals, double* V);
+/* The column prox of the ADMM iteration on its own (block F of DESIGN.md section 3.1), for B inputs at once, through the launcher a
+ * relaxation uses.  mode 0 (prox): per column j with observed rows O, B_j = I + gamma (Y[O,O] - gamma/(2 rho_f) a_old a_old'), cp = gamma^2 /
+ * (2 rho_f); s >= 0 with ||(B_j + cp s I)^-1 a_j||^2 = s and alpha = (B_j + cp s I)^-1 a_j.  Y is the matrix whose blocks enter B_j (2 Y - Yp of
+ * the iteration).  mode 1 (exact multipliers of the certificate): alpha = (I + gamma Y[O,O])^-1 a_j, objcol = a_j'alpha / 2, c0col = a_j'alpha -
+ * ||alpha||^2 / 2; objcol = 1e300 where the factorization fails.
+ * algo: 0 = the solver's dispatch under the instance's knobs; 1 = the dispatch without k_colprox_block (as under an OMC_COLPROX_BLOCK_MIN above
+ * every column: k_colprox_pair, k_colprox_wide, k_colprox); 2 = k_colprox_block for every non-empty column whatever its length (no pair kernel).
+ * Y: B*n*n column-major.  alpha_old: B*nnz (NULL = zeros), rho_f: B, s0: B*m starting values of s (NULL = cold) -- mode 0 only.  Outputs: alpha
+ * (B*nnz); s (B*m, mode 0); objcol, c0col (B*m, mode 1); nfact (B*m, may be NULL): factorizations per column, -1 where the kernel that ran the
+ * column does not count them (k_colprox_pair, k_colprox_wide) and for empty columns.  The nnz order is the instance's: columns in order,
+ * observed rows ascending.  OMC_ERR_ARGUMENT (before any device call) for a NULL handle, a mode or algo out of range, B <= 0 or a missing
+ * array.  Restages the instance: a staged batch is gone afterwards. */
+int omc_column_prox_batch(omc_instance* h, int B, int mode, int algo, const double* Y, const double* alpha_old, const double* rho_f,
+                          const double* s0, double* alpha, double* s, double* objcol, double* c0col, int* nfact);
+/* Launch plan of k_colprox_block for columns of at most cmax observed rows (cmax <= n) under OMC_COLPROX_BLOCK_MIN = block_min, computed on the
+ * host from the layout the kernel uses (no device call, no handle).  out[5] = the longest column whose tiles live in LDS; dynamic LDS bytes of
+ * the launch that holds a column of cmax rows; its global slab in doubles (0: the tiles are in LDS); workgroups per CU by LDS; 1 if a column
+ * of cmax rows is a block column (0: cmax < block_min, or beyond the kernel -- then the three numbers before are 0). */
+int omc_colprox_plan(int n, int cmax, int block_min, int64_t* out);
 /* out[5] of the multi-workgroup eigen-kernels in the last omc_relax_solve (base cone and big cone of Shor mode together), or of the last
  * omc_psd_project_batch (either algo): calls, most sweeps of one call (at the last check of a solve), calls that used up their sweep
  * budget without meeting the stop rule, most sweeps of one call overall, device microseconds of the last omc_psd_project_batch

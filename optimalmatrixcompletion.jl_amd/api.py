@@ -131,6 +131,13 @@ def _close_all():
 atexit.register(_close_all)
 
 
+def colprox_plan(n, cmax, block_min=65):
+    """omc_colprox_plan (host only, no GPU): where k_colprox_block keeps a column of cmax observed rows."""
+    out = np.zeros(5, np.int64)
+    _lib.check(_lib.load().omc_colprox_plan(int(n), int(cmax), int(block_min), _lib.ptr(out)))
+    return dict(lds_cmax=int(out[0]), lds_bytes=int(out[1]), slab_doubles=int(out[2]), workgroups_per_cu=int(out[3]), block=bool(out[4]))
+
+
 class Engine:
     """Device-resident instance + the four call sites of the reference driver."""
 
@@ -561,6 +568,43 @@ class Engine:
         if single:
             out = [o[0] for o in out]
         return out[0] if len(out) == 1 else tuple(out)
+
+    def column_prox(self, Y, alpha_old=None, rho_f=1.0, s0=None, mode=0, algo=0):
+        """The column prox of the ADMM iteration on its own (omc_column_prox_batch).  Y: (n, n) or (B, n, n); alpha_old: dense (B, n, m) with
+        zeros off the support (None = zeros); rho_f: scalar or (B,); s0: (B, m) starting values (None = cold).  mode 0: the prox, mode 1: the
+        exact multipliers of the certificate.  algo: 0 = the solver's dispatch, 1 = without the block kernel, 2 = the block kernel for every
+        non-empty column.  Returns a dict: alpha (B, n, m) dense, s (B, m; mode 0), objcol, c0col (B, m; mode 1), nfact (B, m)."""
+        n, m = self.n, self.m
+        Yb = np.asarray(Y, dtype=np.float64)
+        Yb = Yb[None] if Yb.ndim == 2 else Yb
+        if Yb.ndim != 3 or Yb.shape[1:] != (n, n):
+            raise ValueError("column_prox: Y must be n x n or B x n x n")
+        B = Yb.shape[0]
+        cols, rows = np.nonzero(self.indices.T)      # the library's nnz order: columns in order, rows ascending
+        nnz = rows.size
+        Yf = np.ascontiguousarray(np.stack([np.asfortranarray(y).ravel(order="F") for y in Yb]))
+        ao = None
+        if alpha_old is not None:
+            ad = np.asarray(alpha_old, dtype=np.float64)
+            ad = ad[None] if ad.ndim == 2 else ad
+            if ad.shape != (B, n, m):
+                raise ValueError("column_prox: alpha_old must be B x n x m")
+            ao = np.ascontiguousarray(ad[:, rows, cols])
+        rf = np.ascontiguousarray(np.broadcast_to(np.asarray(rho_f, dtype=np.float64), (B,)))
+        s0f = None
+        if s0 is not None:
+            s0f = np.ascontiguousarray(np.asarray(s0, dtype=np.float64).reshape(B, m))
+        al = np.zeros((B, max(nnz, 1))); sv = np.zeros((B, m)); oc = np.zeros((B, m)); cc = np.zeros((B, m)); nf = np.zeros((B, m), np.int32)
+        _lib.check(self._lib.omc_column_prox_batch(self._h, B, int(mode), int(algo), _lib.ptr(Yf), _lib.ptr(ao), _lib.ptr(rf), _lib.ptr(s0f),
+                                                   _lib.ptr(al), _lib.ptr(sv), _lib.ptr(oc), _lib.ptr(cc), _lib.ptr(nf)))
+        dense = np.zeros((B, n, m))
+        dense[:, rows, cols] = al[:, :nnz]
+        return dict(alpha=dense, s=sv, objcol=oc, c0col=cc, nfact=nf)
+
+    def colprox_plan(self, block_min=65, cmax=None):
+        """Launch plan of k_colprox_block for this instance's longest column (or cmax) under OMC_COLPROX_BLOCK_MIN = block_min
+        (omc_colprox_plan, host only)."""
+        return colprox_plan(self.n, int(self.indices.sum(axis=0).max()) if cmax is None else int(cmax), block_min)
 
     def cone_multi_stats(self):
         """Sweep accounting of the multi-workgroup eigen-kernels in the last solve, or of the last psd_project call (omc_last_cone_multi_stats)."""

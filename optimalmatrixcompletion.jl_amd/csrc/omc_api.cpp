@@ -9,6 +9,7 @@
 // throwing.  No torch types, no host pointer retained after return.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -103,6 +104,7 @@ struct Tuning {
   bool shor_explicit = false;      // OMC_SHOR_EXPLICIT: rank k > 1 Shor batches by the Shor engine even where the base engine would serve them
   bool shor_no_subspace = false;   // OMC_SHOR_NO_SUBSPACE: no tracked subspace for the order-(n+m) cone of Shor mode
   int check_xs = 16;               // OMC_CHECK_XS: cut vectors of the rows with a nonzero multiplier that k_check_build stages in LDS (the rest is read from global memory)
+  int colprox_block_min = 65;      // OMC_COLPROX_BLOCK_MIN: columns with at least this many observed rows take k_colprox_block (one workgroup per column, blocked MFMA Cholesky); a value above every column length is the path without it
   int cone_multi_min = 1025;       // OMC_CONE_MULTI_MIN: cone orders from this value on (never below 145) take the multi-workgroup eigen-kernels; the default is where only the cold kernel existed
   int graph_max = 16;              // OMC_GRAPH_MAX: hipGraph replay for batches staged with at most this many nodes
   int shor_select_kb = 1048576;    // OMC_SHOR_SELECT_KB: violated-minor selection streams (no materialised keys) when 16 B per candidate exceed this many KiB; 0 = always materialise
@@ -121,6 +123,7 @@ static const Knob OMC_KNOBS[] = {
   {"OMC_NO_WS_SPLIT", &Tuning::no_ws_split, nullptr},        {"OMC_SEGV_TRACE", &Tuning::segv_trace, nullptr},
   {"OMC_SETUP_GRAM_INLINE", &Tuning::setup_gram_inline, nullptr},
   {"OMC_SHOR_EXPLICIT", &Tuning::shor_explicit, nullptr},    {"OMC_SHOR_NO_SUBSPACE", &Tuning::shor_no_subspace, nullptr},
+  {"OMC_COLPROX_BLOCK_MIN", nullptr, &Tuning::colprox_block_min},
   {"OMC_CHECK_XS", nullptr, &Tuning::check_xs},              {"OMC_CONE_MULTI_MIN", nullptr, &Tuning::cone_multi_min},
   {"OMC_GRAPH_MAX", nullptr, &Tuning::graph_max},            {"OMC_SHOR_SELECT_KB", nullptr, &Tuning::shor_select_kb},
   {"OMC_STREAMS", nullptr, &Tuning::streams},
@@ -170,6 +173,12 @@ struct omc_instance {
   DevBuf dA, dmask, dcol_ptr, dcol_idx, dcol_val, dNcnt, dwY, dsolo, dwide;
   int nwide = 0;      // columns outside the pairs with at most 64 observed rows (k_colprox_wide)
   int nsolo = 0;      // columns that k_colprox_pair leaves to k_colprox (more than 32 observed rows, unpaired last column)
+  // k_colprox_block: its two column lists (tiles in LDS / in the slab), the per-column flag, the longest column of each list, the non-empty
+  // columns it leaves and the longest of them; the lists follow (block_min, pair kernel on) and are rebuilt at a stage call when either changed
+  DevBuf dblock, dslab, disblock, bcpb, bnfact;
+  int nblock = 0, nslab = 0, nrest = 0, cpb_cl = 0, cpb_cs = 0, crest_max = 0;
+  bool lists_valid = false; int lists_block_min = 0; bool lists_pair = true;
+  int cp_force = 0;   // set by omc_column_prox_batch for the omc_relax_stage call it makes: 1 = no block kernel, 2 = the block kernel for every non-empty column
   // batch workspace
   DevBuf bYx, bY, bYp, bU, bD1, bD3, bW1, bE3, bQb, brr, bsm, bdS, balpha, balphaX, bsval, bMchk, bsmall, bchk;
   DevBuf bR, brkind, brcut, brbi, brbj, brcoef, brrhs, bcutx, bG, blam;
@@ -257,6 +266,45 @@ static int upload(DevBuf& b, const void* src, size_t bytes, hipStream_t s) {
   return 0;
 }
 
+// Column lists of the column prox for a value of OMC_COLPROX_BLOCK_MIN.  With the pair kernel on, a pair (2p, 2p + 1) of columns with at most
+// 32 observed rows each belongs to k_colprox_pair whatever block_min says (that kernel selects its pairs itself).  Of the other non-empty
+// columns, those with block_min <= c <= cp_block_cmax() are block columns (LDS list up to cp_block_lds_cmax() rows, slab list above); the rest
+// go to k_colprox_wide (c <= 64) or stay with k_colprox, as before.
+static int build_colprox_lists(omc_instance* h, int block_min, bool pair_on) {
+  if (h->lists_valid && h->lists_block_min == block_min && h->lists_pair == pair_on) return 0;
+  const int m = h->m, lds_c = cp_block_lds_cmax(), max_c = cp_block_cmax();
+  std::vector<int> solo, wide, blk, slab;
+  std::vector<uint8_t> isb(m, 0);
+  h->cpb_cl = h->cpb_cs = h->crest_max = h->nrest = 0;
+  for (int j0 = 0; j0 < m; j0 += 2) {
+    const int j1 = j0 + 1;
+    const int c0 = h->col_ptr[j0 + 1] - h->col_ptr[j0], c1 = (j1 < m) ? h->col_ptr[j1 + 1] - h->col_ptr[j1] : 0;
+    const bool paired = j1 < m && c0 <= 32 && c1 <= 32;
+    for (int j = j0; j <= j1 && j < m; ++j) {
+      const int c = (j == j0) ? c0 : c1;
+      if (c == 0) continue;
+      if (!(paired && pair_on) && c >= block_min && c <= max_c) {
+        isb[j] = 1;
+        if (c <= lds_c) { blk.push_back(j); h->cpb_cl = std::max(h->cpb_cl, c); } else { slab.push_back(j); h->cpb_cs = std::max(h->cpb_cs, c); }
+        continue;
+      }
+      ++h->nrest; h->crest_max = std::max(h->crest_max, c);
+      if (paired) continue;
+      if (c <= 64) wide.push_back(j); else solo.push_back(j);
+    }
+  }
+  h->nsolo = (int)solo.size(); h->nwide = (int)wide.size(); h->nblock = (int)blk.size(); h->nslab = (int)slab.size();
+  int rc = 0;
+  if (h->nsolo && (rc = upload(h->dsolo, solo.data(), sizeof(int) * solo.size(), h->stream))) return rc;
+  if (h->nwide && (rc = upload(h->dwide, wide.data(), sizeof(int) * wide.size(), h->stream))) return rc;
+  if (h->nblock && (rc = upload(h->dblock, blk.data(), sizeof(int) * blk.size(), h->stream))) return rc;
+  if (h->nslab && (rc = upload(h->dslab, slab.data(), sizeof(int) * slab.size(), h->stream))) return rc;
+  if ((rc = upload(h->disblock, isb.data(), (size_t)m, h->stream))) return rc;
+  HIPCHK(hipStreamSynchronize(h->stream));      // the vectors die with this call
+  h->lists_valid = true; h->lists_block_min = block_min; h->lists_pair = pair_on;
+  return 0;
+}
+
 int omc_instance_create(int n, int m, int k, const double* A, const uint8_t* mask, double gamma, int device,
                         omc_instance** out) {
   if (!out) return fail(OMC_ERR_ARGUMENT, "out is NULL");
@@ -313,19 +361,7 @@ int omc_instance_create(int n, int m, int k, const double* A, const uint8_t* mas
   if ((rc = upload(h->dA, h->A.data(), sizeof(double) * n * m, h->stream))) return rc;
   if ((rc = upload(h->dmask, h->mask.data(), (size_t)n * m, h->stream))) return rc;
   if ((rc = upload(h->dcol_ptr, h->col_ptr.data(), sizeof(int) * (m + 1), h->stream))) return rc;
-  {
-    std::vector<int> solo, wide;
-    auto place = [&](int j) { const int c = h->col_ptr[j + 1] - h->col_ptr[j]; if (c == 0) return; if (c <= 64) wide.push_back(j); else solo.push_back(j); };
-    for (int j0 = 0; j0 < m; j0 += 2) {
-      const int j1 = j0 + 1;
-      const int c0 = h->col_ptr[j0 + 1] - h->col_ptr[j0], c1 = (j1 < m) ? h->col_ptr[j1 + 1] - h->col_ptr[j1] : 0;
-      if (j1 < m && c0 <= 32 && c1 <= 32) continue;
-      place(j0); if (j1 < m) place(j1);
-    }
-    h->nsolo = (int)solo.size(); h->nwide = (int)wide.size();
-    if (h->nsolo && (rc = upload(h->dsolo, solo.data(), sizeof(int) * solo.size(), h->stream))) return rc;
-    if (h->nwide && (rc = upload(h->dwide, wide.data(), sizeof(int) * wide.size(), h->stream))) return rc;
-  }
+  if ((rc = build_colprox_lists(h, h->tun.colprox_block_min, !h->tun.no_colprox_pair))) return rc;
   if ((rc = upload(h->dcol_idx, h->col_idx.data(), sizeof(int) * h->nnz, h->stream))) return rc;
   if ((rc = upload(h->dcol_val, h->col_val.data(), sizeof(double) * h->nnz, h->stream))) return rc;
   if ((rc = upload(h->dNcnt, h->Ncnt.data(), sizeof(double) * n * n, h->stream))) return rc;
@@ -664,7 +700,17 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   int rc_ = 0;
   if ((rc_ = upload(h->dwY, wY.data(), sizeof(double) * n * n, h->stream))) return rc_;
   w.col_ptr = h->dcol_ptr.as<int>(); w.col_idx = h->dcol_idx.as<int>(); w.col_val = h->dcol_val.as<double>();
-  w.cp_pair = h->tun.no_colprox_pair ? 0 : 1; w.cone_512 = h->tun.cone_512 ? 1 : 0; w.cp_series = CP_SERIES; w.cp_maxpass = CP_MAXPASS; w.cp_xcd = h->tun.colprox_no_xcd ? 0 : 1;
+  const int cp_force = h->cp_force;      // omc_column_prox_batch: for this call only
+  h->cp_force = 0;
+  {
+    const bool pair_on = !h->tun.no_colprox_pair && cp_force != 2;
+    if ((rc_ = build_colprox_lists(h, cp_force == 1 ? INT_MAX : cp_force == 2 ? 1 : h->tun.colprox_block_min, pair_on))) return rc_;
+    w.cp_pair = pair_on ? 1 : 0;
+  }
+  w.cp_nblock = h->nblock; w.cp_block = h->nblock ? h->dblock.as<int>() : nullptr;
+  w.cp_nslab = h->nslab; w.cp_slab = h->nslab ? h->dslab.as<int>() : nullptr;
+  w.cp_isblock = (h->nblock + h->nslab) ? h->disblock.as<unsigned char>() : nullptr; w.cp_nrest = h->nrest; w.cp_nfact = nullptr;
+  w.cone_512 = h->tun.cone_512 ? 1 : 0; w.cp_series = CP_SERIES; w.cp_maxpass = CP_MAXPASS; w.cp_xcd = h->tun.colprox_no_xcd ? 0 : 1;
   w.cp_nsolo = h->nsolo; w.cp_solo = h->nsolo ? h->dsolo.as<int>() : nullptr;
   w.cp_nwide = h->nwide; w.cp_wide = h->nwide ? h->dwide.as<int>() : nullptr;
   w.Ncnt = h->dNcnt.as<double>(); w.wY1 = h->dwY.as<double>();
@@ -806,6 +852,11 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   w.geo = omc_plan_geometry(n, w.np16, k, rmax, Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
   ENS(h->bmwstat, sB * 4 * sizeof(int)); HIPCHK(hipMemsetAsync(h->bmwstat.p, 0, sB * 4 * sizeof(int), h->stream));
   w.mw_stat = h->bmwstat.as<int>(); w.mw_budget = MAX_SWEEPS; w.ev_out = nullptr;
+  // k_colprox_block: the dynamic LDS of its launches and the slab of the columns beyond the LDS, for those columns only.  The slab of
+  // colprox_body (one block per slot and column) is sized by the longest column that still runs it
+  geom_set_cpblock(w.geo, h->cpb_cl, h->cpb_cs);
+  w.geo.cp_scratch_stride = h->crest_max > w.geo.cp_lds_c ? cp_body_layout(h->crest_max).doubles : 0;
+  if (w.geo.cpb_slab_stride && !shor) { ENS(h->bcpb, sB * h->nslab * w.geo.cpb_slab_stride * 8); w.cp_bslab = h->bcpb.as<double>(); }
   if (w.geo.cp_scratch_stride) { ENS(h->bcp, sB * m * w.geo.cp_scratch_stride * 8); w.cp_scratch = h->bcp.as<double>(); }
   if (w.geo.ws.slab_stride) { ENS(h->bcone, sB * w.geo.ws.slab_stride * 8); w.cone_scratch = h->bcone.as<double>(); }
   if (w.geo.glob.slab_stride) { ENS(h->bglob, sB * w.geo.glob.slab_stride * 8); w.glob_scratch = h->bglob.as<double>(); }
@@ -2353,6 +2404,69 @@ int omc_psd_project_batch(omc_instance* h, int B, int N, const double* M, double
       }
     }
   }
+  return 0;
+}
+
+// The column prox (block F of the ADMM iteration; the exact multipliers of the certificate in mode 1) on its own, through the launcher the solver
+// uses: an empty batch is staged for a workspace of the right size with the identity slot map (as omc_separation_batch does), the inputs are
+// written over it and omc_launch_colprox runs once.
+int omc_column_prox_batch(omc_instance* h, int B, int mode, int algo, const double* Y, const double* alpha_old, const double* rho_f,
+                          const double* s0, double* alpha, double* s, double* objcol, double* c0col, int* nfact) {
+  if (mode != 0 && mode != 1) return fail(OMC_ERR_ARGUMENT, "omc_column_prox_batch: mode must be 0 or 1");
+  if (algo < 0 || algo > 2) return fail(OMC_ERR_ARGUMENT, "omc_column_prox_batch: algo must be 0, 1 or 2");
+  if (!h) return fail(OMC_ERR_ARGUMENT, "omc_column_prox_batch: handle is NULL");
+  if (B <= 0) return fail(OMC_ERR_ARGUMENT, "omc_column_prox_batch: B must be positive");
+  if (!Y || !alpha) return fail(OMC_ERR_ARGUMENT, "omc_column_prox_batch: Y / alpha is NULL");
+  if (mode == 0 && (!rho_f || !s)) return fail(OMC_ERR_ARGUMENT, "omc_column_prox_batch: mode 0 needs rho_f and s");
+  if (mode == 1 && (!objcol || !c0col)) return fail(OMC_ERR_ARGUMENT, "omc_column_prox_batch: mode 1 needs objcol and c0col");
+  std::vector<int> Lz(B, 0);
+  const omc_relax_params keep = h->params;
+  omc_relax_params P = keep; P.slots = B; P.accel = 0;      // identity slot map; without acceleration the workspace has Yx
+  h->cp_force = algo;
+  int rc = omc_relax_stage(h, B, &P, OMC_CUT_LINEAR, Lz.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+  h->cp_force = 0; h->params = keep;
+  if (rc) return rc;
+  h->staged = false;
+  OmcWS w = h->ws;
+  w.rho_f_ratio = 1.0;      // rho_b carries the caller's rho_f itself
+  const size_t sB = (size_t)B, n = h->n, m = h->m, nnz = h->nnz;
+  hipStream_t st = h->stream;
+  ENS(h->bnfact, sB * m * sizeof(int));
+  w.cp_nfact = h->bnfact.as<int>();
+  HIPCHK(hipMemsetAsync(w.cp_nfact, 0xFF, sB * m * sizeof(int), st));      // -1: the kernel that ran the column does not count (k_colprox_pair, k_colprox_wide)
+  HIPCHK(hipMemsetAsync(w.done, 0, sB * sizeof(int), st));
+  HIPCHK(hipMemcpyAsync(mode == 0 ? w.Yx : w.Y, Y, sB * n * n * 8, hipMemcpyHostToDevice, st));
+  std::vector<double> hs;
+  if (mode == 0) {
+    HIPCHK(hipMemcpyAsync(w.rho_b, rho_f, sB * 8, hipMemcpyHostToDevice, st));
+    if (alpha_old) HIPCHK(hipMemcpyAsync(w.alpha, alpha_old, sB * nnz * 8, hipMemcpyHostToDevice, st));
+    else HIPCHK(hipMemsetAsync(w.alpha, 0, sB * nnz * 8, st));
+    if (s0) HIPCHK(hipMemcpyAsync(w.sval, s0, sB * m * 8, hipMemcpyHostToDevice, st));
+    else { hs.assign(sB * m, -1.0); HIPCHK(hipMemcpyAsync(w.sval, hs.data(), sB * m * 8, hipMemcpyHostToDevice, st)); }
+  } else {
+    hs.assign(sB, 1.0);      // unused by mode 1 beyond being finite
+    HIPCHK(hipMemcpyAsync(w.rho_b, hs.data(), sB * 8, hipMemcpyHostToDevice, st));
+  }
+  omc_launch_colprox(&w, mode, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(alpha, mode == 0 ? w.alpha : w.alphaX, sB * nnz * 8, hipMemcpyDeviceToHost, st));
+  if (mode == 0) HIPCHK(hipMemcpyAsync(s, w.sval, sB * m * 8, hipMemcpyDeviceToHost, st));
+  else {
+    HIPCHK(hipMemcpyAsync(objcol, w.objcol, sB * m * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c0col, w.c0col, sB * m * 8, hipMemcpyDeviceToHost, st));
+  }
+  if (nfact) HIPCHK(hipMemcpyAsync(nfact, w.cp_nfact, sB * m * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int omc_colprox_plan(int n, int cmax, int block_min, int64_t* out) {
+  if (!out) return fail(OMC_ERR_ARGUMENT, "out is NULL");
+  if (n <= 0 || cmax <= 0 || cmax > n) return fail(OMC_ERR_ARGUMENT, "omc_colprox_plan: need 0 < cmax <= n");
+  long long o[5];
+  cp_block_plan(cmax, block_min, o);
+  for (int q = 0; q < 5; ++q) out[q] = o[q];
   return 0;
 }
 

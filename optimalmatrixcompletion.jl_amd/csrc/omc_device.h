@@ -130,6 +130,12 @@ struct OmcWS {
   // most 32 observed rows each; the other columns (cp_solo, cp_nsolo of them) keep the one-column-per-wave kernel
   int cp_pair; int cp_nsolo; const int* cp_solo;
   int cp_nwide; const int* cp_wide;      // columns outside the pairs with at most 64 observed rows: k_colprox_wide (one column per wave, same algorithm)
+  // k_colprox_block (omc_colprox_block.hip): one workgroup per column for the columns of at least OMC_COLPROX_BLOCK_MIN observed rows, in both
+  // modes.  cp_block: those whose tiles fit the LDS; cp_slab: the longer ones (slab cp_bslab, geo.cpb_slab_stride doubles per (slot, list
+  // position)); cp_isblock[j] = 1: column j is on one of the two lists and k_colprox leaves it alone.  cp_nfact (B*m, or NULL): factorizations
+  // of the last call per column, written by k_colprox and k_colprox_block (omc_column_prox_batch)
+  int cp_nrest;      // non-empty columns that are not block columns (0: a mode-0 launch without the pair kernel has nothing left for k_colprox)
+  int cp_nblock, cp_nslab; const int *cp_block, *cp_slab; const unsigned char* cp_isblock; double* cp_bslab; int* cp_nfact;
   double* Yx;                // B*n*n: 2 Y - Yp, written by k_global (and k_setup) for the column gathers of k_colprox* (one load per entry instead of two); NULL with acceleration or Shor mode
   int cone_512;              // diagnostics (OMC_CONE_512): the 512-thread form of the L2-resident eigen-kernel at orders 193..256
   int cp_series;             // Neumann-series order of k_colprox_pair's finish (6; 3 = the second-order finish of colprox_reg)
@@ -178,6 +184,8 @@ void omc_query_residency(const OmcWS* w, int* out /* OMC_RES_N */);      /* work
 void omc_colprox_sweep_residency(int* pair, int* wide);                /* omc_colprox.hip: k_colprox_pair, k_colprox_wide as omc_launch_colprox_sweep launches them */
 void omc_launch_gram_XXt(const OmcWS* w, const double* X, int B, hipStream_t s);
 void omc_launch_colprox_sweep(const OmcWS* w, hipStream_t s);      /* omc_colprox.hip */
+void omc_launch_colprox_block(const OmcWS* w, int mode, hipStream_t s);      /* omc_colprox_block.hip: nothing to launch when both lists are empty */
+int omc_colprox_block_set_lds(void);                                       /* omc_colprox_block.hip: dynamic LDS limit of its kernels, once per process */
 #ifdef __cplusplus
 }
 #endif

@@ -320,6 +320,7 @@ __device__ __forceinline__ void colprox_body(const OmcWS& w, int mode, int b, in
       solve2(yr, zr, false);
     }
     if (lane == 0) w.sval[(size_t)b * w.m + j] = s;
+    if (lane == 0 && w.cp_nfact) w.cp_nfact[(size_t)b * w.m + j] = nfact_;
     if (lane == 0) DIAG_ADD(1, b, nfact_);
     double* lamD = w.lamD + ((size_t)b * w.m + j) * n;      // dense copy (zeros off the support) for the output-stationary Lambda Lambda'
     if (regpath) { if (lane < c) { alpha[lane] = yr; lamD[idx[lane]] = yr; } }
@@ -332,7 +333,7 @@ __device__ __forceinline__ void colprox_body(const OmcWS& w, int mode, int b, in
     WAVE_SYNC();
     bool ok = wave_cholesky(Lm, c, lane);
     if (!ok) {  // Y not PSD enough on this block: report +inf objective contribution
-      if (lane == 0) { w.objcol[(size_t)b * w.m + j] = 1e300; w.c0col[(size_t)b * w.m + j] = 0.0; }
+      if (lane == 0) { w.objcol[(size_t)b * w.m + j] = 1e300; w.c0col[(size_t)b * w.m + j] = 0.0; if (w.cp_nfact) w.cp_nfact[(size_t)b * w.m + j] = 1; }
       return;
     }
     double yr = 0.0, zr = 0.0;
@@ -342,7 +343,7 @@ __device__ __forceinline__ void colprox_body(const OmcWS& w, int mode, int b, in
     if (regpath) { aa = a_reg * yr; al2 = yr * yr; if (lane < c) { alpha[lane] = yr; if (lamX) lamX[idx[lane]] = yr; } }
     else for (int p = lane; p < c; p += WAVE) { aa += va[p] * vy[p]; al2 += vy[p] * vy[p]; alpha[p] = vy[p]; if (lamX) lamX[idx[p]] = vy[p]; }
     aa = wave_sum(aa); al2 = wave_sum(al2);
-    if (lane == 0) { w.objcol[(size_t)b * w.m + j] = 0.5 * aa; w.c0col[(size_t)b * w.m + j] = aa - 0.5 * al2; }   // summed in a fixed order by k_check_build
+    if (lane == 0) { w.objcol[(size_t)b * w.m + j] = 0.5 * aa; w.c0col[(size_t)b * w.m + j] = aa - 0.5 * al2; if (w.cp_nfact) w.cp_nfact[(size_t)b * w.m + j] = 1; }   // summed in a fixed order by k_check_build
   }
 }
 
@@ -476,19 +477,20 @@ __device__ __forceinline__ void colprox_reg(const OmcWS& w, int mode, int b, int
       yr = wave_ldl_solve_reg(Lm, pinv, c, a_reg, lane);
     }
     if (lane == 0) w.sval[(size_t)b * w.m + j] = s;
+    if (lane == 0 && w.cp_nfact) w.cp_nfact[(size_t)b * w.m + j] = nfact_;
     if (lane == 0) DIAG_ADD(1, b, nfact_);
     double* lamD = w.lamD + ((size_t)b * w.m + j) * n;      // dense copy (zeros off the support) for the output-stationary Lambda Lambda'
     if (lane < c) { alpha[lane] = yr; lamD[my] = yr; }
     WSTAMP(27);
   } else {
     if (!wave_ldl(Lm, pinv, c, lane)) {  // Y not PSD enough on this block: report +inf objective contribution
-      if (lane == 0) { w.objcol[(size_t)b * w.m + j] = 1e300; w.c0col[(size_t)b * w.m + j] = 0.0; }
+      if (lane == 0) { w.objcol[(size_t)b * w.m + j] = 1e300; w.c0col[(size_t)b * w.m + j] = 0.0; if (w.cp_nfact) w.cp_nfact[(size_t)b * w.m + j] = 1; }
       return;
     }
     const double yr = wave_ldl_solve_reg(Lm, pinv, c, a_reg, lane);
     if (lane < c) { alpha[lane] = yr; if (w.lamDX) w.lamDX[((size_t)b * w.m + j) * n + my] = yr; }
     const double aa = wave_sum(a_reg * yr), al2 = wave_sum(yr * yr);
-    if (lane == 0) { w.objcol[(size_t)b * w.m + j] = 0.5 * aa; w.c0col[(size_t)b * w.m + j] = aa - 0.5 * al2; }   // summed in a fixed order by k_check_build
+    if (lane == 0) { w.objcol[(size_t)b * w.m + j] = 0.5 * aa; w.c0col[(size_t)b * w.m + j] = aa - 0.5 * al2; if (w.cp_nfact) w.cp_nfact[(size_t)b * w.m + j] = 1; }   // summed in a fixed order by k_check_build
   }
 }
 
@@ -502,6 +504,7 @@ __global__ void __launch_bounds__(256) k_colprox(OmcWS w, int mode) {
   const int j = (mode == 0 && w.cp_pair) ? w.cp_solo[jj] : jj;
   const int b = slot_of(w, bl);
   if (w.done[b]) return;
+  if (w.cp_isblock && w.cp_isblock[j]) return;      // k_colprox_block's column (omc_colprox_block.hip)
   const int off = w.col_ptr[j], c = w.col_ptr[j + 1] - off;
   if (c == 0) { if (mode == 1 && lane == 0) { w.objcol[(size_t)b * w.m + j] = 0.0; w.c0col[(size_t)b * w.m + j] = 0.0; } return; }
   DIAG_T0();
@@ -2908,6 +2911,8 @@ void omc_launch_setup_gram(const OmcWS* w, const int* jobs, int njobs, int nnode
 }
 void omc_launch_colprox(const OmcWS* w, int mode, hipStream_t s) {
   const int wpb = 4;
+  omc_launch_colprox_block(w, mode, s);      // omc_colprox_block.hip: the columns of w.cp_block / w.cp_slab, one workgroup each (k_colprox returns at once for them)
+  if (mode == 0 && !w->cp_pair && w->cp_nrest == 0) return;      // every non-empty column is a block column
   if (mode == 0 && w->cp_pair) {
     omc_launch_colprox_sweep(w, s);      // omc_colprox.hip: k_colprox_pair (two columns per wave) and k_colprox_wide (one column, up to 64 rows)
     if (w->cp_nsolo == 0) return;
@@ -2987,6 +2992,7 @@ int omc_set_max_lds(void) {
   if (e2 != hipSuccess) return 2000 + (int)e2;
   if (e3 != hipSuccess) return 3000 + (int)e3;
   if (e4 != hipSuccess) return 4000 + (int)e4;
+  { const int e5 = omc_colprox_block_set_lds(); if (e5) return 6000 + e5; }
   return 0;
 }
 // Workgroups per CU that the HIP runtime grants each iteration kernel at the block size and dynamic LDS the launchers above use for this

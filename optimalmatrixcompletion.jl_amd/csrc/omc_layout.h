@@ -99,6 +99,32 @@ struct CpRegLayout { int Lm, vo, pinv, sidx, doubles; };
 OMC_HD CpRegLayout cp_reg_layout(int c, int keepB) { const int tri = (c * (c + 1)) >> 1, vo = (keepB ? 2 : 1) * tri; return {keepB ? tri : 0, vo, vo + c, vo + 2 * c, vo + 4 * c + 8}; }
 struct CpBodyLayout { size_t Lm, va, vy, vz, vo, doubles; };
 OMC_HD CpBodyLayout cp_body_layout(int c) { const size_t tri = (size_t)c * (c + 1) / 2, va = 2 * tri; return {tri, va, va + c, va + 2 * c, va + 3 * c, va + 4 * c + 8}; }
+// ---- k_colprox_block (omc_colprox_block.hip), one workgroup per column of c observed rows.  The matrix is a blocked lower triangle of
+// nb (nb + 1) / 2 tiles of 16 x 16 doubles, nb = ceil(c / 16); tile (I, J), J <= I, is number I (I + 1) / 2 + J and holds its entry (r, q) at
+// q * 16 + r.  LDS variant: the tiles, then the vectors (a, y, z, w, previous alpha: 16 nb doubles each; row indices: 16 nb ints).  Slab
+// variant: the tiles live in a per-(slot, column) global slab (slab doubles), the LDS block holds the current panel (nb - 1 tiles) and the
+// vectors.  The kernel's static LDS (inverse of the diagonal tile, its factor, reduction words) is CPB_STATIC_LDS bytes at most.
+#define CPB_TILE 256
+#define CPB_STATIC_LDS 4352
+struct CpBlockLayout { int nb, ntiles; size_t panel, va, vy, vz, vw, vo, sidx, doubles, slab; };
+OMC_HD int cpb_tile(int I, int J) { return ((I * (I + 1)) >> 1) + J; }
+OMC_HD CpBlockLayout cp_block_layout(int c, int lds) {
+  const int nb = c > 0 ? (c + 15) >> 4 : 1, nt = (nb * (nb + 1)) >> 1;
+  const size_t cp = (size_t)16 * nb, va = (size_t)CPB_TILE * (lds ? nt : (nb > 1 ? nb - 1 : 1));
+  return {nb, nt, 0, va, va + cp, va + 2 * cp, va + 3 * cp, va + 4 * cp, va + 5 * cp, va + 5 * cp + cp / 2, lds ? 0 : (size_t)CPB_TILE * nt};
+}
+OMC_HD int cp_block_fits(int c, int lds) { return cp_block_layout(c, lds).doubles * 8 <= (size_t)OMC_MAX_DYN_LDS; }
+OMC_HD int cp_block_lds_cmax() { int nb = 1; while (cp_block_fits(16 * (nb + 1), 1)) ++nb; return 16 * nb; }      // longest column whose tiles fit the LDS (176)
+OMC_HD int cp_block_cmax() { int nb = 1; while (cp_block_fits(16 * (nb + 1), 0)) ++nb; return 16 * nb; }          // longest column the slab variant takes (its panel and vectors fit)
+// plan for the columns of at least block_min rows among columns of at most cmax: out = {longest LDS column, dynamic LDS bytes of the launch
+// that holds a column of cmax rows, slab stride in doubles (0: LDS), workgroups per CU by LDS (160 KiB per CU), 1 if a column of cmax rows
+// goes to the block kernel}
+OMC_HD void cp_block_plan(int cmax, int block_min, long long* out) {
+  const int ldsc = cp_block_lds_cmax(), on = cmax >= block_min && cmax >= 1 && cmax <= cp_block_cmax();
+  const CpBlockLayout L = cp_block_layout(cmax, cmax <= ldsc);
+  out[0] = ldsc; out[1] = on ? (long long)(L.doubles * 8) : 0; out[2] = on ? (long long)L.slab : 0;
+  out[3] = on ? (long long)((160 * 1024) / (L.doubles * 8 + CPB_STATIC_LDS)) : 0; out[4] = on;
+}
 // ---- altmin kernels (omc_altmin.hip); 8 doubles of margin ---------------------------------------------------------------------------------
 struct Altmin1Layout { size_t v, h, g, u0, cvec, mu, bytes; };       // k_altmin (rank 1): u (n), v (m), h, g, u0 (n each), cvec, mu (Rmax each)
 OMC_HD Altmin1Layout altmin1_layout(int n, int m, int Rmax) { const size_t h = (size_t)n + m, cvec = h + 3 * n; return {(size_t)n, h, h + n, h + 2 * n, cvec, cvec + Rmax, (cvec + 2 * Rmax + 8) * 8}; }
@@ -130,6 +156,7 @@ OMC_HD KernelPlan altmin_plan(int n, int m, int k, int Rmax, int nolds) {
 struct OmcGeom {
   KernelPlan cone, ws, glob, small;       // cone and ws share one slab (cone_scratch) and its stride
   int ws_lpp, ws_rpl2, ws_ld;             // k_cone_ws: lanes per pair (0: order beyond the kernel), rows per lane / 2, leading dimension of G
+  size_t cpb_lds_bytes, cpb_slab_lds_bytes, cpb_slab_stride;      // k_colprox_block: dynamic LDS of its two launches, slab doubles per (slot, slab column); set by geom_set_cpblock
   int cp_lds_c, cp_lds_doubles, cp_keepB; // k_colprox: columns up to cp_lds_c rows in LDS (cp_lds_doubles per wave); cp_keepB = 0: dense columns, B is gathered again instead of kept
   size_t cp_scratch_stride, sub_lds;      // k_colprox slab per wave (B*m waves), 0 when every column fits the LDS ; dynamic LDS of k_cone_sub
   int mw; MwLayout mwl;                   // 1: omc_launch_cone_ws takes the multi-workgroup kernels (their slab layout; it shares cone_scratch and its stride)
@@ -139,6 +166,12 @@ OMC_HD void geom_set_mw(OmcGeom& g, int n) {
   g.mw = 1; g.mwl = mw_layout(n);
   size_t st = g.mwl.bytes / 8 + 8; if (st < g.ws.slab_stride) st = g.ws.slab_stride;
   g.cone.slab_stride = g.ws.slab_stride = (st + 3) & ~(size_t)3;
+}
+// k_colprox_block: cl, cs = longest column of its LDS list and of its slab list (0: the list is empty)
+OMC_HD void geom_set_cpblock(OmcGeom& g, int cl, int cs) {
+  g.cpb_lds_bytes = cl > 0 ? cp_block_layout(cl, 1).doubles * 8 : 0;
+  g.cpb_slab_lds_bytes = cs > 0 ? cp_block_layout(cs, 0).doubles * 8 : 0;
+  g.cpb_slab_stride = cs > 0 ? cp_block_layout(cs, 0).slab : 0;
 }
 // n, np16: order of the cone matrix and its padding to 16 (the Shor view of the big cone passes n + m); cmax: longest column;
 // cone_multi_min: orders from this value on (and never below MW_MIN_ORDER) take the multi-workgroup eigen-kernels
@@ -157,6 +190,7 @@ OMC_HD OmcGeom omc_plan_geometry(int n, int np16, int k, int rmax, int Rmax, int
   g.cp_lds_doubles = cp_reg_layout(g.cp_lds_c, g.cp_keepB).doubles;
   g.cp_scratch_stride = cmax > g.cp_lds_c ? cp_body_layout(cmax).doubles : 0;
   g.mw = 0; g.mwl = MwLayout{};
+  g.cpb_lds_bytes = g.cpb_slab_lds_bytes = g.cpb_slab_stride = 0;
   if (n >= MW_MIN_ORDER && !wg.use_lds && n >= cone_multi_min && n <= MW_MAX_ORDER) geom_set_mw(g, n);
   return g;
 }

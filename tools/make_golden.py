@@ -67,8 +67,25 @@ def make_shor_golden():
     print("shor fixture:", {k_: v.shape for k_, v in rec.items()})
 
 
+def make_colprox_block_golden():
+    """The oracle's certified root of the 130 x 132 instance of tests/test_colprox_block.py (minutes on a CPU: recorded, not recomputed per run)."""
+    import json
+    n, m, frac, seed = 130, 132, 0.97, 5
+    rng = np.random.default_rng(seed)
+    mask = rng.random((n, m)) < frac
+    mask[0, :] = True; mask[:, 0] = True
+    A = (rng.standard_normal((n, 1)) @ rng.standard_normal((1, m)) + 0.01 * rng.standard_normal((n, m))) * mask
+    ref = orc.sdp_relaxation(orc.Instance(A, mask, 80.0, 1), [], "linear", params=orc.RelaxParams(rho_scale=4.0))
+    rec = dict(n=n, m=m, frac=frac, seed=seed, gamma=80.0, k=1, rho_scale=4.0, sum_A=float(A.sum()), nnz=int(mask.sum()),
+               objective=float(ref["objective"]), dual_bound=float(ref["dual_bound"]), termination_status=int(ref["termination_status"]))
+    json.dump(rec, open(os.path.join(ROOT, "tests", "golden", "colprox_block_root_130x132.json"), "w"), indent=1)
+    print("colprox block fixture:", rec)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "shor":
+    if len(sys.argv) > 1 and sys.argv[1] == "colprox":
+        make_colprox_block_golden()
+    elif len(sys.argv) > 1 and sys.argv[1] == "shor":
         make_shor_golden()
     else:
         main(); make_shor_golden()
