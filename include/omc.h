@@ -350,6 +350,16 @@ int omc_last_cone_multi_stats(omc_instance* h, int64_t* out);
  * one call since the last check, 0 when that interval had no call.  What the last interval needed + 2, at most the full bound (30); the
  * full bound after an interval without a call (the next call starts from a stale basis). */
 int omc_cone_multi_budget(int interval_max);
+/* What omc_relax_solve does with the finished slots at a certificate check (host arithmetic only, no device call, no handle).
+ * nlive: slots whose node keeps running; nfin: finished slots not yet harvested; pending: 1 when nodes wait for a slot; check_index: the
+ * number of this check (from 1); async_min_live: live slots from which the harvest kernels run beside the next interval (<= 0: never).
+ * NONE: the finished slots stay parked.  SYNC: harvest, wait, book and refill before the next iteration.  ASYNC: enqueue the harvest kernels
+ * and go on; the bookkeeping and the refill happen at the next check.  With pending nodes a harvest falls on every third check, on every
+ * check when fewer than 256 slots are live; without, on every twelfth; always when nothing is live. */
+#define OMC_HARVEST_NONE 0
+#define OMC_HARVEST_SYNC 1
+#define OMC_HARVEST_ASYNC 2
+int omc_harvest_plan(int nlive, int nfin, int pending, int check_index, int async_min_live);
 
 /* ---- Shor minors ------------------------------------------------------------------------------------------
  * generate_rank1_matrix_completion_Shor_constraints_indexes (OMC.jl:2545-2612): the 2 x 2 minors (i1 < i2, j1 < j2) whose
@@ -460,7 +470,8 @@ int omc_last_kernel_stats(omc_instance* h, int64_t* launches /*NCLASS*/, double*
  * piece ran.  A check: the wait for its kernels and the done flags, the bookkeeping up to the decision what to harvest, the new slot list, the
  * drain of the timing events (after the next iteration has been enqueued).  A harvest: the first flags upload, enqueueing its kernels, the wait
  * for them with the second upload, the pool / queue bookkeeping, enqueueing the setup.  The last two are whole events: from the end of a check's
- * wait to the next iteration's enqueue (without / with a harvest).  No counterpart in the reference. */
+ * wait to the next iteration's enqueue (without / with a harvest).  After an asynchronous harvest (omc_harvest_plan) harvest_wait has no event
+ * and harvest_book / setup_enqueue are stamped at the next check.  The last two entries are counts only (ms 0).  No counterpart in the reference. */
 #define OMC_HOST_CHECK_WAIT 0
 #define OMC_HOST_CHECK_SCAN 1
 #define OMC_HOST_LIST 2
@@ -472,7 +483,9 @@ int omc_last_kernel_stats(omc_instance* h, int64_t* launches /*NCLASS*/, double*
 #define OMC_HOST_SETUP_ENQUEUE 8
 #define OMC_HOST_CHECK_TOTAL 9
 #define OMC_HOST_HARVEST_TOTAL 10
-#define OMC_HOST_NPHASE 11
+#define OMC_HOST_ASYNC_HARVESTS 11   /* count only: harvests whose kernels ran beside the next interval (booked and refilled at the next check) */
+#define OMC_HOST_QUIET_INTERVALS 12  /* count only: check intervals whose iterations enqueued the full eigen-kernel once instead of twice */
+#define OMC_HOST_NPHASE 13
 int omc_last_host_phases(omc_instance* h, double* ms /*NPHASE*/, int64_t* count /*NPHASE*/);
 
 #ifdef __cplusplus

@@ -33,7 +33,7 @@ KERNEL_CLASSES = ["colprox", "cone", "global", "check", "setup", "small", "accel
                   "shor_bigcone", "shor_minors", "shor_cols"]
 # omc_last_host_phases, in the order of OMC_HOST_* (include/omc.h)
 HOST_PHASES = ["check_wait", "check_scan", "list", "event_drain", "harvest_flags", "harvest_enqueue", "harvest_wait", "harvest_book",
-               "setup_enqueue", "check_total", "harvest_total"]
+               "setup_enqueue", "check_total", "harvest_total", "async_harvests", "quiet_intervals"]      # the last two are counts only
 # order of omc_kernel_residency's output (OMC_RES_* in include/omc.h)
 RESIDENCY_KERNELS = ["k_cone_sub<0>", "k_cone_sub<1>", "k_cone_sub<2>", "k_global", "k_small", "k_colprox_pair", "k_colprox_wide", "k_colprox",
                      "k_cone_ws", "k_cone"]
@@ -437,7 +437,8 @@ class Engine:
         return {KERNEL_CLASSES[i]: dict(launches=int(la[i]), ms=float(ms[i]), units=int(un[i])) for i in range(nc)}
 
     def host_phases(self):
-        """Host time of the last solve between its iterations, by piece (omc_last_host_phases): {piece: dict(ms, count)}."""
+        """Host time of the last solve between its iterations, by piece (omc_last_host_phases): {piece: dict(ms, count)}; "async_harvests" and
+        "quiet_intervals" are counts (harvests run beside the next interval; intervals with one launch of the full eigen-kernel per iteration)."""
         if not hasattr(self._lib, "omc_last_host_phases"):
             raise OmcError(-100, "this build of the library has no omc_last_host_phases")
         ms = np.zeros(len(HOST_PHASES)); cnt = np.zeros(len(HOST_PHASES), np.int64)

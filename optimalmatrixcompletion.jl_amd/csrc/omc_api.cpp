@@ -107,11 +107,14 @@ struct Tuning {
   int colprox_block_min = 65;      // OMC_COLPROX_BLOCK_MIN: columns with at least this many observed rows take k_colprox_block (one workgroup per column, blocked MFMA Cholesky); a value above every column length is the path without it
   int cone_multi_min = 1025;       // OMC_CONE_MULTI_MIN: cone orders from this value on (never below 145) take the multi-workgroup eigen-kernels; the default is where only the cold kernel existed
   int graph_max = 16;              // OMC_GRAPH_MAX: hipGraph replay for batches staged with at most this many nodes
+  int harvest_async = 1;           // OMC_HARVEST_ASYNC: 0 = every harvest is waited for, booked and refilled before the next iteration
+  int harvest_async_min_live = 256;   // OMC_HARVEST_ASYNC_MIN_LIVE: live slots from which a harvest runs beside the next interval (omc_harvest_plan)
   int shor_select_kb = 1048576;    // OMC_SHOR_SELECT_KB: violated-minor selection streams (no materialised keys) when 16 B per candidate exceed this many KiB; 0 = always materialise
   int streams = 4;                 // OMC_STREAMS: <= 1 serialises a solve on one stream
   int sub_debug = 0;               // OMC_SUB_DEBUG: diagnostics of k_cone_sub (3: histograms for omc_debug_stamps)
   int sub_qmax = 24;               // OMC_SUB_QMAX: step budget of k_cone_sub
   int timing_stride = 1;           // OMC_TIMING_STRIDE: event timing of every s-th iteration, 0 = none
+  int ws_quiet = 1;                // OMC_WS_QUIET: 0 = every iteration enqueues both phases of the full eigen-kernel, also in quiet intervals
 };
 struct Knob { const char* name; bool Tuning::*flag; int Tuning::*num; };
 static const Knob OMC_KNOBS[] = {
@@ -126,6 +129,8 @@ static const Knob OMC_KNOBS[] = {
   {"OMC_COLPROX_BLOCK_MIN", nullptr, &Tuning::colprox_block_min},
   {"OMC_CHECK_XS", nullptr, &Tuning::check_xs},              {"OMC_CONE_MULTI_MIN", nullptr, &Tuning::cone_multi_min},
   {"OMC_GRAPH_MAX", nullptr, &Tuning::graph_max},            {"OMC_SHOR_SELECT_KB", nullptr, &Tuning::shor_select_kb},
+  {"OMC_HARVEST_ASYNC", nullptr, &Tuning::harvest_async},    {"OMC_HARVEST_ASYNC_MIN_LIVE", nullptr, &Tuning::harvest_async_min_live},
+  {"OMC_WS_QUIET", nullptr, &Tuning::ws_quiet},
   {"OMC_STREAMS", nullptr, &Tuning::streams},
   {"OMC_SUB_DEBUG", nullptr, &Tuning::sub_debug},            {"OMC_SUB_QMAX", nullptr, &Tuning::sub_qmax},
   {"OMC_TIMING_STRIDE", nullptr, &Tuning::timing_stride},
@@ -799,7 +804,9 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
     HIPCHK(hipMemsetAsync(ai, 0, sB * 6 * sizeof(int), h->stream));
   }
   int* ip = h->bint.as<int>();
-  w.done = ip; w.status = ip + sB; w.iters = ip + 2 * sB; w.sweeps = ip + 3 * sB; w.stall = ip + 4 * sB; w.vvalid = ip + 5 * sB; w.nbump = ip + 6 * sB; w.lastbump = ip + 7 * sB; w.rowov = ip + 8 * sB;
+  w.rowov = ip; w.status = ip + sB; w.iters = ip + 2 * sB; w.sweeps = ip + 3 * sB; w.stall = ip + 4 * sB; w.vvalid = ip + 5 * sB; w.nbump = ip + 6 * sB; w.lastbump = ip + 7 * sB;
+  w.done = ip + 8 * sB; w.ws_need = w.ws_first ? ip + 9 * sB : nullptr;      // the word behind done[S]: one copy brings both back at a check
+  if (w.ws_need) HIPCHK(hipMemsetAsync(w.ws_need, 0, sizeof(int), h->stream));
   {
     ENS(h->bslotint, sB * 3 * sizeof(int));
     int* si = h->bslotint.as<int>();
@@ -1009,6 +1016,23 @@ int omc_relax_set_warm(omc_instance* h, int B, const int* load_from, const int* 
 }
 
 static constexpr int REFILL_EVERY = 3;      // finished slots are harvested and refilled at every third check (see omc_relax_solve)
+static constexpr int REFILL_AT_ONCE_LIVE = 256;      // fewer live slots than this no longer fill the chip: harvest and refill at every check
+
+// Harvest and refill every REFILL_EVERY-th check only (or when nothing is left running): a refilled slot spends its first dozen
+// iterations in the full eigendecomposition, the straggler of every launch it is part of, and each harvest is 1 - 3 ms of few-workgroup
+// kernels on the main stream -- batching them halves the launches that carry young slots.  A finished slot waits (done = 1, skipped
+// by every kernel and left out of the slot list) for at most REFILL_EVERY - 1 check intervals.
+// With pending nodes: every REFILL_EVERY-th check, at once when the live slots no longer fill the chip; without: the finished slots can
+// wait longer (nothing to hand them), until nothing runs any more.
+// Nothing a live slot reads is written by the harvest kernels, so with enough live slots to fill the chip they run beside the next interval
+// (ASYNC) and the host books and refills at the next check; below that, refilling at once is worth more than the stall.
+int omc_harvest_plan(int nlive, int nfin, int pending, int check_index, int async_min_live) {
+  if (nfin <= 0) return OMC_HARVEST_NONE;
+  if (nlive <= 0) return OMC_HARVEST_SYNC;
+  const bool now = pending ? (check_index % REFILL_EVERY == 0 || nlive < REFILL_AT_ONCE_LIVE) : (check_index % (4 * REFILL_EVERY) == 0);
+  if (!now) return OMC_HARVEST_NONE;
+  return (async_min_live > 0 && nlive >= async_min_live) ? OMC_HARVEST_ASYNC : OMC_HARVEST_SYNC;
+}
 
 int omc_relax_solve(omc_instance* h) {
   if (!h || !h->staged) return fail(OMC_ERR_ARGUMENT, "omc_relax_solve: nothing staged");
@@ -1035,7 +1059,7 @@ int omc_relax_solve(omc_instance* h) {
   // Page-locked images (see omc_instance): an upload returns at once, and an image is rewritten only after the copy that last read it has
   // completed (its event; two images alternate, so that wait is over long before it is asked for)
   for (int q = 0; q < 2; ++q) { int rc = h->pin_flags[q].ensure(sizeof(int) * 3 * (size_t)S); if (rc) return rc; rc = h->pin_list[q].ensure(sizeof(int) * (size_t)S); if (rc) return rc; }
-  { int rc = h->pin_done.ensure(sizeof(int) * (size_t)S); if (rc) return rc; rc = h->pin_jobs.ensure(sizeof(int) * 2 * (size_t)S); if (rc) return rc; rc = h->bgramjobs.ensure(sizeof(int) * 2 * (size_t)S); if (rc) return rc; }
+  { int rc = h->pin_done.ensure(sizeof(int) * ((size_t)S + 1)); if (rc) return rc; rc = h->pin_jobs.ensure(sizeof(int) * 2 * (size_t)S); if (rc) return rc; rc = h->bgramjobs.ensure(sizeof(int) * 2 * (size_t)S); if (rc) return rc; }
   for (int q = 0; q < 4; ++q) { if (!h->ev_up[q]) HIPCHK(hipEventCreateWithFlags(&h->ev_up[q], hipEventDisableTiming)); h->ev_up_rec[q] = false; }
   if (!h->ev_gram) HIPCHK(hipEventCreateWithFlags(&h->ev_gram, hipEventDisableTiming));
   h->ev_gram_rec = false;
@@ -1183,8 +1207,15 @@ int omc_relax_solve(omc_instance* h) {
     }
     return 0;
   };
-  const bool split = multi && !tun.no_ws_split && w.sub_enable && w.geo.ws_lpp && w.ws_first;
+  const bool split_solve = multi && !tun.no_ws_split && w.sub_enable && w.geo.ws_lpp && w.ws_first;
+  // Quiet intervals: with warm starts the full kernel has nothing to do for whole intervals (w.ws_need stayed 0), and its two launches are then
+  // two empty links in the latency chain of an iteration that is not saturated.  An interval after a check that found the word 0 and set no
+  // slot up enqueues the unsplit form -- one launch behind k_cone_sub, which also serves a call that fails inside the interval (serially, for
+  // that iteration; the word is then set and the next interval is split again).  The two forms are bit-identical.  A captured graph keeps
+  // the split it was captured with.
+  bool quiet = false;
   auto body = [&](const OmcWS& wg, bool timed, bool with_aa, bool capturing) -> int {
+    const bool split = split_solve && (capturing || !quiet);
     hipEvent_t* const ev = capturing ? h->gevc : h->gev;
     if (multi) {
       HIPCHK(hipEventRecord(ev[0], sm));
@@ -1253,10 +1284,39 @@ int omc_relax_solve(omc_instance* h) {
     TIMED(OMC_KERNEL_SETUP, ninit2, omc_launch_setup(&w, s));
     rc = gram_join(); if (rc) return rc;
     mw_budget[0] = mw_budget[1] = MAX_SWEEPS;
+    quiet = false;
     recount();
     rc = push_list(); if (rc) return rc;
     wait_main = true;
     return 0;
+  };
+  // An asynchronous harvest (omc_harvest_plan): its slots stay parked with their node until the next check books and refills them
+  std::vector<char> inflight(S, 0); int npend = 0;
+  bool ev_main_set = false;      // ev_main has been recorded for the next iteration already (ahead of the harvest kernels)
+  auto enqueue_harvest = [&](int nslots) {
+    TIMED(OMC_KERNEL_HARVEST, nslots, {
+      if (w.save_to) omc_launch_state_save(&w, s);                              // warm-start pool: before the recovery overwrites the iterate U = Q Vt
+      if (shor) omc_shor_launch_state_save(&sw, s);                             // its Shor extension (no-op without indices)
+      omc_launch_small(&w, SMALL_RECOVER, s);   // a U with U U' <= Y and the same Q'U
+      if (w.sep_done) omc_launch_sep_sub(&w, s);                                // separation vector from the tracked block where there is one
+      omc_launch_cone(&w, CONE_SEP, s);           // separation vector (OMC.jl:2466-2477)
+      omc_launch_harvest(&w, s);
+      if (shor) omc_shor_launch_harvest(&sw, s);
+    });
+  };
+  // the nodes of harvested_ids, once the stream has been synchronised behind their harvest kernels: the entries they saved to hold their state
+  // from here on, and their results can be fetched
+  auto book_harvested = [&]() {
+    if (w.save_to) {
+      std::lock_guard<std::mutex> lk(h->sig_mu);
+      for (int id : harvested_ids) {
+        const int sv = (size_t)id < h->save_host.size() ? h->save_host[id] : -1;
+        if (sv < 0 || (size_t)sv >= h->pool_sig.size()) continue;
+        if (shor) { h->pool_sig[sv] = h->node_sig[id]; ++h->shor_warm_stats[3]; }
+        else { h->pool_sig[sv] = omc_instance::PoolSig{}; h->pool_sig[sv].kind = 1; }
+      }
+    }
+    std::lock_guard<std::mutex> lk(h->done_mu); h->done_q.insert(h->done_q.end(), harvested_ids.begin(), harvested_ids.end());
   };
   for (;;) {
     if (nactive == 0) {
@@ -1275,7 +1335,8 @@ int omc_relax_solve(omc_instance* h) {
     }
     ++it;
     const bool is_check = (it % check == 0);
-    if (multi && wait_main) HIPCHK(hipEventRecord(h->ev_main, s));
+    if (multi && wait_main && !ev_main_set) HIPCHK(hipEventRecord(h->ev_main, s));
+    ev_main_set = false;
     // per-kernel HIP-event timing brackets every launch of a sampled iteration (two event records per kernel: ~25 us of queue bubbles per
     // iteration at small batches); OMC_TIMING_STRIDE=s samples every s-th iteration (averages per launch are over the sampled launches), 0 = none
     const bool sampled = tun.timing_stride > 0 && (it % tun.timing_stride) == 0;
@@ -1303,6 +1364,7 @@ int omc_relax_solve(omc_instance* h) {
         HIPCHK(hipGraphLaunch(gexec[q], sm));
         h->launches[OMC_KERNEL_GLOBAL] += 1; h->units[OMC_KERNEL_GLOBAL] += gact;
       } else {
+        if (quiet && split_solve && (it - 1) % check == 0) h->host_cnt[OMC_HOST_QUIET_INTERVALS] += 1;
         int rc = body(wg, sampled, !is_check && w.accel, false); if (rc) return rc;
       }
       if (multi && is_check) { HIPCHK(hipEventRecord(h->gev[3], sm)); HIPCHK(hipStreamWaitEvent(s, h->gev[3], 0)); }
@@ -1335,9 +1397,13 @@ int omc_relax_solve(omc_instance* h) {
       if (w.accel) omc_launch_aa(&w, s);      // after the certificate (computed on an image of the map), skips finished slots
     });
     stamp_begin();
-    HIPCHK(hipMemcpyAsync(done, w.done, sizeof(int) * S, hipMemcpyDeviceToHost, s));
+    const bool track_quiet = split_solve && tun.ws_quiet && w.ws_need;
+    done[S] = 1;
+    HIPCHK(hipMemcpyAsync(done, w.done, sizeof(int) * ((size_t)S + (track_quiet ? 1 : 0)), hipMemcpyDeviceToHost, s));      // with w.ws_need behind the flags
+    if (track_quiet) HIPCHK(hipMemsetAsync(w.ws_need, 0, sizeof(int), s));      // ahead of everything the next interval runs
     HIPCHK(hipStreamSynchronize(s));
     stamp(OMC_HOST_CHECK_WAIT);
+    bool quiet_next = track_quiet && done[S] == 0;
     const auto t_check = t_last;
     { int rc = mw_collect(); if (rc) return rc; }
     // every timed launch of the interval has joined s (the side streams join sm before k_global, sm joins s at a check) and so has completed:
@@ -1358,11 +1424,31 @@ int omc_relax_solve(omc_instance* h) {
         int rc = close_unslotted(OMC_ST_SLOW); if (rc) return rc;
       }
     }
-    // harvest finished slots, hand them the next pending nodes
-    // Harvest and refill every REFILL_EVERY-th check only (or when nothing is left running): a refilled slot spends its first dozen
-    // iterations in the full eigendecomposition, the straggler of every launch it is part of, and each harvest is 1 - 3 ms of few-workgroup
-    // kernels on the main stream -- batching them halves the launches that carry young slots.  A finished slot waits (done = 1, skipped
-    // by every kernel and left out of the slot list) for at most REFILL_EVERY - 1 check intervals.
+    // an asynchronous harvest of the previous check: the wait above was also the wait for its kernels (s is in order), so its nodes are
+    // booked and its slots refilled now -- a node still starts at a check boundary, one interval later than after a synchronous harvest
+    int nrefilled = 0;
+    if (npend) {
+      harvested += npend; h->nodes_done.store(harvested);
+      std::fill(init2.begin(), init2.end(), 0); std::fill(fin2.begin(), fin2.end(), 0);
+      int rc = gram_jobs_free(); if (rc) return rc;
+      harvested_ids.clear();
+      for (int b = 0; b < S; ++b) {
+        if (!inflight[b]) continue;
+        inflight[b] = 0; parked[b] = 0;
+        harvested_ids.push_back(node_of[b]);
+        if (next < Btot && !timed_out) { jobs[2 * nrefilled] = b; jobs[2 * nrefilled + 1] = next; node_of[b] = next++; init2[b] = 1; done[b] = 0; ++nrefilled; }
+        else node_of[b] = -1;
+      }
+      npend = 0;
+      book_harvested();
+      stamp(OMC_HOST_HARVEST_BOOK);
+      rc = gram_launch(nrefilled); if (rc) return rc;
+      rc = push_flags(init2, fin2, false); if (rc) return rc;      // the new nodes and their init flags; the fin flags of the harvest are cleared
+      if (nrefilled) { if (shor) omc_shor_launch_setup(&sw, s); TIMED(OMC_KERNEL_SETUP, nrefilled, omc_launch_setup(&w, s)); mw_budget[0] = mw_budget[1] = MAX_SWEEPS; quiet_next = false; }
+      rc = gram_join(); if (rc) return rc;
+      stamp(OMC_HOST_SETUP_ENQUEUE);
+    }
+    // harvest finished slots, hand them the next pending nodes (when and how: omc_harvest_plan)
     std::fill(init.begin(), init.end(), 0); std::fill(fin.begin(), fin.end(), 0);
     int nfin = 0, nlive = 0, nnew = 0;
     for (int b = 0; b < S; ++b) {
@@ -1370,13 +1456,28 @@ int omc_relax_solve(omc_instance* h) {
       if (done[b]) { ++nfin; if (!parked[b]) { parked[b] = 1; ++nnew; } } else ++nlive;
     }
     ++check_index;
-    // with pending nodes: every REFILL_EVERY-th check, at once when the live slots no longer fill the chip; without: the finished slots can
-    // wait longer (nothing to hand them), until nothing runs any more
-    const bool harvest_now = nfin > 0 && (nlive == 0 || (next < Btot ? (check_index % REFILL_EVERY == 0 || nlive < 256) : (check_index % (4 * REFILL_EVERY) == 0)));
-    if (harvest_now) for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && done[b]) { fin[b] = 1; parked[b] = 0; }
-    if (!harvest_now) nfin = 0;
+    int plan = omc_harvest_plan(nlive, nfin, next < Btot ? 1 : 0, check_index, tun.harvest_async ? tun.harvest_async_min_live : 0);
+    // the synchronous path where the stall buys something or the end of the batch is near: one stream, the time limit, first_wins, and idle
+    // slots that pending nodes are about to take (refill_idle sets them up on the main stream, which the next iteration then waits for)
+    if (plan == OMC_HARVEST_ASYNC && (!multi || timed_out || P.first_wins || (next < Btot && nfin + nlive < S))) plan = OMC_HARVEST_SYNC;
+    if (plan == OMC_HARVEST_NONE) nfin = 0;
     stamp(OMC_HOST_CHECK_SCAN);
-    if (nfin) {
+    bool list_pushed = false;
+    if (plan == OMC_HARVEST_ASYNC) {
+      for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && done[b]) { fin[b] = 1; inflight[b] = 1; ++npend; }      // they stay parked: out of the slot list, done on the device
+      // the slot list and the event the next iteration waits for go ahead of the harvest kernels: nothing a live slot reads is written by them
+      recount();
+      int rc = push_list(); if (rc) return rc;
+      list_pushed = true;
+      stamp(OMC_HOST_LIST);
+      if (multi) { HIPCHK(hipEventRecord(h->ev_main, s)); ev_main_set = true; }
+      rc = push_flags(init, fin, false); if (rc) return rc;
+      stamp(OMC_HOST_HARVEST_FLAGS);
+      enqueue_harvest(npend);
+      stamp(OMC_HOST_HARVEST_ENQUEUE);
+      h->host_cnt[OMC_HOST_ASYNC_HARVESTS] += 1;
+    } else if (nfin) {
+      for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && done[b]) { fin[b] = 1; parked[b] = 0; }
       // which pending node goes to which finished slot is known now (ascending slots take ascending nodes, as the loop below hands them out)
       int rc = gram_jobs_free(); if (rc) return rc;
       int nj = 0;
@@ -1384,15 +1485,7 @@ int omc_relax_solve(omc_instance* h) {
       rc = gram_launch(nj); if (rc) return rc;
       rc = push_flags(init, fin, false); if (rc) return rc;
       stamp(OMC_HOST_HARVEST_FLAGS);
-      TIMED(OMC_KERNEL_HARVEST, nfin, {
-        if (w.save_to) omc_launch_state_save(&w, s);                              // warm-start pool: before the recovery overwrites the iterate U = Q Vt
-        if (shor) omc_shor_launch_state_save(&sw, s);                             // its Shor extension (no-op without indices)
-        omc_launch_small(&w, SMALL_RECOVER, s);   // a U with U U' <= Y and the same Q'U
-        if (w.sep_done) omc_launch_sep_sub(&w, s);                                // separation vector from the tracked block where there is one
-        omc_launch_cone(&w, CONE_SEP, s);           // separation vector (OMC.jl:2466-2477)
-        omc_launch_harvest(&w, s);
-        if (shor) omc_shor_launch_harvest(&sw, s);
-      });
+      enqueue_harvest(nfin);
       stamp(OMC_HOST_HARVEST_ENQUEUE);
       harvested += nfin; h->nodes_done.store(harvested);
       int ninit = 0;
@@ -1406,23 +1499,15 @@ int omc_relax_solve(omc_instance* h) {
       }
       rc = push_flags(init, fin, true); if (rc) return rc;      // synchronises the stream: the harvest kernels have written the per-node outputs
       stamp(OMC_HOST_HARVEST_WAIT);
-      if (w.save_to) {      // the entries these nodes saved to hold their state from here on (push_flags has synchronised the stream)
-        std::lock_guard<std::mutex> lk(h->sig_mu);
-        for (int id : harvested_ids) {
-          const int sv = (size_t)id < h->save_host.size() ? h->save_host[id] : -1;
-          if (sv < 0 || (size_t)sv >= h->pool_sig.size()) continue;
-          if (shor) { h->pool_sig[sv] = h->node_sig[id]; ++h->shor_warm_stats[3]; }
-          else { h->pool_sig[sv] = omc_instance::PoolSig{}; h->pool_sig[sv].kind = 1; }
-        }
-      }
-      { std::lock_guard<std::mutex> lk(h->done_mu); h->done_q.insert(h->done_q.end(), harvested_ids.begin(), harvested_ids.end()); }
+      book_harvested();
       stamp(OMC_HOST_HARVEST_BOOK);
-      if (ninit) { if (shor) omc_shor_launch_setup(&sw, s); TIMED(OMC_KERNEL_SETUP, ninit, omc_launch_setup(&w, s)); mw_budget[0] = mw_budget[1] = MAX_SWEEPS; }
+      if (ninit) { if (shor) omc_shor_launch_setup(&sw, s); TIMED(OMC_KERNEL_SETUP, ninit, omc_launch_setup(&w, s)); mw_budget[0] = mw_budget[1] = MAX_SWEEPS; quiet_next = false; }
       rc = gram_join(); if (rc) return rc;
       stamp(OMC_HOST_SETUP_ENQUEUE);
     }
+    quiet = quiet_next;      // refill_idle below takes it back when it sets slots up
     recount();
-    if (nfin || nnew) { int rc = push_list(); if (rc) return rc; stamp(OMC_HOST_LIST); }
+    if (!list_pushed && (nfin || nnew || nrefilled)) { int rc = push_list(); if (rc) return rc; stamp(OMC_HOST_LIST); }
     if (next < Btot && !timed_out && nactive < S) { int rc = refill_idle(); if (rc) return rc; }      // appended nodes for slots that had gone idle
     if (timed_out) { int rc = close_unslotted(OMC_ST_TIME); if (rc) return rc; }
     {
@@ -1457,7 +1542,7 @@ int omc_relax_solve(omc_instance* h) {
   h->last_solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   h->last_iters_total = it;
   if (tun.host_phases) {
-    static const char* const nm[OMC_HOST_NPHASE] = {"check_wait", "check_scan", "list", "event_drain", "harvest_flags", "harvest_enqueue", "harvest_wait", "harvest_book", "setup_enqueue", "check_total", "harvest_total"};
+    static const char* const nm[OMC_HOST_NPHASE] = {"check_wait", "check_scan", "list", "event_drain", "harvest_flags", "harvest_enqueue", "harvest_wait", "harvest_book", "setup_enqueue", "check_total", "harvest_total", "async_harvests", "quiet_intervals"};
     fprintf(stderr, "omc host phases (solve %.1f ms, %d iterations):", 1e3 * h->last_solve_seconds, it);
     for (int q = 0; q < OMC_HOST_NPHASE; ++q) fprintf(stderr, " %s %.3f ms / %lld", nm[q], h->host_ms[q], (long long)h->host_cnt[q]);
     fprintf(stderr, "\n");
@@ -1998,7 +2083,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   OmcWS& wb = h->wbig;
   wb = w;
   wb.n = N; wb.np16 = NPb; wb.Mbuf = sh.MbufB; wb.Vrow = sh.VrowB; wb.vvalid = sh.vvalidB; wb.fro2 = sh.fro2B; wb.W1 = sh.P0;
-  wb.sub_enable = 0; wb.cert_enable = 0; wb.ws_mode = 0; wb.clip_hi = 1e300; wb.sub_debug = 0; wb.ws_first = nullptr; wb.ws_phase = 0;
+  wb.sub_enable = 0; wb.cert_enable = 0; wb.ws_mode = 0; wb.clip_hi = 1e300; wb.sub_debug = 0; wb.ws_first = nullptr; wb.ws_need = nullptr; wb.ws_phase = 0;
   // the view's own geometry (only the eigen-kernels are launched through it)
   wb.geo = omc_plan_geometry(N, NPb, wb.k, wb.rmax, wb.Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
   ENS(h->sbigmw, sB * 4 * sizeof(int)); HIPCHK(hipMemsetAsync(h->sbigmw.p, 0, sB * 4 * sizeof(int), s));
@@ -2017,7 +2102,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
     wb.sub_enable = 1; wb.Xs = h->sXsB.as<double>(); wb.sub_theta = h->ssubSB.as<double>();
     wb.sub_zscratch = nullptr;
     if (NPb > 512) { ENS(h->bsubz, sB * 16 * (size_t)(NPb + 2) * 8); wb.sub_zscratch = h->bsubz.as<double>(); }
-    wb.ws_first = nullptr; wb.ws_phase = 0; wb.sub_on = sh.sub_onB; wb.cone_done = sh.cone_doneB; wb.sub_wait = sh.sub_waitB; wb.sub_nfail = sh.sub_nfailB; wb.sub_stat = si + 4 * sB;
+    wb.ws_first = nullptr; wb.ws_need = nullptr; wb.ws_phase = 0; wb.sub_on = sh.sub_onB; wb.cone_done = sh.cone_doneB; wb.sub_wait = sh.sub_waitB; wb.sub_nfail = sh.sub_nfailB; wb.sub_stat = si + 4 * sB;
     wb.sep_done = nullptr;
   }
   HIPCHK(hipStreamSynchronize(s));

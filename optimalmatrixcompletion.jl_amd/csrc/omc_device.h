@@ -91,6 +91,10 @@ struct OmcWS {
   // k_setup / k_global.  ws_phase 1 = those slots only (runs beside k_cone_sub on its own stream), 2 = what k_cone_sub then left (a failed
   // call: ~1 in 30 000), 0 = both in one launch after k_cone_sub (ws_first NULL: the Shor-mode views)
   int* ws_first; int ws_phase;
+  // one word for all slots, set to 1 (plain store, thread 0) wherever ws_first[b] becomes 1 and where k_cone_sub<0> gives a call up: the host
+  // reads and clears it at a check, and an interval after a check that found 0 enqueues the full kernel once per iteration (phase 0) instead
+  // of twice.  It sits behind done[B], so the copy that brings the done flags back brings it too.  NULL: not kept (the Shor-mode views)
+  int* ws_need;
   int sub_guard;             // Ritz values of the tracked block that must stay negative (the block holds at most 16 - sub_guard positive ones)
   // certificate estimator (k_cone_sub<1>): block of the most negative eigenvectors of Mchk, its Ritz values (of -Mchk), trace of MbufC
   int* sep_done;          // B: the separation vector of this harvested slot came from the tracked block (k_cone_sub<2>); NULL = feature off

@@ -131,7 +131,7 @@ __global__ void k_setup(OmcWS w) {
     if (tid < 16) w.sub_theta[(size_t)b * 16 + tid] = w.ptheta[(size_t)lf * 16 + tid];
     fr2 = block_sum(fr2, red); tr1 = block_sum(tr1, red);
     if (tid == 0) {
-      w.fro2[b] = fr2; w.trM[b] = tr1; w.sub_on[b] = (w.sub_enable && w.pscal[(size_t)lf * 4 + 1] != 0.0) ? 1 : 0; w.sub_wait[b] = 0; w.sub_nfail[b] = 0; w.cone_done[b] = 0; if (w.w1_fac) w.w1_fac[b] = 0; w.v3valid[b] = 0; w.sub_onC[b] = 0; w.confirm[b] = 1; w.lb_est[b] = -1e300; w.vvalid[b] = 0; if (w.vvalidC) w.vvalidC[b] = 0; if (w.ws_first) w.ws_first[b] = w.sub_on[b] ? 0 : 1;
+      w.fro2[b] = fr2; w.trM[b] = tr1; w.sub_on[b] = (w.sub_enable && w.pscal[(size_t)lf * 4 + 1] != 0.0) ? 1 : 0; w.sub_wait[b] = 0; w.sub_nfail[b] = 0; w.cone_done[b] = 0; if (w.w1_fac) w.w1_fac[b] = 0; w.v3valid[b] = 0; w.sub_onC[b] = 0; w.confirm[b] = 1; w.lb_est[b] = -1e300; w.vvalid[b] = 0; if (w.vvalidC) w.vvalidC[b] = 0; if (w.ws_first) { w.ws_first[b] = w.sub_on[b] ? 0 : 1; if (w.ws_need && !w.sub_on[b]) *w.ws_need = 1; }
     }
     // Vt = Q_child' U_parent, U = Q_child Vt
     for (int e = tid; e < rm * k; e += T) {
@@ -165,7 +165,7 @@ __global__ void k_setup(OmcWS w) {
       w.Vrow[(size_t)b * NP * NP + e] = 0.0;
     }
     if (tid == 0) {
-      w.fro2[b] = d0 * d0 * n; w.trM[b] = d0 * n; w.sub_on[b] = 0; w.sub_wait[b] = 0; w.sub_nfail[b] = 0; w.cone_done[b] = 0; if (w.w1_fac) w.w1_fac[b] = 0; w.v3valid[b] = 0; w.sub_onC[b] = 0; w.confirm[b] = 1; w.lb_est[b] = -1e300; w.vvalid[b] = 0; if (w.vvalidC) w.vvalidC[b] = 0; if (w.ws_first) w.ws_first[b] = w.sub_on[b] ? 0 : 1;
+      w.fro2[b] = d0 * d0 * n; w.trM[b] = d0 * n; w.sub_on[b] = 0; w.sub_wait[b] = 0; w.sub_nfail[b] = 0; w.cone_done[b] = 0; if (w.w1_fac) w.w1_fac[b] = 0; w.v3valid[b] = 0; w.sub_onC[b] = 0; w.confirm[b] = 1; w.lb_est[b] = -1e300; w.vvalid[b] = 0; if (w.vvalidC) w.vvalidC[b] = 0; if (w.ws_first) { w.ws_first[b] = w.sub_on[b] ? 0 : 1; if (w.ws_need && !w.sub_on[b]) *w.ws_need = 1; }
     }
   }
   for (int e = tid; e < n * k; e += T) w.U[(size_t)b * n * k + e] = 0.0;
@@ -1616,6 +1616,7 @@ __global__ void __launch_bounds__(256, 2) k_cone_sub(OmcWS w) {
       atomicAdd(&w.sub_stat[8 * b + 2], 1); atomicAdd(&w.sub_stat[8 * b + 3 + fail], 1);   // 4: too many positive Ritz values, 5: step cap, 6: Cholesky
       const int nf = w.sub_nfail[b] + 1;          // exponential back-off: the spectrum still moves too fast for the tracked block
       w.sub_nfail[b] = nf; w.sub_wait[b] = (nf >= 7) ? 128 : (1 << nf);
+      if (MODE == 0 && w.ws_need) *w.ws_need = 1;      // the full kernel has a slot to serve behind this launch
     } else if (w.sub_nfail[b] > 0 && (w.iters[b] & 15) == 0) {
       w.sub_nfail[b] -= 1;                        // ... and forgets: a failure every few hundred calls (long solves: Shor mode runs thousands of iterations) must not cost 128 full decompositions each
     }
@@ -2353,7 +2354,7 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   rd2 = block_sum(rd2, red);
   fr2 = block_sum(fr2, red);
   tr1 = block_sum(tr1, red);
-  if (tid == 0) { w.rp[b] = sqrt(rp2); w.rd[b] = sqrt(rd2); w.fro2[b] = fr2; w.trM[b] = tr1; w.cone_done[b] = 0; if (w.w1_fac) w.w1_fac[b] = 0; w.iters[b] += 1; if (w.ws_first) w.ws_first[b] = (!w.sub_on[b] || w.sub_wait[b] > 0) ? 1 : 0; DIAG_CYC(4, b); }
+  if (tid == 0) { w.rp[b] = sqrt(rp2); w.rd[b] = sqrt(rd2); w.fro2[b] = fr2; w.trM[b] = tr1; w.cone_done[b] = 0; if (w.w1_fac) w.w1_fac[b] = 0; w.iters[b] += 1; if (w.ws_first) { const int f = (!w.sub_on[b] || w.sub_wait[b] > 0) ? 1 : 0; w.ws_first[b] = f; if (f && w.ws_need) *w.ws_need = 1; } DIAG_CYC(4, b); }
 }
 
 // ---------------------------------------------------------------------------------------------------------
