@@ -34,107 +34,10 @@
 #include <unistd.h>
 #include <rccl/rccl.h>   // types only: the library is loaded with dlopen on first use, so that libomc_hip.so has no hard dependency on it
 
-static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(x)                                                                                         \
-  do {                                                                                                    \
-    hipError_t e_ = (x);                                                                                  \
-    if (e_ != hipSuccess) {                                                                               \
-      g_err = std::string(#x) + ": " + hipGetErrorString(e_);                                             \
-      return (int)e_ > 0 ? (int)e_ : 999;                                                                 \
-    }                                                                                                     \
-  } while (0)
+#include "omc_host.h"
 
-struct DevBuf {
-  void* p = nullptr; size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = hipMalloc(&p, want);
-    if (e != hipSuccess) { g_err = std::string("hipMalloc: ") + hipGetErrorString(e); return (int)e; }
-    cap = want;
-    return 0;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <class T> T* as() { return (T*)p; }
-};
+thread_local std::string g_err;
 
-// page-locked host memory: copies from and to it are asynchronous, so the host may go on while one is in flight
-struct PinBuf {
-  void* p = nullptr; size_t cap = 0;
-  PinBuf() = default;
-  PinBuf(const PinBuf&) = delete;
-  PinBuf& operator=(const PinBuf&) = delete;
-  ~PinBuf() { if (p) (void)hipHostFree(p); }
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return 0;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) { g_err = std::string("hipHostMalloc: ") + hipGetErrorString(e); return (int)e; }
-    cap = bytes;
-    return 0;
-  }
-  template <class T> T* as() { return (T*)p; }
-};
-
-// Tuning knobs.  The environment is read in ONE place -- tuning_from_env, called by omc_instance_create and by omc_tuning_reload_env -- and a
-// caller that does not want its environment to matter sets the knobs through omc_tuning_set; nothing else in the library calls getenv
-// (behaviour of the shipped library depended on the caller's environment at every solve, one knob even per iteration).
-// A flag is on when its variable is set to any value ("0" included); a number is atoi of the value when set, its default otherwise.
-struct Tuning {
-  bool altmin_nolds = false;       // OMC_ALTMIN_NOLDS: the altmin kernel on its global slab even where its LDS would do
-  bool colprox_no_xcd = false;     // OMC_COLPROX_NO_XCD: no XCD-local placement of the column workgroups
-  bool cone_512 = false;           // OMC_CONE_512: 512-thread form of the full eigen-kernel at large orders
-  bool dense_proj = false;         // OMC_DENSE_PROJ: dense W1 and the Yp store instead of the factored projections
-  bool host_phases = false;        // OMC_HOST_PHASES: every solve prints its host time between the iterations (omc_last_host_phases) to stderr when it ends
-  bool global_nolds = false;       // OMC_GLOBAL_NOLDS: k_global's target in its L2-resident scratch instead of LDS
-  bool no_colprox_pair = false;    // OMC_NO_COLPROX_PAIR: k_colprox for every column
-  bool no_graph = false;           // OMC_NO_GRAPH: no hipGraph replay of the iteration body
-  bool no_subspace = false;        // OMC_NO_SUBSPACE: no tracked subspace (k_cone_sub) for the cone block
-  bool no_ws_split = false;        // OMC_NO_WS_SPLIT: the full eigen-kernel as one launch after k_cone_sub
-  bool segv_trace = false;         // OMC_SEGV_TRACE: print the native frames of a crashing thread
-  bool setup_gram_inline = false;  // OMC_SETUP_GRAM_INLINE: k_setup forms the rows' Gram matrix itself (one workgroup per slot) instead of k_setup_gram
-  bool shor_explicit = false;      // OMC_SHOR_EXPLICIT: rank k > 1 Shor batches by the Shor engine even where the base engine would serve them
-  bool shor_no_subspace = false;   // OMC_SHOR_NO_SUBSPACE: no tracked subspace for the order-(n+m) cone of Shor mode
-  int check_xs = 16;               // OMC_CHECK_XS: cut vectors of the rows with a nonzero multiplier that k_check_build stages in LDS (the rest is read from global memory)
-  int colprox_block_min = 65;      // OMC_COLPROX_BLOCK_MIN: columns with at least this many observed rows take k_colprox_block (one workgroup per column, blocked MFMA Cholesky); a value above every column length is the path without it
-  int cone_multi_min = 1025;       // OMC_CONE_MULTI_MIN: cone orders from this value on (never below 145) take the multi-workgroup eigen-kernels; the default is where only the cold kernel existed
-  int graph_max = 16;              // OMC_GRAPH_MAX: hipGraph replay for batches staged with at most this many nodes
-  int harvest_async = 1;           // OMC_HARVEST_ASYNC: 0 = every harvest is waited for, booked and refilled before the next iteration
-  int harvest_async_min_live = 256;   // OMC_HARVEST_ASYNC_MIN_LIVE: live slots from which a harvest runs beside the next interval (omc_harvest_plan)
-  int shor_select_kb = 1048576;    // OMC_SHOR_SELECT_KB: violated-minor selection streams (no materialised keys) when 16 B per candidate exceed this many KiB; 0 = always materialise
-  int streams = 4;                 // OMC_STREAMS: <= 1 serialises a solve on one stream
-  int sub_debug = 0;               // OMC_SUB_DEBUG: diagnostics of k_cone_sub (3: histograms for omc_debug_stamps)
-  int sub_qmax = 24;               // OMC_SUB_QMAX: step budget of k_cone_sub
-  int timing_stride = 1;           // OMC_TIMING_STRIDE: event timing of every s-th iteration, 0 = none
-  int ws_quiet = 1;                // OMC_WS_QUIET: 0 = every iteration enqueues both phases of the full eigen-kernel, also in quiet intervals
-};
-struct Knob { const char* name; bool Tuning::*flag; int Tuning::*num; };
-static const Knob OMC_KNOBS[] = {
-  {"OMC_ALTMIN_NOLDS", &Tuning::altmin_nolds, nullptr},      {"OMC_COLPROX_NO_XCD", &Tuning::colprox_no_xcd, nullptr},
-  {"OMC_CONE_512", &Tuning::cone_512, nullptr},              {"OMC_DENSE_PROJ", &Tuning::dense_proj, nullptr},
-  {"OMC_GLOBAL_NOLDS", &Tuning::global_nolds, nullptr},      {"OMC_HOST_PHASES", &Tuning::host_phases, nullptr},
-  {"OMC_NO_COLPROX_PAIR", &Tuning::no_colprox_pair, nullptr},
-  {"OMC_NO_GRAPH", &Tuning::no_graph, nullptr},              {"OMC_NO_SUBSPACE", &Tuning::no_subspace, nullptr},
-  {"OMC_NO_WS_SPLIT", &Tuning::no_ws_split, nullptr},        {"OMC_SEGV_TRACE", &Tuning::segv_trace, nullptr},
-  {"OMC_SETUP_GRAM_INLINE", &Tuning::setup_gram_inline, nullptr},
-  {"OMC_SHOR_EXPLICIT", &Tuning::shor_explicit, nullptr},    {"OMC_SHOR_NO_SUBSPACE", &Tuning::shor_no_subspace, nullptr},
-  {"OMC_COLPROX_BLOCK_MIN", nullptr, &Tuning::colprox_block_min},
-  {"OMC_CHECK_XS", nullptr, &Tuning::check_xs},              {"OMC_CONE_MULTI_MIN", nullptr, &Tuning::cone_multi_min},
-  {"OMC_GRAPH_MAX", nullptr, &Tuning::graph_max},            {"OMC_SHOR_SELECT_KB", nullptr, &Tuning::shor_select_kb},
-  {"OMC_HARVEST_ASYNC", nullptr, &Tuning::harvest_async},    {"OMC_HARVEST_ASYNC_MIN_LIVE", nullptr, &Tuning::harvest_async_min_live},
-  {"OMC_WS_QUIET", nullptr, &Tuning::ws_quiet},
-  {"OMC_STREAMS", nullptr, &Tuning::streams},
-  {"OMC_SUB_DEBUG", nullptr, &Tuning::sub_debug},            {"OMC_SUB_QMAX", nullptr, &Tuning::sub_qmax},
-  {"OMC_TIMING_STRIDE", nullptr, &Tuning::timing_stride},
-};
 static void knob_set(Tuning& t, const Knob& kb, const char* value) {      // value NULL: the default
   if (kb.flag) t.*kb.flag = value != nullptr;
   else t.*kb.num = value ? atoi(value) : Tuning{}.*kb.num;
@@ -153,97 +56,6 @@ static void tuning_from_env(Tuning& t) {
   for (const Knob& kb : OMC_KNOBS) knob_set(t, kb, getenv(kb.name));
 }
 
-struct omc_instance {
-  int n = 0, m = 0, k = 0, device = 0, nnz = 0, cmax = 0;
-  double gamma = 0, sumA2 = 0;
-  std::vector<int> col_ptr, col_idx; std::vector<double> col_val;
-  std::vector<double> A; std::vector<uint8_t> mask;
-  std::vector<double> Ncnt;
-  std::vector<int> row_ptr, row_idx; std::vector<double> row_val;
-  DevBuf drow_ptr, drow_idx, drow_val, aR, arkind, arcut, arbi, arbj, arcoef, arrhs, acutx, aU0, aU, aV, aobj, aint, aG, aG2;
-  hipStream_t stream = nullptr;
-  Tuning tun;
-  // main / column / small-cone streams of an iteration and its fork, join, done events (see omc_relax_solve)
-  hipStream_t gs[3] = {};
-  hipEvent_t gev[5] = {};
-  hipEvent_t gevc[5] = {};      // the same fork / join events for bodies recorded under stream capture: an event is never used both inside a captured graph and eagerly
-  hipEvent_t ev_main = nullptr;
-  // between the iterations (check, harvest, refill): page-locked images of the slot flags and of the slot list, two of each so that the host
-  // writes one while the copy of the other may still be in flight (ev_up: recorded behind each copy, waited for before the image is rewritten),
-  // of the done flags, and of the (slot, node) jobs of k_setup_gram with their device copy; ev_gram marks that kernel's end on its stream
-  PinBuf pin_flags[2], pin_list[2], pin_done, pin_jobs; DevBuf bgramjobs;
-  hipEvent_t ev_up[4] = {}; bool ev_up_rec[4] = {}; hipEvent_t ev_gram = nullptr; bool ev_gram_rec = false;
-  // host time of the last solve between the iterations, by piece (omc_last_host_phases): milliseconds and events
-  double host_ms[OMC_HOST_NPHASE] = {0}; int64_t host_cnt[OMC_HOST_NPHASE] = {0};
-  DevBuf dA, dmask, dcol_ptr, dcol_idx, dcol_val, dNcnt, dwY, dsolo, dwide;
-  int nwide = 0;      // columns outside the pairs with at most 64 observed rows (k_colprox_wide)
-  int nsolo = 0;      // columns that k_colprox_pair leaves to k_colprox (more than 32 observed rows, unpaired last column)
-  // k_colprox_block: its two column lists (tiles in LDS / in the slab), the per-column flag, the longest column of each list, the non-empty
-  // columns it leaves and the longest of them; the lists follow (block_min, pair kernel on) and are rebuilt at a stage call when either changed
-  DevBuf dblock, dslab, disblock, bcpb, bnfact;
-  int nblock = 0, nslab = 0, nrest = 0, cpb_cl = 0, cpb_cs = 0, crest_max = 0;
-  bool lists_valid = false; int lists_block_min = 0; bool lists_pair = true;
-  int cp_force = 0;   // set by omc_column_prox_batch for the omc_relax_stage call it makes: 1 = no block kernel, 2 = the block kernel for every non-empty column
-  // batch workspace
-  DevBuf bYx, bY, bYp, bU, bD1, bD3, bW1, bE3, bQb, brr, bsm, bdS, balpha, balphaX, bsval, bMchk, bsmall, bchk;
-  DevBuf bR, brkind, brcut, brbi, brbj, brcoef, brrhs, bcutx, bG, blam;
-  DevBuf bobjcol, baaF, baaG, baaZ, baaS, baaI, bMbufC, bVrowC, bchkS, bchkI;
-  DevBuf bslotlist, bgap, bvotes, blamDX, bXsC, bsubSC, bsubIC;
-  DevBuf bsubz, bscal, bbx, bint, bcp, bcone, bglob, bXout, bThout, bXin, bMbuf, bVrow, bXs, bsubS, bsubI;
-  long long sub_tot[8] = {0};
-  DevBuf bmwstat, sbigmw, pjM, pjV, pjW, pjS, pjD, pjI;      // sweep statistics of the multi-workgroup eigen-kernels (base workspace, Shor view) ; buffers of omc_psd_project_batch
-  long long mw_tot[5] = {0};      // omc_last_cone_multi_stats
-  OmcWS ws{};
-  omc_relax_params params{};
-  bool staged = false;
-  double last_solve_seconds = 0; long long total_sweeps = 0; int last_iters_total = 0;
-  std::thread worker; std::atomic<int> worker_running{0}, nodes_done{0}; int worker_rc = 0; std::string worker_err;
-  // appending nodes to a staged / running batch (omc_relax_reserve, omc_relax_append): descriptor and output arrays are sized for node_cap nodes,
-  // the strides (rows, row-subspace columns, cuts per node) for reserve_cuts cuts; Btot_live is what the solve loop reads at its refill points
-  int reserve_nodes = 0, reserve_cuts = 0, node_cap = 0, staged_cut_type = 0; std::atomic<int> Btot_live{0}; bool append_closed = true; std::mutex append_mu; hipStream_t append_stream = nullptr;
-  std::atomic<int> hold{0};      // omc_relax_hold: a solve that has run dry waits for omc_relax_append instead of ending
-  std::vector<int> done_q; size_t done_read = 0; std::mutex done_mu; hipStream_t fetch_stream = nullptr;      // nodes harvested so far, in harvest order (omc_relax_fetch_done)
-  void* comm = nullptr; int comm_rank = 0, comm_world = 1; DevBuf bcomm, amobj; int amobj_B = 0;
-  int wall_khz = 0;      // rate of the device's constant clock (wall_clock64) for the time_limit of omc_altmin_batch; 0: unknown, the limit is not enforced inside a launch
-  std::vector<double> rho_scale_per_node; DevBuf brho, brhon, blamD, bslotint, boY, boU, boal, bobx, boscal, boint;
-  int Btot = 0;
-  // Shor minors (a10 / a11): row bitsets and per-pair popcounts, built at the first call
-  DevBuf sbits, scb, scx, scz, soff, stot, sout, shi, slo, sexist, shist, sohi, solo, scnt;
-  bool shor_ready = false; int shor_W = 0; long long shor_pairs = 0;
-  double shor_last_ms = 0; long long shor_last_candidates = 0;
-  int64_t shor_sel[4] = {0, 0, 0, 0};      // omc_shor_last_select_stats: streamed, tiles, compactions, peak key / survivor bytes
-  // Shor-mode relaxation (omc_relax_stage_shor): index structures of the distinct lists, explicit X / W / Theta state, view of the workspace
-  // through which the base eigen-kernels project the order-(n+m) cone
-  bool shor_req = false, shor_on = false, shor_keep_V = false, shor_via_base = false; std::vector<int> shor_slackrow; DevBuf soV; double shor_rho = 0.05, shor_r4 = 0.0, shor_r5 = 2.0;      // r4 = 0: automatic per list
-  ShWS sh{}; OmcWS wbig{};
-  DevBuf sgInts, sgBytes, sgGroups, sgNodeGroup, sAh, sX, sW, sTh, sV1, sV2, sV3, sD0, sP0, sMbufB, sVrowB, sTq, sPq, sNq, sD5x, sD5t, snu5, sP5x,
-      scolpart, sminpart, sminpart2, sfroB, svvB, se1, se2, soX, soW, soTh, sbigscr, sXsB, ssubSB, ssubIB;
-  long long big_sub_tot[8] = {0};
-  // appending Shor nodes (omc_relax_reserve_shor, omc_relax_append_shor): the reservation of the NEXT omc_relax_stage_shor, and for the life of the
-  // staged batch the lists it knows (staged or appended; hash -> groups, with a host copy of every list to tell equal hashes apart), the group
-  // table's capacity and how much of the two index arenas is in use.  Written at stage time and under append_mu.
-  struct ShorListKey { int64_t nq = 0, nsoc = 0; uint64_t hlist = 0; std::vector<int64_t> idx, soc; };
-  int64_t reserve_shor_nq = 0; int reserve_shor_lists = 0; bool reserve_shor_set = false;
-  std::unordered_map<uint64_t, std::vector<int>> sh_byhash; std::vector<ShorListKey> sh_lists;
-  int sh_group_cap = 0; size_t sh_int_used = 0, sh_int_cap = 0, sh_byte_used = 0, sh_byte_cap = 0;
-  // warm-start pool (omc_state_pool_create / omc_relax_set_warm)
-  int pool_cap = 0; DevBuf pY, pD1, pD3, pU, palpha, psval, pXs, ptheta, pscal, bwarmL, bwarmS; std::vector<int> warm_load, warm_save;
-  // Shor extension of the pool (omc_state_pool_reserve_shor) and the host's signature of every entry: which mode saved it and for which lists.
-  // A signature is written when the node that saves is harvested (solve thread) and read at stage / append time (caller's thread): sig_mu.
-  struct PoolSig { int kind = 0; int64_t nq = 0, nsoc = 0; uint64_t hlist = 0, hsoc = 0; };      // kind: 0 empty, 1 base, 2 Shor
-  bool pool_shor = false; int64_t pool_nqmax = 0; DevBuf pShor, pShorHdr, sloadpart;
-  std::vector<PoolSig> pool_sig, node_sig; std::mutex sig_mu;
-  std::vector<int> save_host;      // per node of the staged batch: the entry its final state goes to (-1: none), as the device sees it
-  bool shor_warm = false;          // set by omc_relax_stage_shor for the omc_relax_stage call it makes: the indices have passed its filter
-  int64_t shor_warm_stats[4] = {0, 0, 0, 0};      // omc_last_shor_warm_stats
-  // kernel stats
-  int64_t launches[OMC_KERNEL_NCLASS] = {0}; double ms[OMC_KERNEL_NCLASS] = {0}; int64_t units[OMC_KERNEL_NCLASS] = {0};
-  size_t nnz_rows() const { return row_idx.size(); }
-  // timing events: two pools that swap at a check, so that the pool of the interval that has just ended is read (finish_events) after the
-  // next iteration has been enqueued while the launches of that iteration record into the other one
-  std::vector<hipEvent_t> ev_pool[2]; size_t ev_used[2] = {0, 0}; int ev_cur = 0;
-  std::vector<int> ev_class[2];
-};
 
 extern "C" {
 
@@ -426,38 +238,6 @@ static int cut_piece(int cut_type, int dir, double vhat, int q1, double* lo, dou
   return -1;
 }
 
-// Per-kernel timing: a pair of pool events brackets a launch; the pool is drained by finish_events.  If an event cannot be created, or one of
-// the two records fails, the launch runs (and is counted) untimed.
-static bool next_event_pair(omc_instance* h) {
-  std::vector<hipEvent_t>& pool = h->ev_pool[h->ev_cur];
-  while (pool.size() < h->ev_used[h->ev_cur] + 2) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return false;
-    pool.push_back(e);
-  }
-  return true;
-}
-#define TIMED_ON(strm, cls, units_, call)                                                                     \
-  do {                                                                                                        \
-    const int pc_ = h->ev_cur;                                                                                \
-    const bool t0_ = next_event_pair(h) && hipEventRecord(h->ev_pool[pc_][h->ev_used[pc_]], strm) == hipSuccess; \
-    call;                                                                                                     \
-    if (t0_ && hipEventRecord(h->ev_pool[pc_][h->ev_used[pc_] + 1], strm) == hipSuccess) {                    \
-      h->ev_used[pc_] += 2; h->ev_class[pc_].push_back(cls);                                                  \
-    }                                                                                                         \
-    h->launches[cls] += 1; h->units[cls] += (units_);                                                         \
-  } while (0)
-#define TIMED(cls, units_, call) TIMED_ON(h->stream, cls, units_, call)
-// a launch timed into class `cls` that is not one of the class's launches (k_setup_gram: ms of the setup class, see omc_last_kernel_stats)
-#define TIMED_UNCOUNTED_ON(strm, cls, call)                                                                   \
-  do {                                                                                                        \
-    const int pc_ = h->ev_cur;                                                                                \
-    const bool t0_ = next_event_pair(h) && hipEventRecord(h->ev_pool[pc_][h->ev_used[pc_]], strm) == hipSuccess; \
-    call;                                                                                                     \
-    if (t0_ && hipEventRecord(h->ev_pool[pc_][h->ev_used[pc_] + 1], strm) == hipSuccess) {                    \
-      h->ev_used[pc_] += 2; h->ev_class[pc_].push_back(cls);                                                  \
-    }                                                                                                         \
-  } while (0)
 
 // rows (OMC.jl:1558-1685) and row subspace of a set of nodes, on the host: shared by omc_relax_stage and omc_relax_append
 struct NodePack {
@@ -606,13 +386,7 @@ static int put_descriptors(const OmcWS& w, const NodePack& pk, int B, size_t row
   return 0;
 }
 
-// fixed parameters of the eigen-kernels and the column kernel (OmcWS fields)
-static constexpr int MAX_SWEEPS = 30;          // sweep cap of the warm-started Jacobi kernel (k_cone_ws)
-// Sweep budget of the next multi-workgroup calls of a view (omc_relax_solve reads the counts at a certificate check).  interval_max: most
-// sweeps of a call since the last check, 0 = no call in that interval.  Warm calls: what the last interval needed + 2.  After an interval
-// without a call the next one is a fall-back from a basis that has gone stale by an unknown amount (on a warm-started solve not even the
-// first calls were cold): the full bound -- the launches of the sweeps not needed leave at once.  Exported for the tests.
-int omc_cone_multi_budget(int interval_max) { return interval_max > 0 ? std::min(MAX_SWEEPS, interval_max + 2) : MAX_SWEEPS; }
+// fixed parameters of the eigen-kernels and the column kernel (OmcWS fields; MAX_SWEEPS: omc_host.h)
 static constexpr int CP_SERIES = 6;            // Neumann-series order of k_colprox_pair's finish
 static constexpr int CP_MAXPASS = 60;          // cap on the secular passes of k_colprox_pair
 static constexpr int SUB_GUARD = 2;            // Ritz values of the tracked block that must stay negative
@@ -885,15 +659,6 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   return 0;
 }
 
-static int finish_events(omc_instance* h, int pool) {      // every launch the pool has timed must have completed
-  for (size_t i = 0; i + 1 < h->ev_used[pool]; i += 2) {
-    float msv = 0.f;
-    if (hipEventElapsedTime(&msv, h->ev_pool[pool][i], h->ev_pool[pool][i + 1]) == hipSuccess) h->ms[h->ev_class[pool][i / 2]] += msv;
-  }
-  h->ev_used[pool] = 0; h->ev_class[pool].clear();
-  return 0;
-}
-
 int omc_set_node_rho_scales(omc_instance* h, int B, const double* rho_scale) {
   if (!h || B <= 0 || !rho_scale) return fail(OMC_ERR_ARGUMENT, "NULL argument");
   for (int b = 0; b < B; ++b) if (!(rho_scale[b] > 0.0)) return fail(OMC_ERR_ARGUMENT, "rho_scale must be positive");
@@ -1012,542 +777,6 @@ int omc_relax_set_warm(omc_instance* h, int B, const int* load_from, const int* 
   }
   if (load_from) h->warm_load.assign(load_from, load_from + B);
   if (save_to) h->warm_save.assign(save_to, save_to + B);
-  return 0;
-}
-
-static constexpr int REFILL_EVERY = 3;      // finished slots are harvested and refilled at every third check (see omc_relax_solve)
-static constexpr int REFILL_AT_ONCE_LIVE = 256;      // fewer live slots than this no longer fill the chip: harvest and refill at every check
-
-// Harvest and refill every REFILL_EVERY-th check only (or when nothing is left running): a refilled slot spends its first dozen
-// iterations in the full eigendecomposition, the straggler of every launch it is part of, and each harvest is 1 - 3 ms of few-workgroup
-// kernels on the main stream -- batching them halves the launches that carry young slots.  A finished slot waits (done = 1, skipped
-// by every kernel and left out of the slot list) for at most REFILL_EVERY - 1 check intervals.
-// With pending nodes: every REFILL_EVERY-th check, at once when the live slots no longer fill the chip; without: the finished slots can
-// wait longer (nothing to hand them), until nothing runs any more.
-// Nothing a live slot reads is written by the harvest kernels, so with enough live slots to fill the chip they run beside the next interval
-// (ASYNC) and the host books and refills at the next check; below that, refilling at once is worth more than the stall.
-int omc_harvest_plan(int nlive, int nfin, int pending, int check_index, int async_min_live) {
-  if (nfin <= 0) return OMC_HARVEST_NONE;
-  if (nlive <= 0) return OMC_HARVEST_SYNC;
-  const bool now = pending ? (check_index % REFILL_EVERY == 0 || nlive < REFILL_AT_ONCE_LIVE) : (check_index % (4 * REFILL_EVERY) == 0);
-  if (!now) return OMC_HARVEST_NONE;
-  return (async_min_live > 0 && nlive >= async_min_live) ? OMC_HARVEST_ASYNC : OMC_HARVEST_SYNC;
-}
-
-int omc_relax_solve(omc_instance* h) {
-  if (!h || !h->staged) return fail(OMC_ERR_ARGUMENT, "omc_relax_solve: nothing staged");
-  HIPCHK(hipSetDevice(h->device));
-  const OmcWS& w = h->ws;
-  const omc_relax_params& P = h->params;
-  const Tuning tun = h->tun;      // copied once: omc_tuning_set may run on the caller's thread while a submitted solve runs on the worker
-  for (int c = 0; c < OMC_KERNEL_NCLASS; ++c) { h->launches[c] = 0; h->ms[c] = 0; h->units[c] = 0; }
-  for (int q = 0; q < 2; ++q) { h->ev_used[q] = 0; h->ev_class[q].clear(); }
-  h->ev_cur = 0;
-  for (int q = 0; q < OMC_HOST_NPHASE; ++q) { h->host_ms[q] = 0; h->host_cnt[q] = 0; }
-  auto t0 = std::chrono::steady_clock::now();
-  hipStream_t s = h->stream;
-  // host stamps between the iterations (omc_last_host_phases): stamp(q) charges the time since the previous stamp to piece q
-  auto t_last = t0;
-  auto stamp_begin = [&]() { t_last = std::chrono::steady_clock::now(); };
-  auto stamp = [&](int q) { const auto t = std::chrono::steady_clock::now(); h->host_ms[q] += std::chrono::duration<double, std::milli>(t - t_last).count(); h->host_cnt[q] += 1; t_last = t; };
-  const int S = w.B; int Btot = h->Btot_live.load();      // nodes staged so far: omc_relax_append may add more while this loop runs (re-read at every check)
-  struct CloseGuard { omc_instance* h; ~CloseGuard() { std::lock_guard<std::mutex> lk(h->append_mu); h->append_closed = true; h->ws.Btot = h->Btot_live.load(); h->Btot = h->ws.Btot; if (h->shor_on) h->sh.Btot = h->ws.Btot; } } close_guard{h};
-  // slot bookkeeping on the host: node of each slot (-1 = idle), next pending node
-  std::vector<int> node_of(S);
-  for (int b = 0; b < S; ++b) node_of[b] = (b < Btot) ? b : -1;      // with omc_relax_reserve there may be more slots than nodes staged so far: the others start idle
-  int next = std::min(S, Btot), harvested = 0, nactive = next;
-  // Page-locked images (see omc_instance): an upload returns at once, and an image is rewritten only after the copy that last read it has
-  // completed (its event; two images alternate, so that wait is over long before it is asked for)
-  for (int q = 0; q < 2; ++q) { int rc = h->pin_flags[q].ensure(sizeof(int) * 3 * (size_t)S); if (rc) return rc; rc = h->pin_list[q].ensure(sizeof(int) * (size_t)S); if (rc) return rc; }
-  { int rc = h->pin_done.ensure(sizeof(int) * ((size_t)S + 1)); if (rc) return rc; rc = h->pin_jobs.ensure(sizeof(int) * 2 * (size_t)S); if (rc) return rc; rc = h->bgramjobs.ensure(sizeof(int) * 2 * (size_t)S); if (rc) return rc; }
-  for (int q = 0; q < 4; ++q) { if (!h->ev_up[q]) HIPCHK(hipEventCreateWithFlags(&h->ev_up[q], hipEventDisableTiming)); h->ev_up_rec[q] = false; }
-  if (!h->ev_gram) HIPCHK(hipEventCreateWithFlags(&h->ev_gram, hipEventDisableTiming));
-  h->ev_gram_rec = false;
-  int* const done = h->pin_done.as<int>();
-  for (int b = 0; b < S; ++b) done[b] = 0;
-  int flags_cur = 0, list_cur = 0;
-  auto image_free = [&](int q) -> int {      // q: 0, 1 flags; 2, 3 slot list
-    if (h->ev_up_rec[q]) { HIPCHK(hipEventSynchronize(h->ev_up[q])); h->ev_up_rec[q] = false; }
-    return 0;
-  };
-  // sync: the caller needs the stream drained behind the upload (the harvest kernels' outputs); nothing else waits for a flags upload
-  auto push_flags = [&](const std::vector<int>& init, const std::vector<int>& fin, bool sync) -> int {
-    const int q = flags_cur; flags_cur ^= 1;
-    { int rc = image_free(q); if (rc) return rc; }
-    int* flags = h->pin_flags[q].as<int>();
-    for (int b = 0; b < S; ++b) { flags[b] = node_of[b] < 0 ? 0 : node_of[b]; flags[S + b] = init[b]; flags[2 * (size_t)S + b] = fin[b]; }
-    HIPCHK(hipMemcpyAsync(w.node_of, flags, sizeof(int) * 3 * (size_t)S, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(h->ev_up[q], s)); h->ev_up_rec[q] = true;
-    if (sync) HIPCHK(hipStreamSynchronize(s));
-    return 0;
-  };
-  // Streams.  Inside an iteration the three blocks are independent of each other (columns: Y, Yp, alpha -> alpha, Lambda;
-  // cone: Y - D1 -> W1; small cone: Y, D3, V -> E3, W3*): a main stream (cone, then the global step) and two side streams
-  // (columns, small cone) forked and joined by events, so that the latency-bound column waves and the small workgroups
-  // share the CUs with the LDS-bound cone kernel (measured on config 2, 2048 slots: 212 -> 235 node-relaxations/s).
-  // OMC_STREAMS=1 serialises everything on one stream (kernel-by-kernel measurements).
-  const bool multi = tun.streams > 1;
-  if (multi && !h->ev_main) {
-    for (hipStream_t& q : h->gs) HIPCHK(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
-    for (int q = 0; q < 5; ++q) { HIPCHK(hipEventCreateWithFlags(&h->gev[q], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&h->gevc[q], hipEventDisableTiming)); }
-    HIPCHK(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
-  }
-  const hipStream_t sm = multi ? h->gs[0] : s, sb = multi ? h->gs[1] : s, sc = multi ? h->gs[2] : s;
-  // The Gram matrix of the rows of every node that is about to get a slot (k_setup_gram): G depends on the node's descriptor only and nothing
-  // but k_setup and k_global touches it, so it is formed on the column stream -- idle between a check and the next iteration -- beside the
-  // harvest kernels of the slot's previous node, and joined to the main stream behind k_setup (gram_join), ahead of the next k_global.
-  // jobs: (slot, node) pairs in pin_jobs.  Its time goes to the setup class; it is not a launch of that class.
-  h->ws.setup_gram_inline = tun.setup_gram_inline ? 1 : 0;
-  h->ws.check_xs = std::min(std::max(0, tun.check_xs), CB_XS);      // at most CB_XS doubles are staged: more vectors than that never fit
-  int* const jobs = h->pin_jobs.as<int>();
-  auto gram_launch = [&](int njobs) -> int {
-    if (tun.setup_gram_inline || njobs <= 0) return 0;
-    HIPCHK(hipMemcpyAsync(h->bgramjobs.p, jobs, sizeof(int) * 2 * (size_t)njobs, hipMemcpyHostToDevice, sb));
-    for (int q = 0; q < njobs; ++q)      // the host builds the list: a job outside the slots or the nodes is a bookkeeping error, not something to skip
-      if (jobs[2 * q] < 0 || jobs[2 * q] >= S || jobs[2 * q + 1] < 0 || jobs[2 * q + 1] >= Btot) return fail(OMC_ERR_ARGUMENT, "omc_relax_solve: k_setup_gram job outside the slots / nodes");
-    TIMED_UNCOUNTED_ON(sb, OMC_KERNEL_SETUP, omc_launch_setup_gram(&w, h->bgramjobs.as<int>(), njobs, Btot, sb));
-    HIPCHK(hipEventRecord(h->ev_gram, sb)); h->ev_gram_rec = true;
-    return 0;
-  };
-  auto gram_jobs_free = [&]() -> int {      // before pin_jobs is rewritten
-    if (h->ev_gram_rec) { HIPCHK(hipEventSynchronize(h->ev_gram)); h->ev_gram_rec = false; }
-    return 0;
-  };
-  auto gram_join = [&]() -> int {
-    if (h->ev_gram_rec && sb != s) HIPCHK(hipStreamWaitEvent(s, h->ev_gram, 0));
-    return 0;
-  };
-  std::vector<int> init(S, 0), fin(S, 0), init2(S, 0), fin2(S, 0), harvested_ids;      // scratch of a check / a harvest / refill_idle
-  {
-    int nj = 0;
-    for (int b = 0; b < S; ++b) { init[b] = node_of[b] >= 0 ? 1 : 0; done[b] = node_of[b] >= 0 ? 0 : 1; if (node_of[b] >= 0) { jobs[2 * nj] = b; jobs[2 * nj + 1] = node_of[b]; ++nj; } }
-    int rc = gram_launch(nj); if (rc) return rc;
-    rc = push_flags(init, fin, false); if (rc) return rc;
-    if (nactive < S) { HIPCHK(hipMemcpyAsync(w.done, done, sizeof(int) * S, hipMemcpyHostToDevice, s)); HIPCHK(hipStreamSynchronize(s)); }      // idle slots are skipped by every kernel
-  }
-  const bool shor = h->shor_on;
-  const ShWS& sw = h->sh;
-  if (shor) omc_shor_launch_setup(&sw, s);       // before the base setup, which clears the init flags
-  TIMED(OMC_KERNEL_SETUP, S, omc_launch_setup(&w, s));
-  { int rc = gram_join(); if (rc) return rc; }
-  int it = 0;
-  const int check = std::max(1, P.check_every);
-  // compact list of the slots that hold a running node: the per-iteration kernels launch over it (rebuilt when slots finish or are refilled)
-  std::vector<char> parked(S, 0);      // finished, waiting for the next harvest
-  int check_index = 0;
-  int nlist = 0;
-  auto push_list = [&]() -> int {
-    const int q = list_cur; list_cur ^= 1;
-    { int rc = image_free(2 + q); if (rc) return rc; }
-    int* alist = h->pin_list[q].as<int>();
-    nlist = 0;
-    for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && !parked[b]) alist[nlist++] = b;
-    if (nlist) { HIPCHK(hipMemcpyAsync(h->bslotlist.p, alist, sizeof(int) * nlist, hipMemcpyHostToDevice, s)); HIPCHK(hipEventRecord(h->ev_up[2 + q], s)); h->ev_up_rec[2 + q] = true; }
-    return 0;
-  };
-  { int rc = push_list(); if (rc) return rc; }
-  int gact = nactive;      // slots that run (hold a node, not parked): the units of an iteration's launches
-  auto recount = [&]() {
-    nactive = 0; gact = 0;
-    for (int b = 0; b < S; ++b) if (node_of[b] >= 0) { ++nactive; if (!parked[b]) ++gact; }
-  };
-  // nodes [next, Btot) that never got a slot: status `st` without values
-  auto close_unslotted = [&](int st) -> int {
-    if (next >= Btot) return 0;
-    const size_t c = (size_t)(Btot - next);
-    std::vector<int> stv(c, st), itz(c, 0);
-    std::vector<double> inf(c, 1e300), ninf(c, -1e300);
-    HIPCHK(hipMemcpyAsync(w.ostatus + next, stv.data(), sizeof(int) * c, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.oiters + next, itz.data(), sizeof(int) * c, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.oobj + next, inf.data(), 8 * c, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.olb + next, ninf.data(), 8 * c, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    next = Btot;
-    return 0;
-  };
-  bool timed_out = false;
-  h->total_sweeps = 0;
-  int drain_pool = -1;       // timing-event pool that waits to be read (finish_events): filled up to the last check, read after the next iteration is enqueued
-  bool wait_main = true;     // the iteration streams must wait for the work queued on the main stream (setup, checks, refills)
-  // Small batches are launch-bound (batch 1: ~190 us of launches, event records and waits around ~115 us of kernels per iteration):
-  // the body of an iteration (fork, three concurrent blocks, join, global step) is captured once into a hipGraph and replayed.  Per-kernel
-  // HIP-event timing is not available inside a graph, so the large batches that the bench times keep the eager path.
-  // hipGraph replay of the iteration body for small batches (measured at batch 1: 266 instead of 322 us per iteration), only for batches that
-  // are small FROM THE START (<= OMC_GRAPH_MAX = 16 nodes staged: one capture per solve): the draining tail of a large batch re-captured the graph
-  // at every harvest, and a sporadic host crash inside omc_relax_solve was seen three times in round 3, always in or after solves on that path,
-  // never with replay off; not located.
-  const int graph_max = Btot <= tun.graph_max ? tun.graph_max : 0;
-  hipGraphExec_t gexec[2] = {nullptr, nullptr}; int gexec_n = -1;
-  struct GraphGuard { hipGraphExec_t* e; ~GraphGuard() { for (int q = 0; q < 2; ++q) if (e[q]) (void)hipGraphExecDestroy(e[q]); } } gguard{gexec};
-  // The full eigen-kernel runs the slots that have no tracked block (or are backing off) -- a handful per launch, each a long single-workgroup
-  // job, known before the iteration starts (ws_first) -- on a stream of its own beside k_cone_sub; what k_cone_sub then could not do (a failed
-  // call, ~1 in 30 000) is a second, almost empty launch behind both.  One launch after k_cone_sub made every iteration wait for the sum.
-  // Multi-workgroup eigen-kernels (geo.mw): a call is a sequence of launches whose sweep budget the host fixes when it enqueues them.  The
-  // budget is the full bound while a slot may be on its first call (cold start), else the most sweeps a call needed since the last check + 2
-  // (read at the check, where the host synchronises anyway).  An interval without a call (the tracked block served every slot) says nothing
-  // about the next one, a fall-back from a basis that has gone stale: omc_cone_multi_budget then gives the full bound again.
-  // [0] base cone, [1] big cone of Shor mode; the certificate launches keep the bound.
-  const bool mw_any = w.geo.mw || (shor && h->wbig.geo.mw);
-  int mw_budget[2] = {MAX_SWEEPS, MAX_SWEEPS};
-  for (int q = 0; q < 5; ++q) h->mw_tot[q] = 0;
-  auto mw_collect = [&]() -> int {      // statistics since the last call of this function -> totals and the next budgets
-    if (!mw_any) return 0;
-    std::vector<int> st(4 * (size_t)S);
-    for (int v = 0; v < 2; ++v) {
-      const OmcWS& wv = v ? h->wbig : w;
-      if (!(v ? shor && wv.geo.mw : wv.geo.mw)) continue;
-      HIPCHK(hipMemcpyAsync(st.data(), wv.mw_stat, sizeof(int) * st.size(), hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      HIPCHK(hipMemsetAsync(wv.mw_stat, 0, sizeof(int) * st.size(), s));
-      int mx = 0;
-      for (int b = 0; b < S; ++b) { h->mw_tot[0] += st[4 * b]; h->mw_tot[2] += st[4 * b + 2]; mx = std::max(mx, st[4 * b + 3]); }
-      if (mx) h->mw_tot[1] = mx;      // an interval without a call keeps the last figure
-      h->mw_tot[3] = std::max<long long>(h->mw_tot[3], mx);
-      mw_budget[v] = omc_cone_multi_budget(mx);
-    }
-    return 0;
-  };
-  const bool split_solve = multi && !tun.no_ws_split && w.sub_enable && w.geo.ws_lpp && w.ws_first;
-  // Quiet intervals: with warm starts the full kernel has nothing to do for whole intervals (w.ws_need stayed 0), and its two launches are then
-  // two empty links in the latency chain of an iteration that is not saturated.  An interval after a check that found the word 0 and set no
-  // slot up enqueues the unsplit form -- one launch behind k_cone_sub, which also serves a call that fails inside the interval (serially, for
-  // that iteration; the word is then set and the next interval is split again).  The two forms are bit-identical.  A captured graph keeps
-  // the split it was captured with.
-  bool quiet = false;
-  auto body = [&](const OmcWS& wg, bool timed, bool with_aa, bool capturing) -> int {
-    const bool split = split_solve && (capturing || !quiet);
-    hipEvent_t* const ev = capturing ? h->gevc : h->gev;
-    if (multi) {
-      HIPCHK(hipEventRecord(ev[0], sm));
-      HIPCHK(hipStreamWaitEvent(sb, ev[0], 0)); HIPCHK(hipStreamWaitEvent(sc, ev[0], 0));
-    }
-#define MAYBE_TIMED(strm, cls, units_, call) do { if (timed) TIMED_ON(strm, cls, units_, call); else { call; } } while (0)
-    if (shor) {
-      // Shor mode: clip on the main stream, the order-(n+m) cone on the second, small cone + order-5 blocks on the third; then the
-      // global step: rows / Y (base kernel), columns (X, W, Theta, duals of the big cone), duals of the order-5 blocks, per-slot sums
-      OmcWS wb = h->wbig; wb.nB = wg.nB; wb.slot_list = wg.slot_list;
-      if (w.sub_enable) MAYBE_TIMED(sm, OMC_KERNEL_CONESUB, gact, omc_launch_cone_sub(&wg, sm));
-      if (wb.sub_enable) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, 0, omc_launch_cone_sub(&wb, sb));
-      wb.mw_budget = mw_budget[1];
-      if (wb.geo.ws_lpp || wb.geo.mw) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone_ws(&wb, sb));
-      else MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone(&wb, CONE_BIG, sb));
-      if (w.geo.ws_lpp || w.geo.mw) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
-      else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, sm));
-      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
-      MAYBE_TIMED(sc, OMC_KERNEL_SHOR_MINORS, gact, { omc_shor_launch_minor_pre(&sw, sc); omc_shor_launch_vkeys(&sw, sc); });
-      if (multi) {
-        HIPCHK(hipEventRecord(ev[1], sb)); HIPCHK(hipEventRecord(ev[2], sc));
-        HIPCHK(hipStreamWaitEvent(sm, ev[1], 0)); HIPCHK(hipStreamWaitEvent(sm, ev[2], 0));
-      }
-      MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, sm));
-      MAYBE_TIMED(sm, OMC_KERNEL_SHOR_COLS, gact, omc_shor_launch_cols(&sw, sm));
-      MAYBE_TIMED(sm, OMC_KERNEL_SHOR_MINORS, gact, { omc_shor_launch_minor_post(&sw, sm); omc_shor_launch_reduce(&sw, sm); });
-      return 0;
-    }
-    if (split) {      // on the small-cone stream, behind k_small (a fifth stream would share a hardware queue with one of the other four: measured, k_small then ran behind it)
-      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
-      OmcWS wA = wg; wA.ws_phase = 1;
-      MAYBE_TIMED(sc, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wA, sc));
-      HIPCHK(hipEventRecord(ev[4], sc));
-    }
-    // the cone workgroups are few (two per CU, long serial phases) and the column waves many: the cone kernel goes first so that its
-    // workgroups are resident when the column kernel floods the wave slots
-    if (w.sub_enable) MAYBE_TIMED(sm, OMC_KERNEL_CONESUB, gact, omc_launch_cone_sub(&wg, sm));
-    MAYBE_TIMED(sb, OMC_KERNEL_COLPROX, (int64_t)gact * w.m, omc_launch_colprox(&wg, 0, sb));
-    if (split) {
-      HIPCHK(hipStreamWaitEvent(sm, ev[4], 0));
-      OmcWS wB = wg; wB.ws_phase = 2;
-      MAYBE_TIMED(sm, OMC_KERNEL_CONE, 0, omc_launch_cone_ws(&wB, sm));
-    }
-    else if (w.geo.ws_lpp || w.geo.mw) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
-    else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, sm));
-    if (!split) MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
-    if (multi) {
-      HIPCHK(hipEventRecord(ev[1], sb)); HIPCHK(hipEventRecord(ev[2], sc));
-      HIPCHK(hipStreamWaitEvent(sm, ev[1], 0)); HIPCHK(hipStreamWaitEvent(sm, ev[2], 0));
-    }
-    MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, sm));
-    if (with_aa) MAYBE_TIMED(sm, OMC_KERNEL_ACCEL, gact, omc_launch_aa(&wg, sm));
-    return 0;
-  };
-  // nodes appended while every slot was idle (or while the loop was about to end): hand them to idle slots
-  auto refill_idle = [&]() -> int {
-    if (next >= Btot) return 0;
-    std::fill(init2.begin(), init2.end(), 0); std::fill(fin2.begin(), fin2.end(), 0);
-    int rc = gram_jobs_free(); if (rc) return rc;
-    int ninit2 = 0;
-    for (int b = 0; b < S && next < Btot; ++b) if (node_of[b] < 0) { jobs[2 * ninit2] = b; jobs[2 * ninit2 + 1] = next; node_of[b] = next++; init2[b] = 1; parked[b] = 0; ++ninit2; }
-    if (!ninit2) return 0;
-    rc = gram_launch(ninit2); if (rc) return rc;
-    rc = push_flags(init2, fin2, false); if (rc) return rc;
-    if (shor) omc_shor_launch_setup(&sw, s);       // as at the start and at a harvest: the Shor state of the slot, before the base setup clears the init flags
-    TIMED(OMC_KERNEL_SETUP, ninit2, omc_launch_setup(&w, s));
-    rc = gram_join(); if (rc) return rc;
-    mw_budget[0] = mw_budget[1] = MAX_SWEEPS;
-    quiet = false;
-    recount();
-    rc = push_list(); if (rc) return rc;
-    wait_main = true;
-    return 0;
-  };
-  // An asynchronous harvest (omc_harvest_plan): its slots stay parked with their node until the next check books and refills them
-  std::vector<char> inflight(S, 0); int npend = 0;
-  bool ev_main_set = false;      // ev_main has been recorded for the next iteration already (ahead of the harvest kernels)
-  auto enqueue_harvest = [&](int nslots) {
-    TIMED(OMC_KERNEL_HARVEST, nslots, {
-      if (w.save_to) omc_launch_state_save(&w, s);                              // warm-start pool: before the recovery overwrites the iterate U = Q Vt
-      if (shor) omc_shor_launch_state_save(&sw, s);                             // its Shor extension (no-op without indices)
-      omc_launch_small(&w, SMALL_RECOVER, s);   // a U with U U' <= Y and the same Q'U
-      if (w.sep_done) omc_launch_sep_sub(&w, s);                                // separation vector from the tracked block where there is one
-      omc_launch_cone(&w, CONE_SEP, s);           // separation vector (OMC.jl:2466-2477)
-      omc_launch_harvest(&w, s);
-      if (shor) omc_shor_launch_harvest(&sw, s);
-    });
-  };
-  // the nodes of harvested_ids, once the stream has been synchronised behind their harvest kernels: the entries they saved to hold their state
-  // from here on, and their results can be fetched
-  auto book_harvested = [&]() {
-    if (w.save_to) {
-      std::lock_guard<std::mutex> lk(h->sig_mu);
-      for (int id : harvested_ids) {
-        const int sv = (size_t)id < h->save_host.size() ? h->save_host[id] : -1;
-        if (sv < 0 || (size_t)sv >= h->pool_sig.size()) continue;
-        if (shor) { h->pool_sig[sv] = h->node_sig[id]; ++h->shor_warm_stats[3]; }
-        else { h->pool_sig[sv] = omc_instance::PoolSig{}; h->pool_sig[sv].kind = 1; }
-      }
-    }
-    std::lock_guard<std::mutex> lk(h->done_mu); h->done_q.insert(h->done_q.end(), harvested_ids.begin(), harvested_ids.end());
-  };
-  for (;;) {
-    if (nactive == 0) {
-      {   // the end of the batch is decided under the lock omc_relax_append takes: a node is either seen here or refused there
-        std::lock_guard<std::mutex> lk(h->append_mu);
-        Btot = h->Btot_live.load();
-        if (timed_out) { int rc = close_unslotted(OMC_ST_TIME); if (rc) return rc; }      // appended after the time limit struck
-        if (next >= Btot) {
-          const double el_idle = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-          if (!h->hold.load() || el_idle > P.time_limit) { h->append_closed = true; break; }
-        }
-      }
-      if (next >= Btot) { std::this_thread::sleep_for(std::chrono::microseconds(100)); continue; }      // held open (omc_relax_hold): wait for the host's next push
-      int rc = refill_idle(); if (rc) return rc;
-      continue;
-    }
-    ++it;
-    const bool is_check = (it % check == 0);
-    if (multi && wait_main && !ev_main_set) HIPCHK(hipEventRecord(h->ev_main, s));
-    ev_main_set = false;
-    // per-kernel HIP-event timing brackets every launch of a sampled iteration (two event records per kernel: ~25 us of queue bubbles per
-    // iteration at small batches); OMC_TIMING_STRIDE=s samples every s-th iteration (averages per launch are over the sampled launches), 0 = none
-    const bool sampled = tun.timing_stride > 0 && (it % tun.timing_stride) == 0;
-    const bool use_graph = multi && nlist <= graph_max && !tun.no_graph && !(sampled && tun.timing_stride > 1) && !mw_any;      // hundreds of launches per call: eager
-    if (gact > 0) {
-      OmcWS wg = w; wg.slot_list = h->bslotlist.as<int>(); wg.nB = nlist; wg.mw_budget = mw_budget[0];
-      if (multi && wait_main) HIPCHK(hipStreamWaitEvent(sm, h->ev_main, 0));
-      if (use_graph) {
-        if (gexec_n != nlist) {      // (re)capture: one graph without and one with the acceleration kernel at its end
-          for (int q = 0; q < 2; ++q) { if (gexec[q]) { (void)hipGraphExecDestroy(gexec[q]); gexec[q] = nullptr; } }
-          for (int q = 0; q < (w.accel ? 2 : 1); ++q) {
-            hipGraph_t gr = nullptr;
-            HIPCHK(hipStreamBeginCapture(sm, hipStreamCaptureModeThreadLocal));
-            int rc = body(wg, false, q == 1, true);
-            hipError_t ce = hipStreamEndCapture(sm, &gr);
-            if (rc) { if (gr) (void)hipGraphDestroy(gr); return rc; }
-            HIPCHK(ce);
-            hipError_t ie = hipGraphInstantiate(&gexec[q], gr, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(gr);
-            HIPCHK(ie);
-          }
-          gexec_n = nlist;
-        }
-        const int q = (!is_check && w.accel) ? 1 : 0;
-        HIPCHK(hipGraphLaunch(gexec[q], sm));
-        h->launches[OMC_KERNEL_GLOBAL] += 1; h->units[OMC_KERNEL_GLOBAL] += gact;
-      } else {
-        if (quiet && split_solve && (it - 1) % check == 0) h->host_cnt[OMC_HOST_QUIET_INTERVALS] += 1;
-        int rc = body(wg, sampled, !is_check && w.accel, false); if (rc) return rc;
-      }
-      if (multi && is_check) { HIPCHK(hipEventRecord(h->gev[3], sm)); HIPCHK(hipStreamWaitEvent(s, h->gev[3], 0)); }
-    }
-    wait_main = false;
-    if (drain_pool >= 0) {      // the timing events of the interval before the last check, now that the device has the next iteration to run
-      stamp_begin(); finish_events(h, drain_pool); drain_pool = -1; stamp(OMC_HOST_EVENT_DRAIN);
-    }
-    if (!is_check) continue;
-    wait_main = true;
-    const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    timed_out = el > P.time_limit;
-    TIMED(OMC_KERNEL_CHECK_COL, nactive, {
-      if (shor) omc_shor_launch_check(&sw, s);      // primal value, constants and the dense multiplier of the Shor program
-      else { omc_launch_check_zero(&w, s); omc_launch_colprox(&w, 1, s); }
-    });
-    TIMED(OMC_KERNEL_CHECK_BUILD, nactive, omc_launch_check_build(&w, s));
-    TIMED(OMC_KERNEL_CHECK, nactive, {
-      if (w.cert_enable) {        // estimate by the tracked block, decisions, rigorous evaluation of the slots that are about to finish
-        omc_launch_cert_sub(&w, s);
-        omc_launch_check_final(&w, timed_out ? OMC_ST_TIME : 0, 0, s);
-        OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, s);
-        omc_launch_check_final(&w, timed_out ? OMC_ST_TIME : 0, 1, s);
-      } else {
-        if (w.geo.ws_lpp || w.geo.mw) { OmcWS wc = w; wc.ws_mode = 1; omc_launch_cone_ws(&wc, s); }
-        else omc_launch_cone(&w, CONE_EVALS, s);
-        omc_launch_check_final(&w, timed_out ? OMC_ST_TIME : 0, 2, s);      // per-slot iteration cap is applied on the device
-      }
-      if (w.bump_max > 0) { if (shor) omc_shor_launch_rescale(&sw, s); omc_launch_rho_rescale(&w, s); }
-      if (w.accel) omc_launch_aa(&w, s);      // after the certificate (computed on an image of the map), skips finished slots
-    });
-    stamp_begin();
-    const bool track_quiet = split_solve && tun.ws_quiet && w.ws_need;
-    done[S] = 1;
-    HIPCHK(hipMemcpyAsync(done, w.done, sizeof(int) * ((size_t)S + (track_quiet ? 1 : 0)), hipMemcpyDeviceToHost, s));      // with w.ws_need behind the flags
-    if (track_quiet) HIPCHK(hipMemsetAsync(w.ws_need, 0, sizeof(int), s));      // ahead of everything the next interval runs
-    HIPCHK(hipStreamSynchronize(s));
-    stamp(OMC_HOST_CHECK_WAIT);
-    bool quiet_next = track_quiet && done[S] == 0;
-    const auto t_check = t_last;
-    { int rc = mw_collect(); if (rc) return rc; }
-    // every timed launch of the interval has joined s (the side streams join sm before k_global, sm joins s at a check) and so has completed:
-    // its pool is read once the next iteration is enqueued; what is launched from here on records into the other pool, which is empty
-    if (drain_pool >= 0) { finish_events(h, drain_pool); drain_pool = -1; }
-    drain_pool = h->ev_cur; h->ev_cur ^= 1;
-    Btot = h->Btot_live.load();
-    if (P.first_wins) {   // the first certified node ends the batch (penalty autotune): everything still running is harvested as it stands
-      std::vector<int> stv(S);
-      HIPCHK(hipMemcpyAsync(stv.data(), w.status, sizeof(int) * S, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      bool won = false;
-      for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && done[b] && stv[b] == OMC_ST_OPTIMAL) won = true;
-      if (won) {
-        for (int b = 0; b < S; ++b) done[b] = 1;
-        HIPCHK(hipMemcpyAsync(w.done, done, sizeof(int) * S, hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        int rc = close_unslotted(OMC_ST_SLOW); if (rc) return rc;
-      }
-    }
-    // an asynchronous harvest of the previous check: the wait above was also the wait for its kernels (s is in order), so its nodes are
-    // booked and its slots refilled now -- a node still starts at a check boundary, one interval later than after a synchronous harvest
-    int nrefilled = 0;
-    if (npend) {
-      harvested += npend; h->nodes_done.store(harvested);
-      std::fill(init2.begin(), init2.end(), 0); std::fill(fin2.begin(), fin2.end(), 0);
-      int rc = gram_jobs_free(); if (rc) return rc;
-      harvested_ids.clear();
-      for (int b = 0; b < S; ++b) {
-        if (!inflight[b]) continue;
-        inflight[b] = 0; parked[b] = 0;
-        harvested_ids.push_back(node_of[b]);
-        if (next < Btot && !timed_out) { jobs[2 * nrefilled] = b; jobs[2 * nrefilled + 1] = next; node_of[b] = next++; init2[b] = 1; done[b] = 0; ++nrefilled; }
-        else node_of[b] = -1;
-      }
-      npend = 0;
-      book_harvested();
-      stamp(OMC_HOST_HARVEST_BOOK);
-      rc = gram_launch(nrefilled); if (rc) return rc;
-      rc = push_flags(init2, fin2, false); if (rc) return rc;      // the new nodes and their init flags; the fin flags of the harvest are cleared
-      if (nrefilled) { if (shor) omc_shor_launch_setup(&sw, s); TIMED(OMC_KERNEL_SETUP, nrefilled, omc_launch_setup(&w, s)); mw_budget[0] = mw_budget[1] = MAX_SWEEPS; quiet_next = false; }
-      rc = gram_join(); if (rc) return rc;
-      stamp(OMC_HOST_SETUP_ENQUEUE);
-    }
-    // harvest finished slots, hand them the next pending nodes (when and how: omc_harvest_plan)
-    std::fill(init.begin(), init.end(), 0); std::fill(fin.begin(), fin.end(), 0);
-    int nfin = 0, nlive = 0, nnew = 0;
-    for (int b = 0; b < S; ++b) {
-      if (node_of[b] < 0) continue;
-      if (done[b]) { ++nfin; if (!parked[b]) { parked[b] = 1; ++nnew; } } else ++nlive;
-    }
-    ++check_index;
-    int plan = omc_harvest_plan(nlive, nfin, next < Btot ? 1 : 0, check_index, tun.harvest_async ? tun.harvest_async_min_live : 0);
-    // the synchronous path where the stall buys something or the end of the batch is near: one stream, the time limit, first_wins, and idle
-    // slots that pending nodes are about to take (refill_idle sets them up on the main stream, which the next iteration then waits for)
-    if (plan == OMC_HARVEST_ASYNC && (!multi || timed_out || P.first_wins || (next < Btot && nfin + nlive < S))) plan = OMC_HARVEST_SYNC;
-    if (plan == OMC_HARVEST_NONE) nfin = 0;
-    stamp(OMC_HOST_CHECK_SCAN);
-    bool list_pushed = false;
-    if (plan == OMC_HARVEST_ASYNC) {
-      for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && done[b]) { fin[b] = 1; inflight[b] = 1; ++npend; }      // they stay parked: out of the slot list, done on the device
-      // the slot list and the event the next iteration waits for go ahead of the harvest kernels: nothing a live slot reads is written by them
-      recount();
-      int rc = push_list(); if (rc) return rc;
-      list_pushed = true;
-      stamp(OMC_HOST_LIST);
-      if (multi) { HIPCHK(hipEventRecord(h->ev_main, s)); ev_main_set = true; }
-      rc = push_flags(init, fin, false); if (rc) return rc;
-      stamp(OMC_HOST_HARVEST_FLAGS);
-      enqueue_harvest(npend);
-      stamp(OMC_HOST_HARVEST_ENQUEUE);
-      h->host_cnt[OMC_HOST_ASYNC_HARVESTS] += 1;
-    } else if (nfin) {
-      for (int b = 0; b < S; ++b) if (node_of[b] >= 0 && done[b]) { fin[b] = 1; parked[b] = 0; }
-      // which pending node goes to which finished slot is known now (ascending slots take ascending nodes, as the loop below hands them out)
-      int rc = gram_jobs_free(); if (rc) return rc;
-      int nj = 0;
-      if (!timed_out) for (int b = 0, nx = next; b < S && nx < Btot; ++b) if (fin[b]) { jobs[2 * nj] = b; jobs[2 * nj + 1] = nx++; ++nj; }
-      rc = gram_launch(nj); if (rc) return rc;
-      rc = push_flags(init, fin, false); if (rc) return rc;
-      stamp(OMC_HOST_HARVEST_FLAGS);
-      enqueue_harvest(nfin);
-      stamp(OMC_HOST_HARVEST_ENQUEUE);
-      harvested += nfin; h->nodes_done.store(harvested);
-      int ninit = 0;
-      harvested_ids.clear();
-      for (int b = 0; b < S; ++b) {
-        if (!fin[b]) continue;
-        fin[b] = 0;
-        harvested_ids.push_back(node_of[b]);
-        if (next < Btot && !timed_out) { node_of[b] = next++; init[b] = 1; ++ninit; }
-        else node_of[b] = -1;
-      }
-      rc = push_flags(init, fin, true); if (rc) return rc;      // synchronises the stream: the harvest kernels have written the per-node outputs
-      stamp(OMC_HOST_HARVEST_WAIT);
-      book_harvested();
-      stamp(OMC_HOST_HARVEST_BOOK);
-      if (ninit) { if (shor) omc_shor_launch_setup(&sw, s); TIMED(OMC_KERNEL_SETUP, ninit, omc_launch_setup(&w, s)); mw_budget[0] = mw_budget[1] = MAX_SWEEPS; quiet_next = false; }
-      rc = gram_join(); if (rc) return rc;
-      stamp(OMC_HOST_SETUP_ENQUEUE);
-    }
-    quiet = quiet_next;      // refill_idle below takes it back when it sets slots up
-    recount();
-    if (!list_pushed && (nfin || nnew || nrefilled)) { int rc = push_list(); if (rc) return rc; stamp(OMC_HOST_LIST); }
-    if (next < Btot && !timed_out && nactive < S) { int rc = refill_idle(); if (rc) return rc; }      // appended nodes for slots that had gone idle
-    if (timed_out) { int rc = close_unslotted(OMC_ST_TIME); if (rc) return rc; }
-    {
-      const int q = nfin ? OMC_HOST_HARVEST_TOTAL : OMC_HOST_CHECK_TOTAL;
-      h->host_ms[q] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_check).count(); h->host_cnt[q] += 1;
-    }
-  }
-  { int rc = mw_collect(); if (rc) return rc; }
-  {
-    std::vector<int> sw(S);
-    HIPCHK(hipMemcpyAsync(sw.data(), w.sweeps, sizeof(int) * S, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int v : sw) h->total_sweeps += v;
-    std::vector<int> ss(8 * (size_t)S);
-    HIPCHK(hipMemcpyAsync(ss.data(), w.sub_stat, sizeof(int) * ss.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int q = 0; q < 8; ++q) h->sub_tot[q] = 0;
-    for (int b = 0; b < S; ++b) for (int q = 0; q < 8; ++q) h->sub_tot[q] += ss[8 * b + q];
-    HIPCHK(hipMemsetAsync(w.sub_stat, 0, sizeof(int) * ss.size(), s));
-  }
-  if (shor && h->wbig.sub_enable) {      // tracked-subspace accounting of the big cone (same layout as omc_last_subspace_stats)
-    std::vector<int> ss(8 * (size_t)S);
-    HIPCHK(hipMemcpyAsync(ss.data(), h->wbig.sub_stat, sizeof(int) * ss.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (int q = 0; q < 8; ++q) h->big_sub_tot[q] = 0;
-    for (int b = 0; b < S; ++b) for (int q = 0; q < 8; ++q) h->big_sub_tot[q] += ss[8 * b + q];
-    HIPCHK(hipMemsetAsync(h->wbig.sub_stat, 0, sizeof(int) * ss.size(), s));
-  }
-  HIPCHK(hipGetLastError());
-  if (drain_pool >= 0) finish_events(h, drain_pool);      // the older pool first: the sums are formed in launch order
-  finish_events(h, h->ev_cur);
-  h->last_solve_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  h->last_iters_total = it;
-  if (tun.host_phases) {
-    static const char* const nm[OMC_HOST_NPHASE] = {"check_wait", "check_scan", "list", "event_drain", "harvest_flags", "harvest_enqueue", "harvest_wait", "harvest_book", "setup_enqueue", "check_total", "harvest_total", "async_harvests", "quiet_intervals"};
-    fprintf(stderr, "omc host phases (solve %.1f ms, %d iterations):", 1e3 * h->last_solve_seconds, it);
-    for (int q = 0; q < OMC_HOST_NPHASE; ++q) fprintf(stderr, " %s %.3f ms / %lld", nm[q], h->host_ms[q], (long long)h->host_cnt[q]);
-    fprintf(stderr, "\n");
-  }
-  (void)harvested;
   return 0;
 }
 
