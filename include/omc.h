@@ -275,6 +275,64 @@ int omc_relax_append_shor(omc_instance* h, int B, const int* L, const double* cu
                           const int* load_from, const int* save_to);
 int omc_relax_fetch_done_shor(omc_instance* h, int n_ids, const int* node_ids, double* X, double* W, double* Theta);
 
+/* ---- certificates: the multipliers behind a node's dual_bound, exported so that a host can re-evaluate the bound on its own -------------------
+ * No counterpart in the reference (quirk Q2: it takes the primal value as node bound).  Base (disjunctive) mode, rank k <= 8, every cut type,
+ * default or caller-supplied U bounds.  Off by default; with it off nothing is allocated and no kernel is added to a solve.
+ *
+ * Rows of a node, in this order (OMC.jl:1558-1683; the order of omc_relax_stage's host code and of the multipliers lam below):
+ *   trace                          tr Y <= k                                                                     (1 row; its lam entry is unused)
+ *   box, j = 0..k-1 outer, i inner -U_ij <= -lower_ij where lower_ij > -1 (`lo`), then U_ij <= upper_ij where upper_ij < 1 (`hi`)
+ *   per cut l, per column j        x'U_j <= hi_j, then -x'U_j <= -lo_j  (piece table OMC.jl:1580-1678), and after the k columns the
+ *   aggregated row                 x'Y x - sum_j slope_j x'U_j <= sum_j intercept_j                              (OMC.jl:1680-1683)
+ * Every row reads <CY_r, Y> + <CU_r, U> <= rhs_r with CY_r = x x' for an aggregated row and 0 otherwise (the trace row stays in the simple set).
+ * Q (n x r, orthonormal columns) spans the columns of every CU_r: modified Gram-Schmidt, twice, over the normalised nonzero columns in row
+ * order, a vector kept when what is left of it exceeds 1e-10.
+ *
+ * Certificate of a node:
+ *   Lam    nnz doubles, the instance's order (columns in order, observed rows ascending): the exact multipliers alpha_j = (I + gamma Y[O,O])^-1 a_j
+ *          of the check (k_colprox mode 1); as a matrix Lam is n x m, zero off the support
+ *   lam    R doubles (>= 0), one per row
+ *   Q, r   the row basis
+ *   Psi3   order r + k, symmetric, column-major with leading dimension r + k: rho [[Q3_11, Q3_12], [Q3_12', Q3_22]], Q3 = P_+(M3) - M3 the
+ *          multiplier direction of the small cone [Q'YQ Q'U; U'Q I] >= 0, rho the penalty in force at that check
+ *   bound  the value these multipliers give:
+ *            M     = -gamma/2 Lam Lam' + sum_{aggregated rows} lam_r x_r x_r' - Q Psi3[0:r,0:r] Q'
+ *            c_j   = (Q' sum_{r != trace} lam_r CU_r)_j - 2 Psi3[0:r, r+j]                                         (j = 0..k-1)
+ *            bound = <A, Lam> - 1/2 ||Lam||_F^2 + sum_{i<k} min(eig_i(M), 0) - sum_j ||c_j|| - sum_{r != trace} lam_r rhs_r - tr Psi3[r:, r:]
+ *          (eig_i ascending).  It is a lower bound on the relaxation optimum for ANY Lam with support in Omega, lam >= 0 and Psi3 >= 0:
+ *          Fenchel's inequality for f, weak duality for the rows and the cone, and the minimum of the Lagrangian over the superset
+ *          {0 <= Y <= I, tr Y <= k} x {||(Q'U)_j|| <= 1}.
+ * Snapshot rule: a node's dual_bound is the largest RIGOROUS bound over its checks, which need not be the last one.  With certificates kept,
+ * the check that raises the reported bound copies its multipliers (with the penalty of that check, before a bump decided at the same check
+ * rescales anything), so the certificate fetched for a node is the one of the check that gave its dual_bound.
+ *
+ *   omc_relax_keep_certificates   on != 0: the omc_relax_stage calls that follow keep them (per slot 8 (2 + nnz + Rmax + (rmax + k)^2) + 8 bytes,
+ *       per node of the capacity -- staged + omc_relax_reserve -- out[4] of omc_certificate_plan at the staged strides).  Refused
+ *       (OMC_ERR_ARGUMENT) while a submitted solve runs.  While it is on omc_relax_stage_shor returns OMC_ERR_UNSUPPORTED.
+ *   omc_relax_fetch_certificate   for node ids that omc_relax_fetch_done has returned (while the solve runs) or that the ended solve has
+ *       harvested (everything omc_relax_fetch returns).  Output i belongs to node_ids[i]; strides nnz (Lam), Rmax (lam), n * rmax (Q),
+ *       (rmax + k)^2 (Psi3), with Rmax = info[7] and rmax = info[3] of omc_last_solver_info; R[i] and r[i] say how much of a stride is used (Q:
+ *       n * r[i] doubles, Psi3: (r[i] + k)^2, both at the head of the stride).  Any output may be NULL.  OMC_ERR_ARGUMENT with a message for
+ *       a batch staged without certificates, an id out of range or not finished, and a node that never reached a rigorous check.
+ *   omc_certificate_plan          host only, no handle: out[6] = strides of Lam, lam, Q, Psi3 in doubles, bytes the arena holds per node, rmax --
+ *       for nodes with at most max_cuts cuts and nonstandard_box_rows box rows beyond the k (k + 1) / 2 of the default bounds:
+ *       Rmax = 1 + k (k + 1) / 2 + nonstandard_box_rows + max_cuts (2 k + 1), rmax = max(1, min(n, k + nonstandard_box_rows + max_cuts)).
+ *       These are what a batch of such nodes is staged with unless its row vectors are linearly dependent (then rmax is smaller).
+ *   omc_dual_bound_batch          the bound above for B nodes and caller-supplied multipliers, on the device: rows and Q on the host as
+ *       omc_relax_stage builds them, the matrix M and the constants by a kernel of its own (Lam Lam' on the matrix cores for n > 144), the k
+ *       smallest eigenvalues by the eigen-kernel a relaxation uses at order n.  The multipliers are evaluated as given (nothing is clamped).
+ *       Strides: nnz, Rmax = the largest row count of the B nodes, n * rmax and (rmax + k)^2 with rmax = max(1, largest r of the B nodes);
+ *       Psi3 per node as above (order r + k at the head of its stride), NULL = zero.  Q_out (n * rmax per node) and r_out (B) may be NULL.
+ *       With Lam, lam, Psi3 and bound all NULL only Q_out / r_out are written, without a device call: a caller gets the basis first and
+ *       forms Psi3 in it.  Stages nothing and leaves a staged batch as it is; refused while a submitted solve runs. */
+int omc_relax_keep_certificates(omc_instance* h, int on);
+int omc_relax_fetch_certificate(omc_instance* h, int n_ids, const int* node_ids, double* Lam, double* lam, int* R, double* Q, int* r,
+                                double* Psi3, double* bound);
+int omc_certificate_plan(int n, int k, int nnz, int max_cuts, int nonstandard_box_rows, int64_t* out);
+int omc_dual_bound_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q1, const int* L, const double* cut_x,
+                         const double* cut_Uhat, const int8_t* cut_dir, const double* U_lower, const double* U_upper, const double* Lam,
+                         const double* lam, const double* Psi3, double* Q_out, int* r_out, double* bound);
+
 /* ---- alternating_minimization (OMC.jl:1979-2279), disjunctive mode, B problems at once, rank k <= 8 --------
  * U_initial n*k per problem; cuts as above (only the per-cut bounds on v = U'x are imposed, OMC.jl:2047-2093);
  * k > 1 adds the pair cones ||U_j1 +- U_j2|| <= sqrt 2 of OMC.jl:2029-2045.

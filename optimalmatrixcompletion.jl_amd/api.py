@@ -7,6 +7,7 @@ backed by the HIP library.  Reference = /root/reference/src/OptimalMatrixComplet
                                                   (add_Shor_valid_inequalities = true, rank 1)
     .reserve / .append / .fetch_done / .hold      nodes pushed into a staged or running batch as their parents finish (the queue of OMC.jl:700-719);
     .reserve_shor / .append_shor / .fetch_done_shor   the same for a Shor-mode batch (rank 1)
+    .keep_certificates / .fetch_certificate       the multipliers behind a node's dual_bound, for certificate.py (numpy) or .dual_bound (device) to re-evaluate
     .matrix_completion_master_feasible(Y, U)      OMC.jl:1261-1277
     .breakpoint_vectors(Y, U, breakpoints)        OMC.jl:2466-2477
     .evaluate_objective(X)                        OMC.jl:2330-2359
@@ -22,7 +23,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, certificate
 from ._lib import RelaxParams, OmcError
 
 CUT_TYPES = {"linear": 0, "linear2": 1, "linear3": 2}
@@ -136,6 +137,13 @@ def colprox_plan(n, cmax, block_min=65):
     out = np.zeros(5, np.int64)
     _lib.check(_lib.load().omc_colprox_plan(int(n), int(cmax), int(block_min), _lib.ptr(out)))
     return dict(lds_cmax=int(out[0]), lds_bytes=int(out[1]), slab_doubles=int(out[2]), workgroups_per_cu=int(out[3]), block=bool(out[4]))
+
+
+def certificate_plan(n, k, nnz, max_cuts=0, nonstandard_box_rows=0):
+    """omc_certificate_plan (host only, no GPU): strides of a certificate in doubles, bytes the arena holds per node, rmax."""
+    out = np.zeros(6, np.int64)
+    _lib.check(_lib.load().omc_certificate_plan(int(n), int(k), int(nnz), int(max_cuts), int(nonstandard_box_rows), _lib.ptr(out)))
+    return dict(Lam=int(out[0]), lam=int(out[1]), Q=int(out[2]), Psi3=int(out[3]), bytes_per_node=int(out[4]), rmax=int(out[5]))
 
 
 class Engine:
@@ -471,6 +479,106 @@ class Engine:
         _lib.check(self._lib.omc_last_solver_info(self._h, _lib.ptr(info)))
         return dict(solve_seconds=info[0], jacobi_sweeps=int(info[1]), rho=info[2], r_max=int(info[3]), cone_lds=bool(info[4]),
                     global_lds=bool(info[5]), small_lds=bool(info[6]), R_max=int(info[7]))
+
+    # ---- certificates (include/omc.h "certificates"; the checker is certificate.py) -------------------------------
+    def keep_certificates(self, on=True):
+        """The stage() calls that follow keep, per node, the multipliers of the check that gave its dual_bound (omc_relax_keep_certificates).
+        Refused while a submitted solve runs; stage_shor raises OMC_ERR_UNSUPPORTED while it is on."""
+        _lib.check(self._lib.omc_relax_keep_certificates(self._h, 1 if on else 0))
+
+    def certificate_plan(self, max_cuts=0, nonstandard_box_rows=0):
+        """Strides and bytes per node of the certificates of this instance (omc_certificate_plan, host only)."""
+        return certificate_plan(self.n, self.k, int(self.indices.sum()), max_cuts, nonstandard_box_rows)
+
+    def _support(self):
+        cols, rows = np.nonzero(self.indices.T)      # the library's nnz order: columns in order, rows ascending
+        return rows, cols
+
+    def fetch_certificate(self, ids):
+        """certificate.Certificate of every node id (omc_relax_fetch_certificate): ids that fetch_done() has returned while the solve runs, or
+        any node of fetch() after it.  Raises OmcError for a batch staged without keep_certificates(), an unfinished id, and a node that
+        never reached a rigorous check."""
+        n, m, k = self.n, self.m, self.k
+        idv = np.ascontiguousarray(np.asarray(list(ids), dtype=np.int32))
+        c = len(idv)
+        info = self.solver_info()
+        Rmax, rmax = max(info["R_max"], 1), max(info["r_max"], 1)
+        rows, cols = self._support()
+        nnz = rows.size
+        ps = (rmax + k) ** 2
+        Lam = np.zeros((max(c, 1), max(nnz, 1))); lam = np.zeros((max(c, 1), Rmax)); R = np.zeros(max(c, 1), np.int32)
+        Q = np.zeros((max(c, 1), n * rmax)); r = np.zeros(max(c, 1), np.int32); Psi = np.zeros((max(c, 1), ps)); bd = np.zeros(max(c, 1))
+        if nnz:
+            Lam = np.zeros((max(c, 1), nnz))
+        _lib.check(self._lib.omc_relax_fetch_certificate(self._h, c, _lib.ptr(idv), _lib.ptr(Lam), _lib.ptr(lam), _lib.ptr(R), _lib.ptr(Q),
+                                                         _lib.ptr(r), _lib.ptr(Psi), _lib.ptr(bd)))
+        out = []
+        for i in range(c):
+            ri = int(r[i]); N3 = ri + k
+            dense = np.zeros((n, m)); dense[rows, cols] = Lam[i, :nnz]
+            out.append(certificate.Certificate(Lam=dense, lam=lam[i, :int(R[i])].copy(), Q=Q[i, :n * ri].reshape((n, ri), order="F").copy(),
+                                               Psi3=Psi[i, :N3 * N3].reshape((N3, N3), order="F").copy(), bound=float(bd[i])))
+        return out
+
+    def _bounds_flat(self, B, U_lower, U_upper):
+        lo = hi = None
+        if U_lower is not None:
+            lo = np.ascontiguousarray(np.stack([np.asfortranarray(np.asarray(u, float)).ravel(order="F") for u in U_lower]))
+        if U_upper is not None:
+            hi = np.ascontiguousarray(np.stack([np.asfortranarray(np.asarray(u, float)).ravel(order="F") for u in U_upper]))
+        for a in (lo, hi):
+            if a is not None and a.shape != (B, self.n * self.k):
+                raise ValueError("U_lower / U_upper: one (n, k) matrix per node")
+        return lo, hi
+
+    def row_basis(self, nodes, disjunctive_cuts_type="linear", U_lower=None, U_upper=None, reference_quirk_q1=True):
+        """The row basis Q (n x r) the library builds for every node (omc_dual_bound_batch without multipliers: host only, no device call)."""
+        n, k, B = self.n, self.k, len(nodes)
+        L, cx, cU, cd = _pack_cuts(nodes, n, k, disjunctive_cuts_type)
+        lo, hi = self._bounds_flat(B, U_lower, U_upper)
+        args = (self._h, B, CUT_TYPES[disjunctive_cuts_type], int(bool(reference_quirk_q1)), _lib.ptr(L), _lib.ptr(cx), _lib.ptr(cU), _lib.ptr(cd),
+                _lib.ptr(lo), _lib.ptr(hi), None, None, None)
+        r = np.zeros(B, np.int32)
+        _lib.check(self._lib.omc_dual_bound_batch(*args, None, _lib.ptr(r), None))
+        rmax = max(1, int(r.max()))
+        Q = np.zeros((B, n * rmax))
+        _lib.check(self._lib.omc_dual_bound_batch(*args, _lib.ptr(Q), _lib.ptr(r), None))
+        return [Q[b, :n * int(r[b])].reshape((n, int(r[b])), order="F").copy() for b in range(B)]
+
+    def dual_bound(self, nodes, certs, disjunctive_cuts_type="linear", U_lower=None, U_upper=None, reference_quirk_q1=True):
+        """The Lagrangian bound of certs[b] (certificate.Certificate: Lam n x m, lam, Q, Psi3) for nodes[b], evaluated on the device as the
+        multipliers are (omc_dual_bound_batch): no sanitising -- certificate.dual_bound is the checker.  Psi3 must be expressed in the basis
+        row_basis() returns (the Q of a fetched certificate is that basis).  Returns the B bounds."""
+        n, m, k, B = self.n, self.m, self.k, len(nodes)
+        if len(certs) != B:
+            raise ValueError("one certificate per node")
+        L, cx, cU, cd = _pack_cuts(nodes, n, k, disjunctive_cuts_type)
+        lo, hi = self._bounds_flat(B, U_lower, U_upper)
+        dlo, dhi = certificate.default_U_bounds(n, k)
+        Rb = []
+        for b in range(B):
+            lb_ = dlo if lo is None else lo[b]; hb_ = dhi if hi is None else hi[b]
+            Rb.append(1 + int((np.asarray(lb_) > -1.0).sum()) + int((np.asarray(hb_) < 1.0).sum()) + int(L[b]) * (2 * k + 1))
+        rb = [int(np.asarray(c.Q).shape[1]) for c in certs]
+        Rmax, rmax = max(Rb), max(1, max(rb))
+        rows, cols = self._support()
+        nnz = rows.size
+        ps = (rmax + k) ** 2
+        Lam = np.zeros((B, max(nnz, 1))); lam = np.zeros((B, Rmax)); Psi = np.zeros((B, ps))
+        for b, c in enumerate(certs):
+            if np.asarray(c.Lam).shape != (n, m) or len(c.lam) != Rb[b] or np.asarray(c.Psi3).shape != (rb[b] + k, rb[b] + k):
+                raise ValueError(f"certificate {b}: Lam must be n x m, lam hold {Rb[b]} multipliers and Psi3 be of order r + k")
+            Lam[b, :nnz] = np.asarray(c.Lam, float)[rows, cols]; lam[b, :Rb[b]] = c.lam
+            Psi[b, :(rb[b] + k) ** 2] = np.asarray(c.Psi3, float).ravel(order="F")
+        r = np.zeros(B, np.int32); bd = np.zeros(B)
+        _lib.check(self._lib.omc_dual_bound_batch(self._h, B, CUT_TYPES[disjunctive_cuts_type], int(bool(reference_quirk_q1)), _lib.ptr(L), _lib.ptr(cx),
+                                                  _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(lo), _lib.ptr(hi), None, None, None, None, _lib.ptr(r), None))
+        if [int(v) for v in r] != rb:
+            raise ValueError(f"Q of the certificates has {rb} columns, the library's row basis {[int(v) for v in r]}: build Psi3 in the basis of row_basis()")
+        _lib.check(self._lib.omc_dual_bound_batch(self._h, B, CUT_TYPES[disjunctive_cuts_type], int(bool(reference_quirk_q1)), _lib.ptr(L), _lib.ptr(cx),
+                                                  _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(Lam), _lib.ptr(lam), _lib.ptr(Psi),
+                                                  None, None, _lib.ptr(bd)))
+        return bd
 
     # ---- multi-GPU exchange behind the C ABI (RCCL; SURVEY.md 8e) ------------------------------------------------
     @staticmethod

@@ -596,6 +596,18 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
     w.oobj = os; w.olb = os + sN; w.olmin = os + 2 * sN; w.orho = os + 4 * sN;
     w.ostatus = h->boint.as<int>(); w.oiters = h->boint.as<int>() + sN;
   }
+  if (h->keep_cert && !shor) {      // best certificate per node: slot buffers and the arena of the nodes, zeroed (no slot and no node holds one)
+    const size_t ps = (size_t)(rmax + k) * (rmax + k), per = (size_t)h->nnz + Rmax + ps;
+    ENS(h->bcbD, sB * (2 + per) * 8); ENS(h->bcbI, sB * 2 * sizeof(int)); ENS(h->bocD, sN * (1 + per) * 8); ENS(h->bocI, sN * sizeof(int));
+    HIPCHK(hipMemsetAsync(h->bcbD.p, 0, sB * (2 + per) * 8, h->stream)); HIPCHK(hipMemsetAsync(h->bcbI.p, 0, sB * 2 * sizeof(int), h->stream));
+    HIPCHK(hipMemsetAsync(h->bocD.p, 0, sN * (1 + per) * 8, h->stream)); HIPCHK(hipMemsetAsync(h->bocI.p, 0, sN * sizeof(int), h->stream));
+    double* cb = h->bcbD.as<double>();
+    w.cb_rho = cb; w.cbBound = cb + sB; w.cbLam = cb + 2 * sB; w.cblam = w.cbLam + sB * h->nnz; w.cbPsi = w.cblam + sB * Rmax;
+    w.cert_flag = h->bcbI.as<int>(); w.cert_have = w.cert_flag + sB;
+    double* oc = h->bocD.as<double>();
+    w.ocBound = oc; w.ocLam = oc + sN; w.oclam = w.ocLam + sN * h->nnz; w.ocPsi = w.oclam + sN * Rmax;
+    w.ocHave = h->bocI.as<int>();
+  }
   // warm-start indices of this batch (consumed: they belong to this stage call only)
   w.load_from = nullptr; w.save_to = nullptr;
   if (h->pool_cap > 0 && (!shor || h->shor_warm) && extra_nodes > 0) {      // appended nodes may name pool entries: both index arrays exist, -1 where nothing was given
@@ -1157,6 +1169,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
   if (B <= 0) return fail(OMC_ERR_ARGUMENT, "B must be positive");
   if (!n_shor || !n_soc) return fail(OMC_ERR_ARGUMENT, "n_shor / n_soc is NULL");
+  if (h->keep_cert) return fail(OMC_ERR_UNSUPPORTED, "omc_relax_stage_shor: certificates are kept (omc_relax_keep_certificates) and the Shor-mode bound has multipliers the certificate layout does not hold");
   const int n = h->n, m = h->m;
   if ((long long)n * m >= (1ll << 30)) return fail(OMC_ERR_UNSUPPORTED, "Shor mode: n * m too large for the 32-bit index structures");
   // ---- group the nodes by identical lists ------------------------------------------------------------------------------------------
@@ -1537,6 +1550,140 @@ int omc_relax_fetch_done_shor(omc_instance* h, int n_ids, const int* node_ids, d
     if (Theta) HIPCHK(hipMemcpyAsync(Theta + i * mm, h->sh.oTh + nb * mm, 8 * mm, hipMemcpyDeviceToHost, fs));
   }
   HIPCHK(hipStreamSynchronize(fs));
+  return 0;
+}
+
+// ---- best certificate per node (omc.h: "certificates") ------------------------------------------------------------------------------------
+// The request applies to the stage calls that follow: they allocate the slot buffers and the arena (OmcWS::cert_flag ...), and the kernels
+// that already run test the pointer.  Off: nothing is allocated and no kernel is added to a solve.
+int omc_relax_keep_certificates(omc_instance* h, int on) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
+  if (h->worker.joinable() || h->worker_running.load()) return fail(OMC_ERR_ARGUMENT, "omc_relax_keep_certificates: a solve is in flight (call omc_relax_wait first)");
+  h->keep_cert = on != 0;
+  return 0;
+}
+
+int omc_certificate_plan(int n, int k, int nnz, int max_cuts, int nonstandard_box_rows, int64_t* out) {
+  if (!out) return fail(OMC_ERR_ARGUMENT, "out is NULL");
+  if (n <= 0 || k <= 0 || nnz < 0 || max_cuts < 0 || nonstandard_box_rows < 0) return fail(OMC_ERR_ARGUMENT, "omc_certificate_plan: n and k must be positive, the counts not negative");
+  if (k > 8) return fail(OMC_ERR_UNSUPPORTED, "omc_certificate_plan: rank k > 8 is not supported");
+  const int64_t Rmax = 1 + (int64_t)k * (k + 1) / 2 + nonstandard_box_rows + (int64_t)max_cuts * (2 * k + 1);
+  const int64_t rmax = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)k + nonstandard_box_rows + max_cuts));
+  out[0] = nnz; out[1] = Rmax; out[2] = (int64_t)n * rmax; out[3] = (rmax + k) * (rmax + k);
+  out[4] = 8 * (1 + out[0] + out[1] + out[3]) + 4;      // what the arena holds per node: bound, Lam, lam, Psi3, the flag (Q is part of the node's descriptor)
+  out[5] = rmax;
+  return 0;
+}
+
+int omc_relax_fetch_certificate(omc_instance* h, int n_ids, const int* node_ids, double* Lam, double* lam, int* R, double* Q, int* r,
+                                double* Psi3, double* bound) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
+  if (!h->staged) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: nothing staged");
+  const OmcWS& w = h->ws;
+  if (!w.cert_flag) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: the batch was staged without omc_relax_keep_certificates(h, 1)");
+  if (n_ids < 0 || (n_ids > 0 && !node_ids)) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: bad arguments");
+  if (n_ids == 0) return 0;
+  {      // an id is known once omc_relax_fetch_done has returned it, or once the solve has ended and harvested it
+    bool ended; { std::lock_guard<std::mutex> lk(h->append_mu); ended = h->append_closed; }
+    std::lock_guard<std::mutex> lk(h->done_mu);
+    std::vector<char> seen((size_t)std::max(h->node_cap, 1), 0);
+    const size_t upto = ended ? h->done_q.size() : h->done_read;
+    for (size_t i = 0; i < upto; ++i) if ((size_t)h->done_q[i] < seen.size()) seen[h->done_q[i]] = 1;
+    for (int i = 0; i < n_ids; ++i)
+      if (node_ids[i] < 0 || (size_t)node_ids[i] >= seen.size() || !seen[node_ids[i]])
+        return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: node " + std::to_string(node_ids[i]) + " is out of range or has not finished (omc_relax_fetch_done has not returned it)");
+  }
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->fetch_stream) HIPCHK(hipStreamCreateWithFlags(&h->fetch_stream, hipStreamNonBlocking));
+  hipStream_t fs = h->fetch_stream;
+  std::vector<int> have(n_ids, 0);
+  for (int i = 0; i < n_ids; ++i) HIPCHK(hipMemcpyAsync(&have[i], w.ocHave + node_ids[i], sizeof(int), hipMemcpyDeviceToHost, fs));
+  HIPCHK(hipStreamSynchronize(fs));
+  for (int i = 0; i < n_ids; ++i)
+    if (!have[i]) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: node " + std::to_string(node_ids[i]) + " never reached a rigorous check (no certificate)");
+  const size_t nnz = (size_t)w.nnz, Rm = (size_t)w.Rmax, nq = (size_t)w.n * w.rmax, ps = (size_t)(w.rmax + w.k) * (w.rmax + w.k);
+  for (int i = 0; i < n_ids; ++i) {
+    const size_t nb = (size_t)node_ids[i], o = (size_t)i;
+    if (Lam) HIPCHK(hipMemcpyAsync(Lam + o * nnz, w.ocLam + nb * nnz, 8 * nnz, hipMemcpyDeviceToHost, fs));
+    if (lam) HIPCHK(hipMemcpyAsync(lam + o * Rm, w.oclam + nb * Rm, 8 * Rm, hipMemcpyDeviceToHost, fs));
+    if (R) HIPCHK(hipMemcpyAsync(R + o, w.R + nb, sizeof(int), hipMemcpyDeviceToHost, fs));
+    if (Q) HIPCHK(hipMemcpyAsync(Q + o * nq, w.Qb + nb * nq, 8 * nq, hipMemcpyDeviceToHost, fs));
+    if (r) HIPCHK(hipMemcpyAsync(r + o, w.rr + nb, sizeof(int), hipMemcpyDeviceToHost, fs));
+    if (Psi3) HIPCHK(hipMemcpyAsync(Psi3 + o * ps, w.ocPsi + nb * ps, 8 * ps, hipMemcpyDeviceToHost, fs));
+    if (bound) HIPCHK(hipMemcpyAsync(bound + o, w.ocBound + nb, 8, hipMemcpyDeviceToHost, fs));
+  }
+  HIPCHK(hipStreamSynchronize(fs));
+  return 0;
+}
+
+// The Lagrangian bound of caller-supplied multipliers (omc.h).  Rows and row basis on the host exactly as omc_relax_stage builds them
+// (pack_nodes, put_descriptors) into buffers of its own, k_dual_assemble for the matrix and the constants, then the eigen-kernel a check of a
+// relaxation at this order would take (k_cone_ws LDS- or L2-resident, k_cone at orders 129 - 144, the multi-workgroup kernels from
+// OMC_CONE_MULTI_MIN on) through a private view, cold.  No batch is staged and a staged one is not touched.
+int omc_dual_bound_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q1, const int* L, const double* cut_x, const double* cut_Uhat,
+                         const int8_t* cut_dir, const double* U_lower, const double* U_upper, const double* Lam, const double* lam,
+                         const double* Psi3, double* Q_out, int* r_out, double* bound) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "omc_dual_bound_batch: handle is NULL");
+  if (B <= 0) return fail(OMC_ERR_ARGUMENT, "omc_dual_bound_batch: B must be positive");
+  if (cut_type != OMC_CUT_LINEAR && cut_type != OMC_CUT_LINEAR2 && cut_type != OMC_CUT_LINEAR3)
+    return fail(OMC_ERR_INVALID_ENUM, "Invalid input for disjunctive cuts type: must be linear, linear2 or linear3 (OMC.jl:1456-1462)");
+  const bool query = !Lam && !lam && !Psi3 && !bound;      // rows and basis only
+  if (!query && (!Lam || !lam || !bound)) return fail(OMC_ERR_ARGUMENT, "omc_dual_bound_batch: Lam, lam and bound are needed (all of Lam, lam, Psi3, bound NULL: Q_out / r_out only)");
+  if (h->worker.joinable() || h->worker_running.load()) return fail(OMC_ERR_ARGUMENT, "omc_dual_bound_batch: a solve is in flight on this handle (call omc_relax_wait first)");
+  omc_relax_params P = h->params; P.reference_quirk_q1 = reference_quirk_q1 ? 1 : 0;
+  NodePack pk;
+  { int rcp = pack_nodes(h, P, cut_type, B, L, cut_x, cut_Uhat, cut_dir, U_lower, U_upper, pk); if (rcp) return rcp; }
+  const size_t sB = (size_t)B, n = h->n, m = h->m, k = h->k, nnz = h->nnz, Rmax = pk.Rmax, rmax = pk.rmax, Lmax = std::max(pk.Lmax, 1);
+  if (r_out) for (int b = 0; b < B; ++b) r_out[b] = pk.rrv[b];
+  if (Q_out)
+    for (size_t b = 0; b < sB; ++b) {
+      std::fill(Q_out + b * n * rmax, Q_out + (b + 1) * n * rmax, 0.0);
+      std::copy(pk.Qn[b].begin(), pk.Qn[b].end(), Q_out + b * n * rmax);
+    }
+  if (query) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t NP = (n + 15) & ~(size_t)15, ps = (rmax + k) * (rmax + k);
+  OmcWS w;
+  memset(&w, 0, sizeof(w));
+  w.nB = w.B = w.Btot = B; w.n = (int)n; w.m = (int)m; w.k = (int)k; w.nnz = (int)nnz; w.Rmax = (int)Rmax; w.Lmax = (int)Lmax; w.rmax = (int)rmax;
+  w.np16 = (int)NP; w.max_sweeps = MAX_SWEEPS; w.mw_budget = MAX_SWEEPS; w.gamma = h->gamma; w.clip_hi = 1.0; w.inv_s2 = 1.0;
+  w.col_ptr = h->dcol_ptr.as<int>(); w.col_idx = h->dcol_idx.as<int>(); w.col_val = h->dcol_val.as<double>();
+  w.geo = omc_plan_geometry((int)n, (int)NP, (int)k, (int)rmax, (int)Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
+  // matrices (32-byte rows for the multi-workgroup kernels: every piece is a multiple of 4 doubles)
+  const size_t nn4 = (n * n + 3) & ~(size_t)3;
+  ENS(h->dbM, sB * (2 * NP * NP + nn4) * 8);
+  w.MbufC = h->dbM.as<double>(); w.VrowC = w.MbufC + sB * NP * NP; w.Mchk = w.VrowC + sB * NP * NP;
+  HIPCHK(hipMemsetAsync(h->dbM.p, 0, sB * 2 * NP * NP * 8, s));      // the zero padding of MbufC; VrowC: cold start, and 0 x garbage could be NaN
+  if (w.geo.ws.slab_stride) { ENS(h->dbS, sB * w.geo.ws.slab_stride * 8); w.cone_scratch = h->dbS.as<double>(); }
+  if (n > 144) { ENS(h->dbL, sB * m * n * 8); HIPCHK(hipMemsetAsync(h->dbL.p, 0, sB * m * n * 8, s)); w.lamDX = h->dbL.as<double>(); }
+  // descriptors, multipliers, scratch and the per-node scalars
+  const size_t dcount = sB * (Rmax * k + Rmax + Lmax * n + n * rmax) + sB * (nnz + Rmax + ps + n * rmax) + sB * n * k + 5 * sB;
+  ENS(h->dbD, dcount * 8);
+  double* dp = h->dbD.as<double>();
+  w.rcoef = dp; dp += sB * Rmax * k; w.rrhs = dp; dp += sB * Rmax; w.cutx = dp; dp += sB * Lmax * n; w.Qb = dp; dp += sB * n * rmax;
+  double* dLam = dp; dp += sB * nnz; double* dlam = dp; dp += sB * Rmax; double* dPsi = dp; dp += sB * ps; double* dT1 = dp; dp += sB * n * rmax;
+  w.chk_scratch = dp; dp += sB * n * k;
+  w.c0 = dp; w.cpen = dp + sB; w.cst = dp + 2 * sB; w.fro2c = dp + 3 * sB; w.evsum = dp + 4 * sB;
+  ENS(h->dbI, sB * (2 + 4 * Rmax + 3 + 4) * sizeof(int));
+  int* ip = h->dbI.as<int>();
+  w.R = ip; ip += sB; w.rr = ip; ip += sB; w.rkind = ip; ip += sB * Rmax; w.rcut = ip; ip += sB * Rmax; w.rbi = ip; ip += sB * Rmax; w.rbj = ip; ip += sB * Rmax;
+  w.done = ip; w.vvalidC = ip + sB; w.sweeps = ip + 2 * sB; w.mw_stat = ip + 3 * sB;
+  HIPCHK(hipMemsetAsync(w.done, 0, sB * 7 * sizeof(int), s));
+  { int rc = put_descriptors(w, pk, B, sB, 0, L, cut_x, s); if (rc) return rc; }
+  HIPCHK(hipMemcpyAsync(dLam, Lam, sB * nnz * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dlam, lam, sB * Rmax * 8, hipMemcpyHostToDevice, s));
+  if (Psi3) HIPCHK(hipMemcpyAsync(dPsi, Psi3, sB * ps * 8, hipMemcpyHostToDevice, s));
+  const OmcDualIn in = {dLam, dlam, Psi3 ? dPsi : nullptr, dT1};
+  omc_launch_dual_assemble(&w, &in, s);
+  if (w.geo.ws_lpp || w.geo.mw) { w.ws_mode = 1; omc_launch_cone_ws(&w, s); }
+  else omc_launch_cone(&w, CONE_EVALS, s);
+  HIPCHK(hipGetLastError());
+  std::vector<double> sc(5 * sB);
+  HIPCHK(hipMemcpyAsync(sc.data(), w.c0, 5 * sB * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  for (size_t b = 0; b < sB; ++b) bound[b] = sc[b] + sc[4 * sB + b] - sc[sB + b] + sc[2 * sB + b];      // c0 + evsum - cpen + cst, the order of k_check_final
   return 0;
 }
 

@@ -288,7 +288,8 @@ __device__ __forceinline__ void colprox_block_body(const OmcWS& w, const int mod
     if (tid == 0) { w.sval[(size_t)b * w.m + j] = s; if (w.cp_nfact) w.cp_nfact[(size_t)b * w.m + j] = nfact; }
   } else {
     gather(0.0);
-    if (!factor()) {  // Y not PSD enough on this block: report +inf objective contribution
+    if (!factor()) {  // Y not PSD enough on this block: report +inf objective contribution; the column's multiplier is 0, not what the slot held before
+      for (int p = tid; p < c; p += 256) { alpha[p] = 0.0; if (w.lamDX) w.lamDX[((size_t)b * w.m + j) * n + sidx[p]] = 0.0; }
       if (tid == 0) { w.objcol[(size_t)b * w.m + j] = 1e300; w.c0col[(size_t)b * w.m + j] = 0.0; if (w.cp_nfact) w.cp_nfact[(size_t)b * w.m + j] = 1; }
       return;
     }

@@ -155,8 +155,18 @@ struct OmcWS {
   double *aa_F, *aa_G, *aa_zin;   // B*(aa_mem+1)*aa_dim, same, B*aa_dim
   double* aa_fn;                  // B: residual norm of the last plain step while a point awaits verification
   int *aa_hist, *aa_head, *aa_pending, *aa_valid, *aa_nacc, *aa_nrej;   // B each; aa_valid = 0 requests "copy the state into zin, forget history"
+  // Best certificate per node (omc_relax_keep_certificates; every pointer NULL when off).  k_check_final sets cert_flag[b] and notes the bound
+  // and the penalty of this check when its RIGOROUS bound raised lb[b]; k_cert_snapshot then copies the multipliers behind that bound (alphaX,
+  // lam, rho x the three blocks of Q3 as one order-(r + k) matrix) into the slot's cb* buffers, before k_rho_rescale acts on a bump decided at
+  // the same check; k_cert_harvest copies them to the per-node arena oc* beside k_harvest.  Strides: nnz, Rmax, (rmax + k)^2, 1.
+  int *cert_flag, *cert_have;                    // B: snapshot wanted at this check ; the slot holds one
+  double *cb_rho, *cbLam, *cblam, *cbPsi, *cbBound;   // per slot
+  double *ocLam, *oclam, *ocPsi, *ocBound; int* ocHave;   // per node
 };
 #define AA_MAXMEM 10
+// caller-supplied multipliers of omc_dual_bound_batch (k_dual_assemble): Lam (nnz per node), lam (Rmax), Psi3 (order r + k, column-major,
+// leading dimension r + k, at the head of a (rmax + k)^2 stride; NULL = zero), and the n x rmax scratch of Q Psi3_11
+struct OmcDualIn { const double *Lam, *lam, *Psi3; double* T1; };
 
 #ifdef __cplusplus
 extern "C" {
@@ -178,6 +188,9 @@ void omc_launch_sep_sub(const OmcWS* w, hipStream_t s);
 void omc_launch_rho_rescale(const OmcWS* w, hipStream_t s);
 void omc_launch_harvest(const OmcWS* w, hipStream_t s);
 void omc_launch_state_save(const OmcWS* w, hipStream_t s);
+void omc_launch_dual_assemble(const OmcWS* w, const OmcDualIn* in, hipStream_t s);      /* w: the private view of omc_dual_bound_batch, node b in slot b */
+void omc_launch_cert_snapshot(const OmcWS* w, hipStream_t s);      /* only with w->cert_flag */
+void omc_launch_cert_harvest(const OmcWS* w, hipStream_t s);       /* only with w->cert_flag */
 void omc_launch_aa(const OmcWS* w, hipStream_t s);
 void omc_launch_make_X(const OmcWS* w, double* X, hipStream_t s);
 void omc_launch_make_Theta(const OmcWS* w, const double* X, double* Th, hipStream_t s);

@@ -332,7 +332,8 @@ __device__ __forceinline__ void colprox_body(const OmcWS& w, int mode, int b, in
     }
     WAVE_SYNC();
     bool ok = wave_cholesky(Lm, c, lane);
-    if (!ok) {  // Y not PSD enough on this block: report +inf objective contribution
+    if (!ok) {  // Y not PSD enough on this block: report +inf objective contribution; the column's multiplier is 0 (c0col = 0 is its Fenchel term), not what the slot held before
+      for (int p = lane; p < c; p += WAVE) { alpha[p] = 0.0; if (w.lamDX) w.lamDX[((size_t)b * w.m + j) * n + idx[p]] = 0.0; }
       if (lane == 0) { w.objcol[(size_t)b * w.m + j] = 1e300; w.c0col[(size_t)b * w.m + j] = 0.0; if (w.cp_nfact) w.cp_nfact[(size_t)b * w.m + j] = 1; }
       return;
     }
@@ -483,7 +484,8 @@ __device__ __forceinline__ void colprox_reg(const OmcWS& w, int mode, int b, int
     if (lane < c) { alpha[lane] = yr; lamD[my] = yr; }
     WSTAMP(27);
   } else {
-    if (!wave_ldl(Lm, pinv, c, lane)) {  // Y not PSD enough on this block: report +inf objective contribution
+    if (!wave_ldl(Lm, pinv, c, lane)) {  // Y not PSD enough on this block: report +inf objective contribution; the column's multiplier is 0, not what the slot held before
+      if (lane < c) { alpha[lane] = 0.0; if (w.lamDX) w.lamDX[((size_t)b * w.m + j) * n + my] = 0.0; }
       if (lane == 0) { w.objcol[(size_t)b * w.m + j] = 1e300; w.c0col[(size_t)b * w.m + j] = 0.0; if (w.cp_nfact) w.cp_nfact[(size_t)b * w.m + j] = 1; }
       return;
     }
@@ -2555,6 +2557,7 @@ __global__ void k_check_final(OmcWS w, int last, int phase) {
   if (est && term >= 0) { w.confirm[b] = 1; return; }      // nothing committed: phase 1 decides on the rigorous bound
   // ---- commit ----------------------------------------------------------------------------------------------------------------
   if (!est) w.lb[b] = fmax(lb_rig, lbv);
+  if (!est && w.cert_flag && lbv > lb_rig) { w.cert_flag[b] = 1; w.cbBound[b] = lbv; w.cb_rho[b] = w.rho_b[b]; }      // before the bump below touches rho_b
   w.lb_est[b] = fmax(w.lb_est[b], lbv);
   w.objout[b] = obj;
   w.stall[b] = stall_new; w.objprev[b] = obj; w.lbprev[b] = lb_dec;
@@ -2790,6 +2793,46 @@ __global__ void __launch_bounds__(256) k_harvest(OmcWS w) {
   }
 }
 
+// Best certificate (omc_relax_keep_certificates): the multipliers behind the rigorous bound that k_check_final has just taken into lb[b], for the
+// slots it flagged.  Runs behind k_check_final and before k_rho_rescale; reads what k_check_build read (alphaX of k_colprox mode 1, lam of the
+// last k_global, dS / Q3V / Q3T of the last k_small) and the penalty k_check_final noted.  Psi3 = rho [[dS, Q3V], [Q3V', Q3T]] is stored as one
+// column-major matrix of order r + k (leading dimension r + k) at the head of its (rmax + k)^2 stride.
+__global__ void __launch_bounds__(256) k_cert_snapshot(OmcWS w) {
+  const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+  if (!w.cert_flag[b]) return;
+  const int nb = w.node_of[b];
+  const int k = w.k, rm = w.rmax, r = w.rr[nb], N3 = r + k;
+  const double rho = w.cb_rho[b];
+  for (int e = tid; e < w.nnz; e += T) w.cbLam[(size_t)b * w.nnz + e] = w.alphaX[(size_t)b * w.nnz + e];
+  for (int e = tid; e < w.Rmax; e += T) w.cblam[(size_t)b * w.Rmax + e] = w.lam[(size_t)b * w.Rmax + e];
+  double* P = w.cbPsi + (size_t)b * (rm + k) * (rm + k);
+  const double* dS = w.dS + (size_t)b * rm * rm;
+  const double* QV = w.Q3V + (size_t)b * rm * k;
+  const double* QT = w.Q3T + (size_t)b * k * k;
+  for (int e = tid; e < N3 * N3; e += T) {
+    const int i = e % N3, j = e / N3;
+    double v;
+    if (i < r && j < r) v = dS[(size_t)j * rm + i];
+    else if (i < r) v = QV[(size_t)(j - r) * rm + i];
+    else if (j < r) v = QV[(size_t)(i - r) * rm + j];
+    else v = QT[(size_t)(j - r) * k + (i - r)];
+    P[e] = rho * v;
+  }
+  if (tid == 0) { w.cert_flag[b] = 0; w.cert_have[b] = 1; }
+}
+
+// the sibling of k_harvest for the best certificates: slot buffers -> per-node arena; the slot is empty afterwards
+__global__ void __launch_bounds__(256) k_cert_harvest(OmcWS w) {
+  const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+  if (!w.fin[b]) return;
+  const int nb = w.node_of[b];
+  const size_t ps = (size_t)(w.rmax + w.k) * (w.rmax + w.k);
+  for (int e = tid; e < w.nnz; e += T) w.ocLam[(size_t)nb * w.nnz + e] = w.cbLam[(size_t)b * w.nnz + e];
+  for (int e = tid; e < w.Rmax; e += T) w.oclam[(size_t)nb * w.Rmax + e] = w.cblam[(size_t)b * w.Rmax + e];
+  for (size_t e = tid; e < ps; e += T) w.ocPsi[(size_t)nb * ps + e] = w.cbPsi[(size_t)b * ps + e];
+  if (tid == 0) { w.ocBound[nb] = w.cbBound[b]; w.ocHave[nb] = w.cert_have[b]; w.cert_have[b] = 0; w.cert_flag[b] = 0; }
+}
+
 // warm-start pool: the final state of the slots flagged fin whose node asked for it (runs BEFORE the recovery of a feasible U overwrites the iterate U = Q Vt)
 __global__ void __launch_bounds__(256) k_state_save(OmcWS w) {
   const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
@@ -2859,6 +2902,112 @@ __global__ void __launch_bounds__(256) k_eval_objective(int n, int m, double gam
   fit = block_sum(fit, red);
   reg = block_sum(reg, red);
   if (threadIdx.x == 0) out[b] = 0.5 * fit + reg / (2.0 * gamma);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_dual_assemble (omc_dual_bound_batch): what k_check_build assembles from slot state, from multipliers the caller supplies.  Node b in
+// workgroup b of a private view (descriptors as omc_relax_stage writes them):
+//   Mchk = -gamma/2 Lam Lam' + sum_cut lam_r x x' - Q Psi3_11 Q' ;  c0 = <A, Lam> - 1/2 ||Lam||^2 ;
+//   cpen = sum_j || Q'(sum_r lam_r CU_r)_j - 2 (Psi3_12)_j || ;  cst = -sum_{r != trace} lam_r rhs_r - tr Psi3_22
+// and the symmetrised, zero-padded copy MbufC with its squared Frobenius norm for the eigen-kernels, which then give evsum.  The rows with a
+// zero multiplier are skipped, the multipliers are taken as they are (nothing is clamped or projected).  Lam Lam' is the MFMA product of a
+// dense copy where the view carries lamDX (n > 144, as in a relaxation) and the scattered walk over the columns below.
+// ---------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(512) k_dual_assemble(OmcWS w, OmcDualIn in) {
+  __shared__ double red[32];
+  const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+  const int n = w.n, k = w.k, m = w.m, R = w.R[b], rm = w.rmax, r = w.rr[b], N3 = r + k;
+  const double g = w.gamma;
+  double* M = w.Mchk + (size_t)b * n * n;
+  const double* Lam = in.Lam + (size_t)b * w.nnz;
+  const double* lam = in.lam + (size_t)b * w.Rmax;
+  const double* Psi = in.Psi3 ? in.Psi3 + (size_t)b * (rm + k) * (rm + k) : nullptr;
+  const double* cutx = w.cutx + (size_t)b * w.Lmax * n;
+  const double* Q = w.Qb + (size_t)b * n * rm;
+  double* cU = w.chk_scratch + (size_t)b * n * k;
+  double* T1 = in.T1 + (size_t)b * n * rm;
+  double c0 = 0.0;
+  for (int e = tid; e < w.nnz; e += T) { const double l = Lam[e]; c0 += w.col_val[e] * l - 0.5 * l * l; }
+  c0 = block_sum(c0, red);
+  if (Psi) {      // T1 = Q Psi3_11 (n x r)
+    for (int e = tid; e < n * r; e += T) {
+      const int i = e % n, a = e / n;
+      double acc = 0.0;
+      for (int c = 0; c < r; ++c) acc += Q[(size_t)c * n + i] * Psi[(size_t)a * N3 + c];
+      T1[(size_t)a * n + i] = acc;
+    }
+    __syncthreads();
+    __threadfence_block();
+  }
+  for (int e = tid; e < n * n; e += T) {
+    const int i = e % n, j = e / n;
+    double v = 0.0;
+    for (int rr = 0; rr < R; ++rr) {
+      const double lv = lam[rr];
+      if (lv != 0.0 && w.rkind[(size_t)b * w.Rmax + rr] == ROW_CUT) {
+        const double* x = cutx + (size_t)w.rcut[(size_t)b * w.Rmax + rr] * n;
+        v += lv * x[i] * x[j];
+      }
+    }
+    if (Psi) for (int a = 0; a < r; ++a) v -= T1[(size_t)a * n + i] * Q[(size_t)a * n + j];
+    M[e] = v;
+  }
+  for (int e = tid; e < n * k; e += T) {
+    const int i = e % n, j = e / n;
+    double cu = 0.0;
+    for (int rr = 0; rr < R; ++rr) { const double lv = lam[rr]; if (lv != 0.0) cu += lv * rowU_entry(w, b, rr, i, j); }
+    cU[e] = cu;
+  }
+  __syncthreads();
+  if (w.lamDX) {      // dense copy (the host has zeroed it), then one MFMA product
+    double* D = w.lamDX + (size_t)b * m * n;
+    for (int j = tid; j < m; j += T) {
+      const int off = w.col_ptr[j], c = w.col_ptr[j + 1] - off;
+      for (int p = 0; p < c; ++p) D[(size_t)j * n + w.col_idx[off + p]] = Lam[off + p];
+    }
+    __syncthreads();
+    __threadfence_block();
+    mfma_LLt<1>(D, n, m, [&](int i, int j, double v) {
+      const double t = 0.5 * g * v;
+      M[(size_t)j * n + i] -= t;
+      if (i != j) M[(size_t)i * n + j] -= t;
+    });
+    __syncthreads();
+  } else {
+    for (int j = 0; j < m; ++j) {
+      const int off = w.col_ptr[j], c = w.col_ptr[j + 1] - off;
+      for (int e = tid; e < c * c; e += T) {
+        const int p = e % c, q = e / c;
+        M[(size_t)w.col_idx[off + q] * n + w.col_idx[off + p]] -= 0.5 * g * Lam[off + p] * Lam[off + q];
+      }
+      __syncthreads();
+    }
+  }
+  double pen = 0.0;
+  for (int j = 0; j < k; ++j) {
+    double acc = 0.0;
+    for (int a = tid; a < r; a += T) {
+      double cv = Psi ? -2.0 * Psi[(size_t)(r + j) * N3 + a] : 0.0;
+      for (int i = 0; i < n; ++i) cv += Q[(size_t)a * n + i] * cU[(size_t)j * n + i];
+      acc += cv * cv;
+    }
+    pen += sqrt(block_sum(acc, red));
+  }
+  const int NP = w.np16;
+  double fr2 = 0.0;
+  for (int e = tid; e < n * n; e += T) {
+    const int i = e % n, j = e / n;
+    const double mv = 0.5 * (M[e] + M[(size_t)i * n + j]);
+    w.MbufC[(size_t)b * NP * NP + (size_t)j * NP + i] = mv; fr2 += mv * mv;
+  }
+  fr2 = block_sum(fr2, red);
+  if (tid == 0) {
+    double cst = 0.0;
+    for (int rr = 0; rr < R; ++rr)
+      if (w.rkind[(size_t)b * w.Rmax + rr] != ROW_TRACE) cst -= lam[rr] * w.rrhs[(size_t)b * w.Rmax + rr];
+    if (Psi) for (int j = 0; j < k; ++j) cst -= Psi[(size_t)(r + j) * N3 + r + j];
+    w.c0[b] = c0; w.cpen[b] = pen; w.cst[b] = cst; w.fro2c[b] = fr2;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2968,6 +3117,9 @@ void omc_launch_check_final(const OmcWS* w, int last, int phase, hipStream_t s) 
 }
 void omc_launch_rho_rescale(const OmcWS* w, hipStream_t s) { hipLaunchKernelGGL(k_rho_rescale, dim3(w->B), dim3(256), 0, s, *w); }
 void omc_launch_harvest(const OmcWS* w, hipStream_t s) { hipLaunchKernelGGL(k_harvest, dim3(w->B), dim3(256), 0, s, *w); }
+void omc_launch_dual_assemble(const OmcWS* w, const OmcDualIn* in, hipStream_t s) { hipLaunchKernelGGL(k_dual_assemble, dim3(w->B), dim3(512), 0, s, *w, *in); }
+void omc_launch_cert_snapshot(const OmcWS* w, hipStream_t s) { hipLaunchKernelGGL(k_cert_snapshot, dim3(w->B), dim3(256), 0, s, *w); }
+void omc_launch_cert_harvest(const OmcWS* w, hipStream_t s) { hipLaunchKernelGGL(k_cert_harvest, dim3(w->B), dim3(256), 0, s, *w); }
 void omc_launch_state_save(const OmcWS* w, hipStream_t s) { hipLaunchKernelGGL(k_state_save, dim3(w->B), dim3(256), 0, s, *w); }
 void omc_launch_aa(const OmcWS* w, hipStream_t s) { hipLaunchKernelGGL(k_aa, dim3(w->nB), dim3(512), 0, s, *w); }
 void omc_launch_make_X(const OmcWS* w, double* X, hipStream_t s) { hipLaunchKernelGGL(k_make_X, dim3(64, w->Btot), dim3(256), 0, s, *w, X); }

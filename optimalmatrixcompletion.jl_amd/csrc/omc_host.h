@@ -170,6 +170,10 @@ struct omc_instance {
   int wall_khz = 0;      // rate of the device's constant clock (wall_clock64) for the time_limit of omc_altmin_batch; 0: unknown, the limit is not enforced inside a launch
   std::vector<double> rho_scale_per_node; DevBuf brho, brhon, blamD, bslotint, boY, boU, boal, bobx, boscal, boint;
   int Btot = 0;
+  // best certificates per node (omc_relax_keep_certificates): asked for before a stage call; that call allocates the per-slot buffers and the
+  // per-node arena (OmcWS::cert_flag ...) and nothing exists while the request is off
+  bool keep_cert = false; DevBuf bcbD, bcbI, bocD, bocI;
+  DevBuf dbD, dbI, dbM, dbS, dbL;      // omc_dual_bound_batch: descriptors and multipliers, ints, matrices, eigen-kernel slab, dense Lam
   // Shor minors (a10 / a11): row bitsets and per-pair popcounts, built at the first call
   DevBuf sbits, scb, scx, scz, soff, stot, sout, shi, slo, sexist, shist, sohi, solo, scnt;
   bool shor_ready = false; int shor_W = 0; long long shor_pairs = 0;
