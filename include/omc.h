@@ -359,7 +359,9 @@ int omc_altmin_plan(int n, int m, int k, int max_cuts, int nolds, int64_t* out);
 int omc_evaluate_objective(omc_instance* h, int B, const double* X, double* objective);
 
 /* ---- separation / feasibility on caller-supplied (Y, U): OMC.jl:1272-1277 and 2466-2477 -----------------
- * eigvals[2*b..] two smallest eigenvalues of U U' - Y; x n per problem; feasible[b] = eigvals[0] >= -1e-6 */
+ * eigvals[2*b..] two smallest eigenvalues of U U' - Y; x n per problem; feasible[b] = eigvals[0] >= -1e-6.
+ * These four entry points return OMC_ERR_ARGUMENT for B <= 0.  The exact zero matrix (U U' = Y; Y = 0; X = 0) has eigenvalues 0, is
+ * feasible, and gives the first coordinate vector as x and the first k coordinate vectors as U. */
 int omc_separation_batch(omc_instance* h, int B, int breakpoints, const double* Y, const double* U,
                          double* eigvals, double* x, int* feasible);
 

@@ -1707,6 +1707,7 @@ int omc_separation_batch(omc_instance* h, int B, int breakpoints, const double* 
   if (!h || !Y || !U) return fail(OMC_ERR_ARGUMENT, "NULL argument");
   if (breakpoints != OMC_SMALLEST_1_EIGVEC && breakpoints != OMC_SMALLEST_2_EIGVEC)
     return fail(OMC_ERR_INVALID_ENUM, "Invalid input for disjunctive cuts breakpoints (OMC.jl:2440-2446)");
+  if (B <= 0) return fail(OMC_ERR_ARGUMENT, "B must be positive");
   // stage an empty batch to get a workspace of the right size, then overwrite (Y, U)
   std::vector<int> L(B, 0);
   omc_relax_params P = h->params; P.breakpoints = breakpoints; P.slots = B;   // identity slot map: the state arrays are addressed by node
@@ -1732,6 +1733,7 @@ int omc_separation_batch(omc_instance* h, int B, int breakpoints, const double* 
 
 int omc_round_Y_batch(omc_instance* h, int B, const double* Y, double* U_rounded) {
   if (!h || !Y || !U_rounded) return fail(OMC_ERR_ARGUMENT, "NULL argument");
+  if (B <= 0) return fail(OMC_ERR_ARGUMENT, "B must be positive");
   std::vector<int> L(B, 0);
   omc_relax_params P = h->params; P.slots = B;
   int rc = omc_relax_stage(h, B, &P, OMC_CUT_LINEAR, L.data(), nullptr, nullptr, nullptr, nullptr, nullptr);

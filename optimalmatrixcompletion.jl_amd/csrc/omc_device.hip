@@ -785,7 +785,8 @@ __device__ __forceinline__ double eig_frontend(double* Gm, double* ev, int N, in
     Gm[(size_t)j * ld + i] = v;
   }
   fro = sqrt(block_sum(fro, red));
-  const double sigma = 1.5 * fro + 1e-300;
+  // the exact zero matrix takes a unit shift: with 1e-300 the squared column norms underflow to 0 and the 1 / sqrt(ev) of the callers is infinite
+  const double sigma = (fro == 0.0) ? 1.0 : 1.5 * fro + 1e-300;
   for (int i = tid; i < N; i += T) Gm[(size_t)i * ld + i] += sigma;
   __syncthreads();
   int lpp = 64;
