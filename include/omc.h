@@ -545,7 +545,9 @@ int omc_last_kernel_stats(omc_instance* h, int64_t* launches /*NCLASS*/, double*
 #define OMC_HOST_HARVEST_TOTAL 10
 #define OMC_HOST_ASYNC_HARVESTS 11   /* count only: harvests whose kernels ran beside the next interval (booked and refilled at the next check) */
 #define OMC_HOST_QUIET_INTERVALS 12  /* count only: check intervals whose iterations enqueued the full eigen-kernel once instead of twice */
-#define OMC_HOST_NPHASE 13
+#define OMC_HOST_BODY_RECORDS 13     /* count only: event records the iterations enqueued on their streams (timing, fork, joins) */
+#define OMC_HOST_BODY_WAITS 14       /* count only: stream waits the iterations enqueued (fork, joins, the wait for the main stream, the check's wait) */
+#define OMC_HOST_NPHASE 15
 int omc_last_host_phases(omc_instance* h, double* ms /*NPHASE*/, int64_t* count /*NPHASE*/);
 
 #ifdef __cplusplus

@@ -34,7 +34,8 @@ KERNEL_CLASSES = ["colprox", "cone", "global", "check", "setup", "small", "accel
                   "shor_bigcone", "shor_minors", "shor_cols"]
 # omc_last_host_phases, in the order of OMC_HOST_* (include/omc.h)
 HOST_PHASES = ["check_wait", "check_scan", "list", "event_drain", "harvest_flags", "harvest_enqueue", "harvest_wait", "harvest_book",
-               "setup_enqueue", "check_total", "harvest_total", "async_harvests", "quiet_intervals"]      # the last two are counts only
+               "setup_enqueue", "check_total", "harvest_total", "async_harvests", "quiet_intervals", "body_records", "body_waits"]      # the last four are counts only
+HOST_BODY_COUNTS = ("body_records", "body_waits")      # counts of the iterations themselves: Engine.event_counts(), not host_phases()
 # order of omc_kernel_residency's output (OMC_RES_* in include/omc.h)
 RESIDENCY_KERNELS = ["k_cone_sub<0>", "k_cone_sub<1>", "k_cone_sub<2>", "k_global", "k_small", "k_colprox_pair", "k_colprox_wide", "k_colprox",
                      "k_cone_ws", "k_cone"]
@@ -446,12 +447,23 @@ class Engine:
 
     def host_phases(self):
         """Host time of the last solve between its iterations, by piece (omc_last_host_phases): {piece: dict(ms, count)}; "async_harvests" and
-        "quiet_intervals" are counts (harvests run beside the next interval; intervals with one launch of the full eigen-kernel per iteration)."""
+        "quiet_intervals" are counts (harvests run beside the next interval; intervals with one launch of the full eigen-kernel per iteration).
+        Everything here is what happens between the iterations, which does not depend on how the iterations record their events; the two
+        counts of the iterations themselves that the same call returns are event_counts()."""
         if not hasattr(self._lib, "omc_last_host_phases"):
             raise OmcError(-100, "this build of the library has no omc_last_host_phases")
         ms = np.zeros(len(HOST_PHASES)); cnt = np.zeros(len(HOST_PHASES), np.int64)
         _lib.check(self._lib.omc_last_host_phases(self._h, _lib.ptr(ms), _lib.ptr(cnt)))
-        return {HOST_PHASES[i]: dict(ms=float(ms[i]), count=int(cnt[i])) for i in range(len(HOST_PHASES))}
+        return {HOST_PHASES[i]: dict(ms=float(ms[i]), count=int(cnt[i])) for i in range(len(HOST_PHASES)) if HOST_PHASES[i] not in HOST_BODY_COUNTS}
+
+    def event_counts(self):
+        """Event records and stream waits the iterations of the last solve enqueued on their streams (timing, fork, joins, the wait for the main
+        stream, the check's wait): dict(records, waits), the last two entries of omc_last_host_phases; zeros from a build without them."""
+        if not hasattr(self._lib, "omc_last_host_phases"):
+            raise OmcError(-100, "this build of the library has no omc_last_host_phases")
+        ms = np.zeros(len(HOST_PHASES)); cnt = np.zeros(len(HOST_PHASES), np.int64)
+        _lib.check(self._lib.omc_last_host_phases(self._h, _lib.ptr(ms), _lib.ptr(cnt)))
+        return {name[len("body_"):]: int(cnt[HOST_PHASES.index(name)]) for name in HOST_BODY_COUNTS}
 
     def subspace_stats(self):
         """k_cone_sub accounting of the last solve: calls, power steps, fall-backs to the full eigendecomposition, seedings."""

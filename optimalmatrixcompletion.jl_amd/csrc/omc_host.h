@@ -86,6 +86,7 @@ struct Tuning {
   int check_xs = 16;               // OMC_CHECK_XS: cut vectors of the rows with a nonzero multiplier that k_check_build stages in LDS (the rest is read from global memory)
   int colprox_block_min = 65;      // OMC_COLPROX_BLOCK_MIN: columns with at least this many observed rows take k_colprox_block (one workgroup per column, blocked MFMA Cholesky); a value above every column length is the path without it
   int cone_multi_min = 1025;       // OMC_CONE_MULTI_MIN: cone orders from this value on (never below 145) take the multi-workgroup eigen-kernels; the default is where only the cold kernel existed
+  int event_merge = 1;             // OMC_EVENT_MERGE: 0 = every timed launch records two events of its own and the forks and joins of an iteration theirs (EventTape, omc_events.h)
   int graph_max = 16;              // OMC_GRAPH_MAX: hipGraph replay for batches staged with at most this many nodes
   int harvest_async = 1;           // OMC_HARVEST_ASYNC: 0 = every harvest is waited for, booked and refilled before the next iteration
   int harvest_async_min_live = 256;   // OMC_HARVEST_ASYNC_MIN_LIVE: live slots from which a harvest runs beside the next interval (omc_harvest_plan)
@@ -108,6 +109,7 @@ inline const Knob OMC_KNOBS[] = {
   {"OMC_SHOR_EXPLICIT", &Tuning::shor_explicit, nullptr},    {"OMC_SHOR_NO_SUBSPACE", &Tuning::shor_no_subspace, nullptr},
   {"OMC_COLPROX_BLOCK_MIN", nullptr, &Tuning::colprox_block_min},
   {"OMC_CHECK_XS", nullptr, &Tuning::check_xs},              {"OMC_CONE_MULTI_MIN", nullptr, &Tuning::cone_multi_min},
+  {"OMC_EVENT_MERGE", nullptr, &Tuning::event_merge},
   {"OMC_GRAPH_MAX", nullptr, &Tuning::graph_max},            {"OMC_SHOR_SELECT_KB", nullptr, &Tuning::shor_select_kb},
   {"OMC_HARVEST_ASYNC", nullptr, &Tuning::harvest_async},    {"OMC_HARVEST_ASYNC_MIN_LIVE", nullptr, &Tuning::harvest_async_min_live},
   {"OMC_WS_QUIET", nullptr, &Tuning::ws_quiet},
@@ -206,27 +208,10 @@ struct omc_instance {
   // kernel stats
   int64_t launches[OMC_KERNEL_NCLASS] = {0}; double ms[OMC_KERNEL_NCLASS] = {0}; int64_t units[OMC_KERNEL_NCLASS] = {0};
   size_t nnz_rows() const { return row_idx.size(); }
-  // timing events: two pools that swap at a check, so that the pool of the interval that has just ended is read (finish_events) after the
-  // next iteration has been enqueued while the launches of that iteration record into the other one
-  std::vector<hipEvent_t> ev_pool[2]; size_t ev_used[2] = {0, 0}; int ev_cur = 0;
-  std::vector<int> ev_class[2];
+  // timing events: two pools that swap at a check, so that the pool of the interval that has just ended is read after the next iteration has
+  // been enqueued while the launches of that iteration record into the other one.  Which event is recorded where, and which launch it times, is
+  // kept by the solve loop's EventTape (omc_events.h) for the length of a solve; the events themselves live as long as the instance.
+  std::vector<hipEvent_t> ev_pool[2];
 };
-
-// Per-kernel timing: a pair of pool events brackets a launch; the pool is drained by finish_events.  If an event cannot be created, or one of
-// the two records fails, the launch runs (and is counted) untimed.  counted = false: a launch timed into class `cls` that is not one of the
-// class's launches (k_setup_gram: ms of the setup class, see omc_last_kernel_stats).
-bool next_event_pair(omc_instance* h);
-int finish_events(omc_instance* h, int pool);      // every launch the pool has timed must have completed
-#define TIMED_ON(strm, cls, counted, units_, call)                                                            \
-  do {                                                                                                        \
-    const int pc_ = h->ev_cur;                                                                                \
-    const bool t0_ = next_event_pair(h) && hipEventRecord(h->ev_pool[pc_][h->ev_used[pc_]], strm) == hipSuccess; \
-    call;                                                                                                     \
-    if (t0_ && hipEventRecord(h->ev_pool[pc_][h->ev_used[pc_] + 1], strm) == hipSuccess) {                    \
-      h->ev_used[pc_] += 2; h->ev_class[pc_].push_back(cls);                                                  \
-    }                                                                                                         \
-    if (counted) { h->launches[cls] += 1; h->units[cls] += (units_); }                                        \
-  } while (0)
-#define TIMED(cls, units_, call) TIMED_ON(h->stream, cls, true, units_, call)
 
 static constexpr int MAX_SWEEPS = 30;          // sweep cap of the warm-started Jacobi kernel (k_cone_ws)

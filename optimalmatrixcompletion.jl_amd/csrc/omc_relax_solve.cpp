@@ -7,29 +7,11 @@
 #include <chrono>
 #include <stdio.h>
 
+#include "omc_events.h"
 #include "omc_host.h"
 #include "omc_slots.h"
 
 static_assert(SLOT_HARVEST_NONE == OMC_HARVEST_NONE && SLOT_HARVEST_SYNC == OMC_HARVEST_SYNC && SLOT_HARVEST_ASYNC == OMC_HARVEST_ASYNC, "omc_slots.h restates the plans of omc.h");
-
-bool next_event_pair(omc_instance* h) {
-  std::vector<hipEvent_t>& pool = h->ev_pool[h->ev_cur];
-  while (pool.size() < h->ev_used[h->ev_cur] + 2) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return false;
-    pool.push_back(e);
-  }
-  return true;
-}
-
-int finish_events(omc_instance* h, int pool) {
-  for (size_t i = 0; i + 1 < h->ev_used[pool]; i += 2) {
-    float msv = 0.f;
-    if (hipEventElapsedTime(&msv, h->ev_pool[pool][i], h->ev_pool[pool][i + 1]) == hipSuccess) h->ms[h->ev_class[pool][i / 2]] += msv;
-  }
-  h->ev_used[pool] = 0; h->ev_class[pool].clear();
-  return 0;
-}
 
 namespace {
 
@@ -45,6 +27,38 @@ int sum_sub_stat(int* sub_stat, int S, long long tot[8], hipStream_t s) {
   HIPCHK(hipMemsetAsync(sub_stat, 0, sizeof(int) * ss.size(), s));
   return 0;
 }
+
+// EventTape's backend: the tape's streams are T_S (the instance's stream) and the three streams of an iteration (with OMC_STREAMS=1 all four
+// are one stream, and one id), its events the two pools of the instance, which grow on demand.
+enum { T_S = 0, T_M = 1, T_B = 2, T_C = 3, T_NSTREAM = 4 };
+struct HipEvents {
+  omc_instance* h; hipStream_t st[T_NSTREAM] = {}; hipError_t last = hipSuccess;
+  bool record(int pool, int i, int stream) {
+    std::vector<hipEvent_t>& p = h->ev_pool[pool];
+    while (p.size() <= (size_t)i) {
+      hipEvent_t e;
+      if ((last = hipEventCreate(&e)) != hipSuccess) return false;
+      p.push_back(e);
+    }
+    return (last = hipEventRecord(p[i], st[stream])) == hipSuccess;
+  }
+  bool wait(int stream, int pool, int i) { return (last = hipStreamWaitEvent(st[stream], h->ev_pool[pool][i], 0)) == hipSuccess; }
+};
+using Tape = EventTape<HipEvents>;
+
+// Per-kernel timing: the launch `call` on the stream with the tape's id `id`, between a start and a stop event of the tape; finish_events reads
+// the pair.  If the tape has no event to give (one cannot be created, a record fails) the launch runs, and is counted, untimed.
+// counted = false: a launch timed into class `cls` that is not one of the class's launches (k_setup_gram: ms of the setup class, see
+// omc_last_kernel_stats).
+#define TIMED_ON(id, cls, counted, units_, call)                                                          \
+  do {                                                                                                    \
+    const Tape::Ev t0_ = tape.begin(id);                                                                  \
+    call;                                                                                                 \
+    tape.touch(id);                                                                                       \
+    if (t0_.valid()) { const Tape::Ev t1_ = tape.end(id); if (t1_.valid()) tape.launch(t0_, t1_, cls); }  \
+    if (counted) { h->launches[cls] += 1; h->units[cls] += (units_); }                                    \
+  } while (0)
+#define TIMED(cls, units_, call) TIMED_ON(T_S, cls, true, units_, call)
 
 // The state of one solve.  Every exit of omc_relax_solve, error exits included, closes the batch to omc_relax_append (CloseGuard) and
 // destroys the graph executables (GraphGuard).
@@ -65,6 +79,18 @@ struct SolveLoop {
   const bool multi, shor;
   const hipStream_t s;
   hipStream_t sm = nullptr, sb = nullptr, sc = nullptr;
+  int im = T_S, ib = T_S, ic = T_S;      // their ids on the tape
+  // Event records.  Timing brackets every launch of a sampled iteration with two events, and the fork and the joins of the three streams are
+  // events too; most of them mark a point of a stream that an event already marks (the stop of k_global, the fork and the start of k_cone_sub
+  // are one point of the main stream).  The tape hands the event that is still adjacent out again (omc_events.h), and the fork and the joins
+  // of a timed iteration wait for the tape's events: 8 records instead of 13 in a quiet iteration, 10 instead of 16 in a split one.  Every
+  // enqueue on one of the four streams that is not a record of the tape tells the tape (touch).  On the instance's stream adjacency is trusted
+  // only inside one enqueue function (setup_slots, enqueue_check, enqueue_harvest touch it when they begin): copies and fills go there from
+  // many places.  OMC_EVENT_MERGE=0: the order before the tape, record for record.
+  // A pool event is recorded once per generation of its pool, and a pool is drained (finish_events) only after the check that follows the
+  // interval it was filled in: every wait that names one of its events was enqueued in that interval, two checks before the event is
+  // recorded again.
+  HipEvents hip_events; Tape tape;
   int Btot;      // nodes staged so far: omc_relax_append may add more while the loop runs (re-read at every check)
   int* done = nullptr; int* jobs = nullptr;      // page-locked images of the done flags and of the k_setup_gram jobs (prepare)
   SlotBook book;
@@ -99,17 +125,56 @@ struct SolveLoop {
   int graph_max = 0, gexec_n = -1; GraphGuard graphs;
   // per check: slots the asynchronous harvest of the previous check refilled; the slot list has gone out already
   int nrefilled = 0; bool list_pushed = false;
+  // (omc_last_host_phases also carries two counts of the iterations themselves: the event records and the stream waits they enqueued)
   // host stamps between the iterations (omc_last_host_phases): stamp(q) charges the time since the previous stamp to piece q
   const Clock::time_point t0; Clock::time_point t_last, t_check;
 
   explicit SolveLoop(omc_instance* h_)
       : h(h_), close_guard{h_}, w(h_->ws), sw(h_->sh), P(h_->params), tun(h_->tun), S(h_->ws.B), check_every(std::max(1, h_->params.check_every)),
-        multi(h_->tun.streams > 1), shor(h_->shor_on), s(h_->stream), Btot(h_->Btot_live.load()),
-        book(h_->ws.B, nullptr, nullptr), t0(Clock::now()), t_last(t0), t_check(t0) {}
+        multi(h_->tun.streams > 1), shor(h_->shor_on), s(h_->stream),
+        hip_events{h_}, tape(&hip_events, T_NSTREAM, h_->tun.event_merge != 0), Btot(h_->Btot_live.load()), book(h_->ws.B, nullptr, nullptr), t0(Clock::now()), t_last(t0), t_check(t0) {}
 
   void stamp_begin() { t_last = Clock::now(); }
   void stamp(int q) { const auto t = Clock::now(); h->host_ms[q] += std::chrono::duration<double, std::milli>(t - t_last).count(); h->host_cnt[q] += 1; t_last = t; }
   double elapsed() const { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+
+  // every launch the pool has timed must have completed
+  void finish_events(int pool) {
+    for (const Tape::Launch& l : tape.launches(pool)) {
+      float msv = 0.f;
+      if (hipEventElapsedTime(&msv, h->ev_pool[pool][l.start], h->ev_pool[pool][l.stop]) == hipSuccess) h->ms[l.cls] += msv;
+    }
+    tape.drain(pool);
+  }
+
+  // `to` (and `to2`, if >= 0) wait for the present end of the queue of `from`.  on_tape: that point is an event of the tape -- the stop event of
+  // the last launch on `from` when nothing has followed it; otherwise, or when the tape has no event to give, `fb` is recorded for it.
+  int depend(int from, int to, int to2, bool on_tape, hipEvent_t fb, bool counted = true) {
+    if (on_tape) {
+      const Tape::Ev e = tape.mark(from);
+      if (e.valid()) {
+        if (!tape.wait(to, e) || (to2 >= 0 && !tape.wait(to2, e))) HIPCHK(hip_events.last);
+        return 0;
+      }
+    }
+    HIPCHK(hipEventRecord(fb, hip_events.st[from])); tape.touch(from); if (counted) tape.count_record();
+    HIPCHK(hipStreamWaitEvent(hip_events.st[to], fb, 0)); tape.touch(to); if (counted) tape.count_wait();
+    if (to2 >= 0) { HIPCHK(hipStreamWaitEvent(hip_events.st[to2], fb, 0)); tape.touch(to2); if (counted) tape.count_wait(); }
+    return 0;
+  }
+  // the two side streams join the main stream: both points first, then both waits
+  int join_sides(bool on_tape, hipEvent_t fb_b, hipEvent_t fb_c, bool counted) {
+    Tape::Ev eb, ec;
+    if (on_tape) eb = tape.mark(ib);
+    if (!eb.valid()) { HIPCHK(hipEventRecord(fb_b, sb)); tape.touch(ib); if (counted) tape.count_record(); }
+    if (on_tape) ec = tape.mark(ic);
+    if (!ec.valid()) { HIPCHK(hipEventRecord(fb_c, sc)); tape.touch(ic); if (counted) tape.count_record(); }
+    if (eb.valid()) { if (!tape.wait(im, eb)) HIPCHK(hip_events.last); }
+    else { HIPCHK(hipStreamWaitEvent(sm, fb_b, 0)); tape.touch(im); if (counted) tape.count_wait(); }
+    if (ec.valid()) { if (!tape.wait(im, ec)) HIPCHK(hip_events.last); }
+    else { HIPCHK(hipStreamWaitEvent(sm, fb_c, 0)); tape.touch(im); if (counted) tape.count_wait(); }
+    return 0;
+  }
 
   // ---- host images and their uploads ------------------------------------------------------------------------------------------------
   // Page-locked images (see omc_instance): an upload returns at once, and an image is rewritten only after the copy that last read it has
@@ -125,6 +190,7 @@ struct SolveLoop {
     int* flags = h->pin_flags[q].as<int>();
     book.write_flags(flags);
     HIPCHK(hipMemcpyAsync(w.node_of, flags, sizeof(int) * 3 * (size_t)S, hipMemcpyHostToDevice, s));
+    tape.touch(T_S);
     HIPCHK(hipEventRecord(h->ev_up[q], s)); h->ev_up_rec[q] = true;
     if (sync) HIPCHK(hipStreamSynchronize(s));
     return 0;
@@ -135,6 +201,7 @@ struct SolveLoop {
     { int rc = image_free(2 + q); if (rc) return rc; }
     int* alist = h->pin_list[q].as<int>();
     nlist = book.write_list(alist);
+    tape.touch(T_S);
     if (nlist) { HIPCHK(hipMemcpyAsync(h->bslotlist.p, alist, sizeof(int) * nlist, hipMemcpyHostToDevice, s)); HIPCHK(hipEventRecord(h->ev_up[2 + q], s)); h->ev_up_rec[2 + q] = true; }
     return 0;
   }
@@ -149,8 +216,10 @@ struct SolveLoop {
     for (int q = 0; q < njobs; ++q)      // the host builds the list: a job outside the slots or the nodes is a bookkeeping error, not something to skip
       if (jobs[2 * q] < 0 || jobs[2 * q] >= S || jobs[2 * q + 1] < 0 || jobs[2 * q + 1] >= Btot) return fail(OMC_ERR_ARGUMENT, "omc_relax_solve: k_setup_gram job outside the slots / nodes");
     HIPCHK(hipMemcpyAsync(h->bgramjobs.p, jobs, sizeof(int) * 2 * (size_t)njobs, hipMemcpyHostToDevice, sb));
-    TIMED_ON(sb, OMC_KERNEL_SETUP, false, 0, omc_launch_setup_gram(&w, h->bgramjobs.as<int>(), njobs, Btot, sb));
-    HIPCHK(hipEventRecord(h->ev_gram, sb)); h->ev_gram_rec = true;
+    tape.touch(ib);
+    TIMED_ON(ib, OMC_KERNEL_SETUP, false, 0, omc_launch_setup_gram(&w, h->bgramjobs.as<int>(), njobs, Btot, sb));
+    HIPCHK(hipEventRecord(h->ev_gram, sb)); h->ev_gram_rec = true;      // the host waits for this one (gram_jobs_free): an event of its own
+    tape.touch(ib);
     return 0;
   }
   int gram_jobs_free() {      // before pin_jobs is rewritten
@@ -158,13 +227,14 @@ struct SolveLoop {
     return 0;
   }
   int gram_join() {
-    if (h->ev_gram_rec && sb != s) HIPCHK(hipStreamWaitEvent(s, h->ev_gram, 0));
+    if (h->ev_gram_rec && sb != s) { HIPCHK(hipStreamWaitEvent(s, h->ev_gram, 0)); tape.touch(T_S); }
     return 0;
   }
   // What every site that hands nodes to slots ends with, once the job list and the init flags have gone out (when they go differs by site):
   // the Shor state of the slots (before the base setup, which clears the init flags), k_setup, the Gram matrices joined behind it, and the
   // first calls of the new nodes are cold -- the full sweep budget, no quiet interval.
   int setup_slots(int units) {
+    tape.touch(T_S);
     if (shor) omc_shor_launch_setup(&sw, s);
     TIMED(OMC_KERNEL_SETUP, units, omc_launch_setup(&w, s));
     { int rc = gram_join(); if (rc) return rc; }
@@ -175,8 +245,7 @@ struct SolveLoop {
 
   int prepare() {
     for (int c = 0; c < OMC_KERNEL_NCLASS; ++c) { h->launches[c] = 0; h->ms[c] = 0; h->units[c] = 0; }
-    for (int q = 0; q < 2; ++q) { h->ev_used[q] = 0; h->ev_class[q].clear(); }
-    h->ev_cur = 0;
+    tape.reset();
     for (int q = 0; q < OMC_HOST_NPHASE; ++q) { h->host_ms[q] = 0; h->host_cnt[q] = 0; }
     for (int q = 0; q < 2; ++q) { int rc = h->pin_flags[q].ensure(sizeof(int) * 3 * (size_t)S); if (rc) return rc; rc = h->pin_list[q].ensure(sizeof(int) * (size_t)S); if (rc) return rc; }
     { int rc = h->pin_done.ensure(sizeof(int) * ((size_t)S + 1)); if (rc) return rc; rc = h->pin_jobs.ensure(sizeof(int) * 2 * (size_t)S); if (rc) return rc; rc = h->bgramjobs.ensure(sizeof(int) * 2 * (size_t)S); if (rc) return rc; }
@@ -189,6 +258,8 @@ struct SolveLoop {
       HIPCHK(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
     }
     sm = multi ? h->gs[0] : s; sb = multi ? h->gs[1] : s; sc = multi ? h->gs[2] : s;
+    if (multi) { im = T_M; ib = T_B; ic = T_C; }
+    hip_events.st[T_S] = s; hip_events.st[T_M] = sm; hip_events.st[T_B] = sb; hip_events.st[T_C] = sc;
     h->ws.setup_gram_inline = tun.setup_gram_inline ? 1 : 0;
     h->ws.check_xs = std::min(std::max(0, tun.check_xs), CB_XS);      // at most CB_XS doubles are staged: more vectors than that never fit
     // with omc_relax_reserve there may be more slots than nodes staged so far: the others start idle
@@ -254,57 +325,55 @@ struct SolveLoop {
     const int gact = book.running();
     const bool split = split_solve && (capturing || !quiet);
     hipEvent_t* const ev = capturing ? h->gevc : h->gev;
-    if (multi) {
-      HIPCHK(hipEventRecord(ev[0], sm));
-      HIPCHK(hipStreamWaitEvent(sb, ev[0], 0)); HIPCHK(hipStreamWaitEvent(sc, ev[0], 0));
-    }
-#define MAYBE_TIMED(strm, cls, units_, call) do { if (timed) TIMED_ON(strm, cls, true, units_, call); else { call; } } while (0)
+    // a timed iteration forks and joins on the tape's events: the fork is the stop event of the previous iteration's last kernel (and the
+    // start event of the first kernel on the main stream), a join the stop event of a side stream's last kernel
+    const bool tp = timed && !capturing && tun.event_merge;
+    const bool cnt = !capturing;
+    if (multi) { int rc = depend(im, ib, ic, tp, ev[0], cnt); if (rc) return rc; }
+#define MAYBE_TIMED(id, cls, units_, call) do { if (timed) TIMED_ON(id, cls, true, units_, call); else { call; tape.touch(id); } } while (0)
     if (shor) {
       // Shor mode: clip on the main stream, the order-(n+m) cone on the second, small cone + order-5 blocks on the third; then the
       // global step: rows / Y (base kernel), columns (X, W, Theta, duals of the big cone), duals of the order-5 blocks, per-slot sums
       OmcWS wb = h->wbig; wb.nB = wg.nB; wb.slot_list = wg.slot_list;
-      if (w.sub_enable) MAYBE_TIMED(sm, OMC_KERNEL_CONESUB, gact, omc_launch_cone_sub(&wg, sm));
-      if (wb.sub_enable) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, 0, omc_launch_cone_sub(&wb, sb));
+      if (w.sub_enable) MAYBE_TIMED(im, OMC_KERNEL_CONESUB, gact, omc_launch_cone_sub(&wg, sm));
+      if (wb.sub_enable) MAYBE_TIMED(ib, OMC_KERNEL_SHOR_BIGCONE, 0, omc_launch_cone_sub(&wb, sb));
       wb.mw_budget = mw_budget[1];
-      if (wb.geo.ws_lpp || wb.geo.mw) MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone_ws(&wb, sb));
-      else MAYBE_TIMED(sb, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone(&wb, CONE_BIG, sb));
-      if (w.geo.ws_lpp || w.geo.mw) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
-      else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, sm));
-      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
-      MAYBE_TIMED(sc, OMC_KERNEL_SHOR_MINORS, gact, { omc_shor_launch_minor_pre(&sw, sc); omc_shor_launch_vkeys(&sw, sc); });
-      if (multi) {
-        HIPCHK(hipEventRecord(ev[1], sb)); HIPCHK(hipEventRecord(ev[2], sc));
-        HIPCHK(hipStreamWaitEvent(sm, ev[1], 0)); HIPCHK(hipStreamWaitEvent(sm, ev[2], 0));
-      }
-      MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, sm));
-      MAYBE_TIMED(sm, OMC_KERNEL_SHOR_COLS, gact, omc_shor_launch_cols(&sw, sm));
-      MAYBE_TIMED(sm, OMC_KERNEL_SHOR_MINORS, gact, { omc_shor_launch_minor_post(&sw, sm); omc_shor_launch_reduce(&sw, sm); });
+      if (wb.geo.ws_lpp || wb.geo.mw) MAYBE_TIMED(ib, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone_ws(&wb, sb));
+      else MAYBE_TIMED(ib, OMC_KERNEL_SHOR_BIGCONE, gact, omc_launch_cone(&wb, CONE_BIG, sb));
+      if (w.geo.ws_lpp || w.geo.mw) MAYBE_TIMED(im, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
+      else MAYBE_TIMED(im, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, sm));
+      MAYBE_TIMED(ic, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
+      MAYBE_TIMED(ic, OMC_KERNEL_SHOR_MINORS, gact, { omc_shor_launch_minor_pre(&sw, sc); omc_shor_launch_vkeys(&sw, sc); });
+      if (multi) { int rc = join_sides(tp, ev[1], ev[2], cnt); if (rc) return rc; }
+      MAYBE_TIMED(im, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, sm));
+      MAYBE_TIMED(im, OMC_KERNEL_SHOR_COLS, gact, omc_shor_launch_cols(&sw, sm));
+      MAYBE_TIMED(im, OMC_KERNEL_SHOR_MINORS, gact, { omc_shor_launch_minor_post(&sw, sm); omc_shor_launch_reduce(&sw, sm); });
       return 0;
     }
+    Tape::Ev e4;
     if (split) {      // on the small-cone stream, behind k_small (a fifth stream would share a hardware queue with one of the other four: measured, k_small then ran behind it)
-      MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
+      MAYBE_TIMED(ic, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
       OmcWS wA = wg; wA.ws_phase = 1;
-      MAYBE_TIMED(sc, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wA, sc));
-      HIPCHK(hipEventRecord(ev[4], sc));
+      MAYBE_TIMED(ic, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wA, sc));
+      if (tp) e4 = tape.mark(ic);      // the stop event of phase 1
+      if (!e4.valid()) { HIPCHK(hipEventRecord(ev[4], sc)); tape.touch(ic); if (cnt) tape.count_record(); }
     }
     // the cone workgroups are few (two per CU, long serial phases) and the column waves many: the cone kernel goes first so that its
     // workgroups are resident when the column kernel floods the wave slots
-    if (w.sub_enable) MAYBE_TIMED(sm, OMC_KERNEL_CONESUB, gact, omc_launch_cone_sub(&wg, sm));
-    MAYBE_TIMED(sb, OMC_KERNEL_COLPROX, (int64_t)gact * w.m, omc_launch_colprox(&wg, 0, sb));
+    if (w.sub_enable) MAYBE_TIMED(im, OMC_KERNEL_CONESUB, gact, omc_launch_cone_sub(&wg, sm));
+    MAYBE_TIMED(ib, OMC_KERNEL_COLPROX, (int64_t)gact * w.m, omc_launch_colprox(&wg, 0, sb));
     if (split) {
-      HIPCHK(hipStreamWaitEvent(sm, ev[4], 0));
+      if (e4.valid()) { if (!tape.wait(im, e4)) HIPCHK(hip_events.last); }
+      else { HIPCHK(hipStreamWaitEvent(sm, ev[4], 0)); tape.touch(im); if (cnt) tape.count_wait(); }
       OmcWS wB = wg; wB.ws_phase = 2;
-      MAYBE_TIMED(sm, OMC_KERNEL_CONE, 0, omc_launch_cone_ws(&wB, sm));
+      MAYBE_TIMED(im, OMC_KERNEL_CONE, 0, omc_launch_cone_ws(&wB, sm));
     }
-    else if (w.geo.ws_lpp || w.geo.mw) MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
-    else MAYBE_TIMED(sm, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, sm));
-    if (!split) MAYBE_TIMED(sc, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
-    if (multi) {
-      HIPCHK(hipEventRecord(ev[1], sb)); HIPCHK(hipEventRecord(ev[2], sc));
-      HIPCHK(hipStreamWaitEvent(sm, ev[1], 0)); HIPCHK(hipStreamWaitEvent(sm, ev[2], 0));
-    }
-    MAYBE_TIMED(sm, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, sm));
-    if (with_aa) MAYBE_TIMED(sm, OMC_KERNEL_ACCEL, gact, omc_launch_aa(&wg, sm));
+    else if (w.geo.ws_lpp || w.geo.mw) MAYBE_TIMED(im, OMC_KERNEL_CONE, gact, omc_launch_cone_ws(&wg, sm));
+    else MAYBE_TIMED(im, OMC_KERNEL_CONE, gact, omc_launch_cone(&wg, CONE_CLIP01, sm));
+    if (!split) MAYBE_TIMED(ic, OMC_KERNEL_SMALL, gact, omc_launch_small(&wg, SMALL_PROJ, sc));
+    if (multi) { int rc = join_sides(tp, ev[1], ev[2], cnt); if (rc) return rc; }
+    MAYBE_TIMED(im, OMC_KERNEL_GLOBAL, gact, omc_launch_global(&wg, sm));
+    if (with_aa) MAYBE_TIMED(im, OMC_KERNEL_ACCEL, gact, omc_launch_aa(&wg, sm));
 #undef MAYBE_TIMED
     return 0;
   }
@@ -331,28 +400,33 @@ struct SolveLoop {
   int enqueue_iteration(bool* is_check) {
     ++it;
     *is_check = (it % check_every == 0);
-    if (multi && wait_main && !ev_main_set) HIPCHK(hipEventRecord(h->ev_main, s));
+    if (multi && wait_main && !ev_main_set) { HIPCHK(hipEventRecord(h->ev_main, s)); tape.touch(T_S); }
     ev_main_set = false;
+    const long long nrec0 = tape.records(), nwait0 = tape.waits();
     // per-kernel HIP-event timing brackets every launch of a sampled iteration (two event records per kernel: ~25 us of queue bubbles per
     // iteration at small batches); OMC_TIMING_STRIDE=s samples every s-th iteration (averages per launch are over the sampled launches), 0 = none
     const bool sampled = tun.timing_stride > 0 && (it % tun.timing_stride) == 0;
     const bool use_graph = multi && nlist <= graph_max && !tun.no_graph && !(sampled && tun.timing_stride > 1) && !mw_any;      // hundreds of launches per call: eager
     if (book.running() > 0) {
       OmcWS wg = w; wg.slot_list = h->bslotlist.as<int>(); wg.nB = nlist; wg.mw_budget = mw_budget[0];
-      if (multi && wait_main) HIPCHK(hipStreamWaitEvent(sm, h->ev_main, 0));
+      if (multi && wait_main) { HIPCHK(hipStreamWaitEvent(sm, h->ev_main, 0)); tape.count_wait(); }
+      if (wait_main) tape.touch(im);      // with one stream: what went onto it since the last iteration
       if (use_graph) {
         if (gexec_n != nlist) { int rc = capture_body(wg); if (rc) return rc; }
         HIPCHK(hipGraphLaunch(graphs.e[(!*is_check && w.accel) ? 1 : 0], sm));
+        tape.touch(im);
         h->launches[OMC_KERNEL_GLOBAL] += 1; h->units[OMC_KERNEL_GLOBAL] += book.running();
       } else {
         if (quiet && split_solve && (it - 1) % check_every == 0) h->host_cnt[OMC_HOST_QUIET_INTERVALS] += 1;
         int rc = enqueue_body(wg, sampled, !*is_check && w.accel, false); if (rc) return rc;
       }
-      if (multi && *is_check) { HIPCHK(hipEventRecord(h->gev[3], sm)); HIPCHK(hipStreamWaitEvent(s, h->gev[3], 0)); }
+      // the check waits for the iteration: for the stop event of its last kernel when the tape has it
+      if (multi && *is_check) { int rc = depend(im, T_S, -1, sampled && !use_graph && tun.event_merge, h->gev[3]); if (rc) return rc; }
     }
+    h->host_cnt[OMC_HOST_BODY_RECORDS] += tape.records() - nrec0; h->host_cnt[OMC_HOST_BODY_WAITS] += tape.waits() - nwait0;
     wait_main = false;
     if (drain_pool >= 0) {      // the timing events of the interval before the last check, now that the device has the next iteration to run
-      stamp_begin(); finish_events(h, drain_pool); drain_pool = -1; stamp(OMC_HOST_EVENT_DRAIN);
+      stamp_begin(); finish_events(drain_pool); drain_pool = -1; stamp(OMC_HOST_EVENT_DRAIN);
     }
     return 0;
   }
@@ -361,6 +435,7 @@ struct SolveLoop {
   void enqueue_check() {
     const int nactive = book.active();
     wait_main = true;
+    tape.touch(T_S);
     timed_out = elapsed() > P.time_limit;
     TIMED(OMC_KERNEL_CHECK_COL, nactive, {
       if (shor) omc_shor_launch_check(&sw, s);      // primal value, constants and the dense multiplier of the Shor program
@@ -418,8 +493,8 @@ struct SolveLoop {
     { int rc = mw_collect(); if (rc) return rc; }
     // every timed launch of the interval has joined s (the side streams join sm before k_global, sm joins s at a check) and so has completed:
     // its pool is read once the next iteration is enqueued; what is launched from here on records into the other pool, which is empty
-    if (drain_pool >= 0) { finish_events(h, drain_pool); drain_pool = -1; }
-    drain_pool = h->ev_cur; h->ev_cur ^= 1;
+    if (drain_pool >= 0) { finish_events(drain_pool); drain_pool = -1; }
+    drain_pool = tape.current(); tape.swap();
     Btot = h->Btot_live.load();
     if (!P.first_wins) return 0;
     // the first certified node ends the batch (penalty autotune): everything still running is harvested as it stands
@@ -436,6 +511,7 @@ struct SolveLoop {
   }
 
   void enqueue_harvest(int nslots) {
+    tape.touch(T_S);
     TIMED(OMC_KERNEL_HARVEST, nslots, {
       if (w.save_to) omc_launch_state_save(&w, s);                              // warm-start pool: before the recovery overwrites the iterate U = Q Vt
       if (shor) omc_shor_launch_state_save(&sw, s);                             // its Shor extension (no-op without indices)
@@ -484,7 +560,7 @@ struct SolveLoop {
     int rc = push_list(); if (rc) return rc;
     list_pushed = true;
     stamp(OMC_HOST_LIST);
-    if (multi) { HIPCHK(hipEventRecord(h->ev_main, s)); ev_main_set = true; }
+    if (multi) { HIPCHK(hipEventRecord(h->ev_main, s)); ev_main_set = true; tape.touch(T_S); }
     rc = push_flags(false); if (rc) return rc;
     stamp(OMC_HOST_HARVEST_FLAGS);
     enqueue_harvest(npend);
@@ -534,12 +610,12 @@ struct SolveLoop {
     { int rc = sum_sub_stat(w.sub_stat, S, h->sub_tot, s); if (rc) return rc; }
     if (shor && h->wbig.sub_enable) { int rc = sum_sub_stat(h->wbig.sub_stat, S, h->big_sub_tot, s); if (rc) return rc; }      // the big cone's (same layout as omc_last_subspace_stats)
     HIPCHK(hipGetLastError());
-    if (drain_pool >= 0) finish_events(h, drain_pool);      // the older pool first: the sums are formed in launch order
-    finish_events(h, h->ev_cur);
+    if (drain_pool >= 0) finish_events(drain_pool);      // the older pool first: the sums are formed in launch order
+    finish_events(tape.current());
     h->last_solve_seconds = elapsed();
     h->last_iters_total = it;
     if (tun.host_phases) {
-      static const char* const nm[OMC_HOST_NPHASE] = {"check_wait", "check_scan", "list", "event_drain", "harvest_flags", "harvest_enqueue", "harvest_wait", "harvest_book", "setup_enqueue", "check_total", "harvest_total", "async_harvests", "quiet_intervals"};
+      static const char* const nm[OMC_HOST_NPHASE] = {"check_wait", "check_scan", "list", "event_drain", "harvest_flags", "harvest_enqueue", "harvest_wait", "harvest_book", "setup_enqueue", "check_total", "harvest_total", "async_harvests", "quiet_intervals", "body_records", "body_waits"};
       fprintf(stderr, "omc host phases (solve %.1f ms, %d iterations):", 1e3 * h->last_solve_seconds, it);
       for (int q = 0; q < OMC_HOST_NPHASE; ++q) fprintf(stderr, " %s %.3f ms / %lld", nm[q], h->host_ms[q], (long long)h->host_cnt[q]);
       fprintf(stderr, "\n");
