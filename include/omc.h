@@ -58,6 +58,7 @@ extern "C" {
 #define OMC_ERR_UNSUPPORTED (-4)    /* valid in the reference, not built yet (see DESIGN.md scope table) */
 #define OMC_ERR_NO_DEVICE (-5)
 #define OMC_ERR_COMM (-6)           /* RCCL not loadable / communicator not initialised / a collective failed */
+#define OMC_ERR_ALLOC (-7)          /* the buffers of the Shor-mode certificates do not fit the device (nothing is staged) */
 
 typedef struct omc_instance omc_instance; /* opaque handle: device copies of A, mask, index lists, workspaces */
 
@@ -308,7 +309,8 @@ int omc_relax_fetch_done_shor(omc_instance* h, int n_ids, const int* node_ids, d
  *
  *   omc_relax_keep_certificates   on != 0: the omc_relax_stage calls that follow keep them (per slot 8 (2 + nnz + Rmax + (rmax + k)^2) + 8 bytes,
  *       per node of the capacity -- staged + omc_relax_reserve -- out[4] of omc_certificate_plan at the staged strides).  Refused
- *       (OMC_ERR_ARGUMENT) while a submitted solve runs.  While it is on omc_relax_stage_shor returns OMC_ERR_UNSUPPORTED.
+ *       (OMC_ERR_ARGUMENT) while a submitted solve runs.  While it is on omc_relax_stage_shor returns OMC_ERR_UNSUPPORTED (unless
+ *       omc_relax_keep_shor_certificates is on: Shor mode has a layout and a switch of its own, below).
  *   omc_relax_fetch_certificate   for node ids that omc_relax_fetch_done has returned (while the solve runs) or that the ended solve has
  *       harvested (everything omc_relax_fetch returns).  Output i belongs to node_ids[i]; strides nnz (Lam), Rmax (lam), n * rmax (Q),
  *       (rmax + k)^2 (Psi3), with Rmax = info[7] and rmax = info[3] of omc_last_solver_info; R[i] and r[i] say how much of a stride is used (Q:
@@ -332,6 +334,50 @@ int omc_certificate_plan(int n, int k, int nnz, int max_cuts, int nonstandard_bo
 int omc_dual_bound_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q1, const int* L, const double* cut_x,
                          const double* cut_Uhat, const int8_t* cut_dir, const double* U_lower, const double* U_upper, const double* Lam,
                          const double* lam, const double* Psi3, double* Q_out, int* r_out, double* bound);
+
+/* ---- Shor-mode certificates: the multipliers behind the dual_bound of a node relaxed with omc_relax_stage_shor, rank k = 1 --------------------
+ * A switch of its own, independent of omc_relax_keep_certificates: with only that one on, omc_relax_stage_shor still returns
+ * OMC_ERR_UNSUPPORTED; with this one on it stages, whatever the other says; this one has no effect on omc_relax_stage.  Rank k > 1 with this
+ * switch on: omc_relax_stage_shor returns OMC_ERR_UNSUPPORTED (quirk Q5 makes the minors vacuous there).  Off by default; with it off nothing is
+ * allocated, no kernel is added and a solve returns what it returned before, bit for bit.
+ *
+ * Certificate of a node.  All values in the engine's scaled variables (it solves the program of scale * A, whose optimum is scale^2 times the
+ * node's), taken at the check that gave the node's dual_bound (the snapshot rule above, with the penalty of that check):
+ *   scale  1 double
+ *   bound  the reported (unscaled) dual_bound, bit for bit
+ *   lam, Q, r, Psi3  as in the base certificate (rows and basis of the node; k = 1)
+ *   Gam    15 doubles per minor: the corrected symmetric multiplier Gamma'_q of the order-5 block (rows: the constant 1, (i1,j1), (i1,j2),
+ *          (i2,j1), (i2,j2)), upper triangle packed by columns -- (0,0)=0, (0,1)=1, (1,1)=2, (0,2)=3, (1,2)=4, (2,2)=5, (0,3)=6, (1,3)=7,
+ *          (2,3)=8, (3,3)=9, (0,4)=10, (1,4)=11, (2,4)=12, (3,4)=13, (4,4)=14 -- stored entry-major: Gam[e * nq_stride + q], q in the order
+ *          of the node's minor list, nq_stride the batch's stride (largest staged list, or nq_max of omc_relax_reserve_shor if larger)
+ *   zeta   m doubles: max(rho r5 nu5_j, 0), the admissible multiplier of column j's paraboloid before the W-stationarity raises it
+ *   xi     n x m column-major: the point at which the paraboloids are linearised
+ *   Xbar   n x m column-major: the tangent point of the quadratic objective term
+ *   nq     the node's own minor count
+ * No Lam: Shor mode has no column multipliers of that kind; the dense multiplier of the order-(n+m) cone follows from the fields above.
+ * The minor list and the SOC list are the caller's; the library does not hand them back.
+ * Every field is an INPUT to a formula that gives a valid lower bound for any values (certificate.py: shor_dual_bound makes them admissible
+ * first -- PSD part of every block, zeta and lam clamped at 0, PSD part of Psi3 -- then spreads what fails to cancel in V1 / V2 / V3, raises
+ * zeta to what the W-stationarity needs, and returns -inf where mu_j = cT_j - zeta_j <= 0 meets a nonzero phi_j).  It is not a claim: nothing has
+ * to be believed about how the library produced it.
+ *
+ * Memory: the arena holds out[7] of omc_shor_certificate_plan per node of the capacity (staged + omc_relax_reserve), 120 bytes per minor of
+ * the stride plus 8 (2 n m + m + Rmax + (rmax + 1)^2) + 16; every slot holds out[8], the same plus 16.  At BASELINE config 3 (200 x 200,
+ * 632 732 minors) that is about 76 MB per node and per slot.  OMC_ERR_ALLOC if it does not fit; the layout is not compressed.
+ *
+ *   omc_relax_keep_shor_certificates   on != 0: the omc_relax_stage_shor / omc_relax_batch_shor calls that follow keep them.  Refused
+ *       (OMC_ERR_ARGUMENT) while a submitted solve runs.
+ *   omc_relax_fetch_shor_certificate   for node ids that omc_relax_fetch_done has returned (while the solve runs) or any node after the solve,
+ *       staged or appended (omc_relax_append_shor).  Output i belongs to node_ids[i]; strides 1 (scale, bound, R, r, nq), Rmax (lam), n * rmax
+ *       (Q), (rmax + 1)^2 (Psi3), 15 * nq_stride (Gam), m (zeta), n * m (xi, Xbar); *nq_stride receives the stride.  Any output may be NULL.
+ *       OMC_ERR_ARGUMENT with a message for a batch staged without the switch, an id out of range or not finished, and a node that never
+ *       reached a rigorous check.
+ *   omc_shor_certificate_plan          host only, no handle: out[10] = strides in doubles of lam, Q, Psi3, Gam, zeta, xi, Xbar, bytes the arena
+ *       holds per node, bytes per slot, rmax (Rmax and rmax as omc_certificate_plan computes them).  OMC_ERR_UNSUPPORTED for k > 1. */
+int omc_relax_keep_shor_certificates(omc_instance* h, int on);
+int omc_relax_fetch_shor_certificate(omc_instance* h, int n_ids, const int* node_ids, double* scale, double* bound, double* lam, int* R, double* Q,
+                                     int* r, double* Psi3, double* Gam, double* zeta, double* xi, double* Xbar, int* nq, int64_t* nq_stride);
+int omc_shor_certificate_plan(int n, int m, int k, int64_t nq_stride, int max_cuts, int nonstandard_box_rows, int64_t* out);
 
 /* ---- alternating_minimization (OMC.jl:1979-2279), disjunctive mode, B problems at once, rank k <= 8 --------
  * U_initial n*k per problem; cuts as above (only the per-cut bounds on v = U'x are imposed, OMC.jl:2047-2093);

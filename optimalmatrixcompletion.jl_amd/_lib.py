@@ -21,6 +21,7 @@ EXPORTS = [
     "omc_state_pool_reserve_shor", "omc_shor_warm_compat", "omc_last_shor_warm_stats", "omc_state_pool_fetch_shor",
     "omc_relax_reserve_shor", "omc_relax_append_shor", "omc_relax_fetch_done_shor",
     "omc_relax_keep_certificates", "omc_relax_fetch_certificate", "omc_certificate_plan", "omc_dual_bound_batch",
+    "omc_relax_keep_shor_certificates", "omc_relax_fetch_shor_certificate", "omc_shor_certificate_plan",
     "omc_altmin_master_objectives", "omc_altmin_plan", "omc_comm_unique_id", "omc_comm_init", "omc_allreduce_bounds", "omc_bcast_incumbent", "omc_allgather_records", "omc_comm_destroy",
 ]
 
@@ -115,6 +116,10 @@ def load():
         lib.omc_relax_fetch_certificate.argtypes = [vp, C.c_int] + [vp] * 8
         lib.omc_certificate_plan.argtypes = [C.c_int] * 5 + [vp]
         lib.omc_dual_bound_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 12
+    if hasattr(lib, "omc_relax_keep_shor_certificates"):      # absent from an older A/B build; the Shor certificate methods of Engine raise there
+        lib.omc_relax_keep_shor_certificates.argtypes = [vp, C.c_int]
+        lib.omc_relax_fetch_shor_certificate.argtypes = [vp, C.c_int] + [vp] * 14
+        lib.omc_shor_certificate_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, vp]
     lib.omc_tuning_set.argtypes = [vp, C.c_char_p, C.c_char_p]
     lib.omc_tuning_reload_env.argtypes = [vp]
     lib.omc_debug_residuals.argtypes = [vp, vp, vp]

@@ -8,6 +8,7 @@ backed by the HIP library.  Reference = /root/reference/src/OptimalMatrixComplet
     .reserve / .append / .fetch_done / .hold      nodes pushed into a staged or running batch as their parents finish (the queue of OMC.jl:700-719);
     .reserve_shor / .append_shor / .fetch_done_shor   the same for a Shor-mode batch (rank 1)
     .keep_certificates / .fetch_certificate       the multipliers behind a node's dual_bound, for certificate.py (numpy) or .dual_bound (device) to re-evaluate
+    .keep_shor_certificates / .fetch_shor_certificate   the same for Shor-mode nodes (rank 1), for certificate.shor_dual_bound (numpy)
     .matrix_completion_master_feasible(Y, U)      OMC.jl:1261-1277
     .breakpoint_vectors(Y, U, breakpoints)        OMC.jl:2466-2477
     .evaluate_objective(X)                        OMC.jl:2330-2359
@@ -145,6 +146,14 @@ def certificate_plan(n, k, nnz, max_cuts=0, nonstandard_box_rows=0):
     out = np.zeros(6, np.int64)
     _lib.check(_lib.load().omc_certificate_plan(int(n), int(k), int(nnz), int(max_cuts), int(nonstandard_box_rows), _lib.ptr(out)))
     return dict(Lam=int(out[0]), lam=int(out[1]), Q=int(out[2]), Psi3=int(out[3]), bytes_per_node=int(out[4]), rmax=int(out[5]))
+
+
+def shor_certificate_plan(n, m, k, nq_stride, max_cuts=0, nonstandard_box_rows=0):
+    """omc_shor_certificate_plan (host only, no GPU): strides of a Shor-mode certificate in doubles, bytes per node of the arena and per slot, rmax."""
+    out = np.zeros(10, np.int64)
+    _lib.check(_lib.load().omc_shor_certificate_plan(int(n), int(m), int(k), int(nq_stride), int(max_cuts), int(nonstandard_box_rows), _lib.ptr(out)))
+    keys = ("lam", "Q", "Psi3", "Gam", "zeta", "xi", "Xbar", "bytes_per_node", "bytes_per_slot", "rmax")
+    return {key: int(v) for key, v in zip(keys, out)}
 
 
 class Engine:
@@ -495,7 +504,7 @@ class Engine:
     # ---- certificates (include/omc.h "certificates"; the checker is certificate.py) -------------------------------
     def keep_certificates(self, on=True):
         """The stage() calls that follow keep, per node, the multipliers of the check that gave its dual_bound (omc_relax_keep_certificates).
-        Refused while a submitted solve runs; stage_shor raises OMC_ERR_UNSUPPORTED while it is on."""
+        Refused while a submitted solve runs; stage_shor raises OMC_ERR_UNSUPPORTED while it is on (Shor mode has keep_shor_certificates)."""
         _lib.check(self._lib.omc_relax_keep_certificates(self._h, 1 if on else 0))
 
     def certificate_plan(self, max_cuts=0, nonstandard_box_rows=0):
@@ -530,6 +539,44 @@ class Engine:
             dense = np.zeros((n, m)); dense[rows, cols] = Lam[i, :nnz]
             out.append(certificate.Certificate(Lam=dense, lam=lam[i, :int(R[i])].copy(), Q=Q[i, :n * ri].reshape((n, ri), order="F").copy(),
                                                Psi3=Psi[i, :N3 * N3].reshape((N3, N3), order="F").copy(), bound=float(bd[i])))
+        return out
+
+    def keep_shor_certificates(self, on=True):
+        """The stage_shor() calls that follow keep, per node, the multipliers of the check that gave its dual_bound
+        (omc_relax_keep_shor_certificates): a switch of its own, independent of keep_certificates().  Rank 1; refused while a submitted solve runs."""
+        _lib.check(self._lib.omc_relax_keep_shor_certificates(self._h, 1 if on else 0))
+
+    def shor_certificate_plan(self, nq_stride, max_cuts=0, nonstandard_box_rows=0):
+        """Strides and bytes per node / per slot of the Shor-mode certificates of this instance (omc_shor_certificate_plan, host only)."""
+        return shor_certificate_plan(self.n, self.m, self.k, nq_stride, max_cuts, nonstandard_box_rows)
+
+    def fetch_shor_certificate(self, ids):
+        """certificate.ShorCertificate of every node id (omc_relax_fetch_shor_certificate): ids that fetch_done() has returned while the solve
+        runs, or any node of fetch() after it, staged or appended.  Raises OmcError for a batch staged without keep_shor_certificates(), an
+        unfinished id, and a node that never reached a rigorous check.  The lists are the caller's: certificate.shor_dual_bound takes them."""
+        n, m, k = self.n, self.m, self.k
+        idv = np.ascontiguousarray(np.asarray(list(ids), dtype=np.int32))
+        c = len(idv); c1 = max(c, 1)
+        stride = np.zeros(1, np.int64)
+        _lib.check(self._lib.omc_relax_fetch_shor_certificate(self._h, 0, None, *([None] * 12), _lib.ptr(stride)))
+        ns = int(stride[0])
+        info = self.solver_info()
+        Rmax, rmax = max(info["R_max"], 1), max(info["r_max"], 1)
+        ps = (rmax + k) ** 2
+        sc = np.zeros(c1); bd = np.zeros(c1); lam = np.zeros((c1, Rmax)); R = np.zeros(c1, np.int32); Q = np.zeros((c1, n * rmax)); r = np.zeros(c1, np.int32)
+        Psi = np.zeros((c1, ps)); Gam = np.zeros((c1, 15 * max(ns, 1))); zeta = np.zeros((c1, m)); xi = np.zeros((c1, n * m)); Xb = np.zeros((c1, n * m))
+        nq = np.zeros(c1, np.int32)
+        _lib.check(self._lib.omc_relax_fetch_shor_certificate(self._h, c, _lib.ptr(idv), _lib.ptr(sc), _lib.ptr(bd), _lib.ptr(lam), _lib.ptr(R), _lib.ptr(Q),
+                                                              _lib.ptr(r), _lib.ptr(Psi), _lib.ptr(Gam) if ns else None, _lib.ptr(zeta), _lib.ptr(xi), _lib.ptr(Xb),
+                                                              _lib.ptr(nq), None))
+        out = []
+        for i in range(c):
+            ri = int(r[i]); N3 = ri + k
+            G = certificate.unpack_gam(Gam[i, :15 * ns].reshape(15, ns), int(nq[i])) if ns else np.zeros((0, 5, 5))
+            out.append(certificate.ShorCertificate(scale=float(sc[i]), lam=lam[i, :int(R[i])].copy(), Q=Q[i, :n * ri].reshape((n, ri), order="F").copy(),
+                                                   Psi3=Psi[i, :N3 * N3].reshape((N3, N3), order="F").copy(), Gam=G, zeta=zeta[i].copy(),
+                                                   xi=xi[i].reshape((n, m), order="F").copy(), Xbar=Xb[i].reshape((n, m), order="F").copy(),
+                                                   bound=float(bd[i])))
         return out
 
     def _bounds_flat(self, B, U_lower, U_upper):

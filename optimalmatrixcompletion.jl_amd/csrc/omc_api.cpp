@@ -596,16 +596,17 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
     w.oobj = os; w.olb = os + sN; w.olmin = os + 2 * sN; w.orho = os + 4 * sN;
     w.ostatus = h->boint.as<int>(); w.oiters = h->boint.as<int>() + sN;
   }
-  if (h->keep_cert && !shor) {      // best certificate per node: slot buffers and the arena of the nodes, zeroed (no slot and no node holds one)
-    const size_t ps = (size_t)(rmax + k) * (rmax + k), per = (size_t)h->nnz + Rmax + ps;
+  if ((h->keep_cert && !shor) || (h->keep_shor_cert && shor)) {      // best certificate per node: slot buffers and the arena of the nodes, zeroed (no slot and no node holds one)
+    const size_t cnnz = shor ? 0 : (size_t)h->nnz;      // Shor mode has no alphaX: its own multipliers are kept by omc_relax_stage_shor (ShWS::cbGam ...)
+    const size_t ps = (size_t)(rmax + k) * (rmax + k), per = cnnz + Rmax + ps;
     ENS(h->bcbD, sB * (2 + per) * 8); ENS(h->bcbI, sB * 2 * sizeof(int)); ENS(h->bocD, sN * (1 + per) * 8); ENS(h->bocI, sN * sizeof(int));
     HIPCHK(hipMemsetAsync(h->bcbD.p, 0, sB * (2 + per) * 8, h->stream)); HIPCHK(hipMemsetAsync(h->bcbI.p, 0, sB * 2 * sizeof(int), h->stream));
     HIPCHK(hipMemsetAsync(h->bocD.p, 0, sN * (1 + per) * 8, h->stream)); HIPCHK(hipMemsetAsync(h->bocI.p, 0, sN * sizeof(int), h->stream));
     double* cb = h->bcbD.as<double>();
-    w.cb_rho = cb; w.cbBound = cb + sB; w.cbLam = cb + 2 * sB; w.cblam = w.cbLam + sB * h->nnz; w.cbPsi = w.cblam + sB * Rmax;
+    w.cb_rho = cb; w.cbBound = cb + sB; w.cbLam = shor ? nullptr : cb + 2 * sB; w.cblam = cb + 2 * sB + sB * cnnz; w.cbPsi = w.cblam + sB * Rmax;
     w.cert_flag = h->bcbI.as<int>(); w.cert_have = w.cert_flag + sB;
     double* oc = h->bocD.as<double>();
-    w.ocBound = oc; w.ocLam = oc + sN; w.oclam = w.ocLam + sN * h->nnz; w.ocPsi = w.oclam + sN * Rmax;
+    w.ocBound = oc; w.ocLam = shor ? nullptr : oc + sN; w.oclam = oc + sN + sN * cnnz; w.ocPsi = w.oclam + sN * Rmax;
     w.ocHave = h->bocI.as<int>();
   }
   // warm-start indices of this batch (consumed: they belong to this stage call only)
@@ -1169,7 +1170,9 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
   if (B <= 0) return fail(OMC_ERR_ARGUMENT, "B must be positive");
   if (!n_shor || !n_soc) return fail(OMC_ERR_ARGUMENT, "n_shor / n_soc is NULL");
-  if (h->keep_cert) return fail(OMC_ERR_UNSUPPORTED, "omc_relax_stage_shor: certificates are kept (omc_relax_keep_certificates) and the Shor-mode bound has multipliers the certificate layout does not hold");
+  if (h->keep_shor_cert && h->k > 1)
+    return fail(OMC_ERR_UNSUPPORTED, "omc_relax_stage_shor: Shor-mode certificates are kept (omc_relax_keep_shor_certificates) and rank k > 1 has no certificate layout (its minors are vacuous, quirk Q5)");
+  if (h->keep_cert && !h->keep_shor_cert) return fail(OMC_ERR_UNSUPPORTED, "omc_relax_stage_shor: certificates are kept (omc_relax_keep_certificates) and the Shor-mode bound has multipliers the certificate layout does not hold");
   const int n = h->n, m = h->m;
   if ((long long)n * m >= (1ll << 30)) return fail(OMC_ERR_UNSUPPORTED, "Shor mode: n * m too large for the 32-bit index structures");
   // ---- group the nodes by identical lists ------------------------------------------------------------------------------------------
@@ -1318,6 +1321,19 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
     sh.load_from = w.load_from; sh.save_to = w.save_to; sh.pscal = w.pscal; sh.pY = w.pY; sh.rho_node = w.rho_node;
     sh.pS = h->pShor.as<double>(); sh.pShdr = h->pShorHdr.as<long long>(); sh.pstride = PL.stride; sh.pnq = (int)h->pool_nqmax;
     ENS(h->sloadpart, sB * NPb * 2 * 8); sh.loadpart = h->sloadpart.as<double>();
+  }
+  if (h->keep_shor_cert) {      // best certificate per node, Shor part: blocks, paraboloid multipliers and points, per slot and per node of the capacity; zeroed
+    const size_t per = 15 * nq1 + (size_t)m + 2 * nm;
+    if (h->scbD.ensure(sB * per * 8) || h->socD.ensure(sN * per * 8) || h->socNq.ensure(sN * sizeof(int))) {
+      (void)hipGetLastError();
+      return fail(OMC_ERR_ALLOC, "omc_relax_stage_shor: the Shor-mode certificates need " + std::to_string(per * 8) + " bytes per slot (" + std::to_string(S) +
+                                 ") and per node of the capacity (" + std::to_string(h->node_cap) + "), which the device does not have (" + g_err + ")");
+    }
+    HIPCHK(hipMemsetAsync(h->scbD.p, 0, sB * per * 8, s)); HIPCHK(hipMemsetAsync(h->socD.p, 0, sN * per * 8, s)); HIPCHK(hipMemsetAsync(h->socNq.p, 0, sN * sizeof(int), s));
+    double* cb = h->scbD.as<double>(); double* oc = h->socD.as<double>();
+    sh.cbGam = cb; sh.cbZeta = cb + sB * 15 * nq1; sh.cbXi = sh.cbZeta + sB * m; sh.cbXbar = sh.cbXi + sB * nm;
+    sh.ocGam = oc; sh.ocZeta = oc + sN * 15 * nq1; sh.ocXi = sh.ocZeta + sN * m; sh.ocXbar = sh.ocXi + sN * nm;
+    sh.ocNq = h->socNq.as<int>(); sh.cert_flag = w.cert_flag; sh.cb_rho = w.cb_rho;
   }
   if (h->shor_keep_V) { ENS(h->soV, sN * 5 * nq1 * 8); HIPCHK(hipMemsetAsync(h->soV.p, 0, sN * 5 * nq1 * 8, s)); sh.oV = h->soV.as<double>(); }
   // ---- base workspace in Shor mode, and the view through which its eigen-kernels project the order-(n+m) cone -------------------------
@@ -1580,7 +1596,8 @@ int omc_relax_fetch_certificate(omc_instance* h, int n_ids, const int* node_ids,
   if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
   if (!h->staged) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: nothing staged");
   const OmcWS& w = h->ws;
-  if (!w.cert_flag) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: the batch was staged without omc_relax_keep_certificates(h, 1)");
+  if (!w.cert_flag || !w.ocLam)      // a Shor-mode batch keeps certificates of its own (omc_relax_fetch_shor_certificate)
+    return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: the batch was staged without omc_relax_keep_certificates(h, 1)");
   if (n_ids < 0 || (n_ids > 0 && !node_ids)) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: bad arguments");
   if (n_ids == 0) return 0;
   {      // an id is known once omc_relax_fetch_done has returned it, or once the solve has ended and harvested it
@@ -1611,6 +1628,77 @@ int omc_relax_fetch_certificate(omc_instance* h, int n_ids, const int* node_ids,
     if (r) HIPCHK(hipMemcpyAsync(r + o, w.rr + nb, sizeof(int), hipMemcpyDeviceToHost, fs));
     if (Psi3) HIPCHK(hipMemcpyAsync(Psi3 + o * ps, w.ocPsi + nb * ps, 8 * ps, hipMemcpyDeviceToHost, fs));
     if (bound) HIPCHK(hipMemcpyAsync(bound + o, w.ocBound + nb, 8, hipMemcpyDeviceToHost, fs));
+  }
+  HIPCHK(hipStreamSynchronize(fs));
+  return 0;
+}
+
+// ---- the same for Shor mode (omc.h: "Shor-mode certificates") -------------------------------------------------------------------------------
+int omc_relax_keep_shor_certificates(omc_instance* h, int on) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
+  if (h->worker.joinable() || h->worker_running.load()) return fail(OMC_ERR_ARGUMENT, "omc_relax_keep_shor_certificates: a solve is in flight (call omc_relax_wait first)");
+  h->keep_shor_cert = on != 0;
+  return 0;
+}
+
+int omc_shor_certificate_plan(int n, int m, int k, int64_t nq_stride, int max_cuts, int nonstandard_box_rows, int64_t* out) {
+  if (!out) return fail(OMC_ERR_ARGUMENT, "out is NULL");
+  if (n <= 0 || m <= 0 || k <= 0 || nq_stride < 0 || max_cuts < 0 || nonstandard_box_rows < 0)
+    return fail(OMC_ERR_ARGUMENT, "omc_shor_certificate_plan: n, m and k must be positive, the counts not negative");
+  if (k > 1) return fail(OMC_ERR_UNSUPPORTED, "omc_shor_certificate_plan: Shor-mode certificates exist for rank 1 only");
+  const int64_t Rmax = 1 + (int64_t)k * (k + 1) / 2 + nonstandard_box_rows + (int64_t)max_cuts * (2 * k + 1);
+  const int64_t rmax = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)k + nonstandard_box_rows + max_cuts));
+  out[0] = Rmax; out[1] = (int64_t)n * rmax; out[2] = (rmax + k) * (rmax + k); out[3] = 15 * nq_stride; out[4] = m; out[5] = (int64_t)n * m; out[6] = (int64_t)n * m;
+  const int64_t per = out[0] + out[2] + out[3] + out[4] + out[5] + out[6];      // Q is part of the node's descriptor
+  out[7] = 8 * (1 + per) + 8;      // arena, per node: the bound, the arrays, the flag and the minor count
+  out[8] = 8 * (2 + per) + 8;      // per slot: penalty and bound of the check, the arrays, two flags
+  out[9] = rmax;
+  return 0;
+}
+
+int omc_relax_fetch_shor_certificate(omc_instance* h, int n_ids, const int* node_ids, double* scale, double* bound, double* lam, int* R, double* Q,
+                                     int* r, double* Psi3, double* Gam, double* zeta, double* xi, double* Xbar, int* nq, int64_t* nq_stride) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
+  if (!h->staged) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_shor_certificate: nothing staged");
+  const OmcWS& w = h->ws; const ShWS& sh = h->sh;
+  if (!h->shor_on || !sh.cbGam || !w.cert_flag)
+    return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_shor_certificate: the batch was staged without omc_relax_keep_shor_certificates(h, 1) (or is not a Shor-mode batch)");
+  if (n_ids < 0 || (n_ids > 0 && !node_ids)) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_shor_certificate: bad arguments");
+  if (nq_stride) *nq_stride = sh.nqmax;
+  if (n_ids == 0) return 0;
+  {      // an id is known once omc_relax_fetch_done has returned it, or once the solve has ended and harvested it
+    bool ended; { std::lock_guard<std::mutex> lk(h->append_mu); ended = h->append_closed; }
+    std::lock_guard<std::mutex> lk(h->done_mu);
+    std::vector<char> seen((size_t)std::max(h->node_cap, 1), 0);
+    const size_t upto = ended ? h->done_q.size() : h->done_read;
+    for (size_t i = 0; i < upto; ++i) if ((size_t)h->done_q[i] < seen.size()) seen[h->done_q[i]] = 1;
+    for (int i = 0; i < n_ids; ++i)
+      if (node_ids[i] < 0 || (size_t)node_ids[i] >= seen.size() || !seen[node_ids[i]])
+        return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_shor_certificate: node " + std::to_string(node_ids[i]) + " is out of range or has not finished (omc_relax_fetch_done has not returned it)");
+  }
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->fetch_stream) HIPCHK(hipStreamCreateWithFlags(&h->fetch_stream, hipStreamNonBlocking));
+  hipStream_t fs = h->fetch_stream;
+  std::vector<int> have(n_ids, 0);
+  for (int i = 0; i < n_ids; ++i) HIPCHK(hipMemcpyAsync(&have[i], w.ocHave + node_ids[i], sizeof(int), hipMemcpyDeviceToHost, fs));
+  HIPCHK(hipStreamSynchronize(fs));
+  for (int i = 0; i < n_ids; ++i)
+    if (!have[i]) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_shor_certificate: node " + std::to_string(node_ids[i]) + " never reached a rigorous check (no certificate)");
+  const size_t Rm = (size_t)w.Rmax, nqd = (size_t)w.n * w.rmax, ps = (size_t)(w.rmax + w.k) * (w.rmax + w.k), gs = (size_t)15 * sh.nqmax, m = (size_t)sh.m, nm = (size_t)sh.n * sh.m;
+  for (int i = 0; i < n_ids; ++i) {
+    const size_t nb = (size_t)node_ids[i], o = (size_t)i;
+    if (scale) scale[o] = sh.sc;
+    if (bound) HIPCHK(hipMemcpyAsync(bound + o, w.ocBound + nb, 8, hipMemcpyDeviceToHost, fs));
+    if (lam) HIPCHK(hipMemcpyAsync(lam + o * Rm, w.oclam + nb * Rm, 8 * Rm, hipMemcpyDeviceToHost, fs));
+    if (R) HIPCHK(hipMemcpyAsync(R + o, w.R + nb, sizeof(int), hipMemcpyDeviceToHost, fs));
+    if (Q) HIPCHK(hipMemcpyAsync(Q + o * nqd, w.Qb + nb * nqd, 8 * nqd, hipMemcpyDeviceToHost, fs));
+    if (r) HIPCHK(hipMemcpyAsync(r + o, w.rr + nb, sizeof(int), hipMemcpyDeviceToHost, fs));
+    if (Psi3) HIPCHK(hipMemcpyAsync(Psi3 + o * ps, w.ocPsi + nb * ps, 8 * ps, hipMemcpyDeviceToHost, fs));
+    if (Gam && gs) HIPCHK(hipMemcpyAsync(Gam + o * gs, sh.ocGam + nb * gs, 8 * gs, hipMemcpyDeviceToHost, fs));
+    if (zeta) HIPCHK(hipMemcpyAsync(zeta + o * m, sh.ocZeta + nb * m, 8 * m, hipMemcpyDeviceToHost, fs));
+    if (xi) HIPCHK(hipMemcpyAsync(xi + o * nm, sh.ocXi + nb * nm, 8 * nm, hipMemcpyDeviceToHost, fs));
+    if (Xbar) HIPCHK(hipMemcpyAsync(Xbar + o * nm, sh.ocXbar + nb * nm, 8 * nm, hipMemcpyDeviceToHost, fs));
+    if (nq) HIPCHK(hipMemcpyAsync(nq + o, sh.ocNq + nb, sizeof(int), hipMemcpyDeviceToHost, fs));
   }
   HIPCHK(hipStreamSynchronize(fs));
   return 0;

@@ -159,6 +159,8 @@ struct OmcWS {
   // and the penalty of this check when its RIGOROUS bound raised lb[b]; k_cert_snapshot then copies the multipliers behind that bound (alphaX,
   // lam, rho x the three blocks of Q3 as one order-(r + k) matrix) into the slot's cb* buffers, before k_rho_rescale acts on a bump decided at
   // the same check; k_cert_harvest copies them to the per-node arena oc* beside k_harvest.  Strides: nnz, Rmax, (rmax + k)^2, 1.
+  // Shor mode (omc_relax_keep_shor_certificates): cbLam = ocLam = NULL (no alphaX there; both kernels test the pointer), the rest as above, and
+  // the multipliers of the Shor program in ShWS::cbGam ... (omc_shor_relax.h).
   int *cert_flag, *cert_have;                    // B: snapshot wanted at this check ; the slot holds one
   double *cb_rho, *cbLam, *cblam, *cbPsi, *cbBound;   // per slot
   double *ocLam, *oclam, *ocPsi, *ocBound; int* ocHave;   // per node

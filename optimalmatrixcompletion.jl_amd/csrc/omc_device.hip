@@ -2804,7 +2804,7 @@ __global__ void __launch_bounds__(256) k_cert_snapshot(OmcWS w) {
   const int nb = w.node_of[b];
   const int k = w.k, rm = w.rmax, r = w.rr[nb], N3 = r + k;
   const double rho = w.cb_rho[b];
-  for (int e = tid; e < w.nnz; e += T) w.cbLam[(size_t)b * w.nnz + e] = w.alphaX[(size_t)b * w.nnz + e];
+  if (w.cbLam) for (int e = tid; e < w.nnz; e += T) w.cbLam[(size_t)b * w.nnz + e] = w.alphaX[(size_t)b * w.nnz + e];      // NULL in Shor mode: no alphaX there
   for (int e = tid; e < w.Rmax; e += T) w.cblam[(size_t)b * w.Rmax + e] = w.lam[(size_t)b * w.Rmax + e];
   double* P = w.cbPsi + (size_t)b * (rm + k) * (rm + k);
   const double* dS = w.dS + (size_t)b * rm * rm;
@@ -2828,7 +2828,7 @@ __global__ void __launch_bounds__(256) k_cert_harvest(OmcWS w) {
   if (!w.fin[b]) return;
   const int nb = w.node_of[b];
   const size_t ps = (size_t)(w.rmax + w.k) * (w.rmax + w.k);
-  for (int e = tid; e < w.nnz; e += T) w.ocLam[(size_t)nb * w.nnz + e] = w.cbLam[(size_t)b * w.nnz + e];
+  if (w.cbLam) for (int e = tid; e < w.nnz; e += T) w.ocLam[(size_t)nb * w.nnz + e] = w.cbLam[(size_t)b * w.nnz + e];
   for (int e = tid; e < w.Rmax; e += T) w.oclam[(size_t)nb * w.Rmax + e] = w.cblam[(size_t)b * w.Rmax + e];
   for (size_t e = tid; e < ps; e += T) w.ocPsi[(size_t)nb * ps + e] = w.cbPsi[(size_t)b * ps + e];
   if (tid == 0) { w.ocBound[nb] = w.cbBound[b]; w.ocHave[nb] = w.cert_have[b]; w.cert_have[b] = 0; w.cert_flag[b] = 0; }

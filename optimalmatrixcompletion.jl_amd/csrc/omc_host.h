@@ -175,6 +175,9 @@ struct omc_instance {
   // best certificates per node (omc_relax_keep_certificates): asked for before a stage call; that call allocates the per-slot buffers and the
   // per-node arena (OmcWS::cert_flag ...) and nothing exists while the request is off
   bool keep_cert = false; DevBuf bcbD, bcbI, bocD, bocI;
+  // the same for Shor mode (omc_relax_keep_shor_certificates), a switch of its own: the omc_relax_stage_shor call allocates the base buffers above
+  // without Lam (lam, Psi3, bound, flags) and the Shor ones (ShWS::cbGam ...)
+  bool keep_shor_cert = false; DevBuf scbD, socD, socNq;
   DevBuf dbD, dbI, dbM, dbS, dbL;      // omc_dual_bound_batch: descriptors and multipliers, ints, matrices, eigen-kernel slab, dense Lam
   // Shor minors (a10 / a11): row bitsets and per-pair popcounts, built at the first call
   DevBuf sbits, scb, scx, scz, soff, stot, sout, shi, slo, sexist, shist, sohi, solo, scnt;

@@ -453,6 +453,7 @@ struct SolveLoop {
         else omc_launch_cone(&w, CONE_EVALS, s);
         omc_launch_check_final(&w, timed_out ? OMC_ST_TIME : 0, 2, s);      // per-slot iteration cap is applied on the device
       }
+      if (shor && sw.cbGam) omc_shor_launch_cert_snapshot(&sw, s);      // Shor mode: blocks, paraboloid multipliers and points, ahead of the kernel that clears the flag
       if (w.cert_flag) omc_launch_cert_snapshot(&w, s);      // the multipliers of a bound that has just been taken, at the penalty it was computed with
       if (w.bump_max > 0) { if (shor) omc_shor_launch_rescale(&sw, s); omc_launch_rho_rescale(&w, s); }
       if (w.accel) omc_launch_aa(&w, s);      // after the certificate (computed on an image of the map), skips finished slots
@@ -520,6 +521,7 @@ struct SolveLoop {
       omc_launch_cone(&w, CONE_SEP, s);           // separation vector (OMC.jl:2466-2477)
       omc_launch_harvest(&w, s);
       if (w.cert_flag) omc_launch_cert_harvest(&w, s);
+      if (shor && sw.cbGam) omc_shor_launch_cert_harvest(&sw, s);
       if (shor) omc_shor_launch_harvest(&sw, s);
     });
   }

@@ -57,6 +57,15 @@ struct ShWS {
   double* pS; long long* pShdr;                 // pool_cap * pstride doubles (layout: shor_pool_*) ; pool_cap * 4: nq, list hash, 0, 0
   size_t pstride; int pnq;                      // doubles per entry ; minors an entry has room for (stride of its per-minor arrays)
   double* loadpart;                             // S * NPb * 2: per-column sums of the rebuilt big-cone input (k_shor_state_load)
+  // Best certificate per node (omc_relax_keep_shor_certificates; every pointer NULL when off), beside lam and Psi3 that the base workspace keeps
+  // (OmcWS::cblam ...).  k_shor_cert_snapshot runs behind the last k_check_final and before the base k_cert_snapshot (which clears the flag) and
+  // the rescale kernels: for the slots with cert_flag set it copies the blocks Gamma' (Nq after k_shor_chk_minor, its six V entries corrected
+  // with e1 / e2 and the penalty cb_rho of that check), zeta_adm = max(cb_rho r5 nu5, 0), P5x and X.  k_shor_cert_harvest copies them to the
+  // per-node arena beside k_shor_harvest.  Per-minor arrays keep the SoA order [entry][minor] with stride nqmax.
+  const int* cert_flag; const double* cb_rho;   // S: of the base workspace
+  double *cbGam, *cbZeta, *cbXi, *cbXbar;       // S * (15 nqmax, m, n*m, n*m)
+  double *ocGam, *ocZeta, *ocXi, *ocXbar;       // node capacity * the same
+  int* ocNq;                                    // node capacity: the node's own minor count
 };
 
 // Shor extension of a pool entry, in doubles: X, W (completed: X^2 off the minors), D5x | Theta | D0 | D5t, nu5 | Tq (15 per minor, SoA with
@@ -83,6 +92,8 @@ void omc_shor_launch_check(const ShWS* w, hipStream_t s);
 void omc_shor_launch_rescale(const ShWS* w, hipStream_t s);
 void omc_shor_launch_harvest(const ShWS* w, hipStream_t s);
 void omc_shor_launch_state_save(const ShWS* w, hipStream_t s);
+void omc_shor_launch_cert_snapshot(const ShWS* w, hipStream_t s);      /* only with w->cbGam */
+void omc_shor_launch_cert_harvest(const ShWS* w, hipStream_t s);       /* only with w->cbGam */
 #ifdef __cplusplus
 }
 #endif

@@ -795,6 +795,58 @@ __global__ void __launch_bounds__(SH_T) k_shor_state_load_fin(ShWS w) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// best certificate per node (omc_relax_keep_shor_certificates): plain copies, one lane per minor over the 15 SoA planes (a wave reads and
+// writes 64 consecutive doubles per plane), grid-stride over the matrices; no LDS, no atomics.  Work is bounded by the node's own nq,
+// addresses use the stride nqmax.
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Slots that k_check_final flagged at this check.  Nq is mixed after k_shor_chk_minor: the first row and the diagonal hold Gamma' already,
+// the six V entries the raw P - input; what the bound used there is sc Nq - e (V1, V2) and +-1/2 sc (Nq[11] - Nq[8]) (V3), sc = cb_rho r4 the
+// penalty of this check (rho_b may carry a bump decided at the same check; e1 / e2 were computed with the check's penalty).
+__global__ void __launch_bounds__(SH_T) k_shor_cert_snapshot(ShWS w) {
+  const int b = blockIdx.y;
+  if (!w.cert_flag[b]) return;
+  const int nb = w.node_of[b];
+  const ShorGroupDev G = w.groups[w.node_group[nb]];
+  const int nq = G.nq, m = w.m;
+  const size_t nm = (size_t)w.n * m, g0 = (size_t)blockIdx.x * SH_T + threadIdx.x, gs = (size_t)gridDim.x * SH_T;
+  const double rho = w.cb_rho[b], sc = rho * G.r4;
+  const double* Nq = w.Nq + (size_t)b * 15 * w.nqmax;
+  double* O = w.cbGam + (size_t)b * 15 * w.nqmax;
+  const double* e1 = w.e1 + (size_t)b * w.nv1max; const double* e2 = w.e2 + (size_t)b * w.nv2max;
+  for (size_t q = g0; q < (size_t)nq; q += gs) {
+    double v[15];
+#pragma unroll
+    for (int e = 0; e < 15; ++e) v[e] = Nq[(size_t)e * w.nqmax + q];
+    v[4] = sc * v[4] - e1[G.kid[q]];
+    v[13] = sc * v[13] - e1[G.kid[nq + q]];
+    v[7] = sc * v[7] - e2[G.kid[2 * (size_t)nq + q]];
+    v[12] = sc * v[12] - e2[G.kid[3 * (size_t)nq + q]];
+    const double d = 0.5 * sc * (v[11] - v[8]);
+    v[11] = d; v[8] = -d;
+#pragma unroll
+    for (int e = 0; e < 15; ++e) O[(size_t)e * w.nqmax + q] = v[e];
+  }
+  for (size_t e = g0; e < nm; e += gs) { w.cbXi[b * nm + e] = w.P5x[b * nm + e]; w.cbXbar[b * nm + e] = w.X[b * nm + e]; }
+  for (size_t j = g0; j < (size_t)m; j += gs) w.cbZeta[(size_t)b * m + j] = fmax(rho * w.r5 * w.nu5[(size_t)b * m + j], 0.0);
+}
+
+// slot buffers -> per-node arena for the slots flagged fin (beside k_shor_harvest and the base k_cert_harvest, which moves the bound and the flag)
+__global__ void __launch_bounds__(SH_T) k_shor_cert_harvest(ShWS w) {
+  const int b = blockIdx.y;
+  if (!w.fin[b]) return;
+  const int nb = w.node_of[b];
+  const int nq = w.groups[w.node_group[nb]].nq, m = w.m;
+  const size_t nm = (size_t)w.n * m, g0 = (size_t)blockIdx.x * SH_T + threadIdx.x, gs = (size_t)gridDim.x * SH_T;
+  const double* I = w.cbGam + (size_t)b * 15 * w.nqmax;
+  double* O = w.ocGam + (size_t)nb * 15 * w.nqmax;
+  for (int e = 0; e < 15; ++e)
+    for (size_t q = g0; q < (size_t)nq; q += gs) O[(size_t)e * w.nqmax + q] = I[(size_t)e * w.nqmax + q];
+  for (size_t e = g0; e < nm; e += gs) { w.ocXi[(size_t)nb * nm + e] = w.cbXi[b * nm + e]; w.ocXbar[(size_t)nb * nm + e] = w.cbXbar[b * nm + e]; }
+  for (size_t j = g0; j < (size_t)m; j += gs) w.ocZeta[(size_t)nb * m + j] = w.cbZeta[(size_t)b * m + j];
+  if (g0 == 0) w.ocNq[nb] = nq;
+}
+
 // blocks per slot of the two state kernels: enough for the largest array of an entry at four elements per thread
 static int shor_state_blocks(const ShWS* w) {
   const size_t big = (size_t)15 * (size_t)(w->nqmax > 0 ? w->nqmax : 1), nn = (size_t)w->NPb * w->NPb;
@@ -836,4 +888,7 @@ void omc_shor_launch_state_save(const ShWS* w, hipStream_t s) {
   if (w->save_to) hipLaunchKernelGGL(k_shor_state_save, dim3(shor_state_blocks(w), w->S), dim3(SH_T), 0, s, *w);
 }
 void omc_shor_launch_harvest(const ShWS* w, hipStream_t s) { hipLaunchKernelGGL(k_shor_harvest, dim3(w->m, w->S), dim3(SH_T), 0, s, *w); }
+// one block per 256 minors (at least one): the matrices ride on the same blocks by grid stride
+void omc_shor_launch_cert_snapshot(const ShWS* w, hipStream_t s) { hipLaunchKernelGGL(k_shor_cert_snapshot, dim3(w->nmb, w->S), dim3(SH_T), 0, s, *w); }
+void omc_shor_launch_cert_harvest(const ShWS* w, hipStream_t s) { hipLaunchKernelGGL(k_shor_cert_harvest, dim3(w->nmb, w->S), dim3(SH_T), 0, s, *w); }
 }
