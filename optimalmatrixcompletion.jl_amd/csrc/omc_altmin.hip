@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(256) k_altmin(AltminWS w) {
         cvec[r] = acc - w.rrhs[(size_t)b * w.Rmax + r];
       }
       __syncthreads();
-      if (R > 0 && tid < 64) { const int ov = wave_nnqp(G, w.Rmax, cvec, mu, R, s_Gp, s_sv, s_tmp, s_pl, tid); if (tid == 0) s_ov = ov; }
+      if (R > 0 && tid < 64) { const int ov = wave_nnqp<true>(G, w.Rmax, cvec, mu, R, s_Gp, s_sv, s_tmp, s_pl, tid); if (tid == 0) s_ov = ov; }
       __syncthreads();
       double nn = 0.0;
       for (int i = tid; i < n; i += T) {
@@ -209,15 +209,22 @@ __device__ __forceinline__ double ak_row_x(const AltminWS& w, int b, int r, int 
   if (kind == ROW_BOX) return (w.rbi[(size_t)b * w.Rmax + r] == i) ? cf : 0.0;
   return cf * w.cutx[((size_t)b * w.Lmax + w.rcut[(size_t)b * w.Rmax + r]) * w.n + i];
 }
-// in-place Gauss-Jordan inverse of a k x k symmetric positive definite matrix held in registers; false if a pivot is not positive
-__device__ __forceinline__ bool ak_inv(double (&a)[AK_KMAX][AK_KMAX], int k) {
+// A pivot of the V-step's normal equations at or below k u max_a M_aa (u = 2^-53) is a null direction of the positive semidefinite matrix
+// (a zero column of U, two equal columns): the right-hand side lies in the range of M, so leaving that row and column out and giving the
+// component 0 is a minimiser of model_V, and U V is the unique one.
+#define AM_NULL_PIVOT_U 1.1102230246251565e-16
+// in-place Gauss-Jordan inverse of a k x k symmetric positive definite matrix held in registers; false if a pivot is not positive.
+// null_tol >= 0: a pivot <= null_tol is not used -- with d = 0 its row and its column of the result become 0 and no other entry changes
+// (the pseudo-inverse on the other coordinates); pivots above it go through the same arithmetic as without a tolerance.
+__device__ __forceinline__ bool ak_inv(double (&a)[AK_KMAX][AK_KMAX], int k, double null_tol = -1.0) {
   bool ok = true;
 #pragma unroll
   for (int p = 0; p < AK_KMAX; ++p) {
     if (p >= k) continue;
     const double piv = a[p][p];
-    if (!(piv > 0.0)) ok = false;
-    const double d = 1.0 / piv;
+    const bool nul = null_tol >= 0.0 && !(piv > null_tol);
+    if (!(piv > 0.0) && !nul) ok = false;
+    const double d = nul ? 0.0 : 1.0 / piv;
     a[p][p] = 1.0;
 #pragma unroll
     for (int c = 0; c < AK_KMAX; ++c) if (c < k) a[p][c] *= d;
@@ -314,7 +321,7 @@ __global__ void __launch_bounds__(256) k_altmin_k(AltminWS w) {
       cvec[r] = acc - w.rrhs[(size_t)b * w.Rmax + r];
     }
     __syncthreads();
-    if (R > 0 && tid < 64) { const int ov = wave_nnqp(G, w.Rmax, cvec, mu, R, s_Gp, s_sv, s_tmp, s_pl, tid); if (tid == 0 && ov) s_ov = 1; }
+    if (R > 0 && tid < 64) { const int ov = wave_nnqp<true>(G, w.Rmax, cvec, mu, R, s_Gp, s_sv, s_tmp, s_pl, tid); if (tid == 0 && ov) s_ov = 1; }
     __syncthreads();
     double pv = 0.0;
     double qa[AK_QMAX];
@@ -397,14 +404,17 @@ __global__ void __launch_bounds__(256) k_altmin_k(AltminWS w) {
           for (int c2 = 0; c2 < AK_KMAX; ++c2) if (c2 < k) a_[a][c2] += ua * u[i * k + c2];
         }
       }
-      const bool ok = ak_inv(a_, k);
+      double dmax = 0.0;
+#pragma unroll
+      for (int a = 0; a < AK_KMAX; ++a) if (a < k) dmax = fmax(dmax, a_[a][a]);
+      ak_inv(a_, k, k * AM_NULL_PIVOT_U * dmax);
 #pragma unroll
       for (int a = 0; a < AK_KMAX; ++a) {
         if (a >= k) continue;
         double acc = 0.0;
 #pragma unroll
         for (int c2 = 0; c2 < AK_KMAX; ++c2) if (c2 < k) acc += a_[a][c2] * rhs[c2];
-        v[j * k + a] = ok ? acc : 0.0;
+        v[j * k + a] = acc;
       }
     }
     __syncthreads();
@@ -588,15 +598,16 @@ __global__ void __launch_bounds__(256) k_altmin_k(AltminWS w) {
 #define AW_QMAX (AW_KMAX * AW_KMAX)
 
 // in-place Gauss-Jordan inverse of a symmetric positive definite matrix spread over 8 lanes (lane a = row a; rows and columns >= k are the
-// identity); false, for the whole group, if a pivot is not positive
-__device__ __forceinline__ bool aw_inv8(double (&row)[AW_KMAX], int k, int a) {
+// identity); false, for the whole group, if a pivot is not positive.  null_tol as in ak_inv (the same value in the 8 lanes of a group).
+__device__ __forceinline__ bool aw_inv8(double (&row)[AW_KMAX], int k, int a, double null_tol = -1.0) {
   bool ok = true;
 #pragma unroll
   for (int p = 0; p < AW_KMAX; ++p) {
     if (p >= k) continue;                            // k is the same in every thread
     const double piv = __shfl(row[p], p, AW_KMAX);
-    if (!(piv > 0.0)) ok = false;
-    const double d = 1.0 / piv;
+    const bool nul = null_tol >= 0.0 && !(piv > null_tol);
+    if (!(piv > 0.0) && !nul) ok = false;
+    const double d = nul ? 0.0 : 1.0 / piv;
     if (a == p) {
       row[p] = 1.0;
 #pragma unroll
@@ -717,7 +728,7 @@ __global__ void __launch_bounds__(256) k_altmin_w(AltminWS w) {
       cvec[r] = acc - w.rrhs[(size_t)b * w.Rmax + r];
     }
     __syncthreads();
-    if (R > 0 && tid < 64) { const int ov = wave_nnqp(G, w.Rmax, cvec, mu, R, s_Gp, s_sv, s_tmp, s_pl, tid); if (tid == 0 && ov) s_ov = 1; }
+    if (R > 0 && tid < 64) { const int ov = wave_nnqp<true>(G, w.Rmax, cvec, mu, R, s_Gp, s_sv, s_tmp, s_pl, tid); if (tid == 0 && ov) s_ov = 1; }
     __syncthreads();
     for (int e = tid; e < n * k; e += T) {      // ut = u0 - sum_r mu_r x_r(i) Hinv_i[:, j_r]
       const int i = e / k, a = e - i * k;
@@ -773,11 +784,15 @@ __global__ void __launch_bounds__(256) k_altmin_w(AltminWS w) {
 #pragma unroll
         for (int c = 0; c < AW_KMAX; ++c) { const double uc = u[i * k + (c < k ? c : 0)]; if (ga < k && c < k) row[c] += ua * uc; }
       }
-      const bool ok = aw_inv8(row, k, ga);
+      double dmax = 0.0;                       // largest diagonal entry of the k x k block: this lane's, then over the group
+#pragma unroll
+      for (int c = 0; c < AW_KMAX; ++c) if (c == ga && c < k) dmax = row[c];
+      for (int o = AW_KMAX >> 1; o > 0; o >>= 1) dmax = fmax(dmax, __shfl_xor(dmax, o, AW_KMAX));
+      aw_inv8(row, k, ga, k * AM_NULL_PIVOT_U * dmax);
       double acc = 0.0;
 #pragma unroll
       for (int c = 0; c < AW_KMAX; ++c) { const double rc = __shfl(rhs, c, AW_KMAX); if (c < k) acc += row[c] * rc; }
-      if (valid && ga < k) v[j * k + ga] = ok ? acc : 0.0;
+      if (valid && ga < k) v[j * k + ga] = acc;
     }
     __syncthreads();
     // ---- U-step quantities: H_i = sum_{j in O_i} v_j v_j' + V V' / gamma, g_i = sum_{j in O_i} A_ij v_j --------------------------

@@ -266,6 +266,10 @@ __device__ __forceinline__ void wave_chol_solve(const double* Lm, int c, const d
 // ---------------------------------------------------------------------------------------------------------
 // Returns 1 (wave-uniform) when the passive set hit NNQP_PMAX with a violated row still outside it -- the result is then NOT the
 // exact projection and the caller must not certify / accept the point (relaxation: no OPTIMAL status; altmin: converged = false).
+// REFINE (the U-step of alternating minimisation): the ridge leaves every passive row with the residual 1e-14 dmax lam_r, i.e. a row
+// of model_U violated by that much; one step of iterative refinement against G itself, with the ridged factor, takes it to the rounding
+// level.  Without REFINE the arithmetic is what it always was.
+template <bool REFINE = false>
 __device__ __forceinline__ int wave_nnqp(const double* G, int ldG, const double* cvec, double* lam, int R, double* Gp, double* sv,
                           double* tmp, int* plist, int lane) {
   // plist: passive indices (LDS, NNQP_PMAX ints); Gp: PMAX x (PMAX+1); sv,tmp: PMAX doubles
@@ -323,6 +327,17 @@ __device__ __forceinline__ int wave_nnqp(const double* G, int ldG, const double*
         continue;
       }
       wave_chol_solve(Gp, np, tmp, sv, lane);
+      if (REFINE) {
+        for (int a = lane; a < np; a += WAVE) {
+          double r = cvec[plist[a]];
+          for (int c2 = 0; c2 < np; ++c2) r -= G[(size_t)plist[a] * ldG + plist[c2]] * sv[c2];
+          tmp[a] = r;
+        }
+        WAVE_SYNC();
+        wave_chol_solve(Gp, np, tmp, tmp, lane);      // in place: either sweep reads rhs[r] before it writes y[r]
+        for (int a = lane; a < np; a += WAVE) sv[a] += tmp[a];
+        WAVE_SYNC();
+      }
       // all positive?
       double mins = 1e300;
       for (int a = lane; a < np; a += WAVE) mins = fmin(mins, sv[a]);
