@@ -379,6 +379,52 @@ int omc_relax_fetch_shor_certificate(omc_instance* h, int n_ids, const int* node
                                      int* r, double* Psi3, double* Gam, double* zeta, double* xi, double* Xbar, int* nq, int64_t* nq_stride);
 int omc_shor_certificate_plan(int n, int m, int k, int64_t nq_stride, int max_cuts, int nonstandard_box_rows, int64_t* out);
 
+/* ---- the Shor-mode bound of caller-supplied multipliers, on the device (rank 1) ---------------------------------------------------------
+ * omc_shor_dual_bound_batch evaluates, for B nodes, the formula that certificate.py gives for a Shor-mode certificate (evaluate_shor for
+ * sanitise = 0, shor_dual_bound for sanitise = 1).  Nodes, cuts and U bounds in the wire format of omc_dual_bound_batch; the lists in the wire
+ * format of omc_relax_stage_shor (n_soc[b] = -1: every coordinate outside the minors); the multipliers in the layout of
+ * omc_relax_fetch_shor_certificate, so that a fetched certificate goes straight back in: scale (1 per node), lam (stride Rmax), Psi3 (order
+ * r + 1 at the head of a stride (rmax + 1)^2; NULL = zero), Gam (entry-major, Gam[b * 15 * nq_stride + e * nq_stride + q]; may be NULL when
+ * every n_shor[b] is 0), zeta (stride m), xi and Xbar (stride n * m, column-major).  Rmax and rmax are taken over the B nodes as
+ * omc_dual_bound_batch takes them, and the row basis is the one its query form returns.
+ *   sanitise = 0  the multipliers as they are: spread of the V residuals with the shift by ||E||_F, the further shift by max(0, -lambda_min) of
+ *                 the shifted block, zeta raised to what the W-stationarity needs, mu, phi, M, the rows, the smallest eigenvalue, ||c||.
+ *   sanitise = 1  zeta clamped at 0 on the type-0/1 columns, lam clamped at 0, Psi3 replaced by its PSD part, and the blocks taken in two ways --
+ *                 minus their negative part, and as given -- each followed by the steps above; the larger value is returned.
+ * bound[b] is in the node's own scale (divided by scale^2) and is -INFINITY exactly where the formula is: a scale that is not positive and
+ * finite (decided on the host: no view of that node reaches the device), mu_j <= 0 meeting a nonzero phi_j, anything not finite on the way.
+ * defects (5 per node, may be NULL): gam_min_eig, v_residual, min_zeta (type-0/1 columns), min_lam, psi_min_eig of the input as given; the
+ * first two are NaN for a node that was refused on the host and 0 for an empty list.  terms (4 per node, may be NULL), in the scaled
+ * variables, of the evaluation that was returned: the constant, min(eig_0(M), 0), ||c||, min_j mu_j (bound scale^2 = constant + second - third);
+ * NaN for a node refused on the host.
+ * It stages nothing and uses buffers of its own: a staged or finished batch and its fetchable results stay exactly as they were.  Identical
+ * (minor list, SOC list) pairs within a call share one index structure.  A node's result does not depend on B, on its position or on the
+ * other nodes of the call.
+ * OMC_ERR_ARGUMENT before any device call: NULL handle, B <= 0, a missing array, nq_stride below the largest n_shor[b], the list errors of
+ * omc_relax_stage_shor, a solve in flight on the handle.  OMC_ERR_UNSUPPORTED: k > 1, 2^28 minors or more, n m >= 2^30.  OMC_ERR_ALLOC: the
+ * buffers do not fit the device.
+ *
+ * omc_shor_dual_bound_plan (host only, no handle): the device bytes a call needs.  With nqs = nq_stride, nmb = ceil(nqs / 256), NP = n rounded
+ * up to 16, nn4 = n^2 rounded up to 4, Rmax = 2 + nonstandard_box_rows + 3 max_cuts, rmax = max(1, min(n, 1 + nonstandard_box_rows +
+ * max_cuts)), Lmax = max(max_cuts, 1), ps = (rmax + 1)^2, S = doubles of the eigen-kernel's slab at order n (0 where it works in LDS):
+ *   node = 8 (1 + 15 nqs + m + 2 n m) + 8 (15 nqs [sanitise] + nmb) + 4 + 4 (20 nqs + n m + m + 3) + ((n m + m + 15) & ~15) + 120
+ *          (the multipliers; the blocks minus their negative part and the per-block minima; the group index; one list's index structure)
+ *   view = 8 (12 nqs + 2 nmb + n m + 2 m) + 4 m + 8 + 8 (2 NP^2 + nn4 + S) + 8 (2 Rmax + Lmax n + n rmax) + 8 (Rmax + ps + n rmax + n + 5)
+ *          + 4 (4 Rmax + 9)
+ *          (key residuals, the 8-plane scratch, partials, the dense multiplier, column constants and flags; matrices and slab; descriptors;
+ *          lam, Psi3 and scratch of the assembly; its ints)
+ * out[0] = node + ways * view (ways = 2 with sanitise, else 1), out[1] = B out[0], out[2] = node, out[3] = view, out[4] = ways, out[5] = S,
+ * out[6] = Rmax, out[7] = rmax.  An upper bound: shared lists and nodes refused on the host need less.  OMC_ERR_UNSUPPORTED for k > 1 and
+ * beyond the size limits above.
+ * omc_last_shor_dual_bound_ms: event time of the kernels of the handle's last omc_shor_dual_bound_batch call, copies excluded. */
+int omc_shor_dual_bound_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q1, const int* L, const double* cut_x,
+                              const double* cut_Uhat, const int8_t* cut_dir, const double* U_lower, const double* U_upper, const int64_t* n_shor,
+                              const int64_t* shor_idx, const int64_t* n_soc, const int64_t* soc_idx, int sanitise, int64_t nq_stride,
+                              const double* scale, const double* lam, const double* Psi3, const double* Gam, const double* zeta, const double* xi,
+                              const double* Xbar, double* bound, double* defects, double* terms);
+int omc_shor_dual_bound_plan(int n, int m, int k, int B, int64_t nq_stride, int max_cuts, int nonstandard_box_rows, int sanitise, int64_t* out);
+int omc_last_shor_dual_bound_ms(omc_instance* h, double* ms);
+
 /* ---- alternating_minimization (OMC.jl:1979-2279), disjunctive mode, B problems at once, rank k <= 8 --------
  * U_initial n*k per problem; cuts as above (only the per-cut bounds on v = U'x are imposed, OMC.jl:2047-2093);
  * k > 1 adds the pair cones ||U_j1 +- U_j2|| <= sqrt 2 of OMC.jl:2029-2045.

@@ -156,6 +156,16 @@ def shor_certificate_plan(n, m, k, nq_stride, max_cuts=0, nonstandard_box_rows=0
     return {key: int(v) for key, v in zip(keys, out)}
 
 
+def shor_dual_bound_plan(n, m, k, B, nq_stride, max_cuts=0, nonstandard_box_rows=0, sanitise=True):
+    """omc_shor_dual_bound_plan (host only, no GPU): device bytes Engine.shor_dual_bound needs -- per node, in total, the node and view parts,
+    views per node, doubles of the eigen-kernel's slab, Rmax, rmax."""
+    out = np.zeros(8, np.int64)
+    _lib.check(_lib.load().omc_shor_dual_bound_plan(int(n), int(m), int(k), int(B), int(nq_stride), int(max_cuts), int(nonstandard_box_rows),
+                                                    1 if sanitise else 0, _lib.ptr(out)))
+    keys = ("bytes_per_node", "bytes_total", "node_bytes", "view_bytes", "ways", "slab_doubles", "Rmax", "rmax")
+    return {key: int(v) for key, v in zip(keys, out)}
+
+
 class Engine:
     """Device-resident instance + the four call sites of the reference driver."""
 
@@ -638,6 +648,74 @@ class Engine:
                                                   _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(Lam), _lib.ptr(lam), _lib.ptr(Psi),
                                                   None, None, _lib.ptr(bd)))
         return bd
+
+    def shor_dual_bound(self, nodes, shor_info, certs, disjunctive_cuts_type="linear", U_lower=None, U_upper=None, reference_quirk_q1=True,
+                        sanitise=True, want_defects=False, want_terms=False, nq_stride=None):
+        """The Shor-mode bound of certs[b] (certificate.ShorCertificate) for nodes[b] with the lists shor_info[b] = (minors, SOC list or None),
+        evaluated on the device (omc_shor_dual_bound_batch).  sanitise=True is certificate.shor_dual_bound (the multipliers are made admissible,
+        the blocks in two ways, the larger value is returned), sanitise=False is certificate.evaluate_shor (as they are).  Psi3 must be expressed
+        in the basis row_basis() returns (the Q of a fetched certificate is that basis).  -inf where the formula gives it.  Returns the B bounds;
+        with want_defects also a list of dicts (gam_min_eig, v_residual, min_zeta, min_lam, psi_min_eig of the input as given), with want_terms
+        also a (B, 4) array (constant, min(eig_0(M), 0), ||c||, min_j mu_j of the evaluation returned, in the scaled variables).  nq_stride:
+        stride of the per-minor planes on the wire (default: the longest list); the result does not depend on it."""
+        if not hasattr(self._lib, "omc_shor_dual_bound_batch"):
+            raise _lib.OmcError(-100, "this libomc_hip.so has no omc_shor_dual_bound_batch")
+        n, m, k, B = self.n, self.m, self.k, len(nodes)
+        if len(certs) != B or len(shor_info) != B:
+            raise ValueError("one certificate and one (minors, SOC list) pair per node")
+        L, cx, cU, cd = _pack_cuts(nodes, n, k, disjunctive_cuts_type)
+        lo, hi = self._bounds_flat(B, U_lower, U_upper)
+        nsh, nso, shi, soi = _pack_shor(shor_info)
+        dlo, dhi = certificate.default_U_bounds(n, k)
+        Rb = []
+        for b in range(B):
+            lb_ = dlo if lo is None else lo[b]; hb_ = dhi if hi is None else hi[b]
+            Rb.append(1 + int((np.asarray(lb_) > -1.0).sum()) + int((np.asarray(hb_) < 1.0).sum()) + int(L[b]) * (2 * k + 1))
+        rb = [int(np.asarray(c.Q).shape[1]) for c in certs]
+        Rmax, rmax = max(Rb), max(1, max(rb))
+        ns = int(nsh.max()) if nq_stride is None else int(nq_stride)
+        ps = (rmax + k) ** 2
+        sc = np.zeros(B); lam = np.zeros((B, Rmax)); Psi = np.zeros((B, ps)); Gam = np.zeros((B, 15, max(ns, 1)))
+        zeta = np.zeros((B, m)); xi = np.zeros((B, n * m)); Xb = np.zeros((B, n * m))
+        for b, c in enumerate(certs):
+            G = np.asarray(c.Gam, float).reshape(-1, 5, 5)
+            if len(c.lam) != Rb[b] or np.asarray(c.Psi3).shape != (rb[b] + k, rb[b] + k) or len(G) != int(nsh[b]):
+                raise ValueError(f"certificate {b}: lam must hold {Rb[b]} multipliers, Psi3 be of order r + k and Gam hold {int(nsh[b])} blocks")
+            sc[b] = float(c.scale); lam[b, :Rb[b]] = c.lam
+            Psi[b, :(rb[b] + k) ** 2] = np.asarray(c.Psi3, float).ravel(order="F")
+            if len(G) and ns >= len(G):
+                Gam[b] = certificate.pack_gam(0.5 * (G + np.transpose(G, (0, 2, 1))), ns)
+            zeta[b] = np.asarray(c.zeta, float)
+            xi[b] = np.asarray(c.xi, float).ravel(order="F"); Xb[b] = np.asarray(c.Xbar, float).ravel(order="F")
+        ct = CUT_TYPES[disjunctive_cuts_type]; q1 = int(bool(reference_quirk_q1))
+        if k == 1:      # the basis check needs no device; for k > 1 the evaluator itself refuses
+            r = np.zeros(B, np.int32)
+            _lib.check(self._lib.omc_dual_bound_batch(self._h, B, ct, q1, _lib.ptr(L), _lib.ptr(cx), _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(lo), _lib.ptr(hi),
+                                                      None, None, None, None, _lib.ptr(r), None))
+            if [int(v) for v in r] != rb:
+                raise ValueError(f"Q of the certificates has {rb} columns, the library's row basis {[int(v) for v in r]}: build Psi3 in the basis of row_basis()")
+        bd = np.zeros(B); df = np.zeros((B, 5)); tm = np.zeros((B, 4))
+        _lib.check(self._lib.omc_shor_dual_bound_batch(self._h, B, ct, q1, _lib.ptr(L), _lib.ptr(cx), _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(lo), _lib.ptr(hi),
+                                                       _lib.ptr(nsh), _lib.ptr(shi), _lib.ptr(nso), _lib.ptr(soi), 1 if sanitise else 0, ns, _lib.ptr(sc),
+                                                       _lib.ptr(lam), _lib.ptr(Psi), _lib.ptr(Gam) if int(nsh.max()) else None, _lib.ptr(zeta), _lib.ptr(xi),
+                                                       _lib.ptr(Xb), _lib.ptr(bd), _lib.ptr(df) if want_defects else None, _lib.ptr(tm) if want_terms else None))
+        out = [bd]
+        if want_defects:
+            keys = ("gam_min_eig", "v_residual", "min_zeta", "min_lam", "psi_min_eig")
+            out.append([{key: float(v) for key, v in zip(keys, df[b])} for b in range(B)])
+        if want_terms:
+            out.append(tm)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def shor_dual_bound_plan(self, B, nq_stride, max_cuts=0, nonstandard_box_rows=0, sanitise=True):
+        """Device bytes shor_dual_bound() needs for B nodes of this instance (omc_shor_dual_bound_plan, host only)."""
+        return shor_dual_bound_plan(self.n, self.m, self.k, B, nq_stride, max_cuts, nonstandard_box_rows, sanitise)
+
+    def last_shor_dual_bound_ms(self):
+        """Event time (ms) of the kernels of the last shor_dual_bound() call, copies excluded."""
+        ms = np.zeros(1)
+        _lib.check(self._lib.omc_last_shor_dual_bound_ms(self._h, _lib.ptr(ms)))
+        return float(ms[0])
 
     # ---- multi-GPU exchange behind the C ABI (RCCL; SURVEY.md 8e) ------------------------------------------------
     @staticmethod

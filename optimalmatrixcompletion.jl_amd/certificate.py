@@ -349,15 +349,21 @@ def sanitise_shor(cert, st):
                            xi=np.asarray(cert.xi, float), Xbar=np.asarray(cert.Xbar, float), bound=cert.bound), df
 
 
-def evaluate_shor(A, mask, gamma, rows, st, cert):
+def evaluate_shor(A, mask, gamma, rows, st, cert, want_terms=False):
     """Steps 2-8 of shor_dual_bound for the multipliers as they are (no sanitising).  The blocks need not be PSD: the shift of step 2 covers
     what is left of their negative part after the spread, so the value is a valid bound for any symmetric Gam; zeta, lam and Psi3 are taken
-    as admissible."""
+    as admissible.  want_terms: (value, terms) with terms = (constant, min(eig_0(M), 0), ||c||, min_j mu_j) in the scaled variables, so that
+    value * scale^2 = constant + second - third (omc_shor_dual_bound_batch reports the same four); entries not reached before a -inf are nan."""
+    terms = [np.nan] * 4
+
+    def out(v):
+        return (v, tuple(terms)) if want_terms else v
+
     A = np.asarray(A, float); mask = np.asarray(mask, bool)
     n, m = A.shape
     sc = float(cert.scale)
     if not (np.isfinite(sc) and sc > 0.0):
-        return -np.inf
+        return out(-np.inf)
     Q = np.asarray(cert.Q, float); Psi = np.asarray(cert.Psi3, float); lam = np.asarray(cert.lam, float)
     r = Q.shape[1]
     if len(lam) != len(rows):
@@ -385,7 +391,7 @@ def evaluate_shor(A, mask, gamma, rows, st, cert):
         shift = np.sqrt((E * E).sum((1, 2)))
         Gm = Gm - E + shift[:, None, None] * np.eye(5)[None]
         if not np.isfinite(Gm).all():
-            return -np.inf
+            return out(-np.inf)
         low = np.linalg.eigvalsh(Gm)[:, 0]                      # 0 for a PSD input: ||E||_F exceeds the spectral norm of the trace-free E
         Gm = Gm + np.maximum(-low, 0.0)[:, None, None] * np.eye(5)[None]
         const -= float(Gm[:, 0, 0].sum())                       # the block's (0,0) entry multiplies the constant 1
@@ -397,6 +403,7 @@ def evaluate_shor(A, mask, gamma, rows, st, cert):
     zeta = np.where(ctype == 2, zmin, np.maximum(zadm, zmin))
     # 4. mu
     mu = cT - zeta
+    terms[3] = float(np.min(mu))
     # 5. phi and M
     xi = np.where(inS & t01, np.asarray(cert.xi, float), 0.0)
     Xbar = np.asarray(cert.Xbar, float)
@@ -406,7 +413,7 @@ def evaluate_shor(A, mask, gamma, rows, st, cert):
     bad = ~(mu > 0.0)
     if bad.any():
         if not np.isfinite(phi[:, bad]).all() or np.abs(phi[:, bad]).max() > 0.0:
-            return -np.inf
+            return out(-np.inf)
         mu = np.where(bad, 1.0, mu)
     M = -(phi / mu[None, :]) @ phi.T
     # 6. rows and the small cone
@@ -423,11 +430,12 @@ def evaluate_shor(A, mask, gamma, rows, st, cert):
     const -= float(np.trace(Psi[r:, r:]))
     # 7. the minimum over the simple set
     if not np.isfinite(M).all():
-        return -np.inf
+        return out(-np.inf)
     ev = np.linalg.eigvalsh(0.5 * (M + M.T))
-    val = const + float(min(ev[0], 0.0)) - float(np.linalg.norm(cV, axis=0).sum())
+    terms[0] = const; terms[1] = float(min(ev[0], 0.0)); terms[2] = float(np.linalg.norm(cV, axis=0).sum())
+    val = terms[0] + terms[1] - terms[2]
     # 8. back to the node's own scale
-    return val / (sc * sc) if np.isfinite(val) else -np.inf
+    return out(val / (sc * sc) if np.isfinite(val) else -np.inf)
 
 
 def shor_dual_bound(A, mask, gamma, node, cut_type, shor_idx, soc_idx, cert, U_lower=None, U_upper=None, q1=True, want_defects=False):

@@ -27,6 +27,7 @@
 #include "omc_altmin.h"
 #include "omc_shor.h"
 #include "omc_shor_relax.h"
+#include "omc_shor_cert.h"
 #include <unordered_map>
 #include <dlfcn.h>
 #include <execinfo.h>
@@ -1772,6 +1773,329 @@ int omc_dual_bound_batch(omc_instance* h, int B, int cut_type, int reference_qui
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipGetLastError());
   for (size_t b = 0; b < sB; ++b) bound[b] = sc[b] + sc[4 * sB + b] - sc[sB + b] + sc[2 * sB + b];      // c0 + evsum - cpen + cst, the order of k_check_final
+  return 0;
+}
+
+// ---- omc_shor_dual_bound_batch: the Shor-mode bound of caller-supplied multipliers (omc.h) ---------------------------------
+namespace {
+// device bytes of omc_shor_dual_bound_batch (the formula of omc_shor_dual_bound_plan in omc.h): per node, per view
+struct ScertBytes { size_t node, view; };
+static_assert(sizeof(ShorGroupDev) == 120, "the plan of omc_shor_dual_bound_batch documents 120 bytes per list");
+static ScertBytes scert_bytes(size_t n, size_t m, size_t nqs, size_t Rmax, size_t rmax, size_t Lmax, size_t slab, bool sanitise) {
+  const size_t nm = n * m, NP = (n + 15) & ~(size_t)15, nn4 = (n * n + 3) & ~(size_t)3, nmb = (nqs + SCERT_T - 1) / SCERT_T, ps = (rmax + 1) * (rmax + 1);
+  ScertBytes r;
+  r.node = 8 * (1 + 15 * nqs + m + 2 * nm) + 8 * ((sanitise ? 15 * nqs : 0) + nmb) + 4 +
+           4 * (20 * nqs + nm + m + 3) + ((nm + m + 15) & ~(size_t)15) + sizeof(ShorGroupDev);
+  r.view = 8 * (12 * nqs + 2 * nmb + nm + 2 * m) + 4 * m + 8 + 8 * (2 * NP * NP + nn4 + slab) + 8 * (2 * Rmax + Lmax * n + n * rmax) +
+           8 * (Rmax + ps + n * rmax + n + 5) + 4 * (4 * Rmax + 9);
+  return r;
+}
+// eigen-decomposition of a symmetric matrix of small order on the host (cyclic Jacobi): A (N x N, overwritten) -> eigenvalues w, vectors V (columns)
+static void host_jacobi(int N, std::vector<double>& A, std::vector<double>& wv, std::vector<double>& V) {
+  V.assign((size_t)N * N, 0.0); wv.assign(N, 0.0);
+  for (int i = 0; i < N; ++i) V[(size_t)i * N + i] = 1.0;
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    double off = 0.0, dg = 0.0;
+    for (int r = 0; r < N; ++r) { dg += A[(size_t)r * N + r] * A[(size_t)r * N + r]; for (int c = 0; c < r; ++c) off += A[(size_t)c * N + r] * A[(size_t)c * N + r]; }
+    if (!(off > 1e-34 * dg)) break;
+    for (int p = 0; p < N - 1; ++p)
+      for (int q = p + 1; q < N; ++q) {
+        const double apq = A[(size_t)q * N + p];
+        if (!(fabs(apq) > 1e-300)) continue;
+        const double theta = (A[(size_t)q * N + q] - A[(size_t)p * N + p]) / (2.0 * apq), at = fabs(theta);
+        double t = 1.0 / (at + sqrt(at * at + 1.0));
+        t = (theta >= 0.0) ? t : -t;
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        A[(size_t)p * N + p] -= t * apq; A[(size_t)q * N + q] += t * apq; A[(size_t)q * N + p] = 0.0; A[(size_t)p * N + q] = 0.0;
+        for (int k = 0; k < N; ++k) {
+          if (k != p && k != q) {
+            const double akp = A[(size_t)p * N + k], akq = A[(size_t)q * N + k];
+            const double np_ = c * akp - s * akq, nq_ = s * akp + c * akq;
+            A[(size_t)p * N + k] = np_; A[(size_t)k * N + p] = np_; A[(size_t)q * N + k] = nq_; A[(size_t)k * N + q] = nq_;
+          }
+          const double vkp = V[(size_t)p * N + k], vkq = V[(size_t)q * N + k];
+          V[(size_t)p * N + k] = c * vkp - s * vkq; V[(size_t)q * N + k] = s * vkp + c * vkq;
+        }
+      }
+  }
+  for (int i = 0; i < N; ++i) wv[i] = A[(size_t)i * N + i];
+}
+}  // namespace
+
+int omc_shor_dual_bound_plan(int n, int m, int k, int B, int64_t nq_stride, int max_cuts, int nonstandard_box_rows, int sanitise, int64_t* out) {
+  if (!out) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_plan: out is NULL");
+  if (n <= 0 || m <= 0 || k <= 0 || B <= 0 || nq_stride < 0 || max_cuts < 0 || nonstandard_box_rows < 0)
+    return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_plan: n, m, k, B must be positive, the other arguments non-negative");
+  if (k > 1) return fail(OMC_ERR_UNSUPPORTED, "omc_shor_dual_bound_plan: Shor-mode certificates exist for rank 1 only");
+  if (nq_stride >= (1ll << 28) || (long long)n * m >= (1ll << 30)) return fail(OMC_ERR_UNSUPPORTED, "omc_shor_dual_bound_plan: beyond the size limits of omc_relax_stage_shor");
+  const int Rmax = 2 + nonstandard_box_rows + 3 * max_cuts, rmax = std::max(1, std::min(n, 1 + nonstandard_box_rows + max_cuts));
+  const Tuning tun;
+  const OmcGeom geo = omc_plan_geometry(n, (n + 15) & ~15, 1, rmax, Rmax, n, 0, tun.cone_multi_min);
+  const ScertBytes sb = scert_bytes(n, m, (size_t)nq_stride, Rmax, rmax, std::max(max_cuts, 1), geo.ws.slab_stride, sanitise != 0);
+  const int ways = sanitise ? 2 : 1;
+  out[0] = (int64_t)(sb.node + ways * sb.view); out[1] = out[0] * B; out[2] = (int64_t)sb.node; out[3] = (int64_t)sb.view; out[4] = ways;
+  out[5] = (int64_t)geo.ws.slab_stride; out[6] = Rmax; out[7] = rmax;
+  return 0;
+}
+
+int omc_last_shor_dual_bound_ms(omc_instance* h, double* ms) {
+  if (!h || !ms) return fail(OMC_ERR_ARGUMENT, "NULL argument");
+  *ms = h->sdb_ms;
+  return 0;
+}
+
+int omc_shor_dual_bound_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q1, const int* L, const double* cut_x, const double* cut_Uhat,
+                              const int8_t* cut_dir, const double* U_lower, const double* U_upper, const int64_t* n_shor, const int64_t* shor_idx,
+                              const int64_t* n_soc, const int64_t* soc_idx, int sanitise, int64_t nq_stride, const double* scale, const double* lam,
+                              const double* Psi3, const double* Gam, const double* zeta, const double* xi, const double* Xbar, double* bound,
+                              double* defects, double* terms) {
+  // ---- refusals, all on the host ------------------------------------------------------------------------------------------------------
+  if (!h) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: handle is NULL");
+  if (B <= 0) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: B must be positive");
+  if (cut_type != OMC_CUT_LINEAR && cut_type != OMC_CUT_LINEAR2 && cut_type != OMC_CUT_LINEAR3)
+    return fail(OMC_ERR_INVALID_ENUM, "Invalid input for disjunctive cuts type: must be linear, linear2 or linear3 (OMC.jl:1456-1462)");
+  if (!n_shor || !n_soc || !scale || !lam || !zeta || !xi || !Xbar || !bound)
+    return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: n_shor, n_soc, scale, lam, zeta, xi, Xbar and bound are needed");
+  if (h->worker.joinable() || h->worker_running.load()) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: a solve is in flight on this handle (call omc_relax_wait first)");
+  if (h->k > 1) return fail(OMC_ERR_UNSUPPORTED, "omc_shor_dual_bound_batch: Shor-mode certificates exist for rank 1 only (quirk Q5 makes the minors vacuous for k > 1)");
+  const size_t n = h->n, m = h->m, nm = n * m;
+  if ((long long)n * (long long)m >= (1ll << 30)) return fail(OMC_ERR_UNSUPPORTED, "Shor mode: n * m too large for the 32-bit index structures");
+  std::vector<size_t> so, co;
+  { int rc0 = shor_list_offsets(B, n_shor, shor_idx, n_soc, soc_idx, so, co); if (rc0) return rc0; }
+  int64_t nqall = 0;
+  for (int b = 0; b < B; ++b) nqall = std::max(nqall, n_shor[b]);
+  if (nq_stride < nqall) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: nq_stride is below the longest minor list");
+  if (nqall > 0 && !Gam) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: Gam is NULL but n_shor > 0");
+  const size_t nqs = (size_t)nq_stride;
+  // identical (minor list, SOC list) pairs share one index structure
+  std::unordered_map<uint64_t, std::vector<int>> byhash;
+  std::vector<ShorListKey> lists;
+  std::vector<int> rep, node_group(B);
+  for (int b = 0; b < B; ++b) {
+    const int64_t* ib = shor_idx + 4 * so[b]; const int64_t* sb = soc_idx + 2 * co[b];
+    const uint64_t hv = shor_pair_hash(n_shor[b], ib, n_soc[b], sb);
+    int gid = find_shor_list(byhash, lists, hv, n_shor[b], ib, n_soc[b], sb);
+    if (gid < 0) { gid = (int)rep.size(); rep.push_back(b); add_shor_list(byhash, lists, hv, n_shor[b], ib, n_soc[b], sb); }
+    node_group[b] = gid;
+  }
+  const int NG = (int)rep.size();
+  std::vector<ShorGroupHost> gh(NG);
+  int nqmax = 0, nv1max = 0, nv2max = 0;
+  size_t tot_int = 0, tot_byte = 0;
+  for (int g = 0; g < NG; ++g) {
+    ShorGroupHost& G = gh[g];
+    const int b = rep[g];
+    { int rc0 = build_shor_group(h, n_shor[b], shor_idx + 4 * so[b], n_soc[b], soc_idx + 2 * co[b], G); if (rc0) return rc0; }
+    nqmax = std::max(nqmax, G.nq); nv1max = std::max(nv1max, G.nv1); nv2max = std::max(nv2max, G.nv2);
+    G.off_int = tot_int; tot_int += G.ints();
+    G.off_byte = tot_byte; tot_byte += G.bytes();
+  }
+  omc_relax_params P = h->params; P.reference_quirk_q1 = reference_quirk_q1 ? 1 : 0;
+  NodePack pk;
+  { int rcp = pack_nodes(h, P, cut_type, B, L, cut_x, cut_Uhat, cut_dir, U_lower, U_upper, pk); if (rcp) return rcp; }
+  const size_t Rmax = pk.Rmax, rmax = pk.rmax, Lmax = std::max(pk.Lmax, 1), ps = (rmax + 1) * (rmax + 1);
+  // ---- host part: which nodes live, lam clamped, PSD part of Psi3, the three defects that need no block --------------------------------
+  const double NINF = -INFINITY;
+  std::vector<uint8_t> live(B, 1);
+  std::vector<double> hlam((size_t)B * Rmax, 0.0), hPsi(Psi3 ? (size_t)B * ps : 0, 0.0);
+  for (int b = 0; b < B; ++b) {
+    const int R = (int)pk.rk[b].size(), N3 = pk.rrv[b] + 1;
+    const double* lb = lam + (size_t)b * Rmax;
+    const double scb = scale[b];
+    if (!(scb > 0.0 && scb - scb == 0.0)) live[b] = 0;      // not positive and finite: -inf, no device work for this node
+    double min_lam = 0.0, psi_min = 0.0, min_zeta = 0.0;
+    for (int r = 0; r < R; ++r) {
+      if (!(lb[r] - lb[r] == 0.0)) live[b] = 0;
+      min_lam = (r == 0) ? lb[r] : std::min(min_lam, lb[r]);
+      hlam[(size_t)b * Rmax + r] = sanitise ? std::max(lb[r], 0.0) : lb[r];
+    }
+    if (Psi3) {
+      const double* Pb = Psi3 + (size_t)b * ps;
+      double* Ph = hPsi.data() + (size_t)b * ps;
+      bool fin = true;
+      for (int e = 0; e < N3 * N3; ++e) { Ph[e] = Pb[e]; fin = fin && (Pb[e] - Pb[e] == 0.0); }
+      if (!fin) live[b] = 0;
+      else if (sanitise || defects) {
+        std::vector<double> S((size_t)N3 * N3), wv, Vv;
+        for (int c = 0; c < N3; ++c) for (int r = 0; r < N3; ++r) S[(size_t)c * N3 + r] = 0.5 * (Pb[(size_t)c * N3 + r] + Pb[(size_t)r * N3 + c]);
+        host_jacobi(N3, S, wv, Vv);
+        psi_min = *std::min_element(wv.begin(), wv.end());
+        if (sanitise)
+          for (int c = 0; c < N3; ++c) for (int r = 0; r < N3; ++r) {
+            double acc = 0.0;
+            for (int i = 0; i < N3; ++i) acc += std::max(wv[i], 0.0) * Vv[(size_t)i * N3 + r] * Vv[(size_t)i * N3 + c];
+            Ph[(size_t)c * N3 + r] = acc;
+          }
+      }
+    }
+    if (defects) {
+      const std::vector<uint8_t>& ct = gh[node_group[b]].ctype;
+      bool any = false;
+      for (size_t j = 0; j < m; ++j) if (ct[j] != 2) { const double z = zeta[(size_t)b * m + j]; min_zeta = any ? std::min(min_zeta, z) : z; any = true; }
+      double* d = defects + 5 * (size_t)b;
+      d[0] = n_shor[b] > 0 ? NAN : 0.0; d[1] = n_shor[b] > 0 ? NAN : 0.0; d[2] = min_zeta; d[3] = min_lam; d[4] = psi_min;
+    }
+    bound[b] = NINF;
+    if (terms) for (int q = 0; q < 4; ++q) terms[4 * (size_t)b + q] = NAN;
+  }
+  // ---- views: every live node as given (way 0); with sanitise and a non-empty list also with the negative part of its blocks removed (way 1) ----
+  std::vector<int> view_node, view_way;
+  for (int b = 0; b < B; ++b) {
+    if (!live[b]) continue;
+    view_node.push_back(b); view_way.push_back(0);
+    if (sanitise && n_shor[b] > 0) { view_node.push_back(b); view_way.push_back(1); }
+  }
+  const int V = (int)view_node.size();
+  if (V == 0) return 0;
+  const size_t sV = (size_t)V, sB = (size_t)B;
+  NodePack pv;
+  std::vector<int> Lv(V, 0); std::vector<double> cxv;
+  {
+    std::vector<size_t> cutoff(B + 1, 0);
+    for (int b = 0; b < B; ++b) cutoff[b + 1] = cutoff[b] + (size_t)(L ? L[b] : 0);
+    pv.rk.resize(V); pv.rc.resize(V); pv.rbi.resize(V); pv.rbj.resize(V); pv.rcoef.resize(V); pv.rrhs.resize(V); pv.Qn.resize(V); pv.rrv.resize(V);
+    for (int v = 0; v < V; ++v) {
+      const int b = view_node[v];
+      pv.rk[v] = pk.rk[b]; pv.rc[v] = pk.rc[b]; pv.rbi[v] = pk.rbi[b]; pv.rbj[v] = pk.rbj[b]; pv.rcoef[v] = pk.rcoef[b]; pv.rrhs[v] = pk.rrhs[b];
+      pv.Qn[v] = pk.Qn[b]; pv.rrv[v] = pk.rrv[b];
+      Lv[v] = L ? L[b] : 0;
+      if (Lv[v] > 0) cxv.insert(cxv.end(), cut_x + cutoff[b] * n, cut_x + cutoff[b + 1] * n);
+    }
+    pv.Rmax = pk.Rmax; pv.rmax = pk.rmax; pv.Lmax = pk.Lmax;
+  }
+  // ---- device buffers of this call ---------------------------------------------------------------------------------------------------
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t NP = (n + 15) & ~(size_t)15, nn4 = (n * n + 3) & ~(size_t)3;
+  const bool want_clean = nqmax > 0 && (sanitise || defects);
+  const bool store_clean = nqmax > 0 && sanitise;
+  OmcWS w;
+  memset(&w, 0, sizeof(w));
+  w.nB = w.B = w.Btot = V; w.n = (int)n; w.m = (int)m; w.k = 1; w.nnz = h->nnz; w.Rmax = (int)Rmax; w.Lmax = (int)Lmax; w.rmax = (int)rmax;
+  w.np16 = (int)NP; w.max_sweeps = MAX_SWEEPS; w.mw_budget = MAX_SWEEPS; w.gamma = h->gamma; w.clip_hi = 1.0; w.inv_s2 = 1.0;
+  w.col_ptr = h->dcol_ptr.as<int>(); w.col_idx = h->dcol_idx.as<int>(); w.col_val = h->dcol_val.as<double>();
+  w.geo = omc_plan_geometry((int)n, (int)NP, 1, (int)rmax, (int)Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
+  ShorCertWS c;
+  memset(&c, 0, sizeof(c));
+  c.n = (int)n; c.m = (int)m; c.B = B; c.V = V; c.nmb = (nqmax + SCERT_T - 1) / SCERT_T; c.nv1max = nv1max; c.nv2max = nv2max; c.clamp_zeta = sanitise ? 1 : 0;
+  c.nqs = (long long)nqs; c.gamma = h->gamma;
+  const size_t nmb = (size_t)c.nmb, slab = w.geo.ws.slab_stride;
+  const size_t dcount = sB * (1 + 15 * nqs + m + 2 * nm) + sB * ((store_clean ? 15 * nqs : 0) + nmb) +
+                        sV * (nv1max + nv2max + 8 * nqs + 2 * nmb + nm + 2 * m) + sV * (2 * NP * NP + nn4 + slab) +
+                        sV * (2 * Rmax + Lmax * n + n * rmax) + sV * (Rmax + ps + n * rmax + n + 5) + 4;
+  const size_t icount = sB + 2 * sV + sV * m + sV * (2 + 4 * Rmax + 7);
+  {
+    int rca = h->sdD.ensure(dcount * 8);
+    if (!rca) rca = h->sdI.ensure(icount * sizeof(int));
+    if (!rca) rca = h->sdGi.ensure(std::max<size_t>(tot_int, 1) * sizeof(int));
+    if (!rca) rca = h->sdGb.ensure(std::max<size_t>(tot_byte, 16));
+    if (!rca) rca = h->sdGr.ensure(sizeof(ShorGroupDev) * (size_t)NG);
+    if (rca) {
+      (void)hipGetLastError();
+      return fail(OMC_ERR_ALLOC, "omc_shor_dual_bound_batch: the evaluation needs " + std::to_string(dcount * 8) + " bytes for " + std::to_string(V) +
+                                 " views of " + std::to_string(B) + " nodes, which the device does not have (" + g_err + ")");
+    }
+  }
+  double* dp = h->sdD.as<double>();
+  double* dscale = dp; dp += sB; double* dGam = dp; dp += sB * 15 * nqs; double* dzeta = dp; dp += sB * m; double* dxi = dp; dp += sB * nm; double* dXbar = dp; dp += sB * nm;
+  c.scale = dscale; c.Gam = dGam; c.zeta = dzeta; c.xi = dxi; c.Xbar = dXbar;
+  if (store_clean) { c.GamC = dp; dp += sB * 15 * nqs; }
+  c.cleanpart = dp; dp += sB * nmb;
+  c.e1 = dp; dp += sV * nv1max; c.e2 = dp; dp += sV * nv2max; c.row8 = dp; dp += sV * 8 * nqs; c.minpart = dp; dp += sV * nmb * 2;
+  c.lamDX = dp; dp += sV * nm; c.c0col = dp; dp += sV * m; c.colmu = dp; dp += sV * m;
+  dp = h->sdD.as<double>() + (((size_t)(dp - h->sdD.as<double>()) + 3) & ~(size_t)3);      // 32-byte rows for the multi-workgroup kernels
+  w.MbufC = dp; dp += sV * NP * NP; w.VrowC = dp; dp += sV * NP * NP; w.Mchk = dp; dp += sV * nn4;
+  if (slab) { w.cone_scratch = dp; dp += sV * slab; }
+  w.rcoef = dp; dp += sV * Rmax; w.rrhs = dp; dp += sV * Rmax; w.cutx = dp; dp += sV * Lmax * n; w.Qb = dp; dp += sV * n * rmax;
+  double* dlam = dp; dp += sV * Rmax; double* dPsi = dp; dp += sV * ps; double* dT1 = dp; dp += sV * n * rmax;
+  w.chk_scratch = dp; dp += sV * n;
+  w.c0 = dp; w.cpen = dp + sV; w.cst = dp + 2 * sV; w.fro2c = dp + 3 * sV; w.evsum = dp + 4 * sV; dp += 5 * sV;
+  w.lamDX = c.lamDX;
+  int* ip = h->sdI.as<int>();
+  int* dng = ip; ip += sB; int* dvn = ip; ip += sV; int* dvw = ip; ip += sV; c.colbad = ip; ip += sV * m;
+  c.node_group = dng; c.view_node = dvn; c.view_way = dvw;
+  w.R = ip; ip += sV; w.rr = ip; ip += sV; w.rkind = ip; ip += sV * Rmax; w.rcut = ip; ip += sV * Rmax; w.rbi = ip; ip += sV * Rmax; w.rbj = ip; ip += sV * Rmax;
+  w.done = ip; w.vvalidC = ip + sV; w.sweeps = ip + 2 * sV; w.mw_stat = ip + 3 * sV;
+  HIPCHK(hipMemsetAsync(w.done, 0, sV * 7 * sizeof(int), s));
+  HIPCHK(hipMemsetAsync(w.MbufC, 0, sV * 2 * NP * NP * 8, s));      // zero padding of MbufC; VrowC: cold start
+  // index structures
+  {
+    std::vector<int> hi(std::max<size_t>(tot_int, 1)); std::vector<uint8_t> hb(std::max<size_t>(tot_byte, 16), 0);
+    std::vector<ShorGroupDev> gd(NG);
+    for (int g = 0; g < NG; ++g) pack_shor_group(gh[g], hi.data(), hb.data(), h->sdGi.as<int>(), h->sdGb.as<uint8_t>(), gd[g]);
+    HIPCHK(hipMemcpyAsync(h->sdGi.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->sdGb.p, hb.data(), hb.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->sdGr.p, gd.data(), sizeof(ShorGroupDev) * NG, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dng, node_group.data(), sizeof(int) * sB, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dvn, view_node.data(), sizeof(int) * sV, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dvw, view_way.data(), sizeof(int) * sV, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));          // the host vectors die with this block
+  }
+  c.groups = (const ShorGroupDev*)h->sdGr.p; c.A = h->dA.as<double>(); c.mask = h->dmask.as<uint8_t>();
+  { int rc = put_descriptors(w, pv, V, sV, 0, Lv.data(), cxv.empty() ? nullptr : cxv.data(), s); if (rc) return rc; }
+  // multipliers: the caller's per node, lam and Psi3 (made admissible above when asked) per view
+  std::vector<double> vlam(sV * Rmax, 0.0), vPsi(Psi3 ? sV * ps : 0, 0.0);
+  for (int v = 0; v < V; ++v) {
+    const size_t b = view_node[v];
+    std::copy(hlam.begin() + b * Rmax, hlam.begin() + (b + 1) * Rmax, vlam.begin() + (size_t)v * Rmax);
+    if (Psi3) std::copy(hPsi.begin() + b * ps, hPsi.begin() + (b + 1) * ps, vPsi.begin() + (size_t)v * ps);
+  }
+  HIPCHK(hipMemcpyAsync(dscale, scale, sB * 8, hipMemcpyHostToDevice, s));
+  if (nqmax > 0) HIPCHK(hipMemcpyAsync(dGam, Gam, sB * 15 * nqs * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dzeta, zeta, sB * m * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dxi, xi, sB * nm * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dXbar, Xbar, sB * nm * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dlam, vlam.data(), sV * Rmax * 8, hipMemcpyHostToDevice, s));
+  if (Psi3) HIPCHK(hipMemcpyAsync(dPsi, vPsi.data(), sV * ps * 8, hipMemcpyHostToDevice, s));
+  // ---- kernels ------------------------------------------------------------------------------------------------------------------------
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1));
+  HIPCHK(hipEventRecord(ev0, s));
+  if (want_clean) omc_scert_launch_clean(&c, store_clean ? 1 : 0, s);
+  if (nqmax > 0) { omc_scert_launch_keys(&c, s); omc_scert_launch_minor(&c, s); }
+  omc_scert_launch_cols(&c, s);
+  const OmcDualIn in = {nullptr, dlam, Psi3 ? dPsi : nullptr, dT1, c.c0col, c.colbad};
+  omc_launch_dual_assemble(&w, &in, s);
+  if (w.geo.ws_lpp || w.geo.mw) { w.ws_mode = 1; omc_launch_cone_ws(&w, s); }
+  else omc_launch_cone(&w, CONE_EVALS, s);
+  HIPCHK(hipEventRecord(ev1, s));
+  HIPCHK(hipGetLastError());
+  std::vector<double> scl(5 * sV), cmu(sV * m), mpart(sV * nmb * 2 + 1), cpart(sB * nmb + 1);
+  std::vector<int> cbad(sV * m);
+  HIPCHK(hipMemcpyAsync(scl.data(), w.c0, 5 * sV * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(cmu.data(), c.colmu, sV * m * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(cbad.data(), c.colbad, sV * m * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (nmb && defects) {
+    HIPCHK(hipMemcpyAsync(mpart.data(), c.minpart, sV * nmb * 2 * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(cpart.data(), c.cleanpart, sB * nmb * 8, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  { float msf = 0.f; HIPCHK(hipEventElapsedTime(&msf, ev0, ev1)); h->sdb_ms = msf; }
+  (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
+  // ---- the host's part of the result: -inf rules, the larger of the two ways, back to the node's scale ---------------------------------
+  for (int v = 0; v < V; ++v) {
+    const size_t b = view_node[v];
+    double val = (scl[v] + scl[2 * sV + v]) + scl[4 * sV + v] - scl[sV + v];      // (c0 + cst) + evsum - cpen
+    double mumin = INFINITY;
+    for (size_t j = 0; j < m; ++j) {
+      if (cbad[(size_t)v * m + j]) val = NINF;
+      mumin = std::min(mumin, cmu[(size_t)v * m + j]);
+    }
+    if (!(val - val == 0.0)) val = NINF;      // NaN or +-inf on the way
+    const double out = (val == NINF) ? NINF : val / (scale[b] * scale[b]);
+    const bool first = view_way[v] == 0;
+    if (first || out > bound[b] || (out == bound[b] && view_way[v] == 1)) {
+      bound[b] = out;
+      if (terms) { double* t = terms + 4 * b; t[0] = scl[v] + scl[2 * sV + v]; t[1] = scl[4 * sV + v]; t[2] = scl[sV + v]; t[3] = mumin; }
+    }
+    if (defects && first && n_shor[b] > 0) {
+      const size_t nblk = ((size_t)n_shor[b] + SCERT_T - 1) / SCERT_T;
+      double lo = INFINITY, res = 0.0;
+      for (size_t t = 0; t < nblk; ++t) { lo = std::min(lo, cpart[b * nmb + t]); res = std::max(res, mpart[((size_t)v * nmb + t) * 2 + 1]); }
+      defects[5 * b] = lo; defects[5 * b + 1] = res;
+    }
+  }
   return 0;
 }
 

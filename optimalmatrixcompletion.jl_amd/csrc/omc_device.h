@@ -167,8 +167,10 @@ struct OmcWS {
 };
 #define AA_MAXMEM 10
 // caller-supplied multipliers of omc_dual_bound_batch (k_dual_assemble): Lam (nnz per node), lam (Rmax), Psi3 (order r + k, column-major,
-// leading dimension r + k, at the head of a (rmax + k)^2 stride; NULL = zero), and the n x rmax scratch of Q Psi3_11
-struct OmcDualIn { const double *Lam, *lam, *Psi3; double* T1; };
+// leading dimension r + k, at the head of a (rmax + k)^2 stride; NULL = zero), and the n x rmax scratch of Q Psi3_11.
+// The Shor arm (omc_shor_dual_bound_batch): Lam = NULL, the dense n x m multiplier is already in the view's lamDX (k_scert_cols), c0col holds
+// the m column constants of every view and colbad its per-column flags (2 = not finite: the matrix handed to the eigen-kernel is -I and c0 NaN).
+struct OmcDualIn { const double *Lam, *lam, *Psi3; double* T1; const double* c0col; const int* colbad; };
 
 #ifdef __cplusplus
 extern "C" {

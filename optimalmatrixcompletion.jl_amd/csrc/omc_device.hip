@@ -2920,7 +2920,7 @@ __global__ void __launch_bounds__(512) k_dual_assemble(OmcWS w, OmcDualIn in) {
   const int n = w.n, k = w.k, m = w.m, R = w.R[b], rm = w.rmax, r = w.rr[b], N3 = r + k;
   const double g = w.gamma;
   double* M = w.Mchk + (size_t)b * n * n;
-  const double* Lam = in.Lam + (size_t)b * w.nnz;
+  const double* Lam = in.Lam ? in.Lam + (size_t)b * w.nnz : nullptr;
   const double* lam = in.lam + (size_t)b * w.Rmax;
   const double* Psi = in.Psi3 ? in.Psi3 + (size_t)b * (rm + k) * (rm + k) : nullptr;
   const double* cutx = w.cutx + (size_t)b * w.Lmax * n;
@@ -2928,8 +2928,17 @@ __global__ void __launch_bounds__(512) k_dual_assemble(OmcWS w, OmcDualIn in) {
   double* cU = w.chk_scratch + (size_t)b * n * k;
   double* T1 = in.T1 + (size_t)b * n * rm;
   double c0 = 0.0;
-  for (int e = tid; e < w.nnz; e += T) { const double l = Lam[e]; c0 += w.col_val[e] * l - 0.5 * l * l; }
-  c0 = block_sum(c0, red);
+  bool poison = false;      // Shor arm only: something not finite came in, the eigen-kernel gets -I and the host reports -inf
+  if (in.c0col) {           // Shor arm: the column constants are given
+    double bad = 0.0;
+    for (int j = tid; j < m; j += T) { c0 += in.c0col[(size_t)b * m + j]; bad += (in.colbad[(size_t)b * m + j] == 2) ? 1.0 : 0.0; }
+    c0 = block_sum(c0, red); bad = block_sum(bad, red);
+    poison = bad > 0.0 || !((c0 - c0) == 0.0);
+    if (poison) c0 = NAN;
+  } else {
+    for (int e = tid; e < w.nnz; e += T) { const double l = Lam[e]; c0 += w.col_val[e] * l - 0.5 * l * l; }
+    c0 = block_sum(c0, red);
+  }
   if (Psi) {      // T1 = Q Psi3_11 (n x r)
     for (int e = tid; e < n * r; e += T) {
       const int i = e % n, a = e / n;
@@ -2962,12 +2971,14 @@ __global__ void __launch_bounds__(512) k_dual_assemble(OmcWS w, OmcDualIn in) {
   __syncthreads();
   if (w.lamDX) {      // dense copy (the host has zeroed it), then one MFMA product
     double* D = w.lamDX + (size_t)b * m * n;
-    for (int j = tid; j < m; j += T) {
-      const int off = w.col_ptr[j], c = w.col_ptr[j + 1] - off;
-      for (int p = 0; p < c; ++p) D[(size_t)j * n + w.col_idx[off + p]] = Lam[off + p];
+    if (Lam) {      // base arm; the Shor arm finds its dense multiplier in place
+      for (int j = tid; j < m; j += T) {
+        const int off = w.col_ptr[j], c = w.col_ptr[j + 1] - off;
+        for (int p = 0; p < c; ++p) D[(size_t)j * n + w.col_idx[off + p]] = Lam[off + p];
+      }
+      __syncthreads();
+      __threadfence_block();
     }
-    __syncthreads();
-    __threadfence_block();
     mfma_LLt<1>(D, n, m, [&](int i, int j, double v) {
       const double t = 0.5 * g * v;
       M[(size_t)j * n + i] -= t;
@@ -2983,6 +2994,10 @@ __global__ void __launch_bounds__(512) k_dual_assemble(OmcWS w, OmcDualIn in) {
       }
       __syncthreads();
     }
+  }
+  if (poison) {
+    for (int e = tid; e < n * n; e += T) M[e] = (e % n == e / n) ? -1.0 : 0.0;
+    __syncthreads();
   }
   double pen = 0.0;
   for (int j = 0; j < k; ++j) {

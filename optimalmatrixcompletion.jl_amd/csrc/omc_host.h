@@ -179,6 +179,9 @@ struct omc_instance {
   // without Lam (lam, Psi3, bound, flags) and the Shor ones (ShWS::cbGam ...)
   bool keep_shor_cert = false; DevBuf scbD, socD, socNq;
   DevBuf dbD, dbI, dbM, dbS, dbL;      // omc_dual_bound_batch: descriptors and multipliers, ints, matrices, eigen-kernel slab, dense Lam
+  // omc_shor_dual_bound_batch: every double (multipliers, scratch, descriptors, matrices, slab), every int, and the index structures of the
+  // call's distinct lists (ints, bytes, group table); event time of the last call's kernels in ms (omc_last_shor_dual_bound_ms)
+  DevBuf sdD, sdI, sdGi, sdGb, sdGr; double sdb_ms = 0.0;
   // Shor minors (a10 / a11): row bitsets and per-pair popcounts, built at the first call
   DevBuf sbits, scb, scx, scz, soff, stot, sout, shi, slo, sexist, shist, sohi, solo, scnt;
   bool shor_ready = false; int shor_W = 0; long long shor_pairs = 0;
