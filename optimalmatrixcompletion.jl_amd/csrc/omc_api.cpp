@@ -36,6 +36,7 @@
 #include <rccl/rccl.h>   // types only: the library is loaded with dlopen on first use, so that libomc_hip.so has no hard dependency on it
 
 #include "omc_host.h"
+#include "omc_walks.h"
 
 thread_local std::string g_err;
 
@@ -395,17 +396,28 @@ static constexpr int SUB_CHUNK = 3;            // power steps per chunk of k_con
 static constexpr double SUB_TOL = 1e-10;       // residual floor of k_cone_sub
 static constexpr double SUB_ADAPT = 1e-3;      // residual target of k_cone_sub relative to the last dual residual
 
-int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int cut_type, const int* L,
-                    const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir, const double* U_lower,
-                    const double* U_upper) {
-  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
-  if (B <= 0) return fail(OMC_ERR_ARGUMENT, "B must be positive");
+// What the callers of the one staging routine ask of it beyond omc_relax_stage's arguments.  It travels with the call: nothing is left on
+// the instance when a stage call returns early.
+struct StageMode {
+  bool shor = false;            // omc_relax_stage_shor: the base workspace of a Shor-mode batch
+  bool warm_filtered = false;   // omc_relax_stage_shor: the warm-start indices have passed its filter
+  int colprox_force = 0;        // omc_column_prox_batch: 1 = no block kernel, 2 = the block kernel for every non-empty column
+};
+static int check_cut_type(int cut_type) {
   if (cut_type != OMC_CUT_LINEAR && cut_type != OMC_CUT_LINEAR2 && cut_type != OMC_CUT_LINEAR3)
     return fail(OMC_ERR_INVALID_ENUM, "Invalid input for disjunctive cuts type: must be linear, linear2 or linear3 (OMC.jl:1456-1462)");
+  return 0;
+}
+
+static int stage_base(omc_instance* h, int B, const omc_relax_params* params, int cut_type, const int* L, const double* cut_x, const double* cut_Uhat,
+                      const int8_t* cut_dir, const double* U_lower, const double* U_upper, const StageMode& mode) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "handle is NULL");
+  if (B <= 0) return fail(OMC_ERR_ARGUMENT, "B must be positive");
+  { int rcc = check_cut_type(cut_type); if (rcc) return rcc; }
   HIPCHK(hipSetDevice(h->device));
   h->staged = false;
-  const bool shor = h->shor_req;      // set by omc_relax_stage_shor for this call only
-  h->shor_req = false; h->shor_on = false; h->shor_via_base = false;
+  const bool shor = mode.shor;
+  h->shor_on = false; h->shor_via_base = false;
   if (params) h->params = *params; else omc_relax_params_default(&h->params);
   if (shor) {      // the bound of a Shor node lags its primal value for the first ~1000 iterations: no early stop, a longer stall window, one bump
     h->params.early_stop_factor = 0.0;
@@ -468,11 +480,14 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   }
   w.relax = P.relax; w.eps_gap = P.eps_gap; w.eps_feas = P.eps_feas;
   w.check_every = std::max(1, P.check_every); w.early_stop_after = P.early_stop_after; w.early_stop_factor = (P.first_wins ? 0.0 : P.early_stop_factor);
+  // what the packed buffers below are carved by (omc_walks.h): state arrays one per slot, descriptor and output arrays one per node (plus
+  // the room reserved for appended nodes)
+  const StageDims sd = {(size_t)S, (size_t)B + (size_t)extra_nodes, (size_t)n, (size_t)m, (size_t)k, (size_t)h->nnz, (size_t)rmax, (size_t)Rmax};
   {
-    int r0 = h->bgap.ensure(sizeof(double) * 2 * (size_t)S); if (r0) return r0;
-    r0 = h->bvotes.ensure(sizeof(int) * (size_t)S); if (r0) return r0;
+    ENS_CARVE(h->bgap, [&](Carve& c) { walk_gap(c, sd, w); });
+    int r0 = h->bvotes.ensure(sizeof(int) * (size_t)S); if (r0) return r0;
     r0 = h->bslotlist.ensure(sizeof(int) * (size_t)S); if (r0) return r0;
-    w.gap_prev = h->bgap.as<double>(); w.gap_rate = h->bgap.as<double>() + S; w.slow_votes = h->bvotes.as<int>();
+    w.slow_votes = h->bvotes.as<int>();
     w.slot_list = nullptr;      // set on the per-iteration copies only (omc_relax_solve)
   }
   std::vector<double> wY((size_t)n * n);
@@ -480,11 +495,9 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   int rc_ = 0;
   if ((rc_ = upload(h->dwY, wY.data(), sizeof(double) * n * n, h->stream))) return rc_;
   w.col_ptr = h->dcol_ptr.as<int>(); w.col_idx = h->dcol_idx.as<int>(); w.col_val = h->dcol_val.as<double>();
-  const int cp_force = h->cp_force;      // omc_column_prox_batch: for this call only
-  h->cp_force = 0;
   {
-    const bool pair_on = !h->tun.no_colprox_pair && cp_force != 2;
-    if ((rc_ = build_colprox_lists(h, cp_force == 1 ? INT_MAX : cp_force == 2 ? 1 : h->tun.colprox_block_min, pair_on))) return rc_;
+    const bool pair_on = !h->tun.no_colprox_pair && mode.colprox_force != 2;
+    if ((rc_ = build_colprox_lists(h, mode.colprox_force == 1 ? INT_MAX : mode.colprox_force == 2 ? 1 : h->tun.colprox_block_min, pair_on))) return rc_;
     w.cp_pair = pair_on ? 1 : 0;
   }
   w.cp_nblock = h->nblock; w.cp_block = h->nblock ? h->dblock.as<int>() : nullptr;
@@ -495,17 +508,20 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   w.cp_nwide = h->nwide; w.cp_wide = h->nwide ? h->dwide.as<int>() : nullptr;
   w.Ncnt = h->dNcnt.as<double>(); w.wY1 = h->dwY.as<double>();
   w.row_ptr = h->drow_ptr.as<int>(); w.row_idx = h->drow_idx.as<int>();
-#define ENS(buf, bytes) do { int r_ = (buf).ensure(bytes); if (r_) return r_; } while (0)
   const size_t sB = (size_t)S;      // state arrays: one per slot
   const size_t sN = (size_t)B + (size_t)extra_nodes;      // descriptor and output arrays: one per node (plus the room reserved for appended nodes)
   ENS(h->bY, sB * n * n * 8); ENS(h->bYp, sB * n * n * 8); ENS(h->bU, sB * n * k * 8);
   ENS(h->bD1, sB * n * n * 8); ENS(h->bD3, sB * n * n * 8); ENS(h->bW1, sB * n * n * 8); ENS(h->bE3, sB * n * n * 8);
   ENS(h->bdS, sB * rmax * rmax * 8);
-  ENS(h->bsm, sB * ((size_t)4 * rmax * k + 3 * k * k) * 8);
+  ENS_CARVE(h->bsm, [&](Carve& c) { walk_small_cone(c, sd, w); });
   ENS(h->balpha, sB * h->nnz * 8); ENS(h->balphaX, sB * h->nnz * 8); ENS(h->bsval, sB * m * 8);
-  ENS(h->bMchk, sB * n * n * 8); ENS(h->bchk, sB * n * k * 8 + (32 + 8 * sB) * 8);
+  ENS(h->bMchk, sB * n * n * 8);
+  size_t chk_bytes = 0;
+  ENS_CARVE(h->bchk, [&](Carve& c) { walk_check(c, sd, w); }, &chk_bytes);
   ENS(h->bG, sB * Rmax * Rmax * 8); ENS(h->blam, sB * Rmax * 8);
-  ENS(h->bscal, sB * 16 * 8); ENS(h->bbx, sB * n * 8); ENS(h->bint, sB * 10 * sizeof(int));
+  ENS_CARVE(h->bscal, [&](Carve& c) { walk_scalars(c, sd, w); });
+  ENS(h->bbx, sB * n * 8);
+  ENS_CARVE(h->bint, [&](Carve& c) { walk_slot_ints(c, sd, w); });
   w.np16 = (n + 15) & ~15;
   ENS(h->bMbuf, sB * w.np16 * w.np16 * 8); ENS(h->bVrow, sB * w.np16 * w.np16 * 8);
   ENS(h->blamD, sB * m * n * 8);
@@ -519,24 +535,25 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   }
   w.Mbuf = h->bMbuf.as<double>(); w.Vrow = h->bVrow.as<double>();
   {   // tracked subspace of the cone block (k_cone_sub)
-    ENS(h->bXs, sB * w.np16 * 16 * 8); ENS(h->bsubS, sB * (17 + 256) * 8); ENS(h->bsubI, sB * 15 * sizeof(int));
+    size_t subS_bytes = 0, subI_bytes = 0;
+    ENS(h->bXs, sB * w.np16 * 16 * 8);
+    ENS_CARVE(h->bsubS, [&](Carve& c) { walk_sub_doubles(c, sd, w); }, &subS_bytes);
+    ENS_CARVE(h->bsubI, [&](Carve& c) { walk_sub_ints(c, sd, w); }, &subI_bytes);      // w1_fac (factored W1): kept or dropped below, once k_global's variant is known
     HIPCHK(hipMemsetAsync(h->bXs.p, 0, sB * w.np16 * 16 * 8, h->stream));
-    HIPCHK(hipMemsetAsync(h->bsubS.p, 0, sB * (17 + 256) * 8, h->stream));
-    HIPCHK(hipMemsetAsync(h->bsubI.p, 0, sB * 15 * sizeof(int), h->stream));
-    w.Xs = h->bXs.as<double>(); w.sub_theta = h->bsubS.as<double>(); w.trM = h->bsubS.as<double>() + sB * 16;
-    w.sub_on = h->bsubI.as<int>(); w.cone_done = h->bsubI.as<int>() + sB; w.sub_stat = h->bsubI.as<int>() + 2 * sB; w.sub_wait = h->bsubI.as<int>() + 10 * sB; w.sub_nfail = h->bsubI.as<int>() + 11 * sB;
-    w.V3 = h->bsubS.as<double>() + sB * 17; w.v3valid = h->bsubI.as<int>() + 12 * sB;
-    w.ws_first = h->bsubI.as<int>() + 13 * sB; w.ws_phase = 0;
-    w.w1_fac = nullptr;     // factored W1: decided below, once k_global's variant is known
+    HIPCHK(hipMemsetAsync(h->bsubS.p, 0, subS_bytes, h->stream));
+    HIPCHK(hipMemsetAsync(h->bsubI.p, 0, subI_bytes, h->stream));
+    w.Xs = h->bXs.as<double>(); w.ws_phase = 0;
     w.sub_guard = SUB_GUARD; w.sub_qmax = h->tun.sub_qmax; w.sub_chunk = SUB_CHUNK;
     w.sub_tol = SUB_TOL; w.sub_adapt = SUB_ADAPT; w.sub_debug = h->tun.sub_debug;
     w.sub_enable = 0;     // decided below, once the cone kernel variant is known
-    ENS(h->bXsC, sB * w.np16 * 16 * 8); ENS(h->bsubSC, sB * 18 * 8); ENS(h->bsubIC, sB * 3 * sizeof(int));
+    size_t subSC_bytes = 0, subIC_bytes = 0;
+    ENS(h->bXsC, sB * w.np16 * 16 * 8);
+    ENS_CARVE(h->bsubSC, [&](Carve& c) { walk_subC_doubles(c, sd, w); }, &subSC_bytes);
+    ENS_CARVE(h->bsubIC, [&](Carve& c) { walk_subC_ints(c, sd, w); }, &subIC_bytes);      // sep_done: kept or dropped below with sub_enable
     HIPCHK(hipMemsetAsync(h->bXsC.p, 0, sB * w.np16 * 16 * 8, h->stream));
-    HIPCHK(hipMemsetAsync(h->bsubSC.p, 0, sB * 18 * 8, h->stream));
-    HIPCHK(hipMemsetAsync(h->bsubIC.p, 0, sB * 3 * sizeof(int), h->stream));
-    w.XsC = h->bXsC.as<double>(); w.sub_thetaC = h->bsubSC.as<double>(); w.trMc = h->bsubSC.as<double>() + sB * 16; w.lb_est = h->bsubSC.as<double>() + sB * 17;
-    w.sub_onC = h->bsubIC.as<int>(); w.confirm = h->bsubIC.as<int>() + sB; w.sep_done = nullptr;
+    HIPCHK(hipMemsetAsync(h->bsubSC.p, 0, subSC_bytes, h->stream));
+    HIPCHK(hipMemsetAsync(h->bsubIC.p, 0, subIC_bytes, h->stream));
+    w.XsC = h->bXsC.as<double>();
     w.cert_enable = 0;
   }
   {   // warm-started eigenvalues for the certificate matrix
@@ -554,65 +571,50 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   w.skip_yp = (w.Yx && !h->tun.dense_proj) ? 1 : 0;
   w.D1 = h->bD1.as<double>(); w.D3 = h->bD3.as<double>(); w.W1 = h->bW1.as<double>(); w.E3 = h->bE3.as<double>();
   w.dS = h->bdS.as<double>();
-  {
-    double* sm = h->bsm.as<double>();
-    const size_t vk = sB * rmax * k, tk = sB * k * k;
-    w.Vt = sm; w.D3V = sm + vk; w.W3V = sm + 2 * vk; w.Q3V = sm + 3 * vk;
-    w.D3T = sm + 4 * vk; w.W3T = sm + 4 * vk + tk; w.Q3T = sm + 4 * vk + 2 * tk;
-  }
   w.alpha = h->balpha.as<double>(); w.alphaX = h->balphaX.as<double>(); w.sval = h->bsval.as<double>();
-  ENS(h->bobjcol, sB * m * 2 * 8);
-  w.objcol = h->bobjcol.as<double>(); w.c0col = w.objcol + sB * m;
-  w.Mchk = h->bMchk.as<double>(); w.chk_scratch = h->bchk.as<double>(); w.stamps = h->bchk.as<double>() + sB * n * k; w.G = h->bG.as<double>(); w.lam = h->blam.as<double>();
-  double* sc = h->bscal.as<double>();
-  w.obj = sc; w.objout = sc + sB; w.lb = sc + 2 * sB; w.c0 = sc + 3 * sB; w.evsum = sc + 4 * sB; w.cpen = sc + 5 * sB;
-  w.cst = sc + 6 * sB; w.rp = sc + 7 * sB; w.rd = sc + 8 * sB; w.lmin = sc + 9 * sB;  // lmin uses 2B (slots 9,10)
-  w.objprev = sc + 11 * sB; w.lbprev = sc + 12 * sB; w.fro2 = sc + 13 * sB; w.bfac = sc + 14 * sB;
+  ENS_CARVE(h->bobjcol, [&](Carve& c) { walk_objcol(c, sd, w); });
+  w.Mchk = h->bMchk.as<double>(); w.G = h->bG.as<double>(); w.lam = h->blam.as<double>();
   w.bx = h->bbx.as<double>();
   if (w.accel) {
     w.aa_dim = 4 * n * n + 2 * rmax * k + k * k + h->nnz;
     const size_t ring = sB * (size_t)(w.aa_mem + 1) * w.aa_dim * 8;
-    ENS(h->baaF, ring); ENS(h->baaG, ring); ENS(h->baaZ, sB * (size_t)w.aa_dim * 8); ENS(h->baaS, sB * 8); ENS(h->baaI, sB * 6 * sizeof(int));
+    size_t aaI_bytes = 0;
+    ENS(h->baaF, ring); ENS(h->baaG, ring); ENS(h->baaZ, sB * (size_t)w.aa_dim * 8); ENS(h->baaS, sB * 8);
+    ENS_CARVE(h->baaI, [&](Carve& c) { walk_aa_ints(c, sd, w); }, &aaI_bytes);
     w.aa_F = h->baaF.as<double>(); w.aa_G = h->baaG.as<double>(); w.aa_zin = h->baaZ.as<double>(); w.aa_fn = h->baaS.as<double>();
-    int* ai = h->baaI.as<int>();
-    w.aa_hist = ai; w.aa_head = ai + sB; w.aa_pending = ai + 2 * sB; w.aa_valid = ai + 3 * sB; w.aa_nacc = ai + 4 * sB; w.aa_nrej = ai + 5 * sB;
-    HIPCHK(hipMemsetAsync(ai, 0, sB * 6 * sizeof(int), h->stream));
+    HIPCHK(hipMemsetAsync(h->baaI.p, 0, aaI_bytes, h->stream));
   }
-  int* ip = h->bint.as<int>();
-  w.rowov = ip; w.status = ip + sB; w.iters = ip + 2 * sB; w.sweeps = ip + 3 * sB; w.stall = ip + 4 * sB; w.vvalid = ip + 5 * sB; w.nbump = ip + 6 * sB; w.lastbump = ip + 7 * sB;
-  w.done = ip + 8 * sB; w.ws_need = w.ws_first ? ip + 9 * sB : nullptr;      // the word behind done[S]: one copy brings both back at a check
-  if (w.ws_need) HIPCHK(hipMemsetAsync(w.ws_need, 0, sizeof(int), h->stream));
+  HIPCHK(hipMemsetAsync(w.ws_need, 0, sizeof(int), h->stream));
   {
-    ENS(h->bslotint, sB * 3 * sizeof(int));
-    int* si = h->bslotint.as<int>();
-    w.node_of = si; w.init = si + sB; w.fin = si + 2 * sB;
-    std::vector<int> hs(sB * 3);
-    for (size_t b = 0; b < sB; ++b) { hs[b] = (int)b; hs[sB + b] = 1; hs[2 * sB + b] = 1; }   // identity map, every slot initialises
-    HIPCHK(hipMemcpyAsync(si, hs.data(), sizeof(int) * hs.size(), hipMemcpyHostToDevice, h->stream));
+    size_t map_bytes = 0;
+    ENS_CARVE(h->bslotint, [&](Carve& c) { walk_slot_map(c, sd, w.node_of, w.init, w.fin); }, &map_bytes);
+    std::vector<int> hs(map_bytes / sizeof(int));      // the host image of the three arrays, laid out by the same walk
+    int *h_node = nullptr, *h_init = nullptr, *h_fin = nullptr;
+    { Carve hc(hs.data()); walk_slot_map(hc, sd, h_node, h_init, h_fin); }
+    for (size_t b = 0; b < sB; ++b) { h_node[b] = (int)b; h_init[b] = 1; h_fin[b] = 1; }   // identity map, every slot initialises
+    HIPCHK(hipMemcpyAsync(h->bslotint.p, hs.data(), map_bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));          // hs dies with this block
     ENS(h->boY, sN * n * n * 8); ENS(h->boU, sN * n * k * 8); ENS(h->boal, sN * h->nnz * 8); ENS(h->bobx, sN * n * 8);
-    ENS(h->boscal, sN * 5 * 8); ENS(h->boint, sN * 2 * sizeof(int));
+    ENS_CARVE(h->boscal, [&](Carve& c) { walk_out_scalars(c, sd, w); });
+    ENS_CARVE(h->boint, [&](Carve& c) { walk_out_ints(c, sd, w); });
     w.oY = h->boY.as<double>(); w.oU = h->boU.as<double>(); w.oalphaX = h->boal.as<double>(); w.obx = h->bobx.as<double>();
-    double* os = h->boscal.as<double>();
-    w.oobj = os; w.olb = os + sN; w.olmin = os + 2 * sN; w.orho = os + 4 * sN;
-    w.ostatus = h->boint.as<int>(); w.oiters = h->boint.as<int>() + sN;
   }
   if ((h->keep_cert && !shor) || (h->keep_shor_cert && shor)) {      // best certificate per node: slot buffers and the arena of the nodes, zeroed (no slot and no node holds one)
     const size_t cnnz = shor ? 0 : (size_t)h->nnz;      // Shor mode has no alphaX: its own multipliers are kept by omc_relax_stage_shor (ShWS::cbGam ...)
-    const size_t ps = (size_t)(rmax + k) * (rmax + k), per = cnnz + Rmax + ps;
-    ENS(h->bcbD, sB * (2 + per) * 8); ENS(h->bcbI, sB * 2 * sizeof(int)); ENS(h->bocD, sN * (1 + per) * 8); ENS(h->bocI, sN * sizeof(int));
-    HIPCHK(hipMemsetAsync(h->bcbD.p, 0, sB * (2 + per) * 8, h->stream)); HIPCHK(hipMemsetAsync(h->bcbI.p, 0, sB * 2 * sizeof(int), h->stream));
-    HIPCHK(hipMemsetAsync(h->bocD.p, 0, sN * (1 + per) * 8, h->stream)); HIPCHK(hipMemsetAsync(h->bocI.p, 0, sN * sizeof(int), h->stream));
-    double* cb = h->bcbD.as<double>();
-    w.cb_rho = cb; w.cbBound = cb + sB; w.cbLam = shor ? nullptr : cb + 2 * sB; w.cblam = cb + 2 * sB + sB * cnnz; w.cbPsi = w.cblam + sB * Rmax;
-    w.cert_flag = h->bcbI.as<int>(); w.cert_have = w.cert_flag + sB;
-    double* oc = h->bocD.as<double>();
-    w.ocBound = oc; w.ocLam = shor ? nullptr : oc + sN; w.oclam = oc + sN + sN * cnnz; w.ocPsi = w.oclam + sN * Rmax;
+    size_t cbD_bytes = 0, cbI_bytes = 0, ocD_bytes = 0;
+    ENS_CARVE(h->bcbD, [&](Carve& c) { walk_cert_slot(c, sd, cnnz, w); }, &cbD_bytes);
+    ENS_CARVE(h->bcbI, [&](Carve& c) { walk_cert_flags(c, sd, w); }, &cbI_bytes);
+    ENS_CARVE(h->bocD, [&](Carve& c) { walk_cert_node(c, sd, cnnz, w); }, &ocD_bytes);
+    ENS(h->bocI, sN * sizeof(int));
+    HIPCHK(hipMemsetAsync(h->bcbD.p, 0, cbD_bytes, h->stream)); HIPCHK(hipMemsetAsync(h->bcbI.p, 0, cbI_bytes, h->stream));
+    HIPCHK(hipMemsetAsync(h->bocD.p, 0, ocD_bytes, h->stream)); HIPCHK(hipMemsetAsync(h->bocI.p, 0, sN * sizeof(int), h->stream));
+    if (shor) { w.cbLam = nullptr; w.ocLam = nullptr; }
     w.ocHave = h->bocI.as<int>();
   }
   // warm-start indices of this batch (consumed: they belong to this stage call only)
   w.load_from = nullptr; w.save_to = nullptr;
-  if (h->pool_cap > 0 && (!shor || h->shor_warm) && extra_nodes > 0) {      // appended nodes may name pool entries: both index arrays exist, -1 where nothing was given
+  const bool warm_ok = !shor || mode.warm_filtered;
+  if (h->pool_cap > 0 && warm_ok && extra_nodes > 0) {      // appended nodes may name pool entries: both index arrays exist, -1 where nothing was given
     if (h->warm_load.size() != (size_t)B) h->warm_load.assign(B, -1);
     if (h->warm_save.size() != (size_t)B) h->warm_save.assign(B, -1);
     h->warm_load.resize(sN, -1); h->warm_save.resize(sN, -1);
@@ -620,8 +622,6 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
     if (h->warm_load.size() != (size_t)B) h->warm_load.clear();
     if (h->warm_save.size() != (size_t)B) h->warm_save.clear();
   }
-  const bool warm_ok = !shor || h->shor_warm;
-  h->shor_warm = false;
   h->save_host.assign(sN, -1);
   if (h->pool_cap > 0 && !shor && h->warm_load.size() == sN) {      // entries saved by a Shor solve do not hold what the base engine loads (alpha, sval)
     std::lock_guard<std::mutex> lk(h->sig_mu);
@@ -661,16 +661,21 @@ int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int 
   w.sub_zscratch = nullptr;
   if (w.sub_enable && w.np16 > 512) { ENS(h->bsubz, sB * 16 * (size_t)(w.np16 + 2) * 8); w.sub_zscratch = h->bsubz.as<double>(); }
   w.cert_enable = (w.sub_enable && w.np16 > 512) ? 1 : 0;      // large orders: the certificate eigenvalues by the tracked block too (rigorous confirmation before anything is reported)
-  w.sep_done = w.sub_enable ? h->bsubIC.as<int>() + 2 * sB : nullptr;
+  if (!w.sub_enable) w.sep_done = nullptr;
   // factored W1 (OmcWS::w1_fac): k_global stages the accepted Ritz vectors of a slot in its NNQP scratch (LDS variant only; glob_w1_fits).
   // Off in Shor mode (its W1 views are other arrays) and with OMC_DENSE_PROJ=1.
-  if (!shor && w.sub_enable && w.geo.glob.use_lds && glob_w1_fits(n) && !h->tun.dense_proj)
-    w.w1_fac = h->bsubI.as<int>() + 14 * sB;
+  if (!(!shor && w.sub_enable && w.geo.glob.use_lds && glob_w1_fits(n) && !h->tun.dense_proj)) w.w1_fac = nullptr;
   HIPCHK(hipMemsetAsync(w.sweeps, 0, sizeof(int) * S, h->stream));
-  HIPCHK(hipMemsetAsync(w.stamps, 0, (32 + 8 * (size_t)S) * 8, h->stream));
+  HIPCHK(hipMemsetAsync(w.stamps, 0, (size_t)((char*)h->bchk.p + chk_bytes - (char*)w.stamps), h->stream));      // from stamps to the end of the walk
   HIPCHK(hipStreamSynchronize(h->stream));
   h->staged = true;
   return 0;
+}
+
+int omc_relax_stage(omc_instance* h, int B, const omc_relax_params* params, int cut_type, const int* L,
+                    const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir, const double* U_lower,
+                    const double* U_upper) {
+  return stage_base(h, B, params, cut_type, L, cut_x, cut_Uhat, cut_dir, U_lower, U_upper, StageMode{});
 }
 
 int omc_set_node_rho_scales(omc_instance* h, int B, const double* rho_scale) {
@@ -806,47 +811,16 @@ int omc_relax_reserve(omc_instance* h, int extra_nodes, int max_cuts) {
   return 0;
 }
 
+// The one append path, defined below behind the Shor list helpers it uses.  `lists`: the lists of the nodes of an omc_relax_append_shor call, NULL in base mode
+struct ShorAppendLists { const int64_t *n_shor, *shor_idx, *n_soc, *soc_idx; };
+static int append_nodes(omc_instance* h, const char* who, int B2, const int* L, const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir,
+                        const int* load_from, const int* save_to, const ShorAppendLists* lists);
 int omc_relax_append(omc_instance* h, int B2, const int* L, const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir,
                      const int* load_from, const int* save_to) {
   if (!h || !h->staged) return fail(OMC_ERR_ARGUMENT, "omc_relax_append: nothing staged");
   if (B2 <= 0) return fail(OMC_ERR_ARGUMENT, "B must be positive");
   if (h->shor_on) return fail(OMC_ERR_UNSUPPORTED, "omc_relax_append: the staged batch is in Shor mode (omc_relax_append_shor)");
-  HIPCHK(hipSetDevice(h->device));
-  std::lock_guard<std::mutex> lk(h->append_mu);
-  if (h->append_closed) return fail(OMC_ERR_ARGUMENT, "omc_relax_append: the solve of this batch has ended (stage a new batch)");
-  const OmcWS& w = h->ws;
-  const int first = h->Btot_live.load();
-  if (first + B2 > h->node_cap) return fail(OMC_ERR_ARGUMENT, "omc_relax_append: beyond the capacity given to omc_relax_reserve");
-  NodePack pk;
-  { int rcp = pack_nodes(h, h->params, h->staged_cut_type, B2, L, cut_x, cut_Uhat, cut_dir, nullptr, nullptr, pk); if (rcp) return rcp; }
-  if (pk.Rmax > w.Rmax || pk.rmax > w.rmax || pk.Lmax > w.Lmax) return fail(OMC_ERR_ARGUMENT, "omc_relax_append: a node has more cuts than omc_relax_reserve allowed for");
-  if ((load_from || save_to) && !(w.load_from && w.save_to)) return fail(OMC_ERR_ARGUMENT, "omc_relax_append: warm-start indices need a state pool created before the batch was staged");
-  for (int b = 0; b < B2; ++b) {
-    if (load_from && load_from[b] >= h->pool_cap) return fail(OMC_ERR_ARGUMENT, "load_from index beyond the pool");
-    if (save_to && save_to[b] >= h->pool_cap) return fail(OMC_ERR_ARGUMENT, "save_to index beyond the pool");
-  }
-  if (!h->append_stream) HIPCHK(hipStreamCreateWithFlags(&h->append_stream, hipStreamNonBlocking));
-  hipStream_t as = h->append_stream;
-  const size_t f = (size_t)first;
-  // the running kernels read the descriptors of nodes below Btot_live only: these rows are not visible to them until the counter moves
-  { int rc = put_descriptors(w, pk, B2, B2, f, L, cut_x, as); if (rc) return rc; }
-  std::vector<double> hrho(B2, w.rho);
-  HIPCHK(hipMemcpyAsync(const_cast<double*>(w.rho_node) + f, hrho.data(), 8 * (size_t)B2, hipMemcpyHostToDevice, as));
-  std::vector<int> lfv;
-  if (load_from) {      // as at stage time: no base start from an entry that a Shor solve saved
-    lfv.assign(load_from, load_from + B2);
-    std::lock_guard<std::mutex> lk2(h->sig_mu);
-    for (int& e : lfv) if (e >= 0 && (size_t)e < h->pool_sig.size() && h->pool_sig[e].kind == 2) e = -1;
-    HIPCHK(hipMemcpyAsync(const_cast<int*>(w.load_from) + f, lfv.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
-  }
-  if (save_to) {
-    HIPCHK(hipMemcpyAsync(const_cast<int*>(w.save_to) + f, save_to, sizeof(int) * B2, hipMemcpyHostToDevice, as));
-    for (int b = 0; b < B2; ++b) h->save_host[f + b] = save_to[b];      // sized for node_cap at stage time; read by the solve only below Btot_live
-  }
-  HIPCHK(hipStreamSynchronize(as));
-  h->Btot_live.store(first + B2); h->Btot = first + B2;
-  if (!h->worker_running.load()) h->ws.Btot = first + B2;      // no solve in flight: the staged batch simply grew
-  return 0;
+  return append_nodes(h, "omc_relax_append", B2, L, cut_x, cut_Uhat, cut_dir, load_from, save_to, nullptr);
 }
 
 // omc_relax_hold(h, 1) after staging: the submitted solve does not end when every staged node has finished but waits for omc_relax_append
@@ -891,6 +865,31 @@ int omc_relax_fetch_done(omc_instance* h, int max_nodes, int* node_ids, double* 
     if (Y) HIPCHK(hipMemcpyAsync(Y + i * n * n, w.oY + nb * n * n, 8 * n * n, hipMemcpyDeviceToHost, fs));
   }
   HIPCHK(hipStreamSynchronize(fs));
+  return 0;
+}
+
+// An id is known once omc_relax_fetch_done has returned it, or (unless upto_read_only) once the solve has ended and harvested it.
+static int require_finished_ids(omc_instance* h, int n_ids, const int* ids, bool upto_read_only, const char* who) {
+  bool ended = false;
+  if (!upto_read_only) { std::lock_guard<std::mutex> lk(h->append_mu); ended = h->append_closed; }
+  std::lock_guard<std::mutex> lk(h->done_mu);
+  std::vector<char> seen((size_t)std::max(h->node_cap, 1), 0);
+  const size_t upto = ended ? h->done_q.size() : h->done_read;
+  for (size_t i = 0; i < upto; ++i) if ((size_t)h->done_q[i] < seen.size()) seen[h->done_q[i]] = 1;
+  for (int i = 0; i < n_ids; ++i)
+    if (ids[i] < 0 || (size_t)ids[i] >= seen.size() || !seen[ids[i]])
+      return fail(OMC_ERR_ARGUMENT, std::string(who) + ": node " + std::to_string(ids[i]) +
+                                        (upto_read_only ? " is out of range or has not been returned by omc_relax_fetch_done"
+                                                        : " is out of range or has not finished (omc_relax_fetch_done has not returned it)"));
+  return 0;
+}
+
+static int require_certificates(const OmcWS& w, int n_ids, const int* ids, hipStream_t fs, const char* who) {
+  std::vector<int> have(n_ids, 0);
+  for (int i = 0; i < n_ids; ++i) HIPCHK(hipMemcpyAsync(&have[i], w.ocHave + ids[i], sizeof(int), hipMemcpyDeviceToHost, fs));
+  HIPCHK(hipStreamSynchronize(fs));
+  for (int i = 0; i < n_ids; ++i)
+    if (!have[i]) return fail(OMC_ERR_ARGUMENT, std::string(who) + ": node " + std::to_string(ids[i]) + " never reached a rigorous check (no certificate)");
   return 0;
 }
 
@@ -1053,7 +1052,7 @@ static void add_shor_list(std::unordered_map<uint64_t, std::vector<int>>& byhash
 }
 
 // One (minor list, SOC list) pair -> the index structure its nodes share (validation, keys, coordinate CSR, entry classes, column types, slack
-// rows, block penalty, list hash).  The one builder: omc_relax_stage_shor and omc_relax_append_shor both come through here.
+// rows, block penalty, list hash).  The one builder: every caller comes through group_shor_lists.
 static int build_shor_group(const omc_instance* h, int64_t nq64, const int64_t* idx, int64_t nsoc, const int64_t* soc, ShorGroupHost& G) {
   const int n = h->n, m = h->m;
   const int nq = (int)nq64;
@@ -1155,6 +1154,74 @@ static void shor_warm_filter(omc_instance* h, const omc_instance::PoolSig& sg, c
   }
   if (save && *save >= 0 && sg.nq > h->pool_nqmax) *save = -1;
 }
+// The lists a staged batch already knows and the room it has left for new ones (omc_relax_append_shor)
+struct ShorKnownLists {
+  const std::unordered_map<uint64_t, std::vector<int>>* byhash; const std::vector<ShorListKey>* lists;
+  int group_cap; size_t int_room, byte_room; int nqmax, nv1max, nv2max;
+};
+// The nodes of a call grouped by identical (minor list, SOC list) pairs.  Group ids: the known lists first (their ids in the batch), the
+// lists new with this call behind them in order of first appearance; `groups`, `lists`, `hashes` hold the new ones only, with arena
+// offsets relative to the first of them.
+struct ShorGrouping {
+  std::vector<size_t> so, co;      // offsets of every node's tuples / pairs in the concatenated arrays (B + 1 each)
+  std::vector<int> node_group;
+  std::vector<ShorGroupHost> groups;
+  std::unordered_map<uint64_t, std::vector<int>> byhash; std::vector<ShorListKey> lists; std::vector<uint64_t> hashes;
+  size_t tot_int = 0, tot_byte = 0;
+  int nqmax = 0, nv1max = 0, nv2max = 0;
+};
+// Groups the nodes (out.so / out.co: from shor_list_offsets) and builds the index structure of every new list.  With `known`, a new list
+// that the batch has no room for is refused (messages of omc_relax_append_shor); nothing is written anywhere but `out`.
+static int group_shor_lists(const omc_instance* h, int B, const int64_t* n_shor, const int64_t* shor_idx, const int64_t* n_soc, const int64_t* soc_idx,
+                            const ShorKnownLists* known, ShorGrouping& out) {
+  const int NG0 = known ? (int)known->lists->size() : 0;
+  out.node_group.assign(B, 0);
+  for (int b = 0; b < B; ++b) {
+    const int64_t* ib = shor_idx + 4 * out.so[b]; const int64_t* sb = soc_idx + 2 * out.co[b];
+    const uint64_t hv = shor_pair_hash(n_shor[b], ib, n_soc[b], sb);
+    int gid = known ? find_shor_list(*known->byhash, *known->lists, hv, n_shor[b], ib, n_soc[b], sb) : -1;
+    if (gid < 0) {
+      const int g2 = find_shor_list(out.byhash, out.lists, hv, n_shor[b], ib, n_soc[b], sb);
+      if (g2 >= 0) gid = NG0 + g2;
+    }
+    if (gid < 0) {      // a list new with this call: built here, so that the first refusal in node order is the one reported
+      if (known && n_shor[b] > known->nqmax)
+        return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a list has " + std::to_string(n_shor[b]) + " minors, the batch has room for " + std::to_string(known->nqmax) + " per node (nq_max of omc_relax_reserve_shor)");
+      if (known && NG0 + (int)out.lists.size() >= known->group_cap)
+        return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a new list, and the list capacity of the batch (" + std::to_string(known->group_cap) + " lists: staged + extra_lists of omc_relax_reserve_shor) is used up");
+      out.groups.emplace_back();
+      ShorGroupHost& G = out.groups.back();
+      { int rc0 = build_shor_group(h, n_shor[b], ib, n_soc[b], sb, G); if (rc0) return rc0; }
+      out.nqmax = std::max(out.nqmax, G.nq); out.nv1max = std::max(out.nv1max, G.nv1); out.nv2max = std::max(out.nv2max, G.nv2);
+      G.off_int = out.tot_int; out.tot_int += G.ints();
+      G.off_byte = out.tot_byte; out.tot_byte += G.bytes();
+      if (known && (G.nv1 > known->nv1max || G.nv2 > known->nv2max || out.tot_int > known->int_room || out.tot_byte > known->byte_room))
+        return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a new list does not fit the index room reserved by omc_relax_reserve_shor (list capacity used up)");
+      gid = NG0 + (int)out.lists.size();
+      add_shor_list(out.byhash, out.lists, hv, n_shor[b], ib, n_soc[b], sb);
+      out.hashes.push_back(hv);
+    }
+    out.node_group[b] = gid;
+  }
+  return 0;
+}
+
+// Host images of the new groups of `g` and their copies to the given arena positions, the group table and the nodes' group ids, enqueued on s.
+// The images must live until the caller has synchronised s.
+struct ShorGroupImages { std::vector<int> hi; std::vector<uint8_t> hb; std::vector<ShorGroupDev> gd; };
+static int upload_shor_groups(const ShorGrouping& g, int* dev_int, uint8_t* dev_byte, ShorGroupDev* dev_groups, int* dev_node_group, hipStream_t s,
+                              ShorGroupImages& img) {
+  if (!g.groups.empty()) {
+    img.hi.assign(g.tot_int, 0); img.hb.assign(g.tot_byte, 0); img.gd.resize(g.groups.size());
+    for (size_t q = 0; q < g.groups.size(); ++q) pack_shor_group(g.groups[q], img.hi.data(), img.hb.data(), dev_int, dev_byte, img.gd[q]);
+    HIPCHK(hipMemcpyAsync(dev_int, img.hi.data(), g.tot_int * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dev_byte, img.hb.data(), g.tot_byte, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dev_groups, img.gd.data(), sizeof(ShorGroupDev) * img.gd.size(), hipMemcpyHostToDevice, s));
+  }
+  HIPCHK(hipMemcpyAsync(dev_node_group, g.node_group.data(), sizeof(int) * g.node_group.size(), hipMemcpyHostToDevice, s));
+  return 0;
+}
+
 }  // namespace
 
 int omc_relax_reserve_shor(omc_instance* h, int64_t nq_max, int extra_lists) {
@@ -1177,31 +1244,14 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   const int n = h->n, m = h->m;
   if ((long long)n * m >= (1ll << 30)) return fail(OMC_ERR_UNSUPPORTED, "Shor mode: n * m too large for the 32-bit index structures");
   // ---- group the nodes by identical lists ------------------------------------------------------------------------------------------
-  std::vector<size_t> so, co;
-  { int rc0 = shor_list_offsets(B, n_shor, shor_idx, n_soc, soc_idx, so, co); if (rc0) return rc0; }
-  std::unordered_map<uint64_t, std::vector<int>> byhash;      // hash -> group ids
-  std::vector<ShorListKey> lists;                               // the list of each group (kept in the handle for the life of the batch)
-  std::vector<int> rep;                                        // representative node of each group
-  std::vector<int> node_group(B);
-  for (int b = 0; b < B; ++b) {
-    const int64_t* ib = shor_idx + 4 * so[b]; const int64_t* sb = soc_idx + 2 * co[b];
-    const uint64_t hv = shor_pair_hash(n_shor[b], ib, n_soc[b], sb);
-    int gid = find_shor_list(byhash, lists, hv, n_shor[b], ib, n_soc[b], sb);
-    if (gid < 0) { gid = (int)rep.size(); rep.push_back(b); add_shor_list(byhash, lists, hv, n_shor[b], ib, n_soc[b], sb); }
-    node_group[b] = gid;
-  }
-  const int NG = (int)rep.size();
-  std::vector<ShorGroupHost> gh(NG);
-  int nqmax = 0, nv1max = 0, nv2max = 0;
-  size_t tot_int = 0, tot_byte = 0;
-  for (int g = 0; g < NG; ++g) {
-    ShorGroupHost& G = gh[g];
-    const int b = rep[g];
-    { int rc0 = build_shor_group(h, n_shor[b], shor_idx + 4 * so[b], n_soc[b], soc_idx + 2 * co[b], G); if (rc0) return rc0; }
-    nqmax = std::max(nqmax, G.nq); nv1max = std::max(nv1max, G.nv1); nv2max = std::max(nv2max, G.nv2);
-    G.off_int = tot_int; tot_int += G.ints();
-    G.off_byte = tot_byte; tot_byte += G.bytes();
-  }
+  ShorGrouping grp;      // its lists are kept in the handle for the life of the batch
+  { int rc0 = shor_list_offsets(B, n_shor, shor_idx, n_soc, soc_idx, grp.so, grp.co); if (rc0) return rc0; }
+  { int rc0 = group_shor_lists(h, B, n_shor, shor_idx, n_soc, soc_idx, nullptr, grp); if (rc0) return rc0; }
+  const std::vector<size_t>& so = grp.so; const std::vector<size_t>& co = grp.co;
+  const std::vector<ShorGroupHost>& gh = grp.groups; const std::vector<int>& node_group = grp.node_group;
+  const int NG = (int)gh.size();
+  int nqmax = grp.nqmax, nv1max = grp.nv1max, nv2max = grp.nv2max;
+  const size_t tot_int = grp.tot_int, tot_byte = grp.tot_byte;
   // omc_relax_reserve_shor: consumed by this call
   const bool res_set = h->reserve_shor_set; const int64_t res_nq = res_set ? h->reserve_shor_nq : 0; const int res_lists = res_set ? h->reserve_shor_lists : 0;
   h->reserve_shor_set = false; h->reserve_shor_nq = 0; h->reserve_shor_lists = 0;
@@ -1223,7 +1273,8 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   // ---- warm start: the indices of omc_relax_set_warm pass the host's filter, so that the kernels see a plain "warm or cold" per node ------
   // With omc_relax_reserve and a pool both index arrays exist (omc_relax_stage fills what was not given with -1): appended nodes may name entries.
   for (int q = 0; q < 4; ++q) h->shor_warm_stats[q] = 0;
-  h->shor_warm = false;
+  StageMode mode;
+  mode.shor = true;
   const int extra_nodes = h->reserve_nodes;      // consumed by omc_relax_stage below
   if (h->pool_cap > 0 && h->pool_shor && h->k == 1 && (h->warm_load.size() == (size_t)B || h->warm_save.size() == (size_t)B || extra_nodes > 0)) {
     std::lock_guard<std::mutex> lk(h->sig_mu);
@@ -1235,14 +1286,12 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
       shor_warm_filter(h, sg, shor_idx + 4 * so[b], h->warm_load.size() == (size_t)B ? &h->warm_load[b] : nullptr,
                        h->warm_save.size() == (size_t)B ? &h->warm_save[b] : nullptr);
     }
-    h->shor_warm = true;
+    mode.warm_filtered = true;
   } else {
     h->warm_load.clear(); h->warm_save.clear();      // no reservation (or rank k > 1): ignored
   }
   // ---- base staging (rows, small cone, clip, certificate machinery) with the Shor flag ----------------------------------------------
-  h->shor_req = true;
-  int rc = omc_relax_stage(h, B, params, cut_type, L, cut_x, cut_Uhat, cut_dir, U_lower, U_upper);
-  h->shor_req = false;
+  int rc = stage_base(h, B, params, cut_type, L, cut_x, cut_Uhat, cut_dir, U_lower, U_upper, mode);
   if (rc) return rc;
   h->staged = false;
   OmcWS& w = h->ws;
@@ -1257,20 +1306,15 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   const size_t byte_cap = tot_byte + (size_t)res_lists * ((((size_t)n * m + (size_t)m) + 15) & ~(size_t)15);
   // ---- upload the index structures ------------------------------------------------------------------------------------------------
   {
-    std::vector<int> hi(tot_int ? tot_int : 1); std::vector<uint8_t> hb(tot_byte ? tot_byte : 16, 0);
-    if ((rc = h->sgInts.ensure(std::max(int_cap, hi.size()) * sizeof(int)))) return rc;
-    if ((rc = h->sgBytes.ensure(std::max(byte_cap, hb.size())))) return rc;
+    if ((rc = h->sgInts.ensure(int_cap * sizeof(int)))) return rc;
+    if ((rc = h->sgBytes.ensure(byte_cap))) return rc;
     if ((rc = h->sgGroups.ensure(sizeof(ShorGroupDev) * ((size_t)NG + (size_t)res_lists)))) return rc;
     if ((rc = h->sgNodeGroup.ensure(sizeof(int) * (size_t)h->node_cap))) return rc;
-    std::vector<ShorGroupDev> gd(NG);
-    for (int g = 0; g < NG; ++g) pack_shor_group(gh[g], hi.data(), hb.data(), h->sgInts.as<int>(), h->sgBytes.as<uint8_t>(), gd[g]);
-    HIPCHK(hipMemcpyAsync(h->sgInts.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->sgBytes.p, hb.data(), hb.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->sgGroups.p, gd.data(), sizeof(ShorGroupDev) * NG, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->sgNodeGroup.p, node_group.data(), sizeof(int) * B, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));          // the host vectors die with this block
+    ShorGroupImages img;
+    if ((rc = upload_shor_groups(grp, h->sgInts.as<int>(), h->sgBytes.as<uint8_t>(), h->sgGroups.as<ShorGroupDev>(), h->sgNodeGroup.as<int>(), s, img))) return rc;
+    HIPCHK(hipStreamSynchronize(s));          // the host images die with this block
   }
-  h->sh_byhash = std::move(byhash); h->sh_lists = std::move(lists);
+  h->sh_byhash = std::move(grp.byhash); h->sh_lists = std::move(grp.lists);
   h->sh_group_cap = NG + res_lists; h->sh_int_used = tot_int; h->sh_int_cap = int_cap; h->sh_byte_used = tot_byte; h->sh_byte_cap = byte_cap;
   // ---- scaling: the program is homogeneous of degree 2 in A (oracle: shor_scale) -------------------------------------------------------
   const double sc = shor_scale(h);
@@ -1293,7 +1337,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   ENS(h->sTq, sB * 15 * nq1 * 8); ENS(h->sPq, sB * 15 * nq1 * 8); ENS(h->sNq, sB * 15 * nq1 * 8);
   ENS(h->sD5x, sB * nm * 8); ENS(h->sD5t, sB * m * 8); ENS(h->snu5, sB * m * 8); ENS(h->sP5x, sB * nm * 8);
   ENS(h->scolpart, sB * m * 4 * 8); ENS(h->sminpart, sB * nmb * 8); ENS(h->sminpart2, sB * nmb * 8);
-  ENS(h->sfroB, sB * 2 * 8); ENS(h->svvB, sB * sizeof(int)); ENS(h->se1, sB * nv11 * 8); ENS(h->se2, sB * nv21 * 8);
+  ENS_CARVE(h->sfroB, [&](Carve& c) { walk_shor_fro(c, sB, sh); }); ENS(h->svvB, sB * sizeof(int)); ENS(h->se1, sB * nv11 * 8); ENS(h->se2, sB * nv21 * 8);
   ENS(h->soX, sN * nm * 8); ENS(h->soW, sN * nm * 8); ENS(h->soTh, sN * m * m * 8);
   HIPCHK(hipMemsetAsync(h->sMbufB.p, 0, sB * NPb * NPb * 8, s));
   HIPCHK(hipMemsetAsync(h->sVrowB.p, 0, sB * NPb * NPb * 8, s));
@@ -1311,7 +1355,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   sh.Tq = h->sTq.as<double>(); sh.Pq = h->sPq.as<double>(); sh.Nq = h->sNq.as<double>();
   sh.D5x = h->sD5x.as<double>(); sh.D5t = h->sD5t.as<double>(); sh.nu5 = h->snu5.as<double>(); sh.P5x = h->sP5x.as<double>();
   sh.colpart = h->scolpart.as<double>(); sh.minpart = h->sminpart.as<double>(); sh.minpart2 = h->sminpart2.as<double>();
-  sh.fro2B = h->sfroB.as<double>(); sh.trB = h->sfroB.as<double>() + sB; sh.vvalidB = h->svvB.as<int>();
+  sh.vvalidB = h->svvB.as<int>();
   sh.Y = w.Y; sh.Yp = w.Yp; sh.rp = w.rp; sh.rd = w.rd;
   sh.e1 = h->se1.as<double>(); sh.e2 = h->se2.as<double>();
   sh.objcol = w.objcol; sh.c0col = w.c0col; sh.lamDX = w.lamDX;
@@ -1324,16 +1368,15 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
     ENS(h->sloadpart, sB * NPb * 2 * 8); sh.loadpart = h->sloadpart.as<double>();
   }
   if (h->keep_shor_cert) {      // best certificate per node, Shor part: blocks, paraboloid multipliers and points, per slot and per node of the capacity; zeroed
-    const size_t per = 15 * nq1 + (size_t)m + 2 * nm;
-    if (h->scbD.ensure(sB * per * 8) || h->socD.ensure(sN * per * 8) || h->socNq.ensure(sN * sizeof(int))) {
+    size_t cb_bytes = 0, oc_bytes = 0;
+    if (carve_ensure(h->scbD, [&](Carve& c) { walk_shor_cert(c, sB, nq1, m, nm, sh.cbGam, sh.cbZeta, sh.cbXi, sh.cbXbar); }, &cb_bytes) ||
+        carve_ensure(h->socD, [&](Carve& c) { walk_shor_cert(c, sN, nq1, m, nm, sh.ocGam, sh.ocZeta, sh.ocXi, sh.ocXbar); }, &oc_bytes) ||
+        h->socNq.ensure(sN * sizeof(int))) {
       (void)hipGetLastError();
-      return fail(OMC_ERR_ALLOC, "omc_relax_stage_shor: the Shor-mode certificates need " + std::to_string(per * 8) + " bytes per slot (" + std::to_string(S) +
+      return fail(OMC_ERR_ALLOC, "omc_relax_stage_shor: the Shor-mode certificates need " + std::to_string(cb_bytes / sB) + " bytes per slot (" + std::to_string(S) +
                                  ") and per node of the capacity (" + std::to_string(h->node_cap) + "), which the device does not have (" + g_err + ")");
     }
-    HIPCHK(hipMemsetAsync(h->scbD.p, 0, sB * per * 8, s)); HIPCHK(hipMemsetAsync(h->socD.p, 0, sN * per * 8, s)); HIPCHK(hipMemsetAsync(h->socNq.p, 0, sN * sizeof(int), s));
-    double* cb = h->scbD.as<double>(); double* oc = h->socD.as<double>();
-    sh.cbGam = cb; sh.cbZeta = cb + sB * 15 * nq1; sh.cbXi = sh.cbZeta + sB * m; sh.cbXbar = sh.cbXi + sB * nm;
-    sh.ocGam = oc; sh.ocZeta = oc + sN * 15 * nq1; sh.ocXi = sh.ocZeta + sN * m; sh.ocXbar = sh.ocXi + sN * nm;
+    HIPCHK(hipMemsetAsync(h->scbD.p, 0, cb_bytes, s)); HIPCHK(hipMemsetAsync(h->socD.p, 0, oc_bytes, s)); HIPCHK(hipMemsetAsync(h->socNq.p, 0, sN * sizeof(int), s));
     sh.ocNq = h->socNq.as<int>(); sh.cert_flag = w.cert_flag; sh.cb_rho = w.cb_rho;
   }
   if (h->shor_keep_V) { ENS(h->soV, sN * 5 * nq1 * 8); HIPCHK(hipMemsetAsync(h->soV.p, 0, sN * 5 * nq1 * 8, s)); sh.oV = h->soV.as<double>(); }
@@ -1352,16 +1395,16 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   // kernel of the base engine follows them; the warm-started full kernel seeds the block and is the fall-back
   wb.trM = sh.trB;
   if (wb.geo.ws_lpp && N >= 48 && wb.geo.sub_lds <= OMC_MAX_DYN_LDS && !h->tun.no_subspace && !h->tun.shor_no_subspace) {
-    ENS(h->sXsB, sB * NPb * 16 * 8); ENS(h->ssubSB, sB * 16 * 8); ENS(h->ssubIB, sB * 12 * sizeof(int));
+    size_t subI_bytes = 0;
+    ENS(h->sXsB, sB * NPb * 16 * 8); ENS(h->ssubSB, sB * 16 * 8);
+    ENS_CARVE(h->ssubIB, [&](Carve& c) { walk_shor_sub_ints(c, sB, sh, wb); }, &subI_bytes);
     HIPCHK(hipMemsetAsync(h->sXsB.p, 0, sB * NPb * 16 * 8, s));
     HIPCHK(hipMemsetAsync(h->ssubSB.p, 0, sB * 16 * 8, s));
-    HIPCHK(hipMemsetAsync(h->ssubIB.p, 0, sB * 12 * sizeof(int), s));
-    int* si = h->ssubIB.as<int>();
-    sh.sub_onB = si; sh.cone_doneB = si + sB; sh.sub_waitB = si + 2 * sB; sh.sub_nfailB = si + 3 * sB;
+    HIPCHK(hipMemsetAsync(h->ssubIB.p, 0, subI_bytes, s));
     wb.sub_enable = 1; wb.Xs = h->sXsB.as<double>(); wb.sub_theta = h->ssubSB.as<double>();
     wb.sub_zscratch = nullptr;
     if (NPb > 512) { ENS(h->bsubz, sB * 16 * (size_t)(NPb + 2) * 8); wb.sub_zscratch = h->bsubz.as<double>(); }
-    wb.ws_first = nullptr; wb.ws_need = nullptr; wb.ws_phase = 0; wb.sub_on = sh.sub_onB; wb.cone_done = sh.cone_doneB; wb.sub_wait = sh.sub_waitB; wb.sub_nfail = sh.sub_nfailB; wb.sub_stat = si + 4 * sB;
+    wb.ws_first = nullptr; wb.ws_need = nullptr; wb.ws_phase = 0; wb.sub_on = sh.sub_onB; wb.cone_done = sh.cone_doneB; wb.sub_wait = sh.sub_waitB; wb.sub_nfail = sh.sub_nfailB;
     wb.sep_done = nullptr;
   }
   HIPCHK(hipStreamSynchronize(s));
@@ -1442,102 +1485,107 @@ int omc_relax_append_shor(omc_instance* h, int B2, const int* L, const double* c
   if (!h->shor_on) return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: the staged batch is not in Shor mode (omc_relax_append)");
   if (B2 <= 0) return fail(OMC_ERR_ARGUMENT, "B must be positive");
   if (!n_shor || !n_soc) return fail(OMC_ERR_ARGUMENT, "n_shor / n_soc is NULL");
+  const ShorAppendLists lists = {n_shor, shor_idx, n_soc, soc_idx};
+  return append_nodes(h, "omc_relax_append_shor", B2, L, cut_x, cut_Uhat, cut_dir, load_from, save_to, &lists);
+}
+
+// lists: known ones share their group, new ones are built (and may still be refused); then the warm-start filter of stage time, where
+// node_sig lets the harvest sign the entry an appended node saves to
+static int shor_append_plan(omc_instance* h, int first, int B2, const ShorAppendLists& l, std::vector<int>& load, std::vector<int>& save, ShorGrouping& g) {
+  const ShWS& sh = h->sh;
+  const ShorKnownLists known = {&h->sh_byhash, &h->sh_lists, h->sh_group_cap, h->sh_int_cap - h->sh_int_used, h->sh_byte_cap - h->sh_byte_used,
+                                sh.nqmax, sh.nv1max, sh.nv2max};
+  { int rc0 = shor_list_offsets(B2, l.n_shor, l.shor_idx, l.n_soc, l.soc_idx, g.so, g.co); if (rc0) return rc0; }
+  { int rc0 = group_shor_lists(h, B2, l.n_shor, l.shor_idx, l.n_soc, l.soc_idx, &known, g); if (rc0) return rc0; }
+  if (load.empty()) return 0;      // the batch has no warm-start arrays
+  const int NG0 = (int)h->sh_lists.size();
+  std::lock_guard<std::mutex> lk2(h->sig_mu);
+  for (int b = 0; b < B2; ++b) {
+    omc_instance::PoolSig sg;
+    sg.kind = 2; sg.nq = l.n_shor[b]; sg.nsoc = l.n_soc[b];
+    sg.hlist = g.node_group[b] < NG0 ? h->sh_lists[g.node_group[b]].hlist : g.lists[g.node_group[b] - NG0].hlist;
+    sg.hsoc = l.n_soc[b] > 0 ? fnv1a(l.soc_idx + 2 * g.co[b], 16 * (size_t)l.n_soc[b], FNV_SEED) : 0;
+    shor_warm_filter(h, sg, l.shor_idx + 4 * g.so[b], &load[b], &save[b]);
+    h->node_sig[(size_t)first + b] = sg;      // sized for node_cap at stage time; read by the solve only below Btot_live
+  }
+  return 0;
+}
+
+// the new groups go into the room that omc_relax_reserve_shor reserved in the index arenas and the group table, behind everything the
+// running kernels can reach (they find a list through node_group of a node below Btot_live)
+static int shor_append_write(omc_instance* h, const ShorGrouping& g, int first, hipStream_t s, ShorGroupImages& img) {
+  return upload_shor_groups(g, h->sgInts.as<int>() + h->sh_int_used, h->sgBytes.as<uint8_t>() + h->sh_byte_used,
+                            h->sgGroups.as<ShorGroupDev>() + h->sh_lists.size(), h->sgNodeGroup.as<int>() + first, s, img);
+}
+
+static void shor_append_commit(omc_instance* h, ShorGrouping& g) {
+  for (size_t q = 0; q < g.lists.size(); ++q) {
+    h->sh_byhash[g.hashes[q]].push_back((int)h->sh_lists.size());
+    h->sh_lists.push_back(std::move(g.lists[q]));
+  }
+  h->sh_int_used += g.tot_int; h->sh_byte_used += g.tot_byte;
+}
+
+// The one append path: omc_relax_append, and with `lists` omc_relax_append_shor, whose list step (known lists share their group, new ones
+// are built and may be refused) sits between the checks and the writes.  Lock, end-of-batch decision, capacity, rows, strides and pool
+// indices first: every refusal is decided before anything is written, and a refused call leaves the batch as it was.  Then the new groups,
+// the descriptors, rho_node and the warm-start indices on the append stream, and the counter last: the running kernels read the
+// descriptors of nodes below Btot_live only, so these rows are not visible to them until it moves.
+static int append_nodes(omc_instance* h, const char* who, int B2, const int* L, const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir,
+                        const int* load_from, const int* save_to, const ShorAppendLists* lists) {
+  const std::string pre = std::string(who) + ": ";
   HIPCHK(hipSetDevice(h->device));
   std::lock_guard<std::mutex> lk(h->append_mu);
-  if (h->append_closed) return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: the solve of this batch has ended (stage a new batch)");
+  if (h->append_closed) return fail(OMC_ERR_ARGUMENT, pre + "the solve of this batch has ended (stage a new batch)");
   const OmcWS& w = h->ws;
-  const ShWS& sh = h->sh;
   const int first = h->Btot_live.load();
-  if (first + B2 > h->node_cap) return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: beyond the node capacity given to omc_relax_reserve");
+  if (first + B2 > h->node_cap) return fail(OMC_ERR_ARGUMENT, pre + (lists ? "beyond the node capacity given to omc_relax_reserve" : "beyond the capacity given to omc_relax_reserve"));
   NodePack pk;
   { int rcp = pack_nodes(h, h->params, h->staged_cut_type, B2, L, cut_x, cut_Uhat, cut_dir, nullptr, nullptr, pk); if (rcp) return rcp; }
-  if (pk.Rmax > w.Rmax || pk.rmax > w.rmax || pk.Lmax > w.Lmax) return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a node has more cuts than omc_relax_reserve allowed for");
+  if (pk.Rmax > w.Rmax || pk.rmax > w.rmax || pk.Lmax > w.Lmax) return fail(OMC_ERR_ARGUMENT, pre + "a node has more cuts than omc_relax_reserve allowed for");
   if ((load_from || save_to) && !(w.load_from && w.save_to))
-    return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: warm-start indices need a state pool with its Shor extension (omc_state_pool_reserve_shor) before the batch was staged");
+    return fail(OMC_ERR_ARGUMENT, pre + (lists ? "warm-start indices need a state pool with its Shor extension (omc_state_pool_reserve_shor) before the batch was staged"
+                                               : "warm-start indices need a state pool created before the batch was staged"));
   for (int b = 0; b < B2; ++b) {
     if (load_from && load_from[b] >= h->pool_cap) return fail(OMC_ERR_ARGUMENT, "load_from index beyond the pool");
     if (save_to && save_to[b] >= h->pool_cap) return fail(OMC_ERR_ARGUMENT, "save_to index beyond the pool");
   }
-  // ---- lists: known ones share their group, new ones are built (and may still be refused) --------------------------------------------------
-  std::vector<size_t> so, co;
-  { int rc0 = shor_list_offsets(B2, n_shor, shor_idx, n_soc, soc_idx, so, co); if (rc0) return rc0; }
-  const int NG0 = (int)h->sh_lists.size();
-  std::unordered_map<uint64_t, std::vector<int>> nhash; std::vector<ShorListKey> nlists; std::vector<uint64_t> nhv;      // lists new with this call
-  std::vector<ShorGroupHost> gh;
-  std::vector<int> node_group(B2);
-  size_t add_int = 0, add_byte = 0;
-  for (int b = 0; b < B2; ++b) {
-    const int64_t* ib = shor_idx + 4 * so[b]; const int64_t* sb = soc_idx + 2 * co[b];
-    const uint64_t hv = shor_pair_hash(n_shor[b], ib, n_soc[b], sb);
-    int gid = find_shor_list(h->sh_byhash, h->sh_lists, hv, n_shor[b], ib, n_soc[b], sb);
-    if (gid < 0) {
-      const int g2 = find_shor_list(nhash, nlists, hv, n_shor[b], ib, n_soc[b], sb);
-      if (g2 >= 0) gid = NG0 + g2;
-    }
-    if (gid < 0) {
-      if (n_shor[b] > sh.nqmax)
-        return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a list has " + std::to_string(n_shor[b]) + " minors, the batch has room for " + std::to_string(sh.nqmax) + " per node (nq_max of omc_relax_reserve_shor)");
-      if (NG0 + (int)nlists.size() >= h->sh_group_cap)
-        return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a new list, and the list capacity of the batch (" + std::to_string(h->sh_group_cap) + " lists: staged + extra_lists of omc_relax_reserve_shor) is used up");
-      gh.emplace_back();
-      ShorGroupHost& G = gh.back();
-      { int rc0 = build_shor_group(h, n_shor[b], ib, n_soc[b], sb, G); if (rc0) return rc0; }
-      G.off_int = add_int; add_int += G.ints();
-      G.off_byte = add_byte; add_byte += G.bytes();
-      if (G.nv1 > sh.nv1max || G.nv2 > sh.nv2max || h->sh_int_used + add_int > h->sh_int_cap || h->sh_byte_used + add_byte > h->sh_byte_cap)
-        return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a new list does not fit the index room reserved by omc_relax_reserve_shor (list capacity used up)");
-      gid = NG0 + (int)nlists.size();
-      add_shor_list(nhash, nlists, hv, n_shor[b], ib, n_soc[b], sb);
-      nhv.push_back(hv);
-    }
-    node_group[b] = gid;
-  }
-  // ---- warm start: the filter of stage time; node_sig lets the harvest sign the entry an appended node saves to ---------------------------
+  // warm-start indices as they are written (empty: that array is not): a base append writes what was given, without the entries that a Shor
+  // solve saved (as at stage time); a Shor append writes both arrays once the batch has them, -1 where nothing was given, through its filter
   std::vector<int> lfv, svv;
-  if (w.load_from && w.save_to) {
-    lfv.assign(B2, -1); svv.assign(B2, -1);
-    if (load_from) lfv.assign(load_from, load_from + B2);
-    if (save_to) svv.assign(save_to, save_to + B2);
-    std::lock_guard<std::mutex> lk2(h->sig_mu);
-    for (int b = 0; b < B2; ++b) {
-      omc_instance::PoolSig sg;
-      sg.kind = 2; sg.nq = n_shor[b]; sg.nsoc = n_soc[b];
-      sg.hlist = node_group[b] < NG0 ? h->sh_lists[node_group[b]].hlist : nlists[node_group[b] - NG0].hlist;
-      sg.hsoc = n_soc[b] > 0 ? fnv1a(soc_idx + 2 * co[b], 16 * (size_t)n_soc[b], FNV_SEED) : 0;
-      shor_warm_filter(h, sg, shor_idx + 4 * so[b], &lfv[b], &svv[b]);
-      h->node_sig[(size_t)first + b] = sg;      // sized for node_cap at stage time; read by the solve only below Btot_live
+  ShorGrouping grouping;
+  if (lists) {
+    if (w.load_from && w.save_to) {
+      lfv.assign(B2, -1); svv.assign(B2, -1);
+      if (load_from) lfv.assign(load_from, load_from + B2);
+      if (save_to) svv.assign(save_to, save_to + B2);
     }
+    int rcl = shor_append_plan(h, first, B2, *lists, lfv, svv, grouping); if (rcl) return rcl;
+  } else {
+    if (load_from) {
+      lfv.assign(load_from, load_from + B2);
+      std::lock_guard<std::mutex> lk2(h->sig_mu);
+      for (int& e : lfv) if (e >= 0 && (size_t)e < h->pool_sig.size() && h->pool_sig[e].kind == 2) e = -1;
+    }
+    if (save_to) svv.assign(save_to, save_to + B2);
   }
-  // ---- write: new groups, then the descriptors of the nodes, all on the append stream; the counter moves last -----------------------------
   if (!h->append_stream) HIPCHK(hipStreamCreateWithFlags(&h->append_stream, hipStreamNonBlocking));
   hipStream_t as = h->append_stream;
   const size_t f = (size_t)first;
-  std::vector<int> hi(add_int ? add_int : 1); std::vector<uint8_t> hb(add_byte ? add_byte : 16, 0);
-  std::vector<ShorGroupDev> gd(gh.size());
-  if (!gh.empty()) {
-    const int* dint = h->sgInts.as<int>() + h->sh_int_used; const uint8_t* dbyte = h->sgBytes.as<uint8_t>() + h->sh_byte_used;
-    for (size_t g = 0; g < gh.size(); ++g) pack_shor_group(gh[g], hi.data(), hb.data(), dint, dbyte, gd[g]);
-    HIPCHK(hipMemcpyAsync(const_cast<int*>(dint), hi.data(), add_int * sizeof(int), hipMemcpyHostToDevice, as));
-    HIPCHK(hipMemcpyAsync(const_cast<uint8_t*>(dbyte), hb.data(), add_byte, hipMemcpyHostToDevice, as));
-    HIPCHK(hipMemcpyAsync(h->sgGroups.as<ShorGroupDev>() + NG0, gd.data(), sizeof(ShorGroupDev) * gd.size(), hipMemcpyHostToDevice, as));
-  }
-  HIPCHK(hipMemcpyAsync(h->sgNodeGroup.as<int>() + f, node_group.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
+  ShorGroupImages img;
+  if (lists) { int rcw = shor_append_write(h, grouping, first, as, img); if (rcw) return rcw; }
   { int rc = put_descriptors(w, pk, B2, B2, f, L, cut_x, as); if (rc) return rc; }
   std::vector<double> hrho(B2, w.rho);
   HIPCHK(hipMemcpyAsync(const_cast<double*>(w.rho_node) + f, hrho.data(), 8 * (size_t)B2, hipMemcpyHostToDevice, as));
-  if (!lfv.empty()) {
-    HIPCHK(hipMemcpyAsync(const_cast<int*>(w.load_from) + f, lfv.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
+  if (!lfv.empty()) HIPCHK(hipMemcpyAsync(const_cast<int*>(w.load_from) + f, lfv.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
+  if (!svv.empty()) {
     HIPCHK(hipMemcpyAsync(const_cast<int*>(w.save_to) + f, svv.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
-    for (int b = 0; b < B2; ++b) h->save_host[f + b] = svv[b];
+    for (int b = 0; b < B2; ++b) h->save_host[f + b] = svv[b];      // sized for node_cap at stage time; read by the solve only below Btot_live
   }
   HIPCHK(hipStreamSynchronize(as));
-  for (size_t g = 0; g < nlists.size(); ++g) {
-    h->sh_byhash[nhv[g]].push_back((int)h->sh_lists.size());
-    h->sh_lists.push_back(std::move(nlists[g]));
-  }
-  h->sh_int_used += add_int; h->sh_byte_used += add_byte;
+  if (lists) shor_append_commit(h, grouping);
   h->Btot_live.store(first + B2); h->Btot = first + B2;
-  if (!h->worker_running.load()) { h->ws.Btot = first + B2; h->sh.Btot = first + B2; }      // no solve in flight: the staged batch simply grew (a running solve sets both when it ends)
+  if (!h->worker_running.load()) { h->ws.Btot = first + B2; if (lists) h->sh.Btot = first + B2; }      // no solve in flight: the staged batch simply grew (a running solve sets both when it ends)
   return 0;
 }
 
@@ -1548,14 +1596,7 @@ int omc_relax_fetch_done_shor(omc_instance* h, int n_ids, const int* node_ids, d
   if (!h->staged || !h->shor_on) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_done_shor: no Shor-mode batch staged");
   if (n_ids < 0 || (n_ids > 0 && !node_ids)) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_done_shor: bad arguments");
   if (n_ids == 0) return 0;
-  {
-    std::lock_guard<std::mutex> lk(h->done_mu);
-    std::vector<char> seen((size_t)std::max(h->node_cap, 1), 0);
-    for (size_t i = 0; i < h->done_read; ++i) if ((size_t)h->done_q[i] < seen.size()) seen[h->done_q[i]] = 1;
-    for (int i = 0; i < n_ids; ++i)
-      if (node_ids[i] < 0 || (size_t)node_ids[i] >= seen.size() || !seen[node_ids[i]])
-        return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_done_shor: node " + std::to_string(node_ids[i]) + " is out of range or has not been returned by omc_relax_fetch_done");
-  }
+  { int rcf = require_finished_ids(h, n_ids, node_ids, true, "omc_relax_fetch_done_shor"); if (rcf) return rcf; }
   HIPCHK(hipSetDevice(h->device));
   if (!h->fetch_stream) HIPCHK(hipStreamCreateWithFlags(&h->fetch_stream, hipStreamNonBlocking));
   hipStream_t fs = h->fetch_stream;
@@ -1601,24 +1642,11 @@ int omc_relax_fetch_certificate(omc_instance* h, int n_ids, const int* node_ids,
     return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: the batch was staged without omc_relax_keep_certificates(h, 1)");
   if (n_ids < 0 || (n_ids > 0 && !node_ids)) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: bad arguments");
   if (n_ids == 0) return 0;
-  {      // an id is known once omc_relax_fetch_done has returned it, or once the solve has ended and harvested it
-    bool ended; { std::lock_guard<std::mutex> lk(h->append_mu); ended = h->append_closed; }
-    std::lock_guard<std::mutex> lk(h->done_mu);
-    std::vector<char> seen((size_t)std::max(h->node_cap, 1), 0);
-    const size_t upto = ended ? h->done_q.size() : h->done_read;
-    for (size_t i = 0; i < upto; ++i) if ((size_t)h->done_q[i] < seen.size()) seen[h->done_q[i]] = 1;
-    for (int i = 0; i < n_ids; ++i)
-      if (node_ids[i] < 0 || (size_t)node_ids[i] >= seen.size() || !seen[node_ids[i]])
-        return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: node " + std::to_string(node_ids[i]) + " is out of range or has not finished (omc_relax_fetch_done has not returned it)");
-  }
+  { int rcf = require_finished_ids(h, n_ids, node_ids, false, "omc_relax_fetch_certificate"); if (rcf) return rcf; }
   HIPCHK(hipSetDevice(h->device));
   if (!h->fetch_stream) HIPCHK(hipStreamCreateWithFlags(&h->fetch_stream, hipStreamNonBlocking));
   hipStream_t fs = h->fetch_stream;
-  std::vector<int> have(n_ids, 0);
-  for (int i = 0; i < n_ids; ++i) HIPCHK(hipMemcpyAsync(&have[i], w.ocHave + node_ids[i], sizeof(int), hipMemcpyDeviceToHost, fs));
-  HIPCHK(hipStreamSynchronize(fs));
-  for (int i = 0; i < n_ids; ++i)
-    if (!have[i]) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_certificate: node " + std::to_string(node_ids[i]) + " never reached a rigorous check (no certificate)");
+  { int rcc = require_certificates(w, n_ids, node_ids, fs, "omc_relax_fetch_certificate"); if (rcc) return rcc; }
   const size_t nnz = (size_t)w.nnz, Rm = (size_t)w.Rmax, nq = (size_t)w.n * w.rmax, ps = (size_t)(w.rmax + w.k) * (w.rmax + w.k);
   for (int i = 0; i < n_ids; ++i) {
     const size_t nb = (size_t)node_ids[i], o = (size_t)i;
@@ -1667,24 +1695,11 @@ int omc_relax_fetch_shor_certificate(omc_instance* h, int n_ids, const int* node
   if (n_ids < 0 || (n_ids > 0 && !node_ids)) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_shor_certificate: bad arguments");
   if (nq_stride) *nq_stride = sh.nqmax;
   if (n_ids == 0) return 0;
-  {      // an id is known once omc_relax_fetch_done has returned it, or once the solve has ended and harvested it
-    bool ended; { std::lock_guard<std::mutex> lk(h->append_mu); ended = h->append_closed; }
-    std::lock_guard<std::mutex> lk(h->done_mu);
-    std::vector<char> seen((size_t)std::max(h->node_cap, 1), 0);
-    const size_t upto = ended ? h->done_q.size() : h->done_read;
-    for (size_t i = 0; i < upto; ++i) if ((size_t)h->done_q[i] < seen.size()) seen[h->done_q[i]] = 1;
-    for (int i = 0; i < n_ids; ++i)
-      if (node_ids[i] < 0 || (size_t)node_ids[i] >= seen.size() || !seen[node_ids[i]])
-        return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_shor_certificate: node " + std::to_string(node_ids[i]) + " is out of range or has not finished (omc_relax_fetch_done has not returned it)");
-  }
+  { int rcf = require_finished_ids(h, n_ids, node_ids, false, "omc_relax_fetch_shor_certificate"); if (rcf) return rcf; }
   HIPCHK(hipSetDevice(h->device));
   if (!h->fetch_stream) HIPCHK(hipStreamCreateWithFlags(&h->fetch_stream, hipStreamNonBlocking));
   hipStream_t fs = h->fetch_stream;
-  std::vector<int> have(n_ids, 0);
-  for (int i = 0; i < n_ids; ++i) HIPCHK(hipMemcpyAsync(&have[i], w.ocHave + node_ids[i], sizeof(int), hipMemcpyDeviceToHost, fs));
-  HIPCHK(hipStreamSynchronize(fs));
-  for (int i = 0; i < n_ids; ++i)
-    if (!have[i]) return fail(OMC_ERR_ARGUMENT, "omc_relax_fetch_shor_certificate: node " + std::to_string(node_ids[i]) + " never reached a rigorous check (no certificate)");
+  { int rcc = require_certificates(w, n_ids, node_ids, fs, "omc_relax_fetch_shor_certificate"); if (rcc) return rcc; }
   const size_t Rm = (size_t)w.Rmax, nqd = (size_t)w.n * w.rmax, ps = (size_t)(w.rmax + w.k) * (w.rmax + w.k), gs = (size_t)15 * sh.nqmax, m = (size_t)sh.m, nm = (size_t)sh.n * sh.m;
   for (int i = 0; i < n_ids; ++i) {
     const size_t nb = (size_t)node_ids[i], o = (size_t)i;
@@ -1705,6 +1720,37 @@ int omc_relax_fetch_shor_certificate(omc_instance* h, int n_ids, const int* node
   return 0;
 }
 
+// ---- the private eigen-kernel view of the two dual-bound evaluators ------------------------------------------------------------------------
+// A workspace of their own with the dimensions of V views, through which k_dual_assemble and the eigen-kernel a check of a relaxation at this
+// order would take run, cold.  No batch is staged and a staged one is not touched.
+static EvalDims eval_view_dims(omc_instance* h, OmcWS& w, int V, int k, const NodePack& pk) {
+  const EvalDims d = {(size_t)V, (size_t)h->n, (size_t)k, (size_t)h->nnz, (size_t)pk.Rmax, (size_t)pk.rmax, (size_t)std::max(pk.Lmax, 1)};
+  memset(&w, 0, sizeof(w));
+  w.nB = w.B = w.Btot = V; w.n = h->n; w.m = h->m; w.k = k; w.nnz = h->nnz; w.Rmax = (int)d.Rmax; w.Lmax = (int)d.Lmax; w.rmax = (int)d.rmax;
+  w.np16 = (h->n + 15) & ~15; w.max_sweeps = MAX_SWEEPS; w.mw_budget = MAX_SWEEPS; w.gamma = h->gamma; w.clip_hi = 1.0; w.inv_s2 = 1.0;
+  w.col_ptr = h->dcol_ptr.as<int>(); w.col_idx = h->dcol_idx.as<int>(); w.col_val = h->dcol_val.as<double>();
+  w.geo = omc_plan_geometry(w.n, w.np16, k, w.rmax, w.Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
+  return d;
+}
+// the flags and statistics the eigen-kernel reads, and the matrices: the zero padding of MbufC; VrowC: cold start, and 0 x garbage could be NaN.
+// Both lengths come from the walks (omc_walks.h)
+static int eval_view_zero(const OmcWS& w, const EvalArrays& a, hipStream_t s) {
+  HIPCHK(hipMemsetAsync(w.done, 0, (size_t)((char*)a.zero_end - (char*)w.done), s));
+  HIPCHK(hipMemsetAsync(w.MbufC, 0, (size_t)((char*)w.Mchk - (char*)w.MbufC), s));
+  return 0;
+}
+// k_cone_ws LDS- or L2-resident and the multi-workgroup kernels from OMC_CONE_MULTI_MIN on, k_cone at orders 129 - 144; then everything from
+// c0 to scalars_end on its way to `scal` (a scalar x of view v is scal[(w.x - w.c0) + v]): the caller synchronises
+static int eval_view_solve(OmcWS& w, const EvalArrays& a, hipEvent_t after, std::vector<double>& scal, hipStream_t s) {
+  if (w.geo.ws_lpp || w.geo.mw) { w.ws_mode = 1; omc_launch_cone_ws(&w, s); }
+  else omc_launch_cone(&w, CONE_EVALS, s);
+  if (after) HIPCHK(hipEventRecord(after, s));
+  HIPCHK(hipGetLastError());
+  scal.resize((size_t)(a.scalars_end - w.c0));
+  HIPCHK(hipMemcpyAsync(scal.data(), w.c0, (size_t)((char*)a.scalars_end - (char*)w.c0), hipMemcpyDeviceToHost, s));
+  return 0;
+}
+
 // The Lagrangian bound of caller-supplied multipliers (omc.h).  Rows and row basis on the host exactly as omc_relax_stage builds them
 // (pack_nodes, put_descriptors) into buffers of its own, k_dual_assemble for the matrix and the constants, then the eigen-kernel a check of a
 // relaxation at this order would take (k_cone_ws LDS- or L2-resident, k_cone at orders 129 - 144, the multi-workgroup kernels from
@@ -1714,15 +1760,14 @@ int omc_dual_bound_batch(omc_instance* h, int B, int cut_type, int reference_qui
                          const double* Psi3, double* Q_out, int* r_out, double* bound) {
   if (!h) return fail(OMC_ERR_ARGUMENT, "omc_dual_bound_batch: handle is NULL");
   if (B <= 0) return fail(OMC_ERR_ARGUMENT, "omc_dual_bound_batch: B must be positive");
-  if (cut_type != OMC_CUT_LINEAR && cut_type != OMC_CUT_LINEAR2 && cut_type != OMC_CUT_LINEAR3)
-    return fail(OMC_ERR_INVALID_ENUM, "Invalid input for disjunctive cuts type: must be linear, linear2 or linear3 (OMC.jl:1456-1462)");
+  { int rcc = check_cut_type(cut_type); if (rcc) return rcc; }
   const bool query = !Lam && !lam && !Psi3 && !bound;      // rows and basis only
   if (!query && (!Lam || !lam || !bound)) return fail(OMC_ERR_ARGUMENT, "omc_dual_bound_batch: Lam, lam and bound are needed (all of Lam, lam, Psi3, bound NULL: Q_out / r_out only)");
   if (h->worker.joinable() || h->worker_running.load()) return fail(OMC_ERR_ARGUMENT, "omc_dual_bound_batch: a solve is in flight on this handle (call omc_relax_wait first)");
   omc_relax_params P = h->params; P.reference_quirk_q1 = reference_quirk_q1 ? 1 : 0;
   NodePack pk;
   { int rcp = pack_nodes(h, P, cut_type, B, L, cut_x, cut_Uhat, cut_dir, U_lower, U_upper, pk); if (rcp) return rcp; }
-  const size_t sB = (size_t)B, n = h->n, m = h->m, k = h->k, nnz = h->nnz, Rmax = pk.Rmax, rmax = pk.rmax, Lmax = std::max(pk.Lmax, 1);
+  const size_t sB = (size_t)B, n = h->n, m = h->m, k = h->k, nnz = h->nnz, Rmax = pk.Rmax, rmax = pk.rmax;
   if (r_out) for (int b = 0; b < B; ++b) r_out[b] = pk.rrv[b];
   if (Q_out)
     for (size_t b = 0; b < sB; ++b) {
@@ -1732,47 +1777,29 @@ int omc_dual_bound_batch(omc_instance* h, int B, int cut_type, int reference_qui
   if (query) return 0;
   HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  const size_t NP = (n + 15) & ~(size_t)15, ps = (rmax + k) * (rmax + k);
+  const size_t ps = (rmax + k) * (rmax + k);
   OmcWS w;
-  memset(&w, 0, sizeof(w));
-  w.nB = w.B = w.Btot = B; w.n = (int)n; w.m = (int)m; w.k = (int)k; w.nnz = (int)nnz; w.Rmax = (int)Rmax; w.Lmax = (int)Lmax; w.rmax = (int)rmax;
-  w.np16 = (int)NP; w.max_sweeps = MAX_SWEEPS; w.mw_budget = MAX_SWEEPS; w.gamma = h->gamma; w.clip_hi = 1.0; w.inv_s2 = 1.0;
-  w.col_ptr = h->dcol_ptr.as<int>(); w.col_idx = h->dcol_idx.as<int>(); w.col_val = h->dcol_val.as<double>();
-  w.geo = omc_plan_geometry((int)n, (int)NP, (int)k, (int)rmax, (int)Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
-  // matrices (32-byte rows for the multi-workgroup kernels: every piece is a multiple of 4 doubles)
-  const size_t nn4 = (n * n + 3) & ~(size_t)3;
-  ENS(h->dbM, sB * (2 * NP * NP + nn4) * 8);
-  w.MbufC = h->dbM.as<double>(); w.VrowC = w.MbufC + sB * NP * NP; w.Mchk = w.VrowC + sB * NP * NP;
-  HIPCHK(hipMemsetAsync(h->dbM.p, 0, sB * 2 * NP * NP * 8, s));      // the zero padding of MbufC; VrowC: cold start, and 0 x garbage could be NaN
+  const EvalDims d = eval_view_dims(h, w, B, (int)k, pk);
+  EvalArrays a{};
+  ENS_CARVE(h->dbM, [&](Carve& c) { walk_dual_matrices(c, d, w); });
   if (w.geo.ws.slab_stride) { ENS(h->dbS, sB * w.geo.ws.slab_stride * 8); w.cone_scratch = h->dbS.as<double>(); }
   if (n > 144) { ENS(h->dbL, sB * m * n * 8); HIPCHK(hipMemsetAsync(h->dbL.p, 0, sB * m * n * 8, s)); w.lamDX = h->dbL.as<double>(); }
   // descriptors, multipliers, scratch and the per-node scalars
-  const size_t dcount = sB * (Rmax * k + Rmax + Lmax * n + n * rmax) + sB * (nnz + Rmax + ps + n * rmax) + sB * n * k + 5 * sB;
-  ENS(h->dbD, dcount * 8);
-  double* dp = h->dbD.as<double>();
-  w.rcoef = dp; dp += sB * Rmax * k; w.rrhs = dp; dp += sB * Rmax; w.cutx = dp; dp += sB * Lmax * n; w.Qb = dp; dp += sB * n * rmax;
-  double* dLam = dp; dp += sB * nnz; double* dlam = dp; dp += sB * Rmax; double* dPsi = dp; dp += sB * ps; double* dT1 = dp; dp += sB * n * rmax;
-  w.chk_scratch = dp; dp += sB * n * k;
-  w.c0 = dp; w.cpen = dp + sB; w.cst = dp + 2 * sB; w.fro2c = dp + 3 * sB; w.evsum = dp + 4 * sB;
-  ENS(h->dbI, sB * (2 + 4 * Rmax + 3 + 4) * sizeof(int));
-  int* ip = h->dbI.as<int>();
-  w.R = ip; ip += sB; w.rr = ip; ip += sB; w.rkind = ip; ip += sB * Rmax; w.rcut = ip; ip += sB * Rmax; w.rbi = ip; ip += sB * Rmax; w.rbj = ip; ip += sB * Rmax;
-  w.done = ip; w.vvalidC = ip + sB; w.sweeps = ip + 2 * sB; w.mw_stat = ip + 3 * sB;
-  HIPCHK(hipMemsetAsync(w.done, 0, sB * 7 * sizeof(int), s));
+  ENS_CARVE(h->dbD, [&](Carve& c) { walk_dual_doubles(c, d, w, a); });
+  ENS_CARVE(h->dbI, [&](Carve& c) { walk_dual_ints(c, d, w, a); });
+  { int rc = eval_view_zero(w, a, s); if (rc) return rc; }
   { int rc = put_descriptors(w, pk, B, sB, 0, L, cut_x, s); if (rc) return rc; }
-  HIPCHK(hipMemcpyAsync(dLam, Lam, sB * nnz * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(dlam, lam, sB * Rmax * 8, hipMemcpyHostToDevice, s));
-  if (Psi3) HIPCHK(hipMemcpyAsync(dPsi, Psi3, sB * ps * 8, hipMemcpyHostToDevice, s));
-  const OmcDualIn in = {dLam, dlam, Psi3 ? dPsi : nullptr, dT1};
+  HIPCHK(hipMemcpyAsync(a.Lam, Lam, sB * nnz * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(a.lam, lam, sB * Rmax * 8, hipMemcpyHostToDevice, s));
+  if (Psi3) HIPCHK(hipMemcpyAsync(a.Psi, Psi3, sB * ps * 8, hipMemcpyHostToDevice, s));
+  const OmcDualIn in = {a.Lam, a.lam, Psi3 ? a.Psi : nullptr, a.T1};
   omc_launch_dual_assemble(&w, &in, s);
-  if (w.geo.ws_lpp || w.geo.mw) { w.ws_mode = 1; omc_launch_cone_ws(&w, s); }
-  else omc_launch_cone(&w, CONE_EVALS, s);
-  HIPCHK(hipGetLastError());
-  std::vector<double> sc(5 * sB);
-  HIPCHK(hipMemcpyAsync(sc.data(), w.c0, 5 * sB * 8, hipMemcpyDeviceToHost, s));
+  std::vector<double> sc;
+  { int rc = eval_view_solve(w, a, nullptr, sc, s); if (rc) return rc; }
   HIPCHK(hipStreamSynchronize(s));
   HIPCHK(hipGetLastError());
-  for (size_t b = 0; b < sB; ++b) bound[b] = sc[b] + sc[4 * sB + b] - sc[sB + b] + sc[2 * sB + b];      // c0 + evsum - cpen + cst, the order of k_check_final
+  const size_t o_cpen = w.cpen - w.c0, o_cst = w.cst - w.c0, o_ev = w.evsum - w.c0;      // where the walk placed them behind c0
+  for (size_t b = 0; b < sB; ++b) bound[b] = sc[b] + sc[o_ev + b] - sc[o_cpen + b] + sc[o_cst + b];      // c0 + evsum - cpen + cst, the order of k_check_final
   return 0;
 }
 
@@ -1852,48 +1879,28 @@ int omc_shor_dual_bound_batch(omc_instance* h, int B, int cut_type, int referenc
   // ---- refusals, all on the host ------------------------------------------------------------------------------------------------------
   if (!h) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: handle is NULL");
   if (B <= 0) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: B must be positive");
-  if (cut_type != OMC_CUT_LINEAR && cut_type != OMC_CUT_LINEAR2 && cut_type != OMC_CUT_LINEAR3)
-    return fail(OMC_ERR_INVALID_ENUM, "Invalid input for disjunctive cuts type: must be linear, linear2 or linear3 (OMC.jl:1456-1462)");
+  { int rcc = check_cut_type(cut_type); if (rcc) return rcc; }
   if (!n_shor || !n_soc || !scale || !lam || !zeta || !xi || !Xbar || !bound)
     return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: n_shor, n_soc, scale, lam, zeta, xi, Xbar and bound are needed");
   if (h->worker.joinable() || h->worker_running.load()) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: a solve is in flight on this handle (call omc_relax_wait first)");
   if (h->k > 1) return fail(OMC_ERR_UNSUPPORTED, "omc_shor_dual_bound_batch: Shor-mode certificates exist for rank 1 only (quirk Q5 makes the minors vacuous for k > 1)");
   const size_t n = h->n, m = h->m, nm = n * m;
   if ((long long)n * (long long)m >= (1ll << 30)) return fail(OMC_ERR_UNSUPPORTED, "Shor mode: n * m too large for the 32-bit index structures");
-  std::vector<size_t> so, co;
-  { int rc0 = shor_list_offsets(B, n_shor, shor_idx, n_soc, soc_idx, so, co); if (rc0) return rc0; }
+  ShorGrouping grp;
+  { int rc0 = shor_list_offsets(B, n_shor, shor_idx, n_soc, soc_idx, grp.so, grp.co); if (rc0) return rc0; }
   int64_t nqall = 0;
   for (int b = 0; b < B; ++b) nqall = std::max(nqall, n_shor[b]);
   if (nq_stride < nqall) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: nq_stride is below the longest minor list");
   if (nqall > 0 && !Gam) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: Gam is NULL but n_shor > 0");
   const size_t nqs = (size_t)nq_stride;
   // identical (minor list, SOC list) pairs share one index structure
-  std::unordered_map<uint64_t, std::vector<int>> byhash;
-  std::vector<ShorListKey> lists;
-  std::vector<int> rep, node_group(B);
-  for (int b = 0; b < B; ++b) {
-    const int64_t* ib = shor_idx + 4 * so[b]; const int64_t* sb = soc_idx + 2 * co[b];
-    const uint64_t hv = shor_pair_hash(n_shor[b], ib, n_soc[b], sb);
-    int gid = find_shor_list(byhash, lists, hv, n_shor[b], ib, n_soc[b], sb);
-    if (gid < 0) { gid = (int)rep.size(); rep.push_back(b); add_shor_list(byhash, lists, hv, n_shor[b], ib, n_soc[b], sb); }
-    node_group[b] = gid;
-  }
-  const int NG = (int)rep.size();
-  std::vector<ShorGroupHost> gh(NG);
-  int nqmax = 0, nv1max = 0, nv2max = 0;
-  size_t tot_int = 0, tot_byte = 0;
-  for (int g = 0; g < NG; ++g) {
-    ShorGroupHost& G = gh[g];
-    const int b = rep[g];
-    { int rc0 = build_shor_group(h, n_shor[b], shor_idx + 4 * so[b], n_soc[b], soc_idx + 2 * co[b], G); if (rc0) return rc0; }
-    nqmax = std::max(nqmax, G.nq); nv1max = std::max(nv1max, G.nv1); nv2max = std::max(nv2max, G.nv2);
-    G.off_int = tot_int; tot_int += G.ints();
-    G.off_byte = tot_byte; tot_byte += G.bytes();
-  }
+  { int rc0 = group_shor_lists(h, B, n_shor, shor_idx, n_soc, soc_idx, nullptr, grp); if (rc0) return rc0; }
+  const std::vector<ShorGroupHost>& gh = grp.groups; const std::vector<int>& node_group = grp.node_group;
+  const int NG = (int)gh.size(), nqmax = grp.nqmax, nv1max = grp.nv1max, nv2max = grp.nv2max;
   omc_relax_params P = h->params; P.reference_quirk_q1 = reference_quirk_q1 ? 1 : 0;
   NodePack pk;
   { int rcp = pack_nodes(h, P, cut_type, B, L, cut_x, cut_Uhat, cut_dir, U_lower, U_upper, pk); if (rcp) return rcp; }
-  const size_t Rmax = pk.Rmax, rmax = pk.rmax, Lmax = std::max(pk.Lmax, 1), ps = (rmax + 1) * (rmax + 1);
+  const size_t Rmax = pk.Rmax, rmax = pk.rmax, ps = (rmax + 1) * (rmax + 1);
   // ---- host part: which nodes live, lam clamped, PSD part of Psi3, the three defects that need no block --------------------------------
   const double NINF = -INFINITY;
   std::vector<uint8_t> live(B, 1);
@@ -1966,70 +1973,38 @@ int omc_shor_dual_bound_batch(omc_instance* h, int B, int cut_type, int referenc
   // ---- device buffers of this call ---------------------------------------------------------------------------------------------------
   HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  const size_t NP = (n + 15) & ~(size_t)15, nn4 = (n * n + 3) & ~(size_t)3;
   const bool want_clean = nqmax > 0 && (sanitise || defects);
   const bool store_clean = nqmax > 0 && sanitise;
   OmcWS w;
-  memset(&w, 0, sizeof(w));
-  w.nB = w.B = w.Btot = V; w.n = (int)n; w.m = (int)m; w.k = 1; w.nnz = h->nnz; w.Rmax = (int)Rmax; w.Lmax = (int)Lmax; w.rmax = (int)rmax;
-  w.np16 = (int)NP; w.max_sweeps = MAX_SWEEPS; w.mw_budget = MAX_SWEEPS; w.gamma = h->gamma; w.clip_hi = 1.0; w.inv_s2 = 1.0;
-  w.col_ptr = h->dcol_ptr.as<int>(); w.col_idx = h->dcol_idx.as<int>(); w.col_val = h->dcol_val.as<double>();
-  w.geo = omc_plan_geometry((int)n, (int)NP, 1, (int)rmax, (int)Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
+  const EvalDims d = eval_view_dims(h, w, V, 1, pk);
   ShorCertWS c;
   memset(&c, 0, sizeof(c));
   c.n = (int)n; c.m = (int)m; c.B = B; c.V = V; c.nmb = (nqmax + SCERT_T - 1) / SCERT_T; c.nv1max = nv1max; c.nv2max = nv2max; c.clamp_zeta = sanitise ? 1 : 0;
   c.nqs = (long long)nqs; c.gamma = h->gamma;
-  const size_t nmb = (size_t)c.nmb, slab = w.geo.ws.slab_stride;
-  const size_t dcount = sB * (1 + 15 * nqs + m + 2 * nm) + sB * ((store_clean ? 15 * nqs : 0) + nmb) +
-                        sV * (nv1max + nv2max + 8 * nqs + 2 * nmb + nm + 2 * m) + sV * (2 * NP * NP + nn4 + slab) +
-                        sV * (2 * Rmax + Lmax * n + n * rmax) + sV * (Rmax + ps + n * rmax + n + 5) + 4;
-  const size_t icount = sB + 2 * sV + sV * m + sV * (2 + 4 * Rmax + 7);
+  const size_t nmb = (size_t)c.nmb;
+  const ScertDims sd = {sB, nqs, nmb, (size_t)nv1max, (size_t)nv2max, m, w.geo.ws.slab_stride, store_clean};
+  ScertArrays in{}; EvalArrays a{};
   {
-    int rca = h->sdD.ensure(dcount * 8);
-    if (!rca) rca = h->sdI.ensure(icount * sizeof(int));
-    if (!rca) rca = h->sdGi.ensure(std::max<size_t>(tot_int, 1) * sizeof(int));
-    if (!rca) rca = h->sdGb.ensure(std::max<size_t>(tot_byte, 16));
+    size_t dbytes = 0;
+    int rca = carve_ensure(h->sdD, [&](Carve& cv) { walk_scert_doubles(cv, sd, d, c, in, w, a); }, &dbytes);
+    if (!rca) rca = carve_ensure(h->sdI, [&](Carve& cv) { walk_scert_ints(cv, sd, d, c, in, w, a); });
+    if (!rca) rca = h->sdGi.ensure(grp.tot_int * sizeof(int));
+    if (!rca) rca = h->sdGb.ensure(grp.tot_byte);
     if (!rca) rca = h->sdGr.ensure(sizeof(ShorGroupDev) * (size_t)NG);
     if (rca) {
       (void)hipGetLastError();
-      return fail(OMC_ERR_ALLOC, "omc_shor_dual_bound_batch: the evaluation needs " + std::to_string(dcount * 8) + " bytes for " + std::to_string(V) +
+      return fail(OMC_ERR_ALLOC, "omc_shor_dual_bound_batch: the evaluation needs " + std::to_string(dbytes) + " bytes for " + std::to_string(V) +
                                  " views of " + std::to_string(B) + " nodes, which the device does not have (" + g_err + ")");
     }
   }
-  double* dp = h->sdD.as<double>();
-  double* dscale = dp; dp += sB; double* dGam = dp; dp += sB * 15 * nqs; double* dzeta = dp; dp += sB * m; double* dxi = dp; dp += sB * nm; double* dXbar = dp; dp += sB * nm;
-  c.scale = dscale; c.Gam = dGam; c.zeta = dzeta; c.xi = dxi; c.Xbar = dXbar;
-  if (store_clean) { c.GamC = dp; dp += sB * 15 * nqs; }
-  c.cleanpart = dp; dp += sB * nmb;
-  c.e1 = dp; dp += sV * nv1max; c.e2 = dp; dp += sV * nv2max; c.row8 = dp; dp += sV * 8 * nqs; c.minpart = dp; dp += sV * nmb * 2;
-  c.lamDX = dp; dp += sV * nm; c.c0col = dp; dp += sV * m; c.colmu = dp; dp += sV * m;
-  dp = h->sdD.as<double>() + (((size_t)(dp - h->sdD.as<double>()) + 3) & ~(size_t)3);      // 32-byte rows for the multi-workgroup kernels
-  w.MbufC = dp; dp += sV * NP * NP; w.VrowC = dp; dp += sV * NP * NP; w.Mchk = dp; dp += sV * nn4;
-  if (slab) { w.cone_scratch = dp; dp += sV * slab; }
-  w.rcoef = dp; dp += sV * Rmax; w.rrhs = dp; dp += sV * Rmax; w.cutx = dp; dp += sV * Lmax * n; w.Qb = dp; dp += sV * n * rmax;
-  double* dlam = dp; dp += sV * Rmax; double* dPsi = dp; dp += sV * ps; double* dT1 = dp; dp += sV * n * rmax;
-  w.chk_scratch = dp; dp += sV * n;
-  w.c0 = dp; w.cpen = dp + sV; w.cst = dp + 2 * sV; w.fro2c = dp + 3 * sV; w.evsum = dp + 4 * sV; dp += 5 * sV;
-  w.lamDX = c.lamDX;
-  int* ip = h->sdI.as<int>();
-  int* dng = ip; ip += sB; int* dvn = ip; ip += sV; int* dvw = ip; ip += sV; c.colbad = ip; ip += sV * m;
-  c.node_group = dng; c.view_node = dvn; c.view_way = dvw;
-  w.R = ip; ip += sV; w.rr = ip; ip += sV; w.rkind = ip; ip += sV * Rmax; w.rcut = ip; ip += sV * Rmax; w.rbi = ip; ip += sV * Rmax; w.rbj = ip; ip += sV * Rmax;
-  w.done = ip; w.vvalidC = ip + sV; w.sweeps = ip + 2 * sV; w.mw_stat = ip + 3 * sV;
-  HIPCHK(hipMemsetAsync(w.done, 0, sV * 7 * sizeof(int), s));
-  HIPCHK(hipMemsetAsync(w.MbufC, 0, sV * 2 * NP * NP * 8, s));      // zero padding of MbufC; VrowC: cold start
+  { int rc = eval_view_zero(w, a, s); if (rc) return rc; }
   // index structures
   {
-    std::vector<int> hi(std::max<size_t>(tot_int, 1)); std::vector<uint8_t> hb(std::max<size_t>(tot_byte, 16), 0);
-    std::vector<ShorGroupDev> gd(NG);
-    for (int g = 0; g < NG; ++g) pack_shor_group(gh[g], hi.data(), hb.data(), h->sdGi.as<int>(), h->sdGb.as<uint8_t>(), gd[g]);
-    HIPCHK(hipMemcpyAsync(h->sdGi.p, hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->sdGb.p, hb.data(), hb.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->sdGr.p, gd.data(), sizeof(ShorGroupDev) * NG, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dng, node_group.data(), sizeof(int) * sB, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dvn, view_node.data(), sizeof(int) * sV, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dvw, view_way.data(), sizeof(int) * sV, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));          // the host vectors die with this block
+    ShorGroupImages img;
+    { int rc = upload_shor_groups(grp, h->sdGi.as<int>(), h->sdGb.as<uint8_t>(), h->sdGr.as<ShorGroupDev>(), in.node_group, s, img); if (rc) return rc; }
+    HIPCHK(hipMemcpyAsync(in.view_node, view_node.data(), sizeof(int) * sV, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(in.view_way, view_way.data(), sizeof(int) * sV, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));          // the host images die with this block
   }
   c.groups = (const ShorGroupDev*)h->sdGr.p; c.A = h->dA.as<double>(); c.mask = h->dmask.as<uint8_t>();
   { int rc = put_descriptors(w, pv, V, sV, 0, Lv.data(), cxv.empty() ? nullptr : cxv.data(), s); if (rc) return rc; }
@@ -2040,13 +2015,13 @@ int omc_shor_dual_bound_batch(omc_instance* h, int B, int cut_type, int referenc
     std::copy(hlam.begin() + b * Rmax, hlam.begin() + (b + 1) * Rmax, vlam.begin() + (size_t)v * Rmax);
     if (Psi3) std::copy(hPsi.begin() + b * ps, hPsi.begin() + (b + 1) * ps, vPsi.begin() + (size_t)v * ps);
   }
-  HIPCHK(hipMemcpyAsync(dscale, scale, sB * 8, hipMemcpyHostToDevice, s));
-  if (nqmax > 0) HIPCHK(hipMemcpyAsync(dGam, Gam, sB * 15 * nqs * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(dzeta, zeta, sB * m * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(dxi, xi, sB * nm * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(dXbar, Xbar, sB * nm * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(dlam, vlam.data(), sV * Rmax * 8, hipMemcpyHostToDevice, s));
-  if (Psi3) HIPCHK(hipMemcpyAsync(dPsi, vPsi.data(), sV * ps * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(in.scale, scale, sB * 8, hipMemcpyHostToDevice, s));
+  if (nqmax > 0) HIPCHK(hipMemcpyAsync(in.Gam, Gam, sB * 15 * nqs * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(in.zeta, zeta, sB * m * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(in.xi, xi, sB * nm * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(in.Xbar, Xbar, sB * nm * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(a.lam, vlam.data(), sV * Rmax * 8, hipMemcpyHostToDevice, s));
+  if (Psi3) HIPCHK(hipMemcpyAsync(a.Psi, vPsi.data(), sV * ps * 8, hipMemcpyHostToDevice, s));
   // ---- kernels ------------------------------------------------------------------------------------------------------------------------
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1));
@@ -2054,15 +2029,11 @@ int omc_shor_dual_bound_batch(omc_instance* h, int B, int cut_type, int referenc
   if (want_clean) omc_scert_launch_clean(&c, store_clean ? 1 : 0, s);
   if (nqmax > 0) { omc_scert_launch_keys(&c, s); omc_scert_launch_minor(&c, s); }
   omc_scert_launch_cols(&c, s);
-  const OmcDualIn in = {nullptr, dlam, Psi3 ? dPsi : nullptr, dT1, c.c0col, c.colbad};
-  omc_launch_dual_assemble(&w, &in, s);
-  if (w.geo.ws_lpp || w.geo.mw) { w.ws_mode = 1; omc_launch_cone_ws(&w, s); }
-  else omc_launch_cone(&w, CONE_EVALS, s);
-  HIPCHK(hipEventRecord(ev1, s));
-  HIPCHK(hipGetLastError());
-  std::vector<double> scl(5 * sV), cmu(sV * m), mpart(sV * nmb * 2 + 1), cpart(sB * nmb + 1);
+  const OmcDualIn din = {nullptr, a.lam, Psi3 ? a.Psi : nullptr, a.T1, c.c0col, c.colbad};
+  omc_launch_dual_assemble(&w, &din, s);
+  std::vector<double> scl, cmu(sV * m), mpart(sV * nmb * 2 + 1), cpart(sB * nmb + 1);
   std::vector<int> cbad(sV * m);
-  HIPCHK(hipMemcpyAsync(scl.data(), w.c0, 5 * sV * 8, hipMemcpyDeviceToHost, s));
+  { int rc = eval_view_solve(w, a, ev1, scl, s); if (rc) return rc; }
   HIPCHK(hipMemcpyAsync(cmu.data(), c.colmu, sV * m * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(cbad.data(), c.colbad, sV * m * sizeof(int), hipMemcpyDeviceToHost, s));
   if (nmb && defects) {
@@ -2074,9 +2045,10 @@ int omc_shor_dual_bound_batch(omc_instance* h, int B, int cut_type, int referenc
   { float msf = 0.f; HIPCHK(hipEventElapsedTime(&msf, ev0, ev1)); h->sdb_ms = msf; }
   (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
   // ---- the host's part of the result: -inf rules, the larger of the two ways, back to the node's scale ---------------------------------
+  const size_t o_cpen = w.cpen - w.c0, o_cst = w.cst - w.c0, o_ev = w.evsum - w.c0;      // where the walk placed them behind c0
   for (int v = 0; v < V; ++v) {
     const size_t b = view_node[v];
-    double val = (scl[v] + scl[2 * sV + v]) + scl[4 * sV + v] - scl[sV + v];      // (c0 + cst) + evsum - cpen
+    double val = (scl[v] + scl[o_cst + v]) + scl[o_ev + v] - scl[o_cpen + v];      // (c0 + cst) + evsum - cpen
     double mumin = INFINITY;
     for (size_t j = 0; j < m; ++j) {
       if (cbad[(size_t)v * m + j]) val = NINF;
@@ -2087,7 +2059,7 @@ int omc_shor_dual_bound_batch(omc_instance* h, int B, int cut_type, int referenc
     const bool first = view_way[v] == 0;
     if (first || out > bound[b] || (out == bound[b] && view_way[v] == 1)) {
       bound[b] = out;
-      if (terms) { double* t = terms + 4 * b; t[0] = scl[v] + scl[2 * sV + v]; t[1] = scl[4 * sV + v]; t[2] = scl[sV + v]; t[3] = mumin; }
+      if (terms) { double* t = terms + 4 * b; t[0] = scl[v] + scl[o_cst + v]; t[1] = scl[o_ev + v]; t[2] = scl[o_cpen + v]; t[3] = mumin; }
     }
     if (defects && first && n_shor[b] > 0) {
       const size_t nblk = ((size_t)n_shor[b] + SCERT_T - 1) / SCERT_T;
@@ -2210,12 +2182,12 @@ int omc_psd_project_batch(omc_instance* h, int B, int N, const double* M, double
   const bool cold = !w.geo.mw && !w.geo.ws_lpp;      // no k_cone_ws at this order (129 .. 144, above 1024): the cold kernel k_cone, as in a relaxation
   if (cold && (evals || V)) return fail(OMC_ERR_UNSUPPORTED, "omc_psd_project_batch: the cold single-workgroup kernel (orders 129 - 144 and above 1024) returns P only");
   ENS(h->pjM, sB * NP * NP * 8); ENS(h->pjV, sB * NP * NP * 8); ENS(h->pjW, sB * N * N * 8);
-  ENS(h->pjD, sB * (1 + NP) * 8); ENS(h->pjI, sB * 7 * sizeof(int));
+  int* ints_end = nullptr;
+  ENS_CARVE(h->pjD, [&](Carve& c) { walk_project_doubles(c, sB, NP, w); });
+  ENS_CARVE(h->pjI, [&](Carve& c) { walk_project_ints(c, sB, w, ints_end); });
   if (w.geo.ws.slab_stride) { ENS(h->pjS, sB * w.geo.ws.slab_stride * 8); w.cone_scratch = h->pjS.as<double>(); }
   w.Mbuf = h->pjM.as<double>(); w.Vrow = h->pjV.as<double>(); w.W1 = h->pjW.as<double>();
-  w.fro2 = h->pjD.as<double>(); w.ev_out = h->pjD.as<double>() + sB;
-  int* ip = h->pjI.as<int>();
-  w.done = ip; w.vvalid = ip + sB; w.sweeps = ip + 2 * sB; w.mw_stat = ip + 3 * sB;
+  int* ip = w.done;      // done, vvalid, sweeps, mw_stat: one host image goes up and comes back, indexed as the walk placed the arrays
   // symmetrised, zero-padded input, its squared Frobenius norm, the starting basis as the row-major Vrow
   std::vector<double> hM(sB * NP * NP, 0.0), hV(V0 ? sB * NP * NP : 0, 0.0), hf(sB, 0.0);
   for (size_t b = 0; b < sB; ++b) {
@@ -2228,8 +2200,8 @@ int omc_psd_project_batch(omc_instance* h, int B, int N, const double* M, double
       for (int t = 0; t < N; ++t)
         for (int kk = 0; kk < N; ++kk) hV[b * NP * NP + (size_t)kk * NP + t] = V0[b * N * N + (size_t)t * N + kk];
   }
-  std::vector<int> hi_(sB * 7, 0);
-  if (V0) for (size_t b = 0; b < sB; ++b) hi_[sB + b] = 1;
+  std::vector<int> hi_((size_t)(ints_end - ip), 0);
+  if (V0) for (size_t b = 0; b < sB; ++b) hi_[(w.vvalid - ip) + b] = 1;
   HIPCHK(hipMemcpyAsync(w.Mbuf, hM.data(), hM.size() * 8, hipMemcpyHostToDevice, s));
   if (V0) HIPCHK(hipMemcpyAsync(w.Vrow, hV.data(), hV.size() * 8, hipMemcpyHostToDevice, s));
   else HIPCHK(hipMemsetAsync(w.Vrow, 0, sB * NP * NP * 8, s));
@@ -2254,8 +2226,8 @@ int omc_psd_project_batch(omc_instance* h, int B, int N, const double* M, double
   // sweep statistics of this call (omc_last_cone_multi_stats): calls, most sweeps of a matrix, exhausted budgets, the same maximum
   h->mw_tot[0] = B; h->mw_tot[1] = 0; h->mw_tot[2] = 0;
   for (size_t b = 0; b < sB; ++b) {
-    h->mw_tot[1] = std::max<long long>(h->mw_tot[1], hi_[2 * sB + b]);
-    if (w.geo.mw) h->mw_tot[2] += hi_[3 * sB + 4 * b + 2];
+    h->mw_tot[1] = std::max<long long>(h->mw_tot[1], hi_[(w.sweeps - ip) + b]);
+    if (w.geo.mw) h->mw_tot[2] += hi_[(w.mw_stat - ip) + 4 * b + 2];
   }
   h->mw_tot[3] = h->mw_tot[1];
   { float msv = 0.f; HIPCHK(hipEventElapsedTime(&msv, e0, e1)); h->mw_tot[4] = (long long)(1000.0 * msv); }
@@ -2297,9 +2269,10 @@ int omc_column_prox_batch(omc_instance* h, int B, int mode, int algo, const doub
   std::vector<int> Lz(B, 0);
   const omc_relax_params keep = h->params;
   omc_relax_params P = keep; P.slots = B; P.accel = 0;      // identity slot map; without acceleration the workspace has Yx
-  h->cp_force = algo;
-  int rc = omc_relax_stage(h, B, &P, OMC_CUT_LINEAR, Lz.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
-  h->cp_force = 0; h->params = keep;
+  StageMode stage_mode;
+  stage_mode.colprox_force = algo;
+  int rc = stage_base(h, B, &P, OMC_CUT_LINEAR, Lz.data(), nullptr, nullptr, nullptr, nullptr, nullptr, stage_mode);
+  h->params = keep;
   if (rc) return rc;
   h->staged = false;
   OmcWS w = h->ws;
@@ -2367,9 +2340,6 @@ int omc_altmin_batch(omc_instance* h, int B, int cut_type, int reference_quirk_q
     h->amobj_B = 0;
     return 0;
   }
-  if (B <= 0 || max_iters <= 0) return fail(OMC_ERR_ARGUMENT, "B and max_iters must be positive");
-  if (cut_type != OMC_CUT_LINEAR && cut_type != OMC_CUT_LINEAR2 && cut_type != OMC_CUT_LINEAR3)
-    return fail(OMC_ERR_INVALID_ENUM, "Invalid input for disjunctive cuts type (OMC.jl:1456-1462)");
   if (h->k > ALTMIN_KMAX) return fail(OMC_ERR_UNSUPPORTED, "omc_altmin_batch: rank k > 8 is not supported");
   HIPCHK(hipSetDevice(h->device));
   const int n = h->n, m = h->m, k = h->k;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "omc.h"
+#include "omc_carve.h"
 #include "omc_device.h"
 #include "omc_shor_relax.h"
 
@@ -44,6 +45,21 @@ struct DevBuf {
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
   template <class T> T* as() { return (T*)p; }
 };
+#define ENS(buf, bytes) do { int r_ = (buf).ensure(bytes); if (r_) return r_; } while (0)
+
+// A packed buffer from one definition: `walk` (a callable over a Carve, omc_walks.h) is run once over a null base for the size, the buffer
+// is made at least that large, and the same walk over the allocation hands out the pointers.  Returns ensure's code; *bytes: the walk's total.
+template <class F> static inline int carve_ensure(DevBuf& b, F&& walk, size_t* bytes = nullptr) {
+  Carve measure;
+  walk(measure);
+  if (bytes) *bytes = measure.bytes();
+  const int rc = b.ensure(measure.bytes());
+  if (rc) return rc;
+  Carve place(b.p);
+  walk(place);
+  return 0;
+}
+#define ENS_CARVE(buf, ...) do { int r_ = carve_ensure(buf, __VA_ARGS__); if (r_) return r_; } while (0)
 
 // page-locked host memory: copies from and to it are asynchronous, so the host may go on while one is in flight
 struct PinBuf {
@@ -148,7 +164,6 @@ struct omc_instance {
   DevBuf dblock, dslab, disblock, bcpb, bnfact;
   int nblock = 0, nslab = 0, nrest = 0, cpb_cl = 0, cpb_cs = 0, crest_max = 0;
   bool lists_valid = false; int lists_block_min = 0; bool lists_pair = true;
-  int cp_force = 0;   // set by omc_column_prox_batch for the omc_relax_stage call it makes: 1 = no block kernel, 2 = the block kernel for every non-empty column
   // batch workspace
   DevBuf bYx, bY, bYp, bU, bD1, bD3, bW1, bE3, bQb, brr, bsm, bdS, balpha, balphaX, bsval, bMchk, bsmall, bchk;
   DevBuf bR, brkind, brcut, brbi, brbj, brcoef, brrhs, bcutx, bG, blam;
@@ -189,7 +204,7 @@ struct omc_instance {
   int64_t shor_sel[4] = {0, 0, 0, 0};      // omc_shor_last_select_stats: streamed, tiles, compactions, peak key / survivor bytes
   // Shor-mode relaxation (omc_relax_stage_shor): index structures of the distinct lists, explicit X / W / Theta state, view of the workspace
   // through which the base eigen-kernels project the order-(n+m) cone
-  bool shor_req = false, shor_on = false, shor_keep_V = false, shor_via_base = false; std::vector<int> shor_slackrow; DevBuf soV; double shor_rho = 0.05, shor_r4 = 0.0, shor_r5 = 2.0;      // r4 = 0: automatic per list
+  bool shor_on = false, shor_keep_V = false, shor_via_base = false; std::vector<int> shor_slackrow; DevBuf soV; double shor_rho = 0.05, shor_r4 = 0.0, shor_r5 = 2.0;      // r4 = 0: automatic per list
   ShWS sh{}; OmcWS wbig{};
   DevBuf sgInts, sgBytes, sgGroups, sgNodeGroup, sAh, sX, sW, sTh, sV1, sV2, sV3, sD0, sP0, sMbufB, sVrowB, sTq, sPq, sNq, sD5x, sD5t, snu5, sP5x,
       scolpart, sminpart, sminpart2, sfroB, svvB, se1, se2, soX, soW, soTh, sbigscr, sXsB, ssubSB, ssubIB;
@@ -209,7 +224,6 @@ struct omc_instance {
   bool pool_shor = false; int64_t pool_nqmax = 0; DevBuf pShor, pShorHdr, sloadpart;
   std::vector<PoolSig> pool_sig, node_sig; std::mutex sig_mu;
   std::vector<int> save_host;      // per node of the staged batch: the entry its final state goes to (-1: none), as the device sees it
-  bool shor_warm = false;          // set by omc_relax_stage_shor for the omc_relax_stage call it makes: the indices have passed its filter
   int64_t shor_warm_stats[4] = {0, 0, 0, 0};      // omc_last_shor_warm_stats
   // kernel stats
   int64_t launches[OMC_KERNEL_NCLASS] = {0}; double ms[OMC_KERNEL_NCLASS] = {0}; int64_t units[OMC_KERNEL_NCLASS] = {0};
