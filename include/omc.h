@@ -498,6 +498,21 @@ int omc_colprox_plan(int n, int cmax, int block_min, int64_t* out);
  * budget without meeting the stop rule, most sweeps of one call overall, device microseconds of the last omc_psd_project_batch
  * (the kernels alone, transfers outside; 0 after a solve) */
 int omc_last_cone_multi_stats(omc_instance* h, int64_t* out);
+/* Separation, rounding and the left singular vectors (omc_separation_batch, omc_round_Y_batch, omc_left_singular_batch, and the separation
+ * launch of every harvest of omc_relax_solve) on the multi-workgroup eigen-kernels: the plan at order n under OMC_PLAIN_MULTI_MIN =
+ * plain_multi_min, from the layout the kernels use (host only, no device call, no handle).  out[6] = 1 if the order takes the path
+ * (n >= max(145, plain_multi_min) and n <= 4096), rows padded to 16 (NP), columns padded to whole pairs of 16-column blocks (Ncp), blocks nb =
+ * Ncp / 16, bytes of the per-slot slab, launches per call (30 (nb - 1) + 4).  The five numbers describe the layout at order n whether or not
+ * the order takes the path. */
+int omc_plain_multi_plan(int n, int plain_multi_min, int64_t* out);
+/* Rotation threshold and stop rule of that path, on the relative cross product of two columns: a pair above it is rotated, a sweep that met
+ * nothing above it is the last.  The cold kernel's threshold (1e-14). */
+double omc_plain_multi_tau(void);
+/* out[4] of that path: calls (matrices decomposed), most sweeps of one call, calls that used up the 30 sweeps without meeting the stop rule,
+ * device microseconds of the eigen-kernel launches -- of the last omc_separation_batch, omc_round_Y_batch or omc_left_singular_batch (all
+ * zero where the cold kernel ran), or of the harvests of the last omc_relax_solve (microseconds 0).  Counters of their own:
+ * omc_last_cone_multi_stats keeps counting clip and certificate calls only. */
+int omc_last_plain_multi_stats(omc_instance* h, int64_t* out);
 /* The sweep budget omc_relax_solve gives the next multi-workgroup calls of a cone at a certificate check.  interval_max: most sweeps of
  * one call since the last check, 0 when that interval had no call.  What the last interval needed + 2, at most the full bound (30); the
  * full bound after an interval without a call (the next call starts from a stale basis). */

@@ -141,6 +141,19 @@ def colprox_plan(n, cmax, block_min=65):
     return dict(lds_cmax=int(out[0]), lds_bytes=int(out[1]), slab_doubles=int(out[2]), workgroups_per_cu=int(out[3]), block=bool(out[4]))
 
 
+def plain_multi_plan(n, plain_multi_min=1025):
+    """omc_plain_multi_plan (host only, no GPU): whether separation, rounding and the left singular vectors at order n take the
+    multi-workgroup eigen-kernels under OMC_PLAIN_MULTI_MIN = plain_multi_min, and their layout there."""
+    out = np.zeros(6, np.int64)
+    _lib.check(_lib.load().omc_plain_multi_plan(int(n), int(plain_multi_min), _lib.ptr(out)))
+    return dict(multi=bool(out[0]), NP=int(out[1]), Ncp=int(out[2]), nb=int(out[3]), slab_bytes=int(out[4]), launches=int(out[5]))
+
+
+def plain_multi_tau():
+    """omc_plain_multi_tau: rotation threshold and stop rule of that path."""
+    return float(_lib.load().omc_plain_multi_tau())
+
+
 def certificate_plan(n, k, nnz, max_cuts=0, nonstandard_box_rows=0):
     """omc_certificate_plan (host only, no GPU): strides of a certificate in doubles, bytes the arena holds per node, rmax."""
     out = np.zeros(6, np.int64)
@@ -857,6 +870,15 @@ class Engine:
         out = np.zeros(5, np.int64)
         _lib.check(self._lib.omc_last_cone_multi_stats(self._h, _lib.ptr(out)))
         return dict(calls=int(out[0]), last_sweeps=int(out[1]), exhausted=int(out[2]), max_sweeps=int(out[3]), device_us=int(out[4]))
+
+    def plain_multi_stats(self):
+        """The multi-workgroup eigen-kernels under breakpoint_vectors, round_Y and left_singular in the last such call, or under the
+        harvests of the last solve (omc_last_plain_multi_stats); counters apart from cone_multi_stats()."""
+        if not hasattr(self._lib, "omc_last_plain_multi_stats"):
+            raise _lib.OmcError(-4, "this build of the library has no omc_last_plain_multi_stats")
+        out = np.zeros(4, np.int64)
+        _lib.check(self._lib.omc_last_plain_multi_stats(self._h, _lib.ptr(out)))
+        return dict(calls=int(out[0]), max_sweeps=int(out[1]), exhausted=int(out[2]), device_us=int(out[3]))
 
     def alternating_minimization(self, U_initials, nodes=None, disjunctive_cuts_type="linear", eps=1e-5, max_iters=100,
                                  time_limit=3600.0, reference_quirk_q1=True):

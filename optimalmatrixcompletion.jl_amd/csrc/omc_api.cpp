@@ -644,9 +644,11 @@ static int stage_base(omc_instance* h, int B, const omc_relax_params* params, in
   w.rbi = h->brbi.as<int>(); w.rbj = h->brbj.as<int>(); w.rcoef = h->brcoef.as<double>(); w.rrhs = h->brrhs.as<double>(); w.cutx = h->bcutx.as<double>();
   if ((rc_ = put_descriptors(w, pk, B, sN, 0, L, cut_x, h->stream))) return rc_;
   // LDS / scratch decisions: one planner (omc_layout.h), the slabs allocated from the strides it reports
-  w.geo = omc_plan_geometry(n, w.np16, k, rmax, Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
+  w.geo = omc_plan_geometry(n, w.np16, k, rmax, Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min, h->tun.plain_multi_min);
   ENS(h->bmwstat, sB * 4 * sizeof(int)); HIPCHK(hipMemsetAsync(h->bmwstat.p, 0, sB * 4 * sizeof(int), h->stream));
   w.mw_stat = h->bmwstat.as<int>(); w.mw_budget = MAX_SWEEPS; w.ev_out = nullptr;
+  w.pmw_stat = nullptr;
+  if (w.geo.plain_mw) { ENS(h->bpmwstat, sB * 4 * sizeof(int)); HIPCHK(hipMemsetAsync(h->bpmwstat.p, 0, sB * 4 * sizeof(int), h->stream)); w.pmw_stat = h->bpmwstat.as<int>(); }
   // k_colprox_block: the dynamic LDS of its launches and the slab of the columns beyond the LDS, for those columns only.  The slab of
   // colprox_body (one block per slot and column) is sized by the longest column that still runs it
   geom_set_cpblock(w.geo, h->cpb_cl, h->cpb_cs);
@@ -1387,7 +1389,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   wb.n = N; wb.np16 = NPb; wb.Mbuf = sh.MbufB; wb.Vrow = sh.VrowB; wb.vvalid = sh.vvalidB; wb.fro2 = sh.fro2B; wb.W1 = sh.P0;
   wb.sub_enable = 0; wb.cert_enable = 0; wb.ws_mode = 0; wb.clip_hi = 1e300; wb.sub_debug = 0; wb.ws_first = nullptr; wb.ws_need = nullptr; wb.ws_phase = 0;
   // the view's own geometry (only the eigen-kernels are launched through it)
-  wb.geo = omc_plan_geometry(N, NPb, wb.k, wb.rmax, wb.Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
+  wb.geo = omc_plan_geometry(N, NPb, wb.k, wb.rmax, wb.Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min, MW_MAX_ORDER + 1);
   ENS(h->sbigmw, sB * 4 * sizeof(int)); HIPCHK(hipMemsetAsync(h->sbigmw.p, 0, sB * 4 * sizeof(int), s));
   wb.mw_stat = h->sbigmw.as<int>();
   if (wb.geo.ws.slab_stride) { ENS(h->sbigscr, sB * wb.geo.ws.slab_stride * 8); wb.cone_scratch = h->sbigscr.as<double>(); }
@@ -1729,7 +1731,7 @@ static EvalDims eval_view_dims(omc_instance* h, OmcWS& w, int V, int k, const No
   w.nB = w.B = w.Btot = V; w.n = h->n; w.m = h->m; w.k = k; w.nnz = h->nnz; w.Rmax = (int)d.Rmax; w.Lmax = (int)d.Lmax; w.rmax = (int)d.rmax;
   w.np16 = (h->n + 15) & ~15; w.max_sweeps = MAX_SWEEPS; w.mw_budget = MAX_SWEEPS; w.gamma = h->gamma; w.clip_hi = 1.0; w.inv_s2 = 1.0;
   w.col_ptr = h->dcol_ptr.as<int>(); w.col_idx = h->dcol_idx.as<int>(); w.col_val = h->dcol_val.as<double>();
-  w.geo = omc_plan_geometry(w.n, w.np16, k, w.rmax, w.Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min);
+  w.geo = omc_plan_geometry(w.n, w.np16, k, w.rmax, w.Rmax, h->cmax, h->tun.global_nolds, h->tun.cone_multi_min, MW_MAX_ORDER + 1);
   return d;
 }
 // the flags and statistics the eigen-kernel reads, and the matrices: the zero padding of MbufC; VrowC: cold start, and 0 x garbage could be NaN.
@@ -1857,7 +1859,7 @@ int omc_shor_dual_bound_plan(int n, int m, int k, int B, int64_t nq_stride, int 
   if (nq_stride >= (1ll << 28) || (long long)n * m >= (1ll << 30)) return fail(OMC_ERR_UNSUPPORTED, "omc_shor_dual_bound_plan: beyond the size limits of omc_relax_stage_shor");
   const int Rmax = 2 + nonstandard_box_rows + 3 * max_cuts, rmax = std::max(1, std::min(n, 1 + nonstandard_box_rows + max_cuts));
   const Tuning tun;
-  const OmcGeom geo = omc_plan_geometry(n, (n + 15) & ~15, 1, rmax, Rmax, n, 0, tun.cone_multi_min);
+  const OmcGeom geo = omc_plan_geometry(n, (n + 15) & ~15, 1, rmax, Rmax, n, 0, tun.cone_multi_min, MW_MAX_ORDER + 1);
   const ScertBytes sb = scert_bytes(n, m, (size_t)nq_stride, Rmax, rmax, std::max(max_cuts, 1), geo.ws.slab_stride, sanitise != 0);
   const int ways = sanitise ? 2 : 1;
   out[0] = (int64_t)(sb.node + ways * sb.view); out[1] = out[0] * B; out[2] = (int64_t)sb.node; out[3] = (int64_t)sb.view; out[4] = ways;
@@ -2086,6 +2088,35 @@ int omc_evaluate_objective(omc_instance* h, int B, const double* X, double* obje
   return 0;
 }
 
+// The eigen-kernel of the three plain entry points below.  Where it is the multi-workgroup sequence (geo.plain_mw, omc_launch_cone_plain_mw) two
+// events take its device time and, once the caller has synchronised the stream, collect() reads the slots' counters: omc_last_plain_multi_stats
+// then speaks of this call alone (all zero where the cold kernel ran).
+static_assert(MW_PLAIN_SWEEPS == MAX_SWEEPS, "the plain sequence enqueues the cold kernel's sweep limit");
+struct PlainCall {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~PlainCall() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+  int launch(omc_instance* h, const OmcWS& w, int mode) {
+    if (w.geo.plain_mw) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, h->stream)); }
+    omc_launch_cone(&w, mode, h->stream);
+    if (w.geo.plain_mw) HIPCHK(hipEventRecord(e1, h->stream));
+    return 0;
+  }
+  int collect(omc_instance* h, const OmcWS& w, int B) {
+    for (int q = 0; q < 4; ++q) h->pmw_tot[q] = 0;
+    if (!w.geo.plain_mw) return 0;
+    std::vector<int> st(4 * (size_t)B);
+    HIPCHK(hipMemcpyAsync(st.data(), w.pmw_stat, sizeof(int) * st.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int b = 0; b < B; ++b) {
+      h->pmw_tot[0] += st[4 * b]; h->pmw_tot[2] += st[4 * b + 2];
+      h->pmw_tot[1] = std::max<long long>(h->pmw_tot[1], st[4 * b + 3]);
+    }
+    float msv = 0.f; HIPCHK(hipEventElapsedTime(&msv, e0, e1));
+    h->pmw_tot[3] = (long long)(1000.0 * msv);
+    return 0;
+  }
+};
+
 int omc_separation_batch(omc_instance* h, int B, int breakpoints, const double* Y, const double* U, double* eigvals,
                          double* x, int* feasible) {
   if (!h || !Y || !U) return fail(OMC_ERR_ARGUMENT, "NULL argument");
@@ -2101,12 +2132,14 @@ int omc_separation_batch(omc_instance* h, int B, int breakpoints, const double* 
   const size_t n = h->n, k = h->k;
   HIPCHK(hipMemcpyAsync(w.Y, Y, 8 * (size_t)B * n * n, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(w.U, U, 8 * (size_t)B * n * k, hipMemcpyHostToDevice, h->stream));
-  omc_launch_cone(&w, CONE_SEP, h->stream);
+  PlainCall pc;
+  if ((rc = pc.launch(h, w, CONE_SEP))) return rc;
   std::vector<double> ev(2 * (size_t)B);
   HIPCHK(hipMemcpyAsync(ev.data(), w.lmin, 16 * (size_t)B, hipMemcpyDeviceToHost, h->stream));
   if (x) HIPCHK(hipMemcpyAsync(x, w.bx, 8 * (size_t)B * n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
+  if ((rc = pc.collect(h, w, B))) return rc;
   for (int b = 0; b < B; ++b) {
     if (eigvals) { eigvals[2 * b] = ev[2 * b]; eigvals[2 * b + 1] = ev[2 * b + 1]; }
     if (feasible) feasible[b] = ev[2 * b] >= -1e-6 ? 1 : 0;   // OMC.jl:1274-1276 projection_tolerance
@@ -2125,10 +2158,12 @@ int omc_round_Y_batch(omc_instance* h, int B, const double* Y, double* U_rounded
   const OmcWS& w = h->ws;
   const size_t n = h->n, k = h->k;
   HIPCHK(hipMemcpyAsync(w.Y, Y, 8 * (size_t)B * n * n, hipMemcpyHostToDevice, h->stream));
-  omc_launch_cone(&w, CONE_TOPK, h->stream);
+  PlainCall pc;
+  if ((rc = pc.launch(h, w, CONE_TOPK))) return rc;
   HIPCHK(hipMemcpyAsync(U_rounded, w.U, 8 * (size_t)B * n * k, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
+  if ((rc = pc.collect(h, w, B))) return rc;
   h->staged = false;
   return 0;
 }
@@ -2148,10 +2183,12 @@ int omc_left_singular_batch(omc_instance* h, int B, const double* X, double* U_o
   ENS(h->bXin, (size_t)B * n * m * 8);
   HIPCHK(hipMemcpyAsync(h->bXin.p, X, 8 * (size_t)B * n * m, hipMemcpyHostToDevice, h->stream));
   omc_launch_gram_XXt(&w, h->bXin.as<double>(), B, h->stream);
-  omc_launch_cone(&w, CONE_TOPK, h->stream);
+  PlainCall pc;
+  if ((rc = pc.launch(h, w, CONE_TOPK))) return rc;
   HIPCHK(hipMemcpyAsync(U_out, w.U, 8 * (size_t)B * n * k, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipGetLastError());
+  if ((rc = pc.collect(h, w, B))) return rc;
   h->staged = false;
   return 0;
 }
@@ -2177,7 +2214,7 @@ int omc_psd_project_batch(omc_instance* h, int B, int N, const double* M, double
   memset(&w, 0, sizeof(w));
   w.nB = w.B = w.Btot = B; w.n = N; w.np16 = (int)NP; w.k = 1; w.max_sweeps = MAX_SWEEPS; w.mw_budget = MAX_SWEEPS;
   w.clip_hi = hi < 1e300 ? hi : 1e300;
-  w.geo = omc_plan_geometry(N, (int)NP, 1, 1, 1, 1, 0, algo == 1 ? MW_MAX_ORDER + 1 : h->tun.cone_multi_min);
+  w.geo = omc_plan_geometry(N, (int)NP, 1, 1, 1, 1, 0, algo == 1 ? MW_MAX_ORDER + 1 : h->tun.cone_multi_min, MW_MAX_ORDER + 1);
   if (algo == 2 && !w.geo.mw) geom_set_mw(w.geo, N);
   const bool cold = !w.geo.mw && !w.geo.ws_lpp;      // no k_cone_ws at this order (129 .. 144, above 1024): the cold kernel k_cone, as in a relaxation
   if (cold && (evals || V)) return fail(OMC_ERR_UNSUPPORTED, "omc_psd_project_batch: the cold single-workgroup kernel (orders 129 - 144 and above 1024) returns P only");
@@ -2315,6 +2352,24 @@ int omc_colprox_plan(int n, int cmax, int block_min, int64_t* out) {
   long long o[5];
   cp_block_plan(cmax, block_min, o);
   for (int q = 0; q < 5; ++q) out[q] = o[q];
+  return 0;
+}
+
+int omc_plain_multi_plan(int n, int plain_multi_min, int64_t* out) {
+  if (!out) return fail(OMC_ERR_ARGUMENT, "out is NULL");
+  if (n <= 0) return fail(OMC_ERR_ARGUMENT, "omc_plain_multi_plan: n must be positive");
+  const int np16 = (n + 15) & ~15;
+  const OmcGeom g = omc_plan_geometry(n, np16, 1, 1, 1, 1, 0, MW_MAX_ORDER + 1, plain_multi_min);
+  const MwLayout L = mw_layout(n);
+  out[0] = g.plain_mw; out[1] = np16; out[2] = L.Ncp; out[3] = L.nb; out[4] = (int64_t)L.bytes; out[5] = mw_plain_launches(L, MAX_SWEEPS);
+  return 0;
+}
+
+double omc_plain_multi_tau(void) { return MW_TAU_PLAIN; }
+
+int omc_last_plain_multi_stats(omc_instance* h, int64_t* out) {
+  if (!h || !out) return fail(OMC_ERR_ARGUMENT, "NULL argument");
+  for (int q = 0; q < 4; ++q) out[q] = h->pmw_tot[q];
   return 0;
 }
 

@@ -7,6 +7,12 @@
 //   k_mw_norms    blocks x slots   squared column norms, eigenvalues, Vrow
 //   k_mw_select   slots            clip selection, seeds of the tracked subspace, evsum, sweep statistics
 //   k_mw_rebuild  tiles x slots    W1 = base M + sum wgt g g' (MFMA rank-c update, symmetric stores)
+// The plain operations (CONE_SEP, CONE_TOPK of k_cone: separation vector, the k dominant eigenvectors) as a sequence on the same round kernel:
+//   k_mw_plain_fro      row tiles x slots   partial sums of squares of the symmetrised input (U U' - Y, or Y), one per 16-row tile
+//   k_mw_plain_prepare  tiles x slots       sigma from the partials in a fixed order, G = M + sigma I with the zero padding
+//   k_mw_round                              rotation threshold and stop rule MW_TAU_PLAIN (the cold kernel's 1e-14)
+//   k_mw_plain_norms    blocks x slots      squared column norms, eigenvalues
+//   k_mw_plain_pick     slots               the selection of k_cone in these modes: lmin, bx / U
 // Workgroups of one launch never wait for each other; rounds are ordered by the stream.  The host cannot see convergence inside a call: it
 // enqueues mw_budget sweeps, every round kernel records the largest squared relative cross product its pair showed BEFORE rotating
 // (atomicMax on the sweep's word: order-independent, so results are run-to-run identical), and the workgroups of sweep s leave at once when
@@ -17,6 +23,7 @@
 
 typedef double double4m __attribute__((ext_vector_type(4)));
 
+// the thresholds of the clip and certificate sequence (MwRound carries them; the plain sequence passes MW_TAU_PLAIN squared for both)
 #define MW_TAU2 1e-20      // rotation threshold 1e-10 on the relative cross product, as k_cone_ws: a pair below it is left alone
 #define MW_STOP2 1e-18     // stop rule: a sweep whose largest relative cross product was below 1e-9 is the last one.  Inside a cluster of
                            // eigenvalues a rotation angle is not small however small the cross product, so the last sweep can leave cross
@@ -25,10 +32,13 @@ typedef double double4m __attribute__((ext_vector_type(4)));
 #define MW_LDW 65          // leading dimension of the Jacobi work array: 32 rows of the Gram matrix, 32 of the accumulated rotation, odd
 
 // the slot filter of k_cone_ws, from the fields it reads
-struct MwFilter { const int *slot_list, *done, *ws_first, *cone_done, *confirm; int sub_enable, ws_mode, ws_phase, cert_enable; };
-static MwFilter mw_filter(const OmcWS* w) { return {w->slot_list, w->done, w->ws_first, w->cone_done, w->confirm, w->sub_enable, w->ws_mode, w->ws_phase, w->cert_enable}; }
+// plain = CONE_SEP or CONE_TOPK: the filter of k_cone in that mode instead (harvested slots; no separation where k_cone_sub<2> has delivered it)
+struct MwFilter { const int *slot_list, *done, *ws_first, *cone_done, *confirm; int sub_enable, ws_mode, ws_phase, cert_enable; int plain; const int *fin, *sep_done; };
+static MwFilter mw_filter(const OmcWS* w) { return {w->slot_list, w->done, w->ws_first, w->cone_done, w->confirm, w->sub_enable, w->ws_mode, w->ws_phase, w->cert_enable, 0, nullptr, nullptr}; }
+static MwFilter mw_plain_filter(const OmcWS* w, int mode) { MwFilter f = {}; f.slot_list = w->slot_list; f.plain = mode; f.fin = w->fin; f.sep_done = w->sep_done; return f; }
 __device__ __forceinline__ int mw_slot(const MwFilter& f, int i) {      // slot of this workgroup, -1: nothing to do for it
   const int b = f.slot_list ? f.slot_list[i] : i;
+  if (f.plain) return (!f.fin[b] || (f.plain == CONE_SEP && f.sep_done && f.sep_done[b])) ? -1 : b;
   if (f.done[b]) return -1;
   if (!f.ws_mode && f.sub_enable) {
     if (f.ws_phase == 1) { if (!f.ws_first[b]) return -1; }
@@ -92,7 +102,13 @@ __global__ void __launch_bounds__(256) k_mw_prepare(OmcWS w, MwFilter f) {
 }
 
 // ---- round -------------------------------------------------------------------------------------------------------------------------------
-struct MwRound { MwFilter f; double* slab; size_t stride, smax; int ld, NP, nb; };
+// tau2, stop2: rotation threshold and stop rule, squared.  unit_q (the plain sequence, whose eigenvalues ||g|| - sigma are compared at the level of
+// the cold kernel's error): a column meets 31 rotations per inner sweep, several inner sweeps per round and nb - 1 rounds per outer sweep, some ten
+// times what the cold kernel's sweep applies to it, and c^2 + s^2 - 1 of every one of them stays in its norm: with Q applied as accumulated the
+// eigenvalues come out 7 - 10 e_ref off at every order from 145 to 1040 (e_ref: tests/test_plain_multi.py), with its columns scaled to unit length
+// first 0.25 e_ref.  (c by division instead of rsqrt, alone, leaves 5 e_ref and adds nothing to the scaling.)  The clip sequence applies Q as it
+// is: its results stay what they were bit for bit.
+struct MwRound { MwFilter f; double* slab; size_t stride, smax; int ld, NP, nb; double tau2, stop2; int unit_q; };
 
 __global__ void __launch_bounds__(256) k_mw_round(MwRound a, int sweep, int round) {
   __shared__ double s_part[4][3][256];      // Gram partials of the four waves (each sums a quarter of the rows)
@@ -102,7 +118,7 @@ __global__ void __launch_bounds__(256) k_mw_round(MwRound a, int sweep, int roun
   if (b < 0) return;
   double* Gm = a.slab + (size_t)b * a.stride;
   unsigned long long* smax = (unsigned long long*)(Gm + a.smax);
-  if (sweep > 0 && mw_word(smax[sweep - 1]) < MW_STOP2) return;
+  if (sweep > 0 && mw_word(smax[sweep - 1]) < a.stop2) return;
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4, ld = a.ld;
   int bp, bq;
   rr_pair(round, blockIdx.x, a.nb, bp, bq);
@@ -147,7 +163,7 @@ __global__ void __launch_bounds__(256) k_mw_round(MwRound a, int sweep, int roun
   __syncthreads();
   mx = fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
   if (tid == 0) atomicMax(&smax[sweep], (unsigned long long)__double_as_longlong(mx));
-  if (!(mx > MW_TAU2)) return;      // already diagonal to the rotation threshold: no write-back
+  if (!(mx > a.tau2)) return;      // already diagonal to the rotation threshold: no write-back
   // ---- eigenvectors of C: one-sided Jacobi on the columns of [C; I] (rows 32 .. 63 accumulate Q), 16 pairs x 16 lanes, the sweep of
   // jacobi_sweeps_t (cached squared norms, fp64 tangent) with jacobi16_fast's ending: a sweep without a relative cross product above
   // 1e-7 leaves them below 1e-14 ---------------------------------------------------------------------------------------------------------------
@@ -184,6 +200,16 @@ __global__ void __launch_bounds__(256) k_mw_round(MwRound a, int sweep, int roun
       }
       if (!__syncthreads_or(big)) break;
     }
+  }
+  if (a.unit_q) {      // unit columns of Q (the barrier above ended the sweeps)
+    if (tid < 32) {
+      double* q = s_W + tid * MW_LDW + 32;
+      double s = 0.0;
+      for (int r = 0; r < 32; ++r) s += q[r] * q[r];
+      const double sc = 1.0 / sqrt(s);
+      for (int r = 0; r < 32; ++r) q[r] *= sc;
+    }
+    __syncthreads();
   }
   // ---- panel <- panel Q, transposed so that loads and stores run along the rows: out'[j][i] = sum_k Q[k][j] panel[i][k] ------------------------
   double qa[2][8];
@@ -391,10 +417,181 @@ extern "C" void omc_launch_cone_mw(const OmcWS* w, hipStream_t s) {
   const int budget = w->mw_budget < 1 ? 1 : (w->mw_budget > MW_MAXSW ? MW_MAXSW : w->mw_budget);
   OmcWS wq = *w; wq.mw_budget = budget;
   hipLaunchKernelGGL(k_mw_prepare, dim3((nti * ntj + 3) / 4, w->nB), dim3(256), 0, s, wq, f);
-  const MwRound a = {f, w->cone_scratch, w->geo.ws.slab_stride, L.smax, L.ld, w->np16, L.nb};
+  const MwRound a = {f, w->cone_scratch, w->geo.ws.slab_stride, L.smax, L.ld, w->np16, L.nb, MW_TAU2, MW_STOP2, 0};
   for (int sw = 0; sw < budget; ++sw)
     for (int r = 0; r < L.nb - 1; ++r) hipLaunchKernelGGL(k_mw_round, dim3(L.nb / 2, w->nB), dim3(256), 0, s, a, sw, r);
   hipLaunchKernelGGL(k_mw_norms, dim3(L.Ncp / 16, w->nB), dim3(256), 0, s, wq, f);
   hipLaunchKernelGGL(k_mw_select, dim3(w->nB), dim3(1024), 0, s, wq, f);
   if (!w->ws_mode) hipLaunchKernelGGL(k_mw_rebuild, dim3((nlow + 3) / 4, w->nB), dim3(256), 0, s, wq, f);
+}
+
+// ---- the plain operations: CONE_SEP and CONE_TOPK of k_cone (omc_device.hip) on the round kernel, always cold ----------------------------------
+// They read (Y, U) and write the slab, lmin / bx or U and pmw_stat: nothing of the warm-started projection (Vrow, vvalid, Mbuf, fro2, sweeps,
+// mw_stat), so a harvest may run behind k_state_save and beside the next interval of the live slots.
+// entry (i, j) of the input as eig_frontend forms it, 1/2 (entry(i, j) + entry(j, i)) of cone_M_entry: U U' - Y (ui = row i of U), or Y
+__device__ __forceinline__ double mw_plain_entry(const double* Y, const double* Ub, const double* ui, int n, int k, int i, int j) {
+  const double yij = Y[(size_t)j * n + i], yji = Y[(size_t)i * n + j];
+  if (!Ub) return 0.5 * (yij + yji);
+  double s = 0.0;
+#pragma unroll
+  for (int t = 0; t < 8; ++t) if (t < k) s += ui[t] * Ub[(size_t)t * n + j];      // k <= 8; unrolled: ui stays in registers
+  return 0.5 * ((s - yij) + (s - yji));
+}
+// ||M||_F^2 from the partial sums of the row tiles, in one order whichever wave forms it: a lane's stride, then the sum over the wave
+__device__ __forceinline__ double mw_plain_fro2(const double* part, int nt, int lane) {
+  double s = 0.0;
+  for (int t = lane; t < nt; t += WAVE) s += part[t];
+  return wave_sum(s);
+}
+
+__global__ void __launch_bounds__(256) k_mw_plain_fro(OmcWS w, MwFilter f) {
+  __shared__ double s_red[4];
+  const int b = mw_slot(f, blockIdx.y);
+  if (b < 0) return;
+  const int n = w.n, k = w.k, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  const MwLayout L = w.geo.mwl;
+  double* Gm = w.cone_scratch + (size_t)b * w.geo.ws.slab_stride;
+  const double* Y = w.Y + (size_t)b * n * n;
+  const double* Ub = (f.plain == CONE_SEP) ? w.U + (size_t)b * n * k : nullptr;
+  const int i = blockIdx.x * 16 + (tid & 15);
+  double ui[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int t = 0; t < 8; ++t) if (Ub && i < n && t < k) ui[t] = Ub[(size_t)t * n + i];
+  double acc = 0.0;
+  if (i < n)
+    for (int j = tid >> 4; j < n; j += 16) { const double v = mw_plain_entry(Y, Ub, ui, n, k, i, j); acc += v * v; }
+  acc = wave_sum(acc);
+  if (lane == 0) s_red[wv] = acc;
+  __syncthreads();
+  if (tid == 0) Gm[L.fro + blockIdx.x] = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+}
+
+__global__ void __launch_bounds__(256) k_mw_plain_prepare(OmcWS w, MwFilter f) {
+  const int b = mw_slot(f, blockIdx.y);
+  if (b < 0) return;
+  const int n = w.n, k = w.k, NP = w.np16, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  const MwLayout L = w.geo.mwl;
+  double* Gm = w.cone_scratch + (size_t)b * w.geo.ws.slab_stride;
+  if (blockIdx.x == 0 && tid < MW_MAXSW) ((unsigned long long*)(Gm + L.smax))[tid] = 0ull;
+  const int nti = NP >> 4, ntj = L.Ncp >> 4;
+  const int tile = blockIdx.x * 4 + wv;
+  if (tile >= nti * ntj) return;
+  const double sigma = mw_sigma(mw_plain_fro2(Gm + L.fro, nti, lane));
+  const double* Y = w.Y + (size_t)b * n * n;
+  const double* Ub = (f.plain == CONE_SEP) ? w.U + (size_t)b * n * k : nullptr;
+  const int ti = tile % nti, tj = tile / nti, i = (ti << 4) + (lane & 15);
+  double ui[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int t = 0; t < 8; ++t) if (Ub && i < n && t < k) ui[t] = Ub[(size_t)t * n + i];
+  // the whole tile is stored (16 rows of a column per quarter wave): rows beyond N up to NP and columns up to Ncp are the zero padding
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int j = (tj << 4) + (lane >> 4) + 4 * r;
+    double v = 0.0;
+    if (i < n && j < n) v = mw_plain_entry(Y, Ub, ui, n, k, i, j) + ((i == j) ? sigma : 0.0);
+    Gm[(size_t)j * L.ld + i] = v;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_mw_plain_norms(OmcWS w, MwFilter f) {
+  const int b = mw_slot(f, blockIdx.y);
+  if (b < 0) return;
+  const int NP = w.np16, tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  const MwLayout L = w.geo.mwl;
+  double* Gm = w.cone_scratch + (size_t)b * w.geo.ws.slab_stride;
+  const double sigma = mw_sigma(mw_plain_fro2(Gm + L.fro, NP >> 4, lane));
+  for (int q = 0; q < 4; ++q) {
+    const int t = blockIdx.x * 16 + 4 * wv + q;
+    double s = 0.0;
+    for (int r = lane; r < NP; r += WAVE) { const double x = Gm[(size_t)t * L.ld + r]; s += x * x; }
+    s = wave_sum(s);
+    if (lane == 0) { Gm[L.ev + t] = s; Gm[L.lam + t] = sqrt(s) - sigma; }
+  }
+}
+
+// the larger value, the lower index among equal ones (what a strict comparison over ascending indices keeps); i < 0: no candidate
+__device__ __forceinline__ void mw_take(double& v, int& i, double ov, int oi) {
+  if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) { v = ov; i = oi; }
+}
+__device__ __forceinline__ int mw_block_argmax(double v, int i, double* s_rv, int* s_ri) {
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int o = 32; o > 0; o >>= 1) { const double ov = __shfl_xor(v, o, WAVE); const int oi = __shfl_xor(i, o, WAVE); mw_take(v, i, ov, oi); }
+  __syncthreads();      // the words of the previous call have been read
+  if (lane == 0) { s_rv[wv] = v; s_ri[wv] = i; }
+  __syncthreads();
+  v = s_rv[0]; i = s_ri[0];
+  for (int q = 1; q < 4; ++q) mw_take(v, i, s_rv[q], s_ri[q]);
+  return i;
+}
+// column c of G: 1 / ||g_c|| with the canonical sign (the first entry of largest magnitude is positive)
+__device__ __forceinline__ double mw_column_scale(const double* g, double ev, int N, double* s_rv, int* s_ri) {
+  double v = 0.0; int i = -1;
+  for (int r = threadIdx.x; r < N; r += 256) mw_take(v, i, fabs(g[r]), r);
+  i = mw_block_argmax(v, i, s_rv, s_ri);
+  return ((g[i] >= 0.0) ? 1.0 : -1.0) / sqrt(ev);
+}
+
+__global__ void __launch_bounds__(256) k_mw_plain_pick(OmcWS w, MwFilter f) {
+  __shared__ double s_rv[4], s_sg[8], s_wt[2];
+  __shared__ int s_ri[4], s_top[8];
+  const int b = mw_slot(f, blockIdx.x);
+  if (b < 0) return;
+  const int N = w.n, k = w.k, tid = threadIdx.x;
+  const MwLayout L = w.geo.mwl;
+  const double* Gm = w.cone_scratch + (size_t)b * w.geo.ws.slab_stride;
+  const double* ev = Gm + L.ev; const double* lam = Gm + L.lam;
+  if (tid == 0 && w.pmw_stat) {      // sweeps that ran, as k_mw_select counts them
+    const unsigned long long* smax = (const unsigned long long*)(Gm + L.smax);
+    const double stop2 = MW_TAU_PLAIN * MW_TAU_PLAIN;
+    int sweeps = 1;
+    while (sweeps < MW_PLAIN_SWEEPS && mw_word(smax[sweeps - 1]) >= stop2) ++sweeps;
+    const int exhausted = sweeps == MW_PLAIN_SWEEPS && mw_word(smax[sweeps - 1]) >= stop2;
+    int* st = w.pmw_stat + 4 * b;
+    st[0] += 1; st[1] = sweeps; st[2] += exhausted; if (sweeps > st[3]) st[3] = sweeps;
+  }
+  const int sep = f.plain == CONE_SEP, npick = sep ? 2 : (k < 8 ? k : 8);
+  for (int j = 0; j < npick; ++j) {      // the two smallest / the k largest eigenvalues, one after the other; ties go to the lowest column
+    double v = 0.0; int i = -1;
+    for (int t = tid; t < N; t += 256) {
+      bool used = false;
+      for (int q = 0; q < j; ++q) used = used || s_top[q] == t;
+      if (!used) mw_take(v, i, sep ? -lam[t] : lam[t], t);
+    }
+    i = mw_block_argmax(v, i, s_rv, s_ri);
+    const double sg = mw_column_scale(Gm + (size_t)i * L.ld, ev[i], N, s_rv, s_ri);
+    if (tid == 0) { s_top[j] = i; s_sg[j] = sg; }
+    __syncthreads();
+  }
+  if (sep) {
+    const double l1 = lam[s_top[0]], l2 = lam[s_top[1]];
+    if (tid == 0) {
+      w.lmin[2 * b] = l1; w.lmin[2 * b + 1] = l2;
+      if (w.breakpoints == 2 && l2 < -1e-10) {       // OMC.jl:2471-2473
+        const double nn = sqrt(l1 * l1 + l2 * l2);
+        s_wt[0] = fabs(l1) / nn; s_wt[1] = fabs(l2) / nn;
+      } else { s_wt[0] = 1.0; s_wt[1] = 0.0; }
+    }
+    __syncthreads();
+    const double* g1 = Gm + (size_t)s_top[0] * L.ld; const double* g2 = Gm + (size_t)s_top[1] * L.ld;
+    for (int r = tid; r < N; r += 256) w.bx[(size_t)b * N + r] = s_wt[0] * s_sg[0] * g1[r] + s_wt[1] * s_sg[1] * g2[r];
+    return;
+  }
+  for (int e = tid; e < N * npick; e += 256) {
+    const int j = e / N, r = e - j * N;
+    w.U[(size_t)b * N * k + e] = s_sg[j] * Gm[(size_t)s_top[j] * L.ld + r];
+  }
+}
+
+extern "C" void omc_launch_cone_plain_mw(const OmcWS* w, int mode, hipStream_t s) {
+  const MwLayout L = w->geo.mwl;
+  const MwFilter f = mw_plain_filter(w, mode);
+  const int nti = w->np16 >> 4, ntj = L.Ncp >> 4;
+  hipLaunchKernelGGL(k_mw_plain_fro, dim3(nti, w->nB), dim3(256), 0, s, *w, f);
+  hipLaunchKernelGGL(k_mw_plain_prepare, dim3((nti * ntj + 3) / 4, w->nB), dim3(256), 0, s, *w, f);
+  const double tau2 = MW_TAU_PLAIN * MW_TAU_PLAIN;
+  const MwRound a = {f, w->cone_scratch, w->geo.ws.slab_stride, L.smax, L.ld, w->np16, L.nb, tau2, tau2, 1};
+  for (int sw = 0; sw < MW_PLAIN_SWEEPS; ++sw)
+    for (int r = 0; r < L.nb - 1; ++r) hipLaunchKernelGGL(k_mw_round, dim3(L.nb / 2, w->nB), dim3(256), 0, s, a, sw, r);
+  hipLaunchKernelGGL(k_mw_plain_norms, dim3(L.Ncp / 16, w->nB), dim3(256), 0, s, *w, f);
+  hipLaunchKernelGGL(k_mw_plain_pick, dim3(w->nB), dim3(256), 0, s, *w, f);
 }

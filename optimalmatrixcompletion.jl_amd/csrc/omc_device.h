@@ -112,6 +112,9 @@ struct OmcWS {
   // used up their budget without meeting the stop rule, most sweeps of a call since the host last cleared it; eigenvalues of the last
   // projection in column order (B * np16; NULL: not wanted)
   int mw_budget; int* mw_stat; double* ev_out;
+  // the plain operations on those kernels (geo.plain_mw, omc_launch_cone_plain_mw): per slot calls, sweeps of the last call, calls that used up
+  // MAX_SWEEPS without meeting the stop rule, most sweeps of a call; counters of their own, mw_stat keeps meaning clip and certificate calls
+  int* pmw_stat;
   int* sub_stat;          // B * 8: calls, power steps, failures (fall back to the full decomposition), seeds, failures by cause (too many positive Ritz values, step cap, Cholesky), Rayleigh-Ritz passes
   // rows
   int* R;                 // B
@@ -183,6 +186,10 @@ void omc_launch_global(const OmcWS* w, hipStream_t s);
 void omc_launch_small(const OmcWS* w, int mode, hipStream_t s);
 void omc_launch_cone_ws(const OmcWS* w, hipStream_t s);
 void omc_launch_cone_mw(const OmcWS* w, hipStream_t s);      /* omc_cone_mw.hip: what omc_launch_cone_ws does when w->geo.mw is set */
+/* omc_cone_mw.hip: what omc_launch_cone does for mode CONE_SEP or CONE_TOPK when w->geo.plain_mw is set.  Always cold: input stage from
+   (Y, U), MAX_SWEEPS sweeps of k_mw_round at the threshold MW_TAU_PLAIN, norms, selection; the outputs of k_cone in these modes (lmin, bx; U)
+   for the slots its filter takes (fin, and for CONE_SEP not sep_done), w->pmw_stat; nothing of the warm-started projection is touched */
+void omc_launch_cone_plain_mw(const OmcWS* w, int mode, hipStream_t s);
 void omc_launch_cone_sub(const OmcWS* w, hipStream_t s);
 void omc_launch_check_zero(const OmcWS* w, hipStream_t s);
 void omc_launch_check_build(const OmcWS* w, hipStream_t s);

@@ -3088,6 +3088,7 @@ void omc_launch_colprox(const OmcWS* w, int mode, hipStream_t s) {
   hipLaunchKernelGGL(k_colprox, dim3(blocks), dim3(wpb * 64), (size_t)wpb * w->geo.cp_lds_doubles * sizeof(double), s, *w, mode);
 }
 void omc_launch_cone(const OmcWS* w, int mode, hipStream_t s) {
+  if (w->geo.plain_mw && (mode == CONE_SEP || mode == CONE_TOPK)) { omc_launch_cone_plain_mw(w, mode, s); return; }      // omc_cone_mw.hip: the same outputs from a sequence of multi-workgroup launches
   if (w->geo.cone.use_lds) hipLaunchKernelGGL(k_cone<true>, dim3(w->nB), dim3(512), w->geo.cone.lds_bytes, s, *w, mode);
   else hipLaunchKernelGGL(k_cone<false>, dim3(w->nB), dim3(512), 0, s, *w, mode);
 }

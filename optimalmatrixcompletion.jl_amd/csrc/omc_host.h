@@ -106,6 +106,7 @@ struct Tuning {
   int graph_max = 16;              // OMC_GRAPH_MAX: hipGraph replay for batches staged with at most this many nodes
   int harvest_async = 1;           // OMC_HARVEST_ASYNC: 0 = every harvest is waited for, booked and refilled before the next iteration
   int harvest_async_min_live = 256;   // OMC_HARVEST_ASYNC_MIN_LIVE: live slots from which a harvest runs beside the next interval (omc_harvest_plan)
+  int plain_multi_min = 1025;      // OMC_PLAIN_MULTI_MIN: cone orders from this value on (never below 145) run separation, rounding and the left singular vectors on the multi-workgroup eigen-kernels; the default is where only the cold kernel existed
   int shor_select_kb = 1048576;    // OMC_SHOR_SELECT_KB: violated-minor selection streams (no materialised keys) when 16 B per candidate exceed this many KiB; 0 = always materialise
   int streams = 4;                 // OMC_STREAMS: <= 1 serialises a solve on one stream
   int sub_debug = 0;               // OMC_SUB_DEBUG: diagnostics of k_cone_sub (3: histograms for omc_debug_stamps)
@@ -129,7 +130,7 @@ inline const Knob OMC_KNOBS[] = {
   {"OMC_GRAPH_MAX", nullptr, &Tuning::graph_max},            {"OMC_SHOR_SELECT_KB", nullptr, &Tuning::shor_select_kb},
   {"OMC_HARVEST_ASYNC", nullptr, &Tuning::harvest_async},    {"OMC_HARVEST_ASYNC_MIN_LIVE", nullptr, &Tuning::harvest_async_min_live},
   {"OMC_WS_QUIET", nullptr, &Tuning::ws_quiet},
-  {"OMC_STREAMS", nullptr, &Tuning::streams},
+  {"OMC_STREAMS", nullptr, &Tuning::streams},                {"OMC_PLAIN_MULTI_MIN", nullptr, &Tuning::plain_multi_min},
   {"OMC_SUB_DEBUG", nullptr, &Tuning::sub_debug},            {"OMC_SUB_QMAX", nullptr, &Tuning::sub_qmax},
   {"OMC_TIMING_STRIDE", nullptr, &Tuning::timing_stride},
 };
@@ -173,6 +174,7 @@ struct omc_instance {
   long long sub_tot[8] = {0};
   DevBuf bmwstat, sbigmw, pjM, pjV, pjW, pjS, pjD, pjI;      // sweep statistics of the multi-workgroup eigen-kernels (base workspace, Shor view) ; buffers of omc_psd_project_batch
   long long mw_tot[5] = {0};      // omc_last_cone_multi_stats
+  DevBuf bpmwstat; long long pmw_tot[4] = {0};      // the plain operations on those kernels: per-slot counters (OmcWS::pmw_stat), omc_last_plain_multi_stats
   OmcWS ws{};
   omc_relax_params params{};
   bool staged = false;

@@ -55,17 +55,23 @@ OMC_HD void gram_pair_of(int p, int R, int* r, int* s) {      // p < gram_npairs
 OMC_HD void gram_pair_next(int R, int* r, int* s) { if (++*s == R) { ++*r; *s = *r; } }
 // ---- multi-workgroup eigen-kernels (omc_cone_mw.hip), per-slot global slab: G (Ncp columns of ld doubles; columns padded to whole block
 // pairs, rows to 16), squared norms ev, eigenvalues lam, weights wgt (Ncp each), selection sel (Ncp ints), the largest squared relative
-// cross product of each sweep smax (MW_MAXSW 64-bit words), head (base, then nsel and nkeep as ints) ---------------------------------------
+// cross product of each sweep smax (MW_MAXSW 64-bit words), head (base, then nsel and nkeep as ints).  The plain sequence (CONE_SEP, CONE_TOPK:
+// omc_launch_cone_plain_mw) selects no weights and keeps the partial sums of squares of its input, one per 16-row tile (NP / 16 <= Ncp),
+// in the words of wgt: fro names them ----------------------------------------------------------------------------------------------------------
 #define MW_B 16         // columns per block: one v_mfma_f64_16x16x4_f64 tile, a 32 x 32 Gram matrix per pair
 #define MW_MAXSW 32     // sweep slots of smax: the sweep budget of a call never exceeds it
 #define MW_MIN_ORDER 145   // below, k_cone_ws holds G in LDS: the multi-workgroup path is never planned there
 #define MW_MAX_ORDER 4096
-struct MwLayout { int ld, Ncp, nb; size_t ev, lam, wgt, sel, smax, head, bytes; };
+#define MW_TAU_PLAIN 1e-14   // rotation threshold and stop rule of the plain sequence: the cold kernel's (eig_frontend), omc_plain_multi_tau()
+#define MW_PLAIN_SWEEPS 30   // sweeps it enqueues: MAX_SWEEPS, the cold kernel's limit
+struct MwLayout { int ld, Ncp, nb; size_t ev, lam, wgt, sel, smax, head, bytes, fro; };
 OMC_HD MwLayout mw_layout(int N) {
   const int NP = (N + 15) & ~15, Ncp = (N + 2 * MW_B - 1) & ~(2 * MW_B - 1), ld = NP + 4;
+  static_assert(2 * MW_B >= 16, "fro: the NP / 16 partial sums of the plain sequence lie in the Ncp words of wgt, NP <= Ncp");
   const size_t ev = (size_t)Ncp * ld, sel = ev + 3 * (size_t)Ncp, smax = sel + Ncp / 2, head = smax + MW_MAXSW;
-  return {ld, Ncp, Ncp / MW_B, ev, ev + Ncp, ev + 2 * (size_t)Ncp, sel, smax, head, (head + 4) * 8};
+  return {ld, Ncp, Ncp / MW_B, ev, ev + Ncp, ev + 2 * (size_t)Ncp, sel, smax, head, (head + 4) * 8, ev + 2 * (size_t)Ncp};
 }
+OMC_HD int mw_plain_launches(const MwLayout& L, int sweeps) { return sweeps * (L.nb - 1) + 4; }      // fro, prepare, the rounds, norms, pick
 // ---- k_cone_sub: X, then Z (SUBP x LD each; Z in a global slab beyond order 512), 4 partial 16 x 16 products (Cs), Gram / Cholesky /
 // Ritz rotation (Hs, 16 x 17), Jacobi work (Gj, 16 x 17), Ritz values (th), squared norms (evj), red (32), wgt (16), sel (16 ints) ------
 struct SubLayout { int LD, zglob; size_t Za, Cs, Hs, Gj, th, evj, red, wgt, sel, bytes; };
@@ -160,12 +166,19 @@ struct OmcGeom {
   int cp_lds_c, cp_lds_doubles, cp_keepB; // k_colprox: columns up to cp_lds_c rows in LDS (cp_lds_doubles per wave); cp_keepB = 0: dense columns, B is gathered again instead of kept
   size_t cp_scratch_stride, sub_lds;      // k_colprox slab per wave (B*m waves), 0 when every column fits the LDS ; dynamic LDS of k_cone_sub
   int mw; MwLayout mwl;                   // 1: omc_launch_cone_ws takes the multi-workgroup kernels (their slab layout; it shares cone_scratch and its stride)
+  int plain_mw;                           // 1: omc_launch_cone takes them for CONE_SEP and CONE_TOPK (omc_launch_cone_plain_mw; mwl is filled, mw may be 0)
 };
 // switch a planned geometry to the multi-workgroup eigen-kernels at order n: the shared slab grows to their need (a multiple of 4 doubles: 32-byte rows)
 OMC_HD void geom_set_mw(OmcGeom& g, int n) {
   g.mw = 1; g.mwl = mw_layout(n);
   size_t st = g.mwl.bytes / 8 + 8; if (st < g.ws.slab_stride) st = g.ws.slab_stride;
   g.cone.slab_stride = g.ws.slab_stride = (st + 3) & ~(size_t)3;
+}
+// the plain operations on the multi-workgroup kernels at order n: the same layout and the same growth of the shared slab, mw as it is
+OMC_HD void geom_set_plain_mw(OmcGeom& g, int n) {
+  const int mw = g.mw;
+  geom_set_mw(g, n);
+  g.mw = mw; g.plain_mw = 1;
 }
 // k_colprox_block: cl, cs = longest column of its LDS list and of its slab list (0: the list is empty)
 OMC_HD void geom_set_cpblock(OmcGeom& g, int cl, int cs) {
@@ -174,8 +187,10 @@ OMC_HD void geom_set_cpblock(OmcGeom& g, int cl, int cs) {
   g.cpb_slab_stride = cs > 0 ? cp_block_layout(cs, 0).slab : 0;
 }
 // n, np16: order of the cone matrix and its padding to 16 (the Shor view of the big cone passes n + m); cmax: longest column;
-// cone_multi_min: orders from this value on (and never below MW_MIN_ORDER) take the multi-workgroup eigen-kernels
-OMC_HD OmcGeom omc_plan_geometry(int n, int np16, int k, int rmax, int Rmax, int cmax, int global_nolds, int cone_multi_min) {
+// cone_multi_min: orders from this value on (and never below MW_MIN_ORDER) take the multi-workgroup eigen-kernels; plain_multi_min: the same
+// for the plain operations (a view on which they never run passes a value above MW_MAX_ORDER)
+OMC_HD bool mw_order_ok(int n, int use_lds, int knob) { return n >= MW_MIN_ORDER && !use_lds && n >= knob && n <= MW_MAX_ORDER; }
+OMC_HD OmcGeom omc_plan_geometry(int n, int np16, int k, int rmax, int Rmax, int cmax, int global_nolds, int cone_multi_min, int plain_multi_min) {
   OmcGeom g;
   const WsGeometry wg = ws_geometry(n);
   g.cone = plan_block(cone_bytes(n), cone_bytes(n) <= OMC_MAX_DYN_LDS);
@@ -189,9 +204,10 @@ OMC_HD OmcGeom omc_plan_geometry(int n, int np16, int k, int rmax, int Rmax, int
   g.cp_lds_c = cmax < 64 ? cmax : 64; g.cp_keepB = g.cp_lds_c <= 40 ? 1 : 0;
   g.cp_lds_doubles = cp_reg_layout(g.cp_lds_c, g.cp_keepB).doubles;
   g.cp_scratch_stride = cmax > g.cp_lds_c ? cp_body_layout(cmax).doubles : 0;
-  g.mw = 0; g.mwl = MwLayout{};
+  g.mw = g.plain_mw = 0; g.mwl = MwLayout{};
   g.cpb_lds_bytes = g.cpb_slab_lds_bytes = g.cpb_slab_stride = 0;
-  if (n >= MW_MIN_ORDER && !wg.use_lds && n >= cone_multi_min && n <= MW_MAX_ORDER) geom_set_mw(g, n);
+  if (mw_order_ok(n, wg.use_lds, cone_multi_min)) geom_set_mw(g, n);
+  if (mw_order_ok(n, wg.use_lds, plain_multi_min)) geom_set_plain_mw(g, n);
   return g;
 }
 #endif

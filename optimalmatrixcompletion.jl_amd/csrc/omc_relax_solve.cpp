@@ -272,8 +272,9 @@ struct SolveLoop {
     rc = push_list(); if (rc) return rc;
     h->total_sweeps = 0;
     graph_max = Btot <= tun.graph_max ? tun.graph_max : 0;
-    mw_any = w.geo.mw || (shor && h->wbig.geo.mw);
+    mw_any = w.geo.mw || w.geo.plain_mw || (shor && h->wbig.geo.mw);      // plain_mw: 30 (nb - 1) + 4 launches per harvest (omc_launch_cone_plain_mw)
     for (int q = 0; q < 5; ++q) h->mw_tot[q] = 0;
+    for (int q = 0; q < 4; ++q) h->pmw_tot[q] = 0;
     split_solve = multi && !tun.no_ws_split && w.sub_enable && w.geo.ws_lpp && w.ws_first;
     return 0;
   }
@@ -605,6 +606,15 @@ struct SolveLoop {
 
   int collect_statistics() {
     { int rc = mw_collect(); if (rc) return rc; }
+    if (w.geo.plain_mw && w.pmw_stat) {      // the separation launches of the harvests: the slots' counters since the batch was staged
+      std::vector<int> st(4 * (size_t)S);
+      HIPCHK(hipMemcpyAsync(st.data(), w.pmw_stat, sizeof(int) * st.size(), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      for (int b = 0; b < S; ++b) {
+        h->pmw_tot[0] += st[4 * b]; h->pmw_tot[2] += st[4 * b + 2];
+        h->pmw_tot[1] = std::max<long long>(h->pmw_tot[1], st[4 * b + 3]);
+      }
+    }
     std::vector<int> sweeps(S);
     HIPCHK(hipMemcpyAsync(sweeps.data(), w.sweeps, sizeof(int) * S, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
