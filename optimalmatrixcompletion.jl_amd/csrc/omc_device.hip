@@ -2515,6 +2515,8 @@ __global__ void k_check_final(OmcWS w, int last, int phase) {
   if (b >= w.B || w.done[b]) return;
   if (phase == 0 && w.confirm[b]) return;
   if (phase == 1 && !w.confirm[b]) return;
+  // Shor mode: the host also checks at a node's own cap (omc_relax_solve.cpp); a slot whose node started elsewhere is not due then
+  if (w.shor && !last && w.iters[b] % w.check_every != 0 && w.iters[b] < w.max_iters) return;
   const bool est = (phase == 0);
   const double lbv = (w.c0[b] + w.evsum[b] - w.cpen[b] + w.cst[b]) * w.inv_s2;      // Shor mode solves for scale * A: values are reported unscaled
   const double lb_rig = w.lb[b];

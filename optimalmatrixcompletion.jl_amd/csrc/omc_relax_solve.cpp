@@ -125,6 +125,10 @@ struct SolveLoop {
   int graph_max = 0, gexec_n = -1; GraphGuard graphs;
   // per check: slots the asynchronous harvest of the previous check refilled; the slot list has gone out already
   int nrefilled = 0; bool list_pushed = false;
+  // Shor mode: a node is also checked at its iteration cap when the cap is no multiple of check_every (as the oracle does: it % check_every
+  // == 0 or it == max_iters, counted from the node's own start).  starts: the iterations at which slots were set up and whose nodes may still
+  // run.  With caps on the grid every start is on it and nothing is added to the checks.
+  std::vector<int> starts;
   // (omc_last_host_phases also carries two counts of the iterations themselves: the event records and the stream waits they enqueued)
   // host stamps between the iterations (omc_last_host_phases): stamp(q) charges the time since the previous stamp to piece q
   const Clock::time_point t0; Clock::time_point t_last, t_check;
@@ -235,6 +239,7 @@ struct SolveLoop {
   // first calls of the new nodes are cold -- the full sweep budget, no quiet interval.
   int setup_slots(int units) {
     tape.touch(T_S);
+    if (shor && std::find(starts.begin(), starts.end(), it) == starts.end()) starts.push_back(it);
     if (shor) omc_shor_launch_setup(&sw, s);
     TIMED(OMC_KERNEL_SETUP, units, omc_launch_setup(&w, s));
     { int rc = gram_join(); if (rc) return rc; }
@@ -401,6 +406,10 @@ struct SolveLoop {
   int enqueue_iteration(bool* is_check) {
     ++it;
     *is_check = (it % check_every == 0);
+    if (shor) {
+      for (int s0 : starts) { const int l = it - s0; if (l == P.max_iters || (s0 % check_every != 0 && l % check_every == 0)) *is_check = true; }
+      starts.erase(std::remove_if(starts.begin(), starts.end(), [&](int s0) { return it - s0 >= P.max_iters; }), starts.end());
+    }
     if (multi && wait_main && !ev_main_set) { HIPCHK(hipEventRecord(h->ev_main, s)); tape.touch(T_S); }
     ev_main_set = false;
     const long long nrec0 = tape.records(), nwait0 = tape.waits();

@@ -263,6 +263,7 @@ def sdp_relaxation_shor(inst, shor_idx, soc_idx, cuts=(), cut_type="linear", U_l
     hist = []; stall = 0; obj_prev = math.inf; lb_prev = -math.inf
     n_bumps = 0; last_bump = 0
     gap_prev = 1e300; gap_rate = 1.0; slow_votes = 0
+    cone_in = [0.0, 0.0, 0.0]      # largest Frobenius norm of what the big cone, the clip and the small cone projected (omc_shor_iter_ref.py)
     it = 0
     for it in range(1, p.max_iters + 1):
         # (B0) big cone
@@ -280,6 +281,7 @@ def sdp_relaxation_shor(inst, shor_idx, soc_idx, cuts=(), cut_type="linear", U_l
         w3, E3 = np.linalg.eigh(0.5 * (M3 + M3.T))
         P3 = (E3 * np.maximum(w3, 0.0)) @ E3.T
         Q3 = P3 - 0.5 * (M3 + M3.T)
+        cone_in = [max(cone_in[0], float(np.linalg.norm(In0))), max(cone_in[1], float(np.linalg.norm(Y - D1))), max(cone_in[2], float(np.linalg.norm(M3)))]
         dS = Q3[:r, :r]; W3V = P3[:r, r:]; W3T = P3[r:, r:]
         # (B4) minors
         if nq:
@@ -407,7 +409,7 @@ def sdp_relaxation_shor(inst, shor_idx, soc_idx, cuts=(), cut_type="linear", U_l
     U = recover_U(Y, Q, Vt)
     out = dict(objective=obj, dual_bound=lb, Y=Y, U=U, X=Xo, Theta=Tho, W=Wo, V1=V1 / s2, V2=V2 / s2, V3=V3 / s2,
                termination_status=status, feasible=status != OMC_INFEASIBLE, solve_time=time.time() - t0, iters=it,
-               hist=hist, rp=rp, rd=rd, rho=rho, structure=st, rows=rows, scale=sc)
+               hist=hist, rp=rp, rd=rd, rho=rho, structure=st, rows=rows, scale=sc, cone_inputs=tuple(cone_in), n_bumps=n_bumps)
     out["objective_reference_formula"] = base.compute_SDP_relaxation_objective(Xo, Tho, inst.A, inst.indices, g, W=Wo)
     out["residuals"] = shor_primal_residuals(inst, st, rows, Xo, Wo, out["V1"], out["V2"], out["V3"], Tho, Y, U)
     if k > 1:
