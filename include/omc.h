@@ -426,6 +426,35 @@ int omc_shor_dual_bound_batch(omc_instance* h, int B, int cut_type, int referenc
 int omc_shor_dual_bound_plan(int n, int m, int k, int B, int64_t nq_stride, int max_cuts, int nonstandard_box_rows, int sanitise, int64_t* out);
 int omc_last_shor_dual_bound_ms(omc_instance* h, double* ms);
 
+/* ---- the index structure of one Shor list, built on the host or on the device -------------------------------------------
+ * Every Shor-mode entry point turns a node's list (nq tuples (i1, i2, j1, j2), 1-based, and its SOC list: n_soc = -1 for every entry, 0, or
+ * n_soc pairs (i, j)) into the arrays its kernels index by.  The knob OMC_SHOR_INDEX_DEVICE_MIN = N > 0 (omc_tuning_set; default 0: every
+ * list on the host) builds the lists with at least N minors on the device in omc_relax_stage_shor, omc_relax_append_shor and
+ * omc_shor_dual_bound_batch; the arrays are bit-identical to the host's, the refusals and their messages the same.  Rank k > 1 always takes
+ * the host path.  A staged batch keeps the value the knob had at its stage call.
+ *
+ * omc_shor_index_build: one list's structure, returned to host arrays.  where = 0: the host builder, where = 1: the device builder, whatever
+ * the knob says.  Any output may be NULL; the arrays the caller gives hold at least
+ *   mi 4 nq, kid 4 nq (both SoA, 0-based), cptr n m + 1, cent 4 nq, v1ptr 2 nq + 1, v1ent 2 nq, v2ptr 2 nq + 1, v2ent 2 nq, slackrow m ints ;
+ *   eclass n m, ctype m bytes
+ * of which nv1 + 1 / nv2 + 1 entries of v1ptr / v2ptr are written.  counts[4] = nq, nv1, nv2, kernels launched (0 on the host); r4: the
+ * list's block penalty; hash: FNV-1a of its tuples.  It stages nothing and leaves a staged batch untouched.  OMC_ERR_ARGUMENT: NULL handle,
+ * where not 0 / 1, a solve in flight on the handle, the list errors of omc_relax_stage_shor.  OMC_ERR_UNSUPPORTED: where = 1 with k > 1 (for
+ * k > 1 the host gives the structure without minors of quirk Q5), 2^28 minors or more, n m >= 2^30.
+ *
+ * omc_shor_index_plan (host only, no device): what the shape fixes.  out[0..3] = 8-bit radix passes of the V1, V2, coordinate and duplicate
+ * sorts (from the largest key the shape allows), out[4] = bytes of sort scratch for a list of nq minors, out[5] = ints (20 nq + n m + m + 3)
+ * and out[6] = bytes (n m + m rounded up to 16) one built list takes in the staging room, out[7] = kernels launched per list (without the
+ * scatter of explicit SOC pairs, one per chunk of max(n m, 1024) pairs), out[8] = items one workgroup sorts per pass.
+ *
+ * omc_last_shor_index_stats: out[5] = lists built on the host, lists built on the device, host milliseconds, device milliseconds (as the
+ * caller sees them, waits included) since the last omc_relax_stage_shor call began, kernels launched by the last device build. */
+int omc_shor_index_build(omc_instance* h, int where, int64_t nq, const int64_t* shor_idx, int64_t n_soc, const int64_t* soc_idx, int64_t* counts,
+                         double* r4, uint64_t* hash, int* mi, int* kid, int* cptr, int* cent, int* v1ptr, int* v1ent, int* v2ptr, int* v2ent,
+                         int* slackrow, uint8_t* eclass, uint8_t* ctype);
+int omc_shor_index_plan(int n, int m, int64_t nq, int64_t* out);
+int omc_last_shor_index_stats(omc_instance* h, double* out);
+
 /* ---- alternating_minimization (OMC.jl:1979-2279), disjunctive mode, B problems at once, rank k <= 8 --------
  * U_initial n*k per problem; cuts as above (only the per-cut bounds on v = U'x are imposed, OMC.jl:2047-2093);
  * k > 1 adds the pair cones ||U_j1 +- U_j2|| <= sqrt 2 of OMC.jl:2029-2045.

@@ -23,6 +23,7 @@ EXPORTS = [
     "omc_relax_keep_certificates", "omc_relax_fetch_certificate", "omc_certificate_plan", "omc_dual_bound_batch",
     "omc_relax_keep_shor_certificates", "omc_relax_fetch_shor_certificate", "omc_shor_certificate_plan",
     "omc_shor_dual_bound_batch", "omc_shor_dual_bound_plan", "omc_last_shor_dual_bound_ms",
+    "omc_shor_index_build", "omc_shor_index_plan", "omc_last_shor_index_stats",
     "omc_altmin_master_objectives", "omc_altmin_plan", "omc_comm_unique_id", "omc_comm_init", "omc_allreduce_bounds", "omc_bcast_incumbent", "omc_allgather_records", "omc_comm_destroy",
 ]
 
@@ -130,6 +131,10 @@ def load():
         lib.omc_shor_dual_bound_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 10 + [C.c_int, C.c_int64] + [vp] * 10
         lib.omc_shor_dual_bound_plan.argtypes = [C.c_int] * 4 + [C.c_int64, C.c_int, C.c_int, C.c_int, vp]
         lib.omc_last_shor_dual_bound_ms.argtypes = [vp, vp]
+    if hasattr(lib, "omc_shor_index_build"):      # absent from an older A/B build; Engine.shor_index raises there
+        lib.omc_shor_index_build.argtypes = [vp, C.c_int, C.c_int64, vp, C.c_int64] + [vp] * 15
+        lib.omc_shor_index_plan.argtypes = [C.c_int, C.c_int, C.c_int64, vp]
+        lib.omc_last_shor_index_stats.argtypes = [vp, vp]
     lib.omc_tuning_set.argtypes = [vp, C.c_char_p, C.c_char_p]
     lib.omc_tuning_reload_env.argtypes = [vp]
     lib.omc_debug_residuals.argtypes = [vp, vp, vp]

@@ -179,6 +179,15 @@ def shor_dual_bound_plan(n, m, k, B, nq_stride, max_cuts=0, nonstandard_box_rows
     return {key: int(v) for key, v in zip(keys, out)}
 
 
+def shor_index_plan(n, m, nq):
+    """omc_shor_index_plan (host only, no GPU): what the shape fixes for the device builder of a Shor list's index structure -- radix passes of
+    its four sorts, bytes of sort scratch, ints and bytes of one built list in the staging room, kernels per list, items per workgroup and pass."""
+    out = np.zeros(9, np.int64)
+    _lib.check(_lib.load().omc_shor_index_plan(int(n), int(m), int(nq), _lib.ptr(out)))
+    keys = ("passes_v1", "passes_v2", "passes_coord", "passes_dup", "scratch_bytes", "stage_ints", "stage_bytes", "launches", "tile")
+    return {key: int(v) for key, v in zip(keys, out)}
+
+
 class Engine:
     """Device-resident instance + the four call sites of the reference driver."""
 
@@ -729,6 +738,48 @@ class Engine:
         ms = np.zeros(1)
         _lib.check(self._lib.omc_last_shor_dual_bound_ms(self._h, _lib.ptr(ms)))
         return float(ms[0])
+
+    # ---- the index structure of one Shor list (omc_shor_index_build) -----------------------------------------------
+    def shor_index(self, shor_idx, soc_idx=None, where="device"):
+        """The index structure of one list of minors ((nq, 4) 1-based tuples; soc_idx: None = every entry on the SOC list, else (n_soc, 2)
+        1-based pairs), built by the host builder (where="host") or the device builder (where="device") whatever OMC_SHOR_INDEX_DEVICE_MIN
+        says.  Returns a dict of numpy arrays at their true lengths (mi and kid as (4, nq)), the counts nq / nv1 / nv2, r4, hash and the
+        kernels launched.  Nothing is staged."""
+        if where not in ("host", "device"):
+            raise ValueError("where is 'host' or 'device'")
+        mq = np.ascontiguousarray(np.asarray(shor_idx, np.int64).reshape(-1, 4)); nq = len(mq)
+        if soc_idx is None:
+            nsoc, sq = -1, np.zeros((1, 2), np.int64)
+        else:
+            sq = np.ascontiguousarray(np.asarray(soc_idx, np.int64).reshape(-1, 2)); nsoc = len(sq)
+            if nsoc == 0:
+                sq = np.zeros((1, 2), np.int64)
+        if nq == 0:
+            mq = np.zeros((1, 4), np.int64)
+        n, m = self.n, self.m
+        counts = np.zeros(4, np.int64); r4 = np.zeros(1); hv = np.zeros(1, np.uint64)
+        i32 = lambda c: np.full(c, -7, np.int32)      # noqa: E731
+        o = dict(mi=i32(4 * nq), kid=i32(4 * nq), cptr=i32(n * m + 1), cent=i32(4 * nq), v1ptr=i32(2 * nq + 1), v1ent=i32(2 * nq),
+                 v2ptr=i32(2 * nq + 1), v2ent=i32(2 * nq), slackrow=i32(m), eclass=np.full(n * m, 255, np.uint8), ctype=np.full(m, 255, np.uint8))
+        _lib.check(self._lib.omc_shor_index_build(self._h, 1 if where == "device" else 0, nq, _lib.ptr(mq), nsoc, _lib.ptr(sq), _lib.ptr(counts),
+                                                  _lib.ptr(r4), _lib.ptr(hv), *[_lib.ptr(o[key]) for key in ("mi", "kid", "cptr", "cent", "v1ptr",
+                                                  "v1ent", "v2ptr", "v2ent", "slackrow", "eclass", "ctype")]))
+        q, nv1, nv2 = int(counts[0]), int(counts[1]), int(counts[2])      # q = 0 for rank k > 1 (quirk Q5)
+        o["mi"] = o["mi"][:4 * q].reshape(4, q); o["kid"] = o["kid"][:4 * q].reshape(4, q); o["cent"] = o["cent"][:4 * q]
+        o["v1ptr"] = o["v1ptr"][:nv1 + 1]; o["v2ptr"] = o["v2ptr"][:nv2 + 1]; o["v1ent"] = o["v1ent"][:2 * q]; o["v2ent"] = o["v2ent"][:2 * q]
+        o.update(nq=q, nv1=nv1, nv2=nv2, launches=int(counts[3]), r4=float(r4[0]), hash=int(hv[0]))
+        return o
+
+    def shor_index_plan(self, nq):
+        """shor_index_plan for this instance's shape."""
+        return shor_index_plan(self.n, self.m, nq)
+
+    def shor_index_stats(self):
+        """Lists whose index structure was built on the host / on the device since the last stage_shor() call began, the milliseconds spent
+        in each as the caller saw them, and the kernels of the last device build (omc_last_shor_index_stats)."""
+        o = np.zeros(5)
+        _lib.check(self._lib.omc_last_shor_index_stats(self._h, _lib.ptr(o)))
+        return dict(host_lists=int(o[0]), device_lists=int(o[1]), host_ms=float(o[2]), device_ms=float(o[3]), last_launches=int(o[4]))
 
     # ---- multi-GPU exchange behind the C ABI (RCCL; SURVEY.md 8e) ------------------------------------------------
     @staticmethod

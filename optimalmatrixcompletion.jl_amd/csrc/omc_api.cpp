@@ -989,8 +989,14 @@ struct ShorGroupHost {
   std::vector<int> mi, kid, cptr, cent, v1ptr, v1ent, v2ptr, v2ent, slackrow;
   std::vector<uint8_t> eclass, ctype;
   size_t off_int = 0, off_byte = 0;       // offsets into the concatenated device buffers
-  size_t ints() const { return mi.size() + kid.size() + cptr.size() + cent.size() + v1ptr.size() + v1ent.size() + v2ptr.size() + v2ent.size() + slackrow.size(); }
-  size_t bytes() const { return (eclass.size() + ctype.size() + 15) & ~(size_t)15; }
+  // built on the device (omc_shor_index.hip): the arrays wait in the staging room at st_int / st_byte, each at its capacity; the vectors stay
+  // empty (ctype is copied back where a caller reads it on the host).  The packed lengths follow from the counts.
+  bool dev = false; size_t st_int = 0, st_byte = 0, nm = 0, m = 0;
+  size_t ints() const {
+    if (dev) return (size_t)16 * nq + nm + m + 3 + (size_t)nv1 + (size_t)nv2;
+    return mi.size() + kid.size() + cptr.size() + cent.size() + v1ptr.size() + v1ent.size() + v2ptr.size() + v2ent.size() + slackrow.size();
+  }
+  size_t bytes() const { return ((dev ? nm + m : eclass.size() + ctype.size()) + 15) & ~(size_t)15; }
 };
 // keys sorted, ids assigned in sorted order (as numpy.unique does in the oracle); members in increasing (minor, position) order
 static void build_keys(const std::vector<uint64_t>& keyA, const std::vector<uint64_t>& keyB, int nq, int& nkeys, int* kidA, int* kidB,
@@ -1053,6 +1059,15 @@ static void add_shor_list(std::unordered_map<uint64_t, std::vector<int>>& byhash
   lists.push_back(std::move(K));
 }
 
+// the weight of the order-5 blocks on an entry of X / W is r4 x (blocks that hold it): r4 follows the mean multiplicity 4 nq / (n m)
+// (measured: 20 at 12 x 14 with 152 minors, 5 at 100 x 100 with 38 813, 1.2 at 200 x 200 with 632 732 certify fastest)
+static double shor_auto_r4(const omc_instance* h, int nq) {
+  return (h->shor_r4 > 0.0) ? h->shor_r4 : std::min(40.0, std::max(0.25, 75.0 * (double)h->n * (double)h->m / (4.0 * (double)std::max(nq, 1))));
+}
+static const char* const SHOR_MSG_RANGE = "Shor minors must satisfy 1 <= i1 < i2 <= n, 1 <= j1 < j2 <= m (OMC.jl:2556-2603)";
+static const char* const SHOR_MSG_DUP = "duplicate Shor minor in a node's list";
+static const char* const SHOR_MSG_SOC = "SOC coordinate out of range";
+
 // One (minor list, SOC list) pair -> the index structure its nodes share (validation, keys, coordinate CSR, entry classes, column types, slack
 // rows, block penalty, list hash).  The one builder: every caller comes through group_shor_lists.
 static int build_shor_group(const omc_instance* h, int64_t nq64, const int64_t* idx, int64_t nsoc, const int64_t* soc, ShorGroupHost& G) {
@@ -1067,14 +1082,14 @@ static int build_shor_group(const omc_instance* h, int64_t nq64, const int64_t* 
     const int64_t* t = idx + 4 * (size_t)q;
     const int64_t i1 = t[0] - 1, i2 = t[1] - 1, j1 = t[2] - 1, j2 = t[3] - 1;
     if (!(0 <= i1 && i1 < i2 && i2 < n && 0 <= j1 && j1 < j2 && j2 < m))
-      return fail(OMC_ERR_ARGUMENT, "Shor minors must satisfy 1 <= i1 < i2 <= n, 1 <= j1 < j2 <= m (OMC.jl:2556-2603)");
+      return fail(OMC_ERR_ARGUMENT, SHOR_MSG_RANGE);
     G.mi[q] = (int)i1; G.mi[(size_t)nq + q] = (int)i2; G.mi[(size_t)2 * nq + q] = (int)j1; G.mi[(size_t)3 * nq + q] = (int)j2;
     enc[q] = (((uint64_t)i1 * n + (uint64_t)i2) * m + (uint64_t)j1) * m + (uint64_t)j2;
     k1a[q] = ((uint64_t)i1 * m + j1) * m + j2; k1b[q] = ((uint64_t)i2 * m + j1) * m + j2;      // V1[i,(j1,j2)]
     k2a[q] = ((uint64_t)i1 * n + i2) * m + j1; k2b[q] = ((uint64_t)i1 * n + i2) * m + j2;      // V2[(i1,i2),j]
     ++cnt[(size_t)j1 * n + i1]; ++cnt[(size_t)j2 * n + i1]; ++cnt[(size_t)j1 * n + i2]; ++cnt[(size_t)j2 * n + i2];
   }
-  { std::vector<uint64_t> se = enc; std::sort(se.begin(), se.end()); if (std::adjacent_find(se.begin(), se.end()) != se.end()) return fail(OMC_ERR_ARGUMENT, "duplicate Shor minor in a node's list"); }
+  { std::vector<uint64_t> se = enc; std::sort(se.begin(), se.end()); if (std::adjacent_find(se.begin(), se.end()) != se.end()) return fail(OMC_ERR_ARGUMENT, SHOR_MSG_DUP); }
   build_keys(k1a, k1b, nq, G.nv1, G.kid.data(), G.kid.data() + nq, G.v1ptr, G.v1ent);
   build_keys(k2a, k2b, nq, G.nv2, G.kid.data() + (size_t)2 * nq, G.kid.data() + (size_t)3 * nq, G.v2ptr, G.v2ent);
   // coordinate CSR: members in increasing (minor, position) order
@@ -1092,7 +1107,7 @@ static int build_shor_group(const omc_instance* h, int64_t nq64, const int64_t* 
   if (nsoc < 0) { for (size_t e = 0; e < (size_t)n * m; ++e) G.eclass[e] = 1; }
   else for (int64_t c = 0; c < nsoc; ++c) {
     const int64_t i = soc[2 * c] - 1, j = soc[2 * c + 1] - 1;
-    if (!(0 <= i && i < n && 0 <= j && j < m)) return fail(OMC_ERR_ARGUMENT, "SOC coordinate out of range");
+    if (!(0 <= i && i < n && 0 <= j && j < m)) return fail(OMC_ERR_ARGUMENT, SHOR_MSG_SOC);
     G.eclass[(size_t)j * n + i] = 1;
   }
   for (size_t e = 0; e < (size_t)n * m; ++e) if (cnt[e] > 0) G.eclass[e] = 2;      // W >= X^2 is implied by the order-5 block there
@@ -1122,9 +1137,68 @@ static int build_shor_group(const omc_instance* h, int64_t nq64, const int64_t* 
     G.mi.clear(); G.kid.clear(); G.cent.clear(); G.v1ent.clear(); G.v2ent.clear();
     G.cptr.assign((size_t)n * m + 1, 0); G.v1ptr.assign(1, 0); G.v2ptr.assign(1, 0);
   }
-  // the weight of the order-5 blocks on an entry of X / W is r4 x (blocks that hold it): r4 follows the mean multiplicity 4 nq / (n m)
-  // (measured: 20 at 12 x 14 with 152 minors, 5 at 100 x 100 with 38 813, 1.2 at 200 x 200 with 632 732 certify fastest)
-  G.r4 = (h->shor_r4 > 0.0) ? h->shor_r4 : std::min(40.0, std::max(0.25, 75.0 * (double)n * (double)m / (4.0 * (double)std::max(G.nq, 1))));
+  G.r4 = shor_auto_r4(h, G.nq);
+  return 0;
+}
+
+// ---- the same structure built on the device (omc_shor_index.hip) ---------------------------------------------------------------
+// Scratch for lists of up to nq minors and a staging room of the given size.  The buffer only grows, and only with `grow` (no solve runs:
+// stage time, the dual-bound evaluator, omc_shor_index_build); an append finds the room its stage call made.
+static int shor_index_room(omc_instance* h, size_t nq, size_t stage_ints, size_t stage_bytes, bool grow) {
+  const ShorIndexDims& have = h->sx_dims;
+  const size_t soc_cap = std::max<size_t>((size_t)h->n * h->m, 1024);
+  if (h->sxD.p && nq <= have.nq && stage_ints <= have.stage_ints && stage_bytes <= have.stage_bytes && soc_cap <= have.soc_cap) return 0;
+  if (!grow) return fail(OMC_ERR_ALLOC, "Shor index structures on the device: the room made at stage time does not hold this list");
+  ShorIndexDims d;
+  d.nq = std::max(nq, have.nq); d.soc_cap = std::max(soc_cap, have.soc_cap);
+  d.stage_ints = std::max(stage_ints, have.stage_ints); d.stage_bytes = std::max(stage_bytes, have.stage_bytes);
+  size_t bytes = 0;
+  if (carve_ensure(h->sxD, [&](Carve& c) { walk_shor_index(c, d, h->sx, h->sx_stage_int, h->sx_stage_byte); }, &bytes)) {
+    (void)hipGetLastError();
+    h->sx_dims = ShorIndexDims{};
+    return fail(OMC_ERR_ALLOC, "Shor index structures on the device: " + std::to_string(bytes) + " bytes of scratch and staging room, which the device does not have (" + g_err + ")");
+  }
+  h->sx_dims = d;
+  return 0;
+}
+static size_t shor_stage_ints(size_t nq, size_t nm, size_t m) { return 20 * nq + nm + m + 3; }
+static size_t shor_stage_bytes(size_t nm, size_t m) { return (nm + m + 15) & ~(size_t)15; }
+// the descriptor of one list whose arrays sit in the staging room at (st_int, st_byte)
+static ShorIndexWS shor_index_view(omc_instance* h, int nq, int64_t nsoc, size_t st_int, size_t st_byte) {
+  ShorIndexWS w = h->sx;
+  const size_t nm = (size_t)h->n * h->m;
+  w.n = h->n; w.m = h->m; w.nq = nq; w.soc_fill = nsoc < 0 ? 1 : 0; w.mask = h->dmask.as<uint8_t>();
+  Carve c(h->sx_stage_int + st_int);
+  walk_shor_index_list(c, (size_t)nq, nm, (size_t)h->m, w);
+  w.eclass = h->sx_stage_byte + st_byte; w.ctype = w.eclass + nm;
+  return w;
+}
+// Builds one list on stream s into the staging room and waits for its result word.  The refusals are the host builder's, in its order.
+static int build_shor_group_device(omc_instance* h, hipStream_t s, int64_t nq64, const int64_t* idx, int64_t nsoc, const int64_t* soc,
+                                   size_t st_int, size_t st_byte, bool want_ctype, ShorGroupHost& G) {
+  const int nq = (int)nq64;
+  const ShorIndexWS w = shor_index_view(h, nq, nsoc, st_int, st_byte);
+  if (nq > 0) HIPCHK(hipMemcpyAsync(const_cast<long long*>(w.idx), idx, 32 * (size_t)nq, hipMemcpyHostToDevice, s));
+  int launches = omc_shidx_launch_sort(&w, s);
+  for (int64_t c0 = 0; c0 < nsoc; c0 += (int64_t)h->sx_dims.soc_cap) {
+    const int64_t cnt = std::min<int64_t>(nsoc - c0, (int64_t)h->sx_dims.soc_cap);
+    HIPCHK(hipMemcpyAsync(const_cast<long long*>(w.soc), soc + 2 * c0, 16 * (size_t)cnt, hipMemcpyHostToDevice, s));
+    omc_shidx_launch_soc(&w, cnt, s);
+  }
+  launches += omc_shidx_launch_finish(&w, s);
+  int meta[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(meta, w.meta, sizeof(meta), hipMemcpyDeviceToHost, s));
+  if (want_ctype) { G.ctype.resize(h->m); HIPCHK(hipMemcpyAsync(G.ctype.data(), w.ctype, (size_t)h->m, hipMemcpyDeviceToHost, s)); }
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  h->shidx_stats[4] = launches;
+  if (meta[0] & SHIDX_ERR_RANGE) return fail(OMC_ERR_ARGUMENT, SHOR_MSG_RANGE);
+  if (meta[0] & SHIDX_ERR_DUP) return fail(OMC_ERR_ARGUMENT, SHOR_MSG_DUP);
+  if (meta[0] & SHIDX_ERR_SOC) return fail(OMC_ERR_ARGUMENT, SHOR_MSG_SOC);
+  G.dev = true; G.st_int = st_int; G.st_byte = st_byte; G.nm = (size_t)h->n * h->m; G.m = (size_t)h->m;
+  G.nq = nq; G.nv1 = meta[1]; G.nv2 = meta[2];
+  G.hash = fnv1a(idx, 32 * (size_t)nq, FNV_SEED);
+  G.r4 = shor_auto_r4(h, nq);
   return 0;
 }
 
@@ -1139,6 +1213,26 @@ static void pack_shor_group(const ShorGroupHost& G, int* hi, uint8_t* hb, const 
   memcpy(hb + G.off_byte, G.eclass.data(), G.eclass.size());
   memcpy(hb + G.off_byte + G.eclass.size(), G.ctype.data(), G.ctype.size());
   d.eclass = dev_byte + G.off_byte; d.ctype = d.eclass + G.eclass.size();
+}
+// The same for a group built on the device: its arrays move from the staging room to the place the host image would have put them (the
+// packed order and lengths of pack_shor_group; the padding behind the bytes is zeroed as the host image has it), on stream s.
+static int place_shor_group_device(omc_instance* h, const ShorGroupHost& G, int* dev_int, uint8_t* dev_byte, ShorGroupDev& d, hipStream_t s) {
+  const ShorIndexWS src = shor_index_view(h, G.nq, 0, G.st_int, G.st_byte);
+  const size_t nq = (size_t)G.nq;
+  int* o = dev_int + G.off_int;
+  auto put = [&](const int* from, size_t count) { const int* dp = o; if (count && hipMemcpyAsync(o, from, count * sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess) return (const int*)nullptr; o += count; return dp; };
+  d.nq = G.nq; d.nv1 = G.nv1; d.nv2 = G.nv2; d.pad = 0; d.hash = G.hash; d.r4 = G.r4;
+  d.mi = put(src.mi, 12 * nq + G.nm + 1);      // mi, kid, cptr, cent: adjacent in both layouts (walk_shor_index_list)
+  d.kid = d.mi + 4 * nq; d.cptr = d.kid + 4 * nq; d.cent = d.cptr + G.nm + 1;
+  d.v1ptr = put(src.v1ptr, (size_t)G.nv1 + 1); d.v1ent = put(src.v1ent, 2 * nq);
+  d.v2ptr = put(src.v2ptr, (size_t)G.nv2 + 1); d.v2ent = put(src.v2ent, 2 * nq);
+  d.slackrow = put(src.slackrow, G.m);
+  if (!d.mi || !d.v1ptr || !d.v2ptr || !d.slackrow || (nq && (!d.v1ent || !d.v2ent))) return fail(999, "hipMemcpyAsync (Shor index structures, staging room to arena) failed");
+  uint8_t* b = dev_byte + G.off_byte;
+  HIPCHK(hipMemcpyAsync(b, src.eclass, G.nm + G.m, hipMemcpyDeviceToDevice, s));
+  if (G.bytes() > G.nm + G.m) HIPCHK(hipMemsetAsync(b + G.nm + G.m, 0, G.bytes() - (G.nm + G.m), s));
+  d.eclass = b; d.ctype = b + G.nm;
+  return 0;
 }
 
 // The host's filter of one node's warm-start indices (omc_relax_stage_shor and omc_relax_append_shor; the caller holds sig_mu): a load index that
@@ -1171,39 +1265,82 @@ struct ShorGrouping {
   std::unordered_map<uint64_t, std::vector<int>> byhash; std::vector<ShorListKey> lists; std::vector<uint64_t> hashes;
   size_t tot_int = 0, tot_byte = 0;
   int nqmax = 0, nv1max = 0, nv2max = 0;
+  // set by the caller: lists with at least index_min minors (0: none) are built on the device on `stream`, whose scratch and staging room may
+  // grow (never during an append) and are made to hold at least the room_* figures ; ctype of such a list is wanted on the host
+  int index_min = 0; hipStream_t stream = nullptr; bool grow = true, want_ctype = false;
+  size_t room_nq = 0, room_ints = 0, room_bytes = 0;
 };
 // Groups the nodes (out.so / out.co: from shor_list_offsets) and builds the index structure of every new list.  With `known`, a new list
 // that the batch has no room for is refused (messages of omc_relax_append_shor); nothing is written anywhere but `out`.
-static int group_shor_lists(const omc_instance* h, int B, const int64_t* n_shor, const int64_t* shor_idx, const int64_t* n_soc, const int64_t* soc_idx,
+static int group_shor_lists(omc_instance* h, int B, const int64_t* n_shor, const int64_t* shor_idx, const int64_t* n_soc, const int64_t* soc_idx,
                             const ShorKnownLists* known, ShorGrouping& out) {
   const int NG0 = known ? (int)known->lists->size() : 0;
+  const size_t nm = (size_t)h->n * h->m, m = (size_t)h->m;
+  const int index_min = h->k == 1 ? out.index_min : 0;      // rank k > 1: the host builder (its structure has no minors, quirk Q5)
   out.node_group.assign(B, 0);
-  for (int b = 0; b < B; ++b) {
-    const int64_t* ib = shor_idx + 4 * out.so[b]; const int64_t* sb = soc_idx + 2 * out.co[b];
-    const uint64_t hv = shor_pair_hash(n_shor[b], ib, n_soc[b], sb);
-    int gid = known ? find_shor_list(*known->byhash, *known->lists, hv, n_shor[b], ib, n_soc[b], sb) : -1;
-    if (gid < 0) {
-      const int g2 = find_shor_list(out.byhash, out.lists, hv, n_shor[b], ib, n_soc[b], sb);
-      if (g2 >= 0) gid = NG0 + g2;
+  // which nodes bring a list new with this call, and which earlier node of the call has the same one: nothing is built or refused here
+  std::vector<uint64_t> hv(B); std::vector<int> first_of(B, -1);
+  {
+    std::unordered_map<uint64_t, std::vector<int>> firsts;
+    size_t dev_nq = out.room_nq, dev_ints = 0, dev_bytes = 0; bool any_dev = false;
+    for (int b = 0; b < B; ++b) {
+      const int64_t* ib = shor_idx + 4 * out.so[b]; const int64_t* sb = soc_idx + 2 * out.co[b];
+      hv[b] = shor_pair_hash(n_shor[b], ib, n_soc[b], sb);
+      const int gid = known ? find_shor_list(*known->byhash, *known->lists, hv[b], n_shor[b], ib, n_soc[b], sb) : -1;
+      if (gid >= 0) { out.node_group[b] = gid; continue; }
+      std::vector<int>& cand = firsts[hv[b]];
+      int f = b;
+      for (int c : cand)
+        if (n_shor[c] == n_shor[b] && n_soc[c] == n_soc[b] && (n_shor[b] == 0 || memcmp(shor_idx + 4 * out.so[c], ib, 32 * (size_t)n_shor[b]) == 0) &&
+            (n_soc[b] <= 0 || memcmp(soc_idx + 2 * out.co[c], sb, 16 * (size_t)n_soc[b]) == 0)) { f = c; break; }
+      if (f == b) {
+        cand.push_back(b);
+        if (index_min > 0 && n_shor[b] >= index_min) {
+          any_dev = true; dev_nq = std::max(dev_nq, (size_t)n_shor[b]);
+          dev_ints += shor_stage_ints((size_t)n_shor[b], nm, m); dev_bytes += shor_stage_bytes(nm, m);
+        }
+      }
+      first_of[b] = f;
     }
-    if (gid < 0) {      // a list new with this call: built here, so that the first refusal in node order is the one reported
+    if (any_dev && out.grow) {
+      int rcr = shor_index_room(h, dev_nq, std::max(dev_ints, out.room_ints), std::max(dev_bytes, out.room_bytes), true);
+      if (rcr) return rcr;
+    }
+  }
+  size_t st_int = 0, st_byte = 0;      // staging room used by the lists built on the device so far
+  for (int b = 0; b < B; ++b) {
+    if (first_of[b] < 0) continue;      // a list the batch knows
+    if (first_of[b] != b) { out.node_group[b] = out.node_group[first_of[b]]; continue; }
+    const int64_t* ib = shor_idx + 4 * out.so[b]; const int64_t* sb = soc_idx + 2 * out.co[b];
+    {      // a list new with this call: built here, so that the first refusal in node order is the one reported
       if (known && n_shor[b] > known->nqmax)
         return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a list has " + std::to_string(n_shor[b]) + " minors, the batch has room for " + std::to_string(known->nqmax) + " per node (nq_max of omc_relax_reserve_shor)");
       if (known && NG0 + (int)out.lists.size() >= known->group_cap)
         return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a new list, and the list capacity of the batch (" + std::to_string(known->group_cap) + " lists: staged + extra_lists of omc_relax_reserve_shor) is used up");
       out.groups.emplace_back();
       ShorGroupHost& G = out.groups.back();
-      { int rc0 = build_shor_group(h, n_shor[b], ib, n_soc[b], sb, G); if (rc0) return rc0; }
+      const auto t0 = std::chrono::steady_clock::now();
+      const bool dev = index_min > 0 && n_shor[b] >= index_min;
+      if (dev) {
+        const size_t need_i = shor_stage_ints((size_t)n_shor[b], nm, m), need_b = shor_stage_bytes(nm, m);
+        { int rcr = shor_index_room(h, (size_t)n_shor[b], st_int + need_i, st_byte + need_b, false); if (rcr) return rcr; }
+        int rc0 = build_shor_group_device(h, out.stream, n_shor[b], ib, n_soc[b], sb, st_int, st_byte, out.want_ctype, G);
+        if (rc0) return rc0;
+        st_int += need_i; st_byte += need_b;
+      } else {
+        int rc0 = build_shor_group(h, n_shor[b], ib, n_soc[b], sb, G); if (rc0) return rc0;
+      }
+      h->shidx_stats[dev ? 1 : 0] += 1.0;
+      h->shidx_stats[dev ? 3 : 2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       out.nqmax = std::max(out.nqmax, G.nq); out.nv1max = std::max(out.nv1max, G.nv1); out.nv2max = std::max(out.nv2max, G.nv2);
       G.off_int = out.tot_int; out.tot_int += G.ints();
       G.off_byte = out.tot_byte; out.tot_byte += G.bytes();
       if (known && (G.nv1 > known->nv1max || G.nv2 > known->nv2max || out.tot_int > known->int_room || out.tot_byte > known->byte_room))
         return fail(OMC_ERR_ARGUMENT, "omc_relax_append_shor: a new list does not fit the index room reserved by omc_relax_reserve_shor (list capacity used up)");
-      gid = NG0 + (int)out.lists.size();
-      add_shor_list(out.byhash, out.lists, hv, n_shor[b], ib, n_soc[b], sb);
-      out.hashes.push_back(hv);
+      out.node_group[b] = NG0 + (int)out.lists.size();
+      add_shor_list(out.byhash, out.lists, hv[b], n_shor[b], ib, n_soc[b], sb);
+      out.hashes.push_back(hv[b]);
     }
-    out.node_group[b] = gid;
   }
   return 0;
 }
@@ -1211,13 +1348,24 @@ static int group_shor_lists(const omc_instance* h, int B, const int64_t* n_shor,
 // Host images of the new groups of `g` and their copies to the given arena positions, the group table and the nodes' group ids, enqueued on s.
 // The images must live until the caller has synchronised s.
 struct ShorGroupImages { std::vector<int> hi; std::vector<uint8_t> hb; std::vector<ShorGroupDev> gd; };
-static int upload_shor_groups(const ShorGrouping& g, int* dev_int, uint8_t* dev_byte, ShorGroupDev* dev_groups, int* dev_node_group, hipStream_t s,
+static int upload_shor_groups(omc_instance* h, const ShorGrouping& g, int* dev_int, uint8_t* dev_byte, ShorGroupDev* dev_groups, int* dev_node_group, hipStream_t s,
                               ShorGroupImages& img) {
   if (!g.groups.empty()) {
+    bool any_dev = false;
+    for (const ShorGroupHost& G : g.groups) any_dev = any_dev || G.dev;
     img.hi.assign(g.tot_int, 0); img.hb.assign(g.tot_byte, 0); img.gd.resize(g.groups.size());
-    for (size_t q = 0; q < g.groups.size(); ++q) pack_shor_group(g.groups[q], img.hi.data(), img.hb.data(), dev_int, dev_byte, img.gd[q]);
-    HIPCHK(hipMemcpyAsync(dev_int, img.hi.data(), g.tot_int * sizeof(int), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dev_byte, img.hb.data(), g.tot_byte, hipMemcpyHostToDevice, s));
+    for (size_t q = 0; q < g.groups.size(); ++q) if (!g.groups[q].dev) pack_shor_group(g.groups[q], img.hi.data(), img.hb.data(), dev_int, dev_byte, img.gd[q]);
+    if (!any_dev) {
+      HIPCHK(hipMemcpyAsync(dev_int, img.hi.data(), g.tot_int * sizeof(int), hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(dev_byte, img.hb.data(), g.tot_byte, hipMemcpyHostToDevice, s));
+    } else {      // group by group: the host's part of the images, and the staging room's lists (s is the stream they were built on)
+      for (size_t q = 0; q < g.groups.size(); ++q) {
+        const ShorGroupHost& G = g.groups[q];
+        if (G.dev) { int rcp = place_shor_group_device(h, G, dev_int, dev_byte, img.gd[q], s); if (rcp) return rcp; continue; }
+        HIPCHK(hipMemcpyAsync(dev_int + G.off_int, img.hi.data() + G.off_int, G.ints() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dev_byte + G.off_byte, img.hb.data() + G.off_byte, G.bytes(), hipMemcpyHostToDevice, s));
+      }
+    }
     HIPCHK(hipMemcpyAsync(dev_groups, img.gd.data(), sizeof(ShorGroupDev) * img.gd.size(), hipMemcpyHostToDevice, s));
   }
   HIPCHK(hipMemcpyAsync(dev_node_group, g.node_group.data(), sizeof(int) * g.node_group.size(), hipMemcpyHostToDevice, s));
@@ -1231,6 +1379,66 @@ int omc_relax_reserve_shor(omc_instance* h, int64_t nq_max, int extra_lists) {
   if (nq_max < 0 || extra_lists < 0) return fail(OMC_ERR_ARGUMENT, "omc_relax_reserve_shor: negative argument");
   if (nq_max >= (1ll << 28)) return fail(OMC_ERR_ARGUMENT, "omc_relax_reserve_shor: nq_max out of range");
   h->reserve_shor_nq = nq_max; h->reserve_shor_lists = extra_lists; h->reserve_shor_set = true;
+  return 0;
+}
+
+// ---- one list's index structure, returned to the caller (omc.h) ---------------------------------------------------------------------------------
+int omc_shor_index_plan(int n, int m, int64_t nq, int64_t* out) {
+  if (!out) return fail(OMC_ERR_ARGUMENT, "omc_shor_index_plan: out is NULL");
+  if (n <= 0 || m <= 0 || nq < 0) return fail(OMC_ERR_ARGUMENT, "omc_shor_index_plan: n and m must be positive, nq not negative");
+  if (nq >= (1ll << 28) || (long long)n * m >= (1ll << 30)) return fail(OMC_ERR_UNSUPPORTED, "omc_shor_index_plan: beyond the size limits of omc_relax_stage_shor");
+  const ShorIndexPlan P = shor_index_plan(n, m, nq);
+  ShorIndexDims d;
+  d.nq = (size_t)nq; d.soc_cap = std::max<size_t>((size_t)n * m, 1024);
+  ShorIndexWS w{}; int* si = nullptr; uint8_t* sb = nullptr;
+  Carve measure;
+  walk_shor_index(measure, d, w, si, sb);
+  out[0] = P.p_v1; out[1] = P.p_v2; out[2] = P.p_co; out[3] = P.p_dup;
+  out[4] = (int64_t)measure.bytes();
+  out[5] = (int64_t)shor_stage_ints((size_t)nq, (size_t)n * m, (size_t)m); out[6] = (int64_t)shor_stage_bytes((size_t)n * m, (size_t)m);
+  out[7] = P.launches; out[8] = SHIDX_TILE;
+  return 0;
+}
+
+int omc_last_shor_index_stats(omc_instance* h, double* out) {
+  if (!h || !out) return fail(OMC_ERR_ARGUMENT, "NULL argument");
+  for (int q = 0; q < 5; ++q) out[q] = h->shidx_stats[q];
+  return 0;
+}
+
+int omc_shor_index_build(omc_instance* h, int where, int64_t nq, const int64_t* shor_idx, int64_t n_soc, const int64_t* soc_idx, int64_t* counts,
+                         double* r4, uint64_t* hash, int* mi, int* kid, int* cptr, int* cent, int* v1ptr, int* v1ent, int* v2ptr, int* v2ent,
+                         int* slackrow, uint8_t* eclass, uint8_t* ctype) {
+  if (!h) return fail(OMC_ERR_ARGUMENT, "omc_shor_index_build: handle is NULL");
+  if (where != 0 && where != 1) return fail(OMC_ERR_ARGUMENT, "omc_shor_index_build: where is 0 (host) or 1 (device)");
+  if (h->worker.joinable() || h->worker_running.load()) return fail(OMC_ERR_ARGUMENT, "omc_shor_index_build: a solve is in flight on this handle (call omc_relax_wait first)");
+  if (where == 1 && h->k > 1) return fail(OMC_ERR_UNSUPPORTED, "omc_shor_index_build: rank k > 1 has no device builder (its structure has no minors, quirk Q5)");
+  const size_t n = h->n, m = h->m, nm = n * m;
+  if ((long long)n * (long long)m >= (1ll << 30)) return fail(OMC_ERR_UNSUPPORTED, "Shor mode: n * m too large for the 32-bit index structures");
+  { std::vector<size_t> so, co; int rc0 = shor_list_offsets(1, &nq, shor_idx, &n_soc, soc_idx, so, co); if (rc0) return rc0; }
+  ShorGroupHost G;
+  if (where == 0) {
+    { int rc0 = build_shor_group(h, nq, shor_idx, n_soc, soc_idx, G); if (rc0) return rc0; }
+    auto give = [](auto* dst, const auto& v) { if (dst && !v.empty()) memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+    give(mi, G.mi); give(kid, G.kid); give(cptr, G.cptr); give(cent, G.cent); give(v1ptr, G.v1ptr); give(v1ent, G.v1ent);
+    give(v2ptr, G.v2ptr); give(v2ent, G.v2ent); give(slackrow, G.slackrow); give(eclass, G.eclass); give(ctype, G.ctype);
+  } else {
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    { int rcr = shor_index_room(h, (size_t)nq, shor_stage_ints((size_t)nq, nm, m), shor_stage_bytes(nm, m), true); if (rcr) return rcr; }
+    { int rc0 = build_shor_group_device(h, s, nq, shor_idx, n_soc, soc_idx, 0, 0, false, G); if (rc0) return rc0; }
+    const ShorIndexWS w = shor_index_view(h, G.nq, 0, 0, 0);
+    const size_t q = (size_t)G.nq;
+    auto back = [&](void* dst, const void* src, size_t bytes) { return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess; };
+    HIPCHK(back(mi, w.mi, 16 * q)); HIPCHK(back(kid, w.kid, 16 * q)); HIPCHK(back(cptr, w.cptr, 4 * (nm + 1))); HIPCHK(back(cent, w.cent, 16 * q));
+    HIPCHK(back(v1ptr, w.v1ptr, 4 * ((size_t)G.nv1 + 1))); HIPCHK(back(v1ent, w.v1ent, 8 * q));
+    HIPCHK(back(v2ptr, w.v2ptr, 4 * ((size_t)G.nv2 + 1))); HIPCHK(back(v2ent, w.v2ent, 8 * q));
+    HIPCHK(back(slackrow, w.slackrow, 4 * m)); HIPCHK(back(eclass, w.eclass, nm)); HIPCHK(back(ctype, w.ctype, m));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  if (counts) { counts[0] = G.nq; counts[1] = G.nv1; counts[2] = G.nv2; counts[3] = where == 1 ? (int64_t)h->shidx_stats[4] : 0; }
+  if (r4) *r4 = G.r4;
+  if (hash) *hash = G.hash;
   return 0;
 }
 
@@ -1248,6 +1456,22 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   // ---- group the nodes by identical lists ------------------------------------------------------------------------------------------
   ShorGrouping grp;      // its lists are kept in the handle for the life of the batch
   { int rc0 = shor_list_offsets(B, n_shor, shor_idx, n_soc, soc_idx, grp.so, grp.co); if (rc0) return rc0; }
+  for (int q = 0; q < 5; ++q) h->shidx_stats[q] = 0.0;
+  h->sh_index_min = h->k == 1 ? std::max(h->tun.shor_index_device_min, 0) : 0;      // the staged batch keeps the knob's value: its appends follow it
+  if (h->sh_index_min > 0) {
+    // lists built on the device: on the instance's stream ; the scratch and the staging room also hold what an append may bring (a call's new
+    // lists: at most extra_lists of them, none longer than the batch's stride), so that an append allocates nothing
+    HIPCHK(hipSetDevice(h->device));
+    grp.index_min = h->sh_index_min; grp.stream = h->stream;
+    if (h->reserve_shor_set) {
+      int64_t nq_all = h->reserve_shor_nq;
+      for (int b = 0; b < B; ++b) nq_all = std::max(nq_all, n_shor[b]);
+      grp.room_nq = (size_t)nq_all;
+      grp.room_ints = (size_t)h->reserve_shor_lists * shor_stage_ints((size_t)nq_all, (size_t)n * m, (size_t)m);
+      grp.room_bytes = (size_t)h->reserve_shor_lists * shor_stage_bytes((size_t)n * m, (size_t)m);
+      if (grp.room_ints) { int rcr = shor_index_room(h, grp.room_nq, grp.room_ints, grp.room_bytes, true); if (rcr) return rcr; }
+    }
+  }
   { int rc0 = group_shor_lists(h, B, n_shor, shor_idx, n_soc, soc_idx, nullptr, grp); if (rc0) return rc0; }
   const std::vector<size_t>& so = grp.so; const std::vector<size_t>& co = grp.co;
   const std::vector<ShorGroupHost>& gh = grp.groups; const std::vector<int>& node_group = grp.node_group;
@@ -1313,7 +1537,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
     if ((rc = h->sgGroups.ensure(sizeof(ShorGroupDev) * ((size_t)NG + (size_t)res_lists)))) return rc;
     if ((rc = h->sgNodeGroup.ensure(sizeof(int) * (size_t)h->node_cap))) return rc;
     ShorGroupImages img;
-    if ((rc = upload_shor_groups(grp, h->sgInts.as<int>(), h->sgBytes.as<uint8_t>(), h->sgGroups.as<ShorGroupDev>(), h->sgNodeGroup.as<int>(), s, img))) return rc;
+    if ((rc = upload_shor_groups(h, grp, h->sgInts.as<int>(), h->sgBytes.as<uint8_t>(), h->sgGroups.as<ShorGroupDev>(), h->sgNodeGroup.as<int>(), s, img))) return rc;
     HIPCHK(hipStreamSynchronize(s));          // the host images die with this block
   }
   h->sh_byhash = std::move(grp.byhash); h->sh_lists = std::move(grp.lists);
@@ -1498,6 +1722,7 @@ static int shor_append_plan(omc_instance* h, int first, int B2, const ShorAppend
   const ShorKnownLists known = {&h->sh_byhash, &h->sh_lists, h->sh_group_cap, h->sh_int_cap - h->sh_int_used, h->sh_byte_cap - h->sh_byte_used,
                                 sh.nqmax, sh.nv1max, sh.nv2max};
   { int rc0 = shor_list_offsets(B2, l.n_shor, l.shor_idx, l.n_soc, l.soc_idx, g.so, g.co); if (rc0) return rc0; }
+  g.index_min = h->sh_index_min; g.stream = h->append_stream; g.grow = false;      // device builds: on the append stream, in the room of stage time
   { int rc0 = group_shor_lists(h, B2, l.n_shor, l.shor_idx, l.n_soc, l.soc_idx, &known, g); if (rc0) return rc0; }
   if (load.empty()) return 0;      // the batch has no warm-start arrays
   const int NG0 = (int)h->sh_lists.size();
@@ -1516,7 +1741,7 @@ static int shor_append_plan(omc_instance* h, int first, int B2, const ShorAppend
 // the new groups go into the room that omc_relax_reserve_shor reserved in the index arenas and the group table, behind everything the
 // running kernels can reach (they find a list through node_group of a node below Btot_live)
 static int shor_append_write(omc_instance* h, const ShorGrouping& g, int first, hipStream_t s, ShorGroupImages& img) {
-  return upload_shor_groups(g, h->sgInts.as<int>() + h->sh_int_used, h->sgBytes.as<uint8_t>() + h->sh_byte_used,
+  return upload_shor_groups(h, g, h->sgInts.as<int>() + h->sh_int_used, h->sgBytes.as<uint8_t>() + h->sh_byte_used,
                             h->sgGroups.as<ShorGroupDev>() + h->sh_lists.size(), h->sgNodeGroup.as<int>() + first, s, img);
 }
 
@@ -1556,6 +1781,7 @@ static int append_nodes(omc_instance* h, const char* who, int B2, const int* L, 
   // solve saved (as at stage time); a Shor append writes both arrays once the batch has them, -1 where nothing was given, through its filter
   std::vector<int> lfv, svv;
   ShorGrouping grouping;
+  if (!h->append_stream) HIPCHK(hipStreamCreateWithFlags(&h->append_stream, hipStreamNonBlocking));
   if (lists) {
     if (w.load_from && w.save_to) {
       lfv.assign(B2, -1); svv.assign(B2, -1);
@@ -1571,7 +1797,6 @@ static int append_nodes(omc_instance* h, const char* who, int B2, const int* L, 
     }
     if (save_to) svv.assign(save_to, save_to + B2);
   }
-  if (!h->append_stream) HIPCHK(hipStreamCreateWithFlags(&h->append_stream, hipStreamNonBlocking));
   hipStream_t as = h->append_stream;
   const size_t f = (size_t)first;
   ShorGroupImages img;
@@ -1896,6 +2121,10 @@ int omc_shor_dual_bound_batch(omc_instance* h, int B, int cut_type, int referenc
   if (nqall > 0 && !Gam) return fail(OMC_ERR_ARGUMENT, "omc_shor_dual_bound_batch: Gam is NULL but n_shor > 0");
   const size_t nqs = (size_t)nq_stride;
   // identical (minor list, SOC list) pairs share one index structure
+  if (h->tun.shor_index_device_min > 0) {      // built on the device: ctype comes back for the defects below
+    HIPCHK(hipSetDevice(h->device));
+    grp.index_min = h->tun.shor_index_device_min; grp.stream = h->stream; grp.want_ctype = defects != nullptr;
+  }
   { int rc0 = group_shor_lists(h, B, n_shor, shor_idx, n_soc, soc_idx, nullptr, grp); if (rc0) return rc0; }
   const std::vector<ShorGroupHost>& gh = grp.groups; const std::vector<int>& node_group = grp.node_group;
   const int NG = (int)gh.size(), nqmax = grp.nqmax, nv1max = grp.nv1max, nv2max = grp.nv2max;
@@ -2003,7 +2232,7 @@ int omc_shor_dual_bound_batch(omc_instance* h, int B, int cut_type, int referenc
   // index structures
   {
     ShorGroupImages img;
-    { int rc = upload_shor_groups(grp, h->sdGi.as<int>(), h->sdGb.as<uint8_t>(), h->sdGr.as<ShorGroupDev>(), in.node_group, s, img); if (rc) return rc; }
+    { int rc = upload_shor_groups(h, grp, h->sdGi.as<int>(), h->sdGb.as<uint8_t>(), h->sdGr.as<ShorGroupDev>(), in.node_group, s, img); if (rc) return rc; }
     HIPCHK(hipMemcpyAsync(in.view_node, view_node.data(), sizeof(int) * sV, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(in.view_way, view_way.data(), sizeof(int) * sV, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));          // the host images die with this block

@@ -14,6 +14,8 @@
 #include "omc_carve.h"
 #include "omc_device.h"
 #include "omc_shor_relax.h"
+#include "omc_shor_index.h"
+#include "omc_walks.h"
 
 extern thread_local std::string g_err;      // omc_last_error of the calling thread (defined in omc_api.cpp)
 static inline int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -107,6 +109,7 @@ struct Tuning {
   int harvest_async = 1;           // OMC_HARVEST_ASYNC: 0 = every harvest is waited for, booked and refilled before the next iteration
   int harvest_async_min_live = 256;   // OMC_HARVEST_ASYNC_MIN_LIVE: live slots from which a harvest runs beside the next interval (omc_harvest_plan)
   int plain_multi_min = 1025;      // OMC_PLAIN_MULTI_MIN: cone orders from this value on (never below 145) run separation, rounding and the left singular vectors on the multi-workgroup eigen-kernels; the default is where only the cold kernel existed
+  int shor_index_device_min = 0;   // OMC_SHOR_INDEX_DEVICE_MIN: Shor lists with at least this many minors get their index structure built on the device (omc_shor_index.hip); 0 = every list on the host
   int shor_select_kb = 1048576;    // OMC_SHOR_SELECT_KB: violated-minor selection streams (no materialised keys) when 16 B per candidate exceed this many KiB; 0 = always materialise
   int streams = 4;                 // OMC_STREAMS: <= 1 serialises a solve on one stream
   int sub_debug = 0;               // OMC_SUB_DEBUG: diagnostics of k_cone_sub (3: histograms for omc_debug_stamps)
@@ -128,6 +131,7 @@ inline const Knob OMC_KNOBS[] = {
   {"OMC_CHECK_XS", nullptr, &Tuning::check_xs},              {"OMC_CONE_MULTI_MIN", nullptr, &Tuning::cone_multi_min},
   {"OMC_EVENT_MERGE", nullptr, &Tuning::event_merge},
   {"OMC_GRAPH_MAX", nullptr, &Tuning::graph_max},            {"OMC_SHOR_SELECT_KB", nullptr, &Tuning::shor_select_kb},
+  {"OMC_SHOR_INDEX_DEVICE_MIN", nullptr, &Tuning::shor_index_device_min},
   {"OMC_HARVEST_ASYNC", nullptr, &Tuning::harvest_async},    {"OMC_HARVEST_ASYNC_MIN_LIVE", nullptr, &Tuning::harvest_async_min_live},
   {"OMC_WS_QUIET", nullptr, &Tuning::ws_quiet},
   {"OMC_STREAMS", nullptr, &Tuning::streams},                {"OMC_PLAIN_MULTI_MIN", nullptr, &Tuning::plain_multi_min},
@@ -218,6 +222,11 @@ struct omc_instance {
   int64_t reserve_shor_nq = 0; int reserve_shor_lists = 0; bool reserve_shor_set = false;
   std::unordered_map<uint64_t, std::vector<int>> sh_byhash; std::vector<ShorListKey> sh_lists;
   int sh_group_cap = 0; size_t sh_int_used = 0, sh_int_cap = 0, sh_byte_used = 0, sh_byte_cap = 0;
+  // index structures built on the device (OMC_SHOR_INDEX_DEVICE_MIN, omc_shor_index_build): sort scratch and the staging room in which built
+  // lists wait until every refusal of a call is decided, one packed buffer (walk_shor_index) that only grows and never while a solve runs;
+  // the knob's value for the staged batch (appends follow it); lists and milliseconds since the last stage call, launches of the last build
+  DevBuf sxD; ShorIndexDims sx_dims{}; ShorIndexWS sx{}; int* sx_stage_int = nullptr; uint8_t* sx_stage_byte = nullptr;
+  int sh_index_min = 0; double shidx_stats[5] = {0, 0, 0, 0, 0};      // host lists, device lists, host ms, device ms, launches
   // warm-start pool (omc_state_pool_create / omc_relax_set_warm)
   int pool_cap = 0; DevBuf pY, pD1, pD3, pU, palpha, psval, pXs, ptheta, pscal, bwarmL, bwarmS; std::vector<int> warm_load, warm_save;
   // Shor extension of the pool (omc_state_pool_reserve_shor) and the host's signature of every entry: which mode saved it and for which lists.

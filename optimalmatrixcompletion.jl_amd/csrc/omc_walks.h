@@ -8,6 +8,7 @@
 #include "omc_device.h"
 #include "omc_shor_relax.h"
 #include "omc_shor_cert.h"
+#include "omc_shor_index.h"
 
 // ---- omc_relax_stage: S slots (state), N nodes of the capacity (descriptors and outputs) ------------------------------------------------------
 struct StageDims { size_t S, N, n, m, k, nnz, rmax, Rmax; };
@@ -167,4 +168,25 @@ inline void walk_project_doubles(Carve& c, size_t B, size_t NP, OmcWS& w) {
 inline void walk_project_ints(Carve& c, size_t B, OmcWS& w, int*& ints_end) {
   w.done = c.take<int>(B); w.vvalid = c.take<int>(B); w.sweeps = c.take<int>(B); w.mw_stat = c.take<int>(4 * B);
   ints_end = c.take<int>(0);
+}
+
+// ---- index structures built on the device (omc_shor_index.h): sxD ---------------------------------------------------------------------------
+// scratch for lists of up to nq minors (two key / member buffers of 4 nq items, tile x digit counts, head flags, block sums, the wire tuples
+// and one chunk of soc_cap SOC pairs, the result word), then the staging room of the built lists: ints, and bytes in 16-byte units
+struct ShorIndexDims { size_t nq = 0, soc_cap = 0, stage_ints = 0, stage_bytes = 0; };
+inline void walk_shor_index(Carve& c, const ShorIndexDims& d, ShorIndexWS& w, int*& stage_int, uint8_t*& stage_byte) {
+  const ShorIndexPlan P = shor_index_plan(2, 2, (long long)d.nq);
+  w.keyA = c.take<unsigned long long>((size_t)P.items); w.keyB = c.take<unsigned long long>((size_t)P.items);
+  w.idx = c.take<long long>(4 * d.nq); w.soc = c.take<long long>(2 * d.soc_cap);
+  w.valA = c.take<unsigned>((size_t)P.items); w.valB = c.take<unsigned>((size_t)P.items);
+  w.hist = c.take<unsigned>((size_t)P.hist); w.flag = c.take<unsigned>((size_t)P.flag); w.sums = c.take<unsigned>((size_t)P.sums);
+  w.meta = c.take<int>(4);
+  stage_int = c.take<int>(d.stage_ints); stage_byte = c.take<uint8_t>(d.stage_bytes, 16);
+}
+// one list in the staging room, every array at its capacity: 20 nq + nm + m + 3 ints.  mi, kid, cptr and cent are adjacent and as long as in
+// the packed arena image, so one copy moves the four
+inline void walk_shor_index_list(Carve& c, size_t nq, size_t nm, size_t m, ShorIndexWS& w) {
+  w.mi = c.take<int>(4 * nq); w.kid = c.take<int>(4 * nq); w.cptr = c.take<int>(nm + 1); w.cent = c.take<int>(4 * nq);
+  w.v1ptr = c.take<int>(2 * nq + 1); w.v1ent = c.take<int>(2 * nq); w.v2ptr = c.take<int>(2 * nq + 1); w.v2ent = c.take<int>(2 * nq);
+  w.slackrow = c.take<int>(m);
 }
