@@ -1,5 +1,6 @@
-// omc_host.h -- what the host sources of libomc_hip.so share (omc_api.cpp, omc_relax_solve.cpp): the error string, the device and
-// page-locked buffers, the tuning knobs, the instance behind the opaque handle of omc.h, and the per-kernel timing events.  Private.
+// omc_host.h -- what the host sources of libomc_hip.so share (omc_api.cpp and the omc_api_*.cpp beside it, omc_relax_solve.cpp): the error
+// string, the device and page-locked buffers, the tuning knobs, the instance behind the opaque handle of omc.h, and the per-kernel timing
+// events.  Private.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,6 +63,23 @@ template <class F> static inline int carve_ensure(DevBuf& b, F&& walk, size_t* b
   return 0;
 }
 #define ENS_CARVE(buf, ...) do { int r_ = carve_ensure(buf, __VA_ARGS__); if (r_) return r_; } while (0)
+
+// A device array that owns its buffer, in one statement: `b` is made to hold `count` elements, `field` (the workspace's pointer to the
+// array) is set, and with a stream exactly those count * sizeof(T) bytes are cleared on it.  Returns ensure's code, or HIPCHK's of the memset.
+template <class T> static inline int bind(DevBuf& b, T*& field, size_t count) {
+  field = nullptr;
+  const int rc = b.ensure(count * sizeof(T));
+  if (rc) return rc;
+  field = (T*)b.p;
+  return 0;
+}
+template <class T> static inline int bind(DevBuf& b, T*& field, size_t count, hipStream_t zero_on) {
+  const int rc = bind(b, field, count);
+  if (rc) return rc;
+  HIPCHK(hipMemsetAsync(b.p, 0, count * sizeof(T), zero_on));
+  return 0;
+}
+#define BIND(...) do { int r_ = bind(__VA_ARGS__); if (r_) return r_; } while (0)
 
 // page-locked host memory: copies from and to it are asynchronous, so the host may go on while one is in flight
 struct PinBuf {

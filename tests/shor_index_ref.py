@@ -1,5 +1,5 @@
 """An independent numpy restatement of the index structure of one Shor list (the arrays of ShorGroupDev), for
-tests/test_shor_index_cpu.py and tests/test_gpu_shor_index.py.  It shares no code with the host builder (build_shor_group, omc_api.cpp) or
+tests/test_shor_index_cpu.py and tests/test_gpu_shor_index.py.  It shares no code with the host builder (build_shor_group, omc_api_shor.cpp) or
 the device builder (omc_shor_index.hip): np.lexsort on (member, key) for the three sorted structures, bincount / cumsum for the
 coordinate CSR, a plain column walk for ctype / slackrow.  Also the lists the two test files share."""
 import numpy as np

@@ -5,7 +5,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 GAMMA = 80.0
-SEL_CAP = 8192                 # slack of the radix select (SHOR_SEL_CAP in omc_api.cpp): it stops refining once at most this many extra keys remain
+SEL_CAP = 8192                 # slack of the radix select (SHOR_SEL_CAP in omc_api_minors.cpp): it stops refining once at most this many extra keys remain
 
 
 @pytest.fixture(scope="module")
