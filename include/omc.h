@@ -518,6 +518,14 @@ int omc_psd_project_batch(omc_instance* h, int B, int N, const double* M, double
  * array.  Restages the instance: a staged batch is gone afterwards. */
 int omc_column_prox_batch(omc_instance* h, int B, int mode, int algo, const double* Y, const double* alpha_old, const double* rho_f,
                           const double* s0, double* alpha, double* s, double* objcol, double* c0col, int* nfact);
+/* The exact projection on the linear rows of the ADMM iteration (step 4 of k_global) on its own, for B problems at once, one wave each:
+ * lam = argmin 1/2 l'G l - c'l over l >= 0, by the active-set method warm-started from lam0 (NULL = zeros).  G: B matrices R x R with
+ * leading dimension Rmax (B*Rmax*Rmax doubles); c, lam0, lam: B*Rmax.  which: 0 = the routines the alternating-minimisation kernels use
+ * (wave_nnqp), 1 = the ones k_global runs (wave_nnqp_g); the two give the same bits.  overflow (B): 1 where the passive set reached its
+ * capacity of 64 rows with a violated row still outside it -- lam is then not the exact projection.  OMC_ERR_ARGUMENT (before any device
+ * call) for a NULL handle or array, which out of range, B <= 0, or R outside 1..Rmax.  Does not touch a staged batch. */
+int omc_row_project_batch(omc_instance* h, int B, int R, int Rmax, int which, const double* G, const double* c, const double* lam0,
+                          double* lam, int* overflow);
 /* Launch plan of k_colprox_block for columns of at most cmax observed rows (cmax <= n) under OMC_COLPROX_BLOCK_MIN = block_min, computed on the
  * host from the layout the kernel uses (no device call, no handle).  out[5] = the longest column whose tiles live in LDS; dynamic LDS bytes of
  * the launch that holds a column of cmax rows; its global slab in doubles (0: the tiles are in LDS); workgroups per CU by LDS; 1 if a column

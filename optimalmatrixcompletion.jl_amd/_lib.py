@@ -15,7 +15,7 @@ EXPORTS = [
     "omc_relax_params_default", "omc_last_error", "omc_version", "omc_device_count", "omc_instance_create",
     "omc_instance_create_bits", "omc_instance_destroy", "omc_relax_batch", "omc_relax_stage", "omc_relax_solve",
     "omc_relax_fetch", "omc_relax_submit", "omc_relax_poll", "omc_relax_wait", "omc_altmin_batch", "omc_evaluate_objective", "omc_separation_batch", "omc_round_Y_batch",
-    "omc_last_kernel_stats", "omc_last_host_phases", "omc_kernel_residency", "omc_last_solver_info", "omc_last_subspace_stats", "omc_set_node_rho_scales", "omc_left_singular_batch", "omc_psd_project_batch", "omc_column_prox_batch", "omc_colprox_plan", "omc_last_cone_multi_stats", "omc_cone_multi_budget", "omc_plain_multi_plan", "omc_plain_multi_tau", "omc_last_plain_multi_stats", "omc_harvest_plan", "omc_relax_reserve", "omc_relax_append", "omc_relax_fetch_done", "omc_relax_hold", "omc_debug_stamps", "omc_tuning_set", "omc_tuning_reload_env", "omc_debug_residuals", "omc_debug_diag", "omc_debug_aa",
+    "omc_last_kernel_stats", "omc_last_host_phases", "omc_kernel_residency", "omc_last_solver_info", "omc_last_subspace_stats", "omc_set_node_rho_scales", "omc_left_singular_batch", "omc_psd_project_batch", "omc_column_prox_batch", "omc_row_project_batch", "omc_colprox_plan", "omc_last_cone_multi_stats", "omc_cone_multi_budget", "omc_plain_multi_plan", "omc_plain_multi_tau", "omc_last_plain_multi_stats", "omc_harvest_plan", "omc_relax_reserve", "omc_relax_append", "omc_relax_fetch_done", "omc_relax_hold", "omc_debug_stamps", "omc_tuning_set", "omc_tuning_reload_env", "omc_debug_residuals", "omc_debug_diag", "omc_debug_aa",
     "omc_shor_count", "omc_shor_indexes", "omc_violated_shor_minors", "omc_shor_last_stats", "omc_shor_last_select_stats",
     "omc_relax_stage_shor", "omc_relax_fetch_shor", "omc_relax_batch_shor", "omc_set_shor_penalties", "omc_set_shor_keep_V", "omc_relax_fetch_shor_V", "omc_last_shor_subspace_stats", "omc_state_pool_create", "omc_relax_set_warm",
     "omc_state_pool_reserve_shor", "omc_shor_warm_compat", "omc_last_shor_warm_stats", "omc_state_pool_fetch_shor",
@@ -102,6 +102,8 @@ def load():
     if hasattr(lib, "omc_column_prox_batch"):      # absent from an older A/B build; Engine.column_prox() raises there
         lib.omc_column_prox_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 9
         lib.omc_colprox_plan.argtypes = [C.c_int, C.c_int, C.c_int, vp]
+    if hasattr(lib, "omc_row_project_batch"):      # absent from an older A/B build; Engine.row_project() raises there
+        lib.omc_row_project_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 5
     lib.omc_last_cone_multi_stats.argtypes = [vp, vp]
     lib.omc_cone_multi_budget.argtypes = [C.c_int]
     if hasattr(lib, "omc_plain_multi_plan"):      # absent from an older A/B build; Engine.plain_multi_stats() raises there

@@ -911,6 +911,26 @@ class Engine:
         dense[:, rows, cols] = al[:, :nnz]
         return dict(alpha=dense, s=sv, objcol=oc, c0col=cc, nfact=nf)
 
+    def row_project(self, G, c, lam0=None, which=1):
+        """The exact projection on the linear rows (step 4 of k_global) on its own (omc_row_project_batch): lam = argmin 1/2 l'G l - c'l,
+        l >= 0.  G: (R, R) or (B, R, R) symmetric; c, lam0: (R,) or (B, R) (lam0 None = zeros, the warm start otherwise).  which: 0 = the
+        routines of the alternating-minimisation kernels, 1 = the ones k_global runs.  Returns (lam (B, R), overflow (B,) int32), or the
+        pair for the one problem."""
+        if not hasattr(self._lib, "omc_row_project_batch"):
+            raise _lib.OmcError(-4, "this build of the library has no omc_row_project_batch")
+        Ga = np.asarray(G, dtype=np.float64)
+        single = Ga.ndim == 2
+        Gb = np.ascontiguousarray(Ga[None] if single else Ga)
+        if Gb.ndim != 3 or Gb.shape[1] != Gb.shape[2]:
+            raise ValueError("row_project: G must be R x R or B x R x R")
+        B, R = Gb.shape[0], Gb.shape[1]
+        cb = np.ascontiguousarray(np.asarray(c, dtype=np.float64).reshape(B, R))
+        l0 = None if lam0 is None else np.ascontiguousarray(np.asarray(lam0, dtype=np.float64).reshape(B, R))
+        lam = np.zeros((B, R)); ov = np.zeros(B, np.int32)
+        _lib.check(self._lib.omc_row_project_batch(self._h, B, R, R, int(which), _lib.ptr(Gb), _lib.ptr(cb), _lib.ptr(l0), _lib.ptr(lam),
+                                                   _lib.ptr(ov)))
+        return (lam[0], int(ov[0])) if single else (lam, ov)
+
     def colprox_plan(self, block_min=65, cmax=None):
         """Launch plan of k_colprox_block for this instance's longest column (or cmax) under OMC_COLPROX_BLOCK_MIN = block_min
         (omc_colprox_plan, host only)."""

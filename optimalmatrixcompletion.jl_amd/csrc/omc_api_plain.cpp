@@ -289,6 +289,33 @@ int omc_column_prox_batch(omc_instance* h, int B, int mode, int algo, const doub
   return 0;
 }
 
+// The row projection of k_global (step 4) on its own, one wave per problem, in a buffer of its own: nothing of the instance is touched
+// beyond its device and stream.
+int omc_row_project_batch(omc_instance* h, int B, int R, int Rmax, int which, const double* G, const double* c, const double* lam0,
+                          double* lam, int* overflow) {
+  if (which != 0 && which != 1) return fail(OMC_ERR_ARGUMENT, "omc_row_project_batch: which must be 0 or 1");
+  if (!h) return fail(OMC_ERR_ARGUMENT, "omc_row_project_batch: handle is NULL");
+  if (B <= 0 || R <= 0 || Rmax < R) return fail(OMC_ERR_ARGUMENT, "omc_row_project_batch: need B > 0 and 0 < R <= Rmax");
+  if (!G || !c || !lam || !overflow) return fail(OMC_ERR_ARGUMENT, "omc_row_project_batch: G / c / lam / overflow is NULL");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t sB = (size_t)B, sR = (size_t)Rmax;
+  DevBuf buf;
+  double *dG = nullptr, *dc = nullptr, *dl = nullptr; int* dov = nullptr;
+  ENS_CARVE(buf, [&](Carve& cv) { dG = cv.take<double>(sB * sR * sR); dc = cv.take<double>(sB * sR); dl = cv.take<double>(sB * sR); dov = cv.take<int>(sB); });
+  hipStream_t st = h->stream;
+  HIPCHK(hipMemcpyAsync(dG, G, sB * sR * sR * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dc, c, sB * sR * 8, hipMemcpyHostToDevice, st));
+  if (lam0) HIPCHK(hipMemcpyAsync(dl, lam0, sB * sR * 8, hipMemcpyHostToDevice, st));
+  else HIPCHK(hipMemsetAsync(dl, 0, sB * sR * 8, st));
+  omc_launch_row_project(B, R, Rmax, which, dG, dc, dl, dov, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(lam, dl, sB * sR * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(overflow, dov, sB * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int omc_colprox_plan(int n, int cmax, int block_min, int64_t* out) {
   if (!out) return fail(OMC_ERR_ARGUMENT, "out is NULL");
   if (n <= 0 || cmax <= 0 || cmax > n) return fail(OMC_ERR_ARGUMENT, "omc_colprox_plan: need 0 < cmax <= n");

@@ -184,6 +184,8 @@ void omc_launch_colprox(const OmcWS* w, int mode, hipStream_t s);
 void omc_launch_cone(const OmcWS* w, int mode, hipStream_t s);
 void omc_launch_global(const OmcWS* w, hipStream_t s);
 void omc_launch_small(const OmcWS* w, int mode, hipStream_t s);
+/* step 4 of k_global alone, one wave per problem (omc_row_project_batch): which 0 = wave_nnqp, 1 = wave_nnqp_g */
+void omc_launch_row_project(int B, int R, int Rmax, int which, const double* G, const double* c, double* lam, int* overflow, hipStream_t s);
 void omc_launch_cone_ws(const OmcWS* w, hipStream_t s);
 void omc_launch_cone_mw(const OmcWS* w, hipStream_t s);      /* omc_cone_mw.hip: what omc_launch_cone_ws does when w->geo.mw is set */
 /* omc_cone_mw.hip: what omc_launch_cone does for mode CONE_SEP or CONE_TOPK when w->geo.plain_mw is set.  Always cold: input stage from

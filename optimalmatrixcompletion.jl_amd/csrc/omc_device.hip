@@ -2240,13 +2240,17 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   __syncthreads();
   STAMP(10);
   // 4. multipliers (mu = lam / rho)
-  if (tid < WAVE) { const int ov = wave_nnqp(G, w.Rmax, cvec, mu, R, s_Gp, s_sv, s_tmp, s_pl, tid); if (tid == 0) w.rowov[b] = ov; }
+  if (tid < WAVE) { const int ov = wave_nnqp_g(G, w.Rmax, cvec, mu, R, s_Gp, s_sv, s_tmp, s_pl, tid); if (tid == 0) w.rowov[b] = ov; }
   __syncthreads();
   for (int e = tid; e < R; e += T) lam[e] = rho * mu[e];
   // The rows with mu != 0, listed once in ascending order by wave 0 (s_pl, the projection's passive list, is idle again; the projection
   // leaves at most NNQP_PMAX of them): all of them for step 5, the cut rows among them (s_act, s_mu) and the sum over the trace rows for
-  // step 6.  The sums that use the lists add their terms in this order, as the loops over all rows did.
+  // step 6.  The sums that use the lists add their terms in this order, as the loops over all rows did.  What step 5 needs of a listed
+  // row is fetched here, once per row: its multiplier (s_sv, idle again like s_pl), its kind (s_rk), where its vector is (s_rx: a cut
+  // row's place in s_act, a bound row's cut index, a box row's i; s_rb: a box row's j) and its coefficients (s_tmp, when the list's fit).
   __shared__ int s_nact; __shared__ int s_act[NNQP_PMAX]; __shared__ double s_mu[NNQP_PMAX]; __shared__ double s_trace_mu;
+  static_assert(3 * NNQP_PMAX * sizeof(int) <= sizeof(s_qp), "the row descriptors of step 5 live in s_qp");
+  int *s_rk = (int*)&s_qp[0][0], *s_rx = s_rk + NNQP_PMAX, *s_rb = s_rx + NNQP_PMAX;      // step 3 is over: its partial sums are idle
   int& s_nnz = s_nc;      // step 3 is over: its counter holds the length of the list
   if (tid < WAVE) {
     int c0 = 0, c2 = 0; double tm = 0.0;
@@ -2254,12 +2258,19 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
     for (int r0 = 0; r0 < R; r0 += WAVE) {
       const int rr = r0 + tid;
       const double mv = (rr < R) ? mu[rr] : 0.0;
-      const int kind = (mv != 0.0) ? w.rkind[(size_t)nb * w.Rmax + rr] : -1;
+      const size_t d = (size_t)nb * w.Rmax + rr;
+      const int kind = (mv != 0.0) ? w.rkind[d] : -1;
       const unsigned long long nz = __ballot(mv != 0.0), cut = __ballot(kind == ROW_CUT);
       unsigned long long trc = __ballot(kind == ROW_TRACE);
       const int p0 = c0 + __popcll(nz & below), p2 = c2 + __popcll(cut & below);
-      if (mv != 0.0 && p0 < NNQP_PMAX) s_pl[p0] = rr;
-      if (kind == ROW_CUT && p2 < NNQP_PMAX) { s_act[p2] = w.rcut[(size_t)nb * w.Rmax + rr]; s_mu[p2] = mv; }
+      const int rc = (kind == ROW_CUT || kind == ROW_BOUND) ? w.rcut[d] : 0;
+      if (mv != 0.0 && p0 < NNQP_PMAX) {
+        s_pl[p0] = rr; s_sv[p0] = mv; s_rk[p0] = kind;
+        s_rx[p0] = (kind == ROW_CUT) ? p2 : (kind == ROW_BOX) ? w.rbi[d] : rc;
+        s_rb[p0] = (kind == ROW_BOX) ? w.rbj[d] : 0;
+        if ((p0 + 1) * k <= NNQP_PMAX) for (int j = 0; j < k; ++j) s_tmp[p0 * k + j] = w.rcoef[d * k + j];
+      }
+      if (kind == ROW_CUT && p2 < NNQP_PMAX) { s_act[p2] = rc; s_mu[p2] = mv; }
       for (; trc; trc &= trc - 1) tm += mu[r0 + __builtin_ctzll(trc)];
       c0 += __popcll(nz); c2 += __popcll(cut);
     }
@@ -2267,19 +2278,39 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   }
   __syncthreads();
   STAMP(11);
-  // 5. U-space correction  corr = A_U' mu / 2  (n x k, stored over tU)  and Vn = tV - Q' corr
-  const int nnz = s_nnz;
-  for (int e = tid; e < n * k; e += T) {
-    int i = e % n, j = e / n;
-    double corr = 0.0;
-    for (int c = 0; c < nnz; ++c) { const int rr = s_pl[c]; corr += mu[rr] * rowU_entry(w, nb, rr, i, j); }
-    tU[e] = 0.5 * corr;
-  }
-  // for step 6: the first GL_XS active cut vectors go to xs (the projection is done with the Gram matrix there), the Ritz vectors of the
-  // factored W1 back to s_Gp
+  // for steps 5 and 6: the first GL_XS active cut vectors go to xs (the projection is done with the Gram matrix there), the Ritz vectors
+  // of the factored W1 back to s_Gp
   const int nact = s_nact, nstg = (nact < GL_XS) ? nact : GL_XS;
   for (int e = tid; e < nstg * n; e += T) { const int a = e / n, i = e - a * n; xs[e] = cutx[(size_t)s_act[a] * n + i]; }
   if (f1) stage_w1();
+  __syncthreads();
+  // 5. U-space correction  corr = A_U' mu / 2  (n x k, stored over tU)  and Vn = tV - Q' corr.  The entry of a listed row is rowU_entry's:
+  //    0 for the trace row, the coefficient at a box row's own entry, x_i * coef_j for a cut or bound row -- x from xs where step 6 has it
+  //    staged (a cut row whose place in s_act is below nstg), from cutx otherwise.
+  const int nnz = s_nnz;
+  const bool cfl = nnz * k <= NNQP_PMAX;
+  const double* rcf = w.rcoef + (size_t)nb * w.Rmax * k;
+  for (int e = tid; e < n * k; e += T) {
+    int i = e % n, j = e / n;
+    double corr = 0.0;
+    for (int c = 0; c < nnz; ++c) {
+      const int kind = s_rk[c], rx = s_rx[c];      // uniform over the workgroup: no divergence below
+      double ent = 0.0;
+      if (kind != ROW_TRACE) {
+        const int jc = (kind == ROW_BOX) ? 0 : j;
+        const double cf = cfl ? s_tmp[c * k + jc] : rcf[(size_t)s_pl[c] * k + jc];
+        if (kind == ROW_BOX) ent = (rx == i && s_rb[c] == j) ? cf : 0.0;
+        else {
+          double xv;
+          if (kind == ROW_CUT && rx < nstg) xv = xs[(size_t)rx * n + i];
+          else xv = cutx[(size_t)((kind == ROW_CUT) ? s_act[rx] : rx) * n + i];
+          ent = xv * cf;
+        }
+      }
+      corr += s_sv[c] * ent;
+    }
+    tU[e] = 0.5 * corr;
+  }
   __syncthreads();
   double rp2 = 0.0, rd2 = 0.0, fr2 = 0.0, tr1 = 0.0;
   double* Mb = w.Mbuf + (size_t)b * NP * NP;
@@ -2358,6 +2389,22 @@ __global__ void __launch_bounds__(512) k_global(OmcWS w) {
   fr2 = block_sum(fr2, red);
   tr1 = block_sum(tr1, red);
   if (tid == 0) { w.rp[b] = sqrt(rp2); w.rd[b] = sqrt(rd2); w.fro2[b] = fr2; w.trM[b] = tr1; w.cone_done[b] = 0; if (w.w1_fac) w.w1_fac[b] = 0; w.iters[b] += 1; if (w.ws_first) { const int f = (!w.sub_on[b] || w.sub_wait[b] > 0) ? 1 : 0; w.ws_first[b] = f; if (f && w.ws_need) *w.ws_need = 1; } DIAG_CYC(4, b); }
+}
+
+// Step 4 of k_global alone (omc_row_project_batch): one wave per problem; G (R x R, ld Rmax), c and lam (Rmax) of problem b at b * Rmax^2 /
+// b * Rmax.  WHICH 0: wave_nnqp, the routines of the altmin kernels; 1: wave_nnqp_g, what k_global runs.
+template <int WHICH>
+__global__ void __launch_bounds__(WAVE) k_row_project(const double* G, const double* c, double* lam, int* overflow, int R, int Rmax) {
+  __shared__ double s_Gp[NNQP_GP_DOUBLES];
+  __shared__ double s_sv[NNQP_PMAX], s_tmp[NNQP_PMAX];
+  __shared__ int s_pl[NNQP_PMAX];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const double* Gb = G + (size_t)b * Rmax * Rmax;
+  const double* cb = c + (size_t)b * Rmax;
+  double* lb = lam + (size_t)b * Rmax;
+  const int ov = WHICH ? wave_nnqp_g(Gb, Rmax, cb, lb, R, s_Gp, s_sv, s_tmp, s_pl, lane)
+                       : wave_nnqp(Gb, Rmax, cb, lb, R, s_Gp, s_sv, s_tmp, s_pl, lane);
+  if (lane == 0) overflow[b] = ov;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -3128,6 +3175,10 @@ void omc_launch_small(const OmcWS* w, int mode, hipStream_t s) {
 void omc_launch_global(const OmcWS* w, hipStream_t s) {
   if (w->geo.glob.use_lds) hipLaunchKernelGGL(k_global<true>, dim3(w->nB), dim3(512), w->geo.glob.lds_bytes, s, *w);
   else hipLaunchKernelGGL(k_global<false>, dim3(w->nB), dim3(512), 0, s, *w);
+}
+void omc_launch_row_project(int B, int R, int Rmax, int which, const double* G, const double* c, double* lam, int* overflow, hipStream_t s) {
+  if (which) hipLaunchKernelGGL(k_row_project<1>, dim3(B), dim3(WAVE), 0, s, G, c, lam, overflow, R, Rmax);
+  else hipLaunchKernelGGL(k_row_project<0>, dim3(B), dim3(WAVE), 0, s, G, c, lam, overflow, R, Rmax);
 }
 void omc_launch_check_zero(const OmcWS* w, hipStream_t s) { hipLaunchKernelGGL(k_zero_check, dim3((w->B + 63) / 64), dim3(64), 0, s, *w); }
 void omc_launch_check_build(const OmcWS* w, hipStream_t s) { hipLaunchKernelGGL(k_check_build, dim3(w->B), dim3(512), 0, s, *w); }

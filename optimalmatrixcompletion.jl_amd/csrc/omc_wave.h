@@ -384,4 +384,246 @@ __device__ __forceinline__ int wave_nnqp(const double* G, int ldG, const double*
   return overflow;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The row projection of k_global: wave_nnqp<false> with the dependent round trips taken out.  Every product, sum, quotient and
+// square root is the one wave_cholesky / wave_chol_solve / wave_nnqp form, with the same operands and the sums in the same order
+// and tree, so the results are the same bits (tests/test_row_project.py compares the two through omc_row_project_batch).  The
+// altmin kernels keep the routines above.
+// ---------------------------------------------------------------------------------------------------------
+// lane l gets v of lane l - 1, lane 0 gets in0 (DPP wave_shr:1; lanes without a source keep the old operand)
+__device__ __forceinline__ double wave_shr1_d(double v, double in0) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(in0), __double2loint(v), 0x138, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(in0), __double2hiint(v), 0x138, 0xF, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+
+// wave-wide max / min / or / arg-max on the VALU like wave_sum (DPP inside a row of 16 lanes, four scalar reads): these are exact in any
+// order, so they stand in for the shuffle loops of wave_nnqp; the result is wave-uniform
+__device__ __forceinline__ int dpp_move_i(int v, const int ctrl_sel) {
+  switch (ctrl_sel) {
+    case 0: return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
+    case 1: return __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
+    case 2: return __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);
+    default: return __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);
+  }
+}
+__device__ __forceinline__ double wave_fmax(double v) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) v = fmax(v, dpp_move(v, s));
+  return fmax(fmax(readlane_d(v, 0), readlane_d(v, 16)), fmax(readlane_d(v, 32), readlane_d(v, 48)));
+}
+__device__ __forceinline__ double wave_fmin(double v) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) v = fmin(v, dpp_move(v, s));
+  return fmin(fmin(readlane_d(v, 0), readlane_d(v, 16)), fmin(readlane_d(v, 32), readlane_d(v, 48)));
+}
+__device__ __forceinline__ unsigned long long wave_or64(unsigned long long v) {
+  int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) { lo |= dpp_move_i(lo, s); hi |= dpp_move_i(hi, s); }
+  const unsigned l = (unsigned)(__builtin_amdgcn_readlane(lo, 0) | __builtin_amdgcn_readlane(lo, 16) | __builtin_amdgcn_readlane(lo, 32) | __builtin_amdgcn_readlane(lo, 48));
+  const unsigned h = (unsigned)(__builtin_amdgcn_readlane(hi, 0) | __builtin_amdgcn_readlane(hi, 16) | __builtin_amdgcn_readlane(hi, 32) | __builtin_amdgcn_readlane(hi, 48));
+  return ((unsigned long long)h << 32) | l;
+}
+// the larger value, the smaller index among equal values (an index below 0 is no candidate): wave_nnqp's rule for the violated row
+__device__ __forceinline__ void argmax_take(double& best, int& bi, double ob, int oi) {
+  if (ob > best || (ob == best && oi >= 0 && (bi < 0 || oi < bi))) { best = ob; bi = oi; }
+}
+__device__ __forceinline__ void wave_argmax(double& best, int& bi) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) { const double ob = dpp_move(best, s); const int oi = dpp_move_i(bi, s); argmax_take(best, bi, ob, oi); }
+  double b0 = readlane_d(best, 0); int i0 = __builtin_amdgcn_readlane(bi, 0);
+#pragma unroll
+  for (int l = 16; l < 64; l += 16) argmax_take(b0, i0, readlane_d(best, l), __builtin_amdgcn_readlane(bi, l));
+  best = b0; bi = i0;
+}
+
+// row of entry e of a packed lower triangle: the largest r with r (r + 1) / 2 <= e (e < 2^20: the float square root is off by one at most)
+__device__ __forceinline__ int tri_row(int e) {
+  int r = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
+  if (tri_i(r, 0) > e) --r;
+  if (tri_i(r + 1, 0) <= e) ++r;
+  return r;
+}
+
+// wave_cholesky and the forward sweep of wave_chol_solve for c <= WAVE in one loop, so that the reduction and the division of a row run in
+// the shadow of the column's LDS round trips.
+// The factorisation, two wave barriers per column and one LDS round trip less: the diagonal entry is written behind the first barrier,
+// beside the trailing update (which reads the column below it only), so the read of the pivot needs no barrier of its own in front of the
+// scaling; the trailing update walks the t (t + 1) / 2 entries of the lower triangle instead of t^2 indices with half the lanes skipped
+// (every entry still gets its updates in ascending k, whichever lane does them); lane 0 updates the next pivot in its first trip and
+// hands it on by v_readlane.
+// The forward sweep with the vector in registers: row kk of L is final left of the diagonal when column kk is reached, and its diagonal
+// entry is the d at hand.  The strided loop of wave_chol_solve gives every lane at most one term per row, lane q the term of y[q]: lane q
+// keeps y[q], forms that term (exactly 0.0 where the loop adds nothing), the same wave_sum adds the same tree, rhs[kk] is broadcast with
+// v_readlane and the quotient is the same division.  yv: y[lane] on exit (true); nothing is written to LDS for it.
+__device__ __forceinline__ bool wave_cholesky_fwd_g(double* Lm, int c, const double* rhs, double& yv, int lane) {
+  const double rv = (lane < c) ? rhs[lane] : 0.0;
+  yv = 0.0;
+  double piv = Lm[0];
+  for (int kk = 0; kk < c; ++kk) {
+    if (!(piv > 0.0)) return false;
+    const double d = sqrt(piv);
+    const double l = (lane < kk) ? Lm[tri_i(kk, lane)] : 0.0;
+    for (int r = kk + 1 + lane; r < c; r += WAVE) Lm[tri_i(r, kk)] = Lm[tri_i(r, kk)] / d;
+    double p = 0.0;
+    if (lane < kk) p += l * yv;
+    p = wave_sum(p);
+    const double v = (readlane_d(rv, kk) - p) / d;
+    if (lane == kk) yv = v;
+    WAVE_SYNC();
+    if (lane == 0) Lm[tri_i(kk, kk)] = d;
+    const int t = c - kk - 1;
+    const int tot = tri_i(t, 0);
+    double first = 0.0;
+    for (int e = lane; e < tot; e += WAVE) {
+      const int rr = tri_row(e), qq = e - tri_i(rr, 0);
+      const int r = kk + 1 + rr, q = kk + 1 + qq;
+      double u = Lm[tri_i(r, q)];
+      u -= Lm[tri_i(r, kk)] * Lm[tri_i(q, kk)];
+      Lm[tri_i(r, q)] = u;
+      if (e == lane) first = u;
+    }
+    piv = readlane_d(first, 0);      // entry (kk + 1, kk + 1), when there is one
+    WAVE_SYNC();
+  }
+  return true;
+}
+
+// the backward sweep of wave_chol_solve for c <= WAVE from the forward result in registers (yv: lane q holds y[q]): lane l forms the
+// term of x[r + 1 + l], as the strided loop has it, from a copy of x shifted along the lanes, so every term stays on the lane that
+// formed it and wave_sum adds the same tree; the column of L is fetched one row ahead; x is written to y[] once at the end.
+__device__ __forceinline__ void wave_chol_back_g(const double* Lm, int c, double yv, double* y, int lane) {
+  const bool in = lane < c;
+  const double dg = in ? Lm[tri_i(in ? lane : 0, in ? lane : 0)] : 1.0;
+  double xv = 0.0, ysh = 0.0, l = 0.0;      // ysh at row r: lane l holds x[r + 1 + l]
+  for (int r = c - 1; r >= 0; --r) {
+    const double ln = (r >= 1 && r + lane < c) ? Lm[tri_i(r + lane, r - 1)] : 0.0;
+    double p = 0.0;
+    if (r + 1 + lane < c) p += l * ysh;
+    p = wave_sum(p);
+    const double v = (readlane_d(yv, r) - p) / readlane_d(dg, r);
+    if (lane == r) xv = v;
+    ysh = wave_shr1_d(ysh, v);
+    l = ln;
+  }
+  if (in) y[lane] = xv;
+  WAVE_SYNC();
+}
+
+// wave_nnqp<false> for k_global (same arguments, same result): the warm-start list by ballot, dmax lane-parallel, the passive set as a
+// 64-bit mask in the KKT test when R <= 64, the max / min / arg-max reductions on the VALU, and the routines above for the passive system
+__device__ __forceinline__ int wave_nnqp_g(const double* G, int ldG, const double* cvec, double* lam, int R, double* Gp, double* sv,
+                                           double* tmp, int* plist, int lane) {
+  int np = 0;
+  int overflow = 0;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  // warm start: passive = {lam > 0} in ascending order, the first NNQP_PMAX of them; every other non-zero entry is zeroed
+  for (int r0 = 0; r0 < R; r0 += WAVE) {
+    const int r = r0 + lane;
+    const double lv = (r < R) ? lam[r] : 0.0;
+    const bool pos = lv > 0.0;
+    const unsigned long long mk = __ballot(pos);
+    const int p = np + __popcll(mk & below);
+    if (pos && p < NNQP_PMAX) plist[p] = r;
+    else if (lv != 0.0) lam[r] = 0.0;
+    if (__ballot(pos && p >= NNQP_PMAX)) overflow = 1;
+    np += __popcll(mk);
+    if (np > NNQP_PMAX) np = NNQP_PMAX;
+  }
+  WAVE_SYNC();
+  double cmax = 0.0;
+  for (int r = lane; r < R; r += WAVE) cmax = fmax(cmax, fabs(cvec[r]));
+  cmax = wave_fmax(cmax);
+  const double tol = 1e-13 * fmax(cmax, 1e-300);
+  bool need_inner = (np > 0);
+  for (int outer = 0; outer < 3 * R + 10; ++outer) {
+    if (!need_inner) {
+      // w = c - G lam over non-passive rows; pick the max
+      unsigned long long pm = 0ull;
+      if (R <= WAVE) {
+        pm = wave_or64((lane < np) ? (1ull << plist[lane]) : 0ull);
+      }
+      double best = -1e300; int bi = -1;
+      for (int r = lane; r < R; r += WAVE) {
+        bool inP = false;
+        if (R <= WAVE) inP = (pm >> r) & 1ull;
+        else for (int a = 0; a < np; ++a) if (plist[a] == r) inP = true;
+        if (inP) continue;
+        double wv = cvec[r];
+        for (int a = 0; a < np; ++a) wv -= G[(size_t)r * ldG + plist[a]] * lam[plist[a]];
+        if (wv > best) { best = wv; bi = r; }
+      }
+      wave_argmax(best, bi);
+      if (bi < 0 || best <= tol) { overflow = 0; break; }      // every row satisfied: whatever was dropped at the warm start is not needed
+      if (np >= NNQP_PMAX) { overflow = 1; break; }
+      if (lane == 0) plist[np] = bi;
+      ++np;
+      WAVE_SYNC();
+    }
+    need_inner = false;
+    // inner loop
+    for (int inner = 0; inner < 3 * NNQP_PMAX + 10; ++inner) {
+      for (int e = lane; e < tri_i(np, 0); e += WAVE) {      // the lower triangle, entry by entry
+        const int a = tri_row(e), c2 = e - tri_i(a, 0);
+        Gp[e] = G[(size_t)plist[a] * ldG + plist[c2]];
+      }
+      double dmax = 0.0;      // np <= WAVE: one entry per lane; fmax is exact in any order
+      if (lane < np) dmax = fmax(dmax, G[(size_t)plist[lane] * ldG + plist[lane]]);
+      dmax = wave_fmax(dmax);
+      WAVE_SYNC();
+      for (int a = lane; a < np; a += WAVE) { Gp[tri_i(a, a)] += 1e-14 * dmax; tmp[a] = cvec[plist[a]]; }
+      WAVE_SYNC();
+      double yv;
+      bool ok = wave_cholesky_fwd_g(Gp, np, tmp, yv, lane);
+      if (!ok) {  // numerically singular: drop the newest index
+        --np; WAVE_SYNC();
+        if (np == 0) break;
+        continue;
+      }
+      wave_chol_back_g(Gp, np, yv, sv, lane);
+      // all positive?
+      double mins = 1e300;
+      for (int a = lane; a < np; a += WAVE) mins = fmin(mins, sv[a]);
+      mins = wave_fmin(mins);
+      if (mins > 0.0) {
+        for (int a = lane; a < np; a += WAVE) lam[plist[a]] = sv[a];
+        WAVE_SYNC();
+        break;
+      }
+      // step toward s until the first multiplier hits zero
+      double al = 1e300;
+      for (int a = lane; a < np; a += WAVE) {
+        double lv = lam[plist[a]];
+        if (sv[a] <= 0.0) al = fmin(al, lv / (lv - sv[a]));
+      }
+      al = wave_fmin(al);
+      if (!(al >= 0.0)) al = 0.0;
+      for (int a = lane; a < np; a += WAVE) {
+        double lv = lam[plist[a]];
+        lam[plist[a]] = lv + al * (sv[a] - lv);
+      }
+      WAVE_SYNC();
+      // remove zeros (serial compaction, uniform)
+      int nn = 0; double minl = 1e300; int mini = -1;
+      for (int a = 0; a < np; ++a) {
+        double lv = lam[plist[a]];
+        if (sv[a] <= 0.0 && lv < minl) { minl = lv; mini = a; }
+      }
+      for (int a = 0; a < np; ++a) {
+        int r = plist[a];
+        double lv = lam[r];
+        bool drop = (sv[a] <= 0.0) && (lv <= 1e-18 * fmax(cmax, 1e-300) || a == mini);
+        WAVE_SYNC();
+        if (drop) { if (lane == 0) lam[r] = 0.0; }
+        else { if (lane == 0) { plist[nn] = r; } ++nn; }
+        WAVE_SYNC();
+      }
+      np = nn;
+      if (np == 0) break;
+    }
+  }
+  return overflow;
+}
+
 #endif
