@@ -1742,6 +1742,253 @@ __device__ __forceinline__ void mfma_LLt(const double* L, int n, int m, StoreF s
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// small_proj_chain: k_small's projection (SMALL_PROJ, LDS variant, r <= 16, n <= 256) with a shorter chain of dependent steps.  Operands,
+// order of every sum, MFMA K order and reduction trees are those of the body in k_small below (kept behind OMC_SMALL_CHAIN=0); what differs
+// is where a value is read, how many loads are in flight, which wave does a piece and how many barriers lie between the pieces:
+//   T1    two row tiles (wv, wv + 4) per wave at once, the first chunk of Y and D3 requested before Q' is staged
+//   M3    Q from its staged copy Qs
+//   eigen the symmetrised entry formed once (Ss), the previous eigenvectors fetched at the top of the kernel (Vs); the wave that ran the sweep
+//         forms the squared norms and the selection list (ballot, ascending t as the serial walk lists them): one barrier instead of three
+//   Q dS  Q from Qs, dS from an LDS copy the rebuild's store writes beside the global array (lane a owns column a of the symmetric dS)
+//   rebuild  a thread per entry of the lower triangle instead of a thread per 4 x 4 tile
+//   E3    a wave owns column tiles and keeps their B operand in registers (two tiles per wave at once read 8.2 us against 7.5: not taken)
+// ---------------------------------------------------------------------------------------------------------
+#define SMALL_T1_NC 1      // chunks of 16 columns of Y and D3 a wave has requested ahead per tile (2: 174 VGPRs, two workgroups per CU instead of three)
+template <bool TWO>
+__device__ __forceinline__ void small_T1_tiles(const double* Y, const double* D3, const double* Qs, double* T1, int n, int r, int t0, int t1, int li, int lk,
+                                               double (&ya)[2][4 * SMALL_T1_NC], double (&da)[2][4 * SMALL_T1_NC]) {
+  constexpr int NT = TWO ? 2 : 1;
+  const int tt[2] = {t0, t1};
+  bool va[2]; int iac[2];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) { const int ia = (tt[t] << 4) + li; va[t] = ia < n; iac[t] = va[t] ? ia : 0; }
+  double4v acc[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+  for (int k0 = 0; k0 < n; k0 += 16 * SMALL_T1_NC) {
+#pragma unroll
+    for (int c = 0; c < SMALL_T1_NC; ++c) {
+      if (c > 0 && k0 + 16 * c >= n) break;      // the MFMA sequence of a tile is that of k_small: ceil(n / 16) chunks, none beyond
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int kk = k0 + 16 * c + 4 * u + lk; const bool vk = kk < n;
+        const double bv = Qs[(vk ? kk : 0) * 16 + li];
+        const int kn = kk + 16 * SMALL_T1_NC, knc = (kn < n) ? kn : 0;          // prefetch (the value past the end is not used)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const double av = ya[t][4 * c + u] - da[t][4 * c + u];
+          ya[t][4 * c + u] = Y[(size_t)knc * n + iac[t]]; da[t][4 * c + u] = D3[(size_t)knc * n + iac[t]];
+          acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64((va[t] && vk) ? av : 0.0, vk ? bv : 0.0, acc[t], 0, 0, 0);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r4 = 0; r4 < 4; ++r4) {
+      const int row = (tt[t] << 4) + lk + 4 * r4;
+      if (row < n && li < r) T1[(size_t)li * n + row] = acc[t][r4];
+    }
+}
+// the list of the eigenpairs the rebuild sums (k_small, SMALL_PROJ) by the lanes of one wave, N3 <= 64: lane t holds ev_t = ev[t]
+__device__ __forceinline__ void small_select_wave(double ev_t, double sigma, int N3, int* sel, double* wgt, int* s_nsel, double* s_base) {
+  const int t = threadIdx.x & 63;
+  const bool valid = t < N3;
+  const double lamv = sqrt(ev_t) - sigma;
+  const unsigned long long pos = __ballot(valid && lamv > 0.0), neg = __ballot(valid && lamv < 0.0);
+  const bool use_neg = __popcll(neg) <= __popcll(pos);
+  const unsigned long long m = use_neg ? neg : pos;
+  if ((m >> t) & 1ull) { const int c = __popcll(m & ((1ull << t) - 1ull)); sel[c] = t; wgt[c] = fabs(lamv) / ev_t; }
+  if (t == 0) { *s_nsel = __popcll(m); *s_base = use_neg ? 1.0 : 0.0; }   // base=1: acc is Q3; base=0: acc is P3
+}
+__device__ __forceinline__ void small_proj_chain(const OmcWS& w, int b, int nb, double* base, double* red, int* s_cnt, int* s_nsel, double* s_base) {
+  const int tid = threadIdx.x, T = blockDim.x, wv = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4, nw = T >> 6;
+  const int n = w.n, k = w.k, rm = w.rmax;
+  const int r = w.rr[nb];
+  const int N3 = r + k;
+  const int Np = (N3 + 1) & ~1, ld = Np | 1, nt = (n + 15) >> 4;
+  const SmallLayout L = small_layout(n, rm, k);
+  const int ld3 = L.ld3;
+  double* T1 = base;
+  double* M3 = base + L.M3;
+  double *Gm = base + L.Gm, *ev = base + L.ev, *wgt = base + L.wgt;
+  int* sel = (int*)(base + L.sel);
+  double* Qs = base + L.Qs;
+  double *Ss = base + L.Cs, *Vs = base + L.Cs + 256, *dSs = base + L.Cs;      // dSs takes the place of Ss once the sweep has started
+  const double* Q = w.Qb + (size_t)nb * n * rm;
+  const double* Y = w.Y + (size_t)b * n * n;
+  const double* D3 = w.D3 + (size_t)b * n * n;
+  const double* Vt = w.Vt + (size_t)b * rm * k;
+  const bool wave16 = Np <= 16;
+  double* Vp = w.V3 + (size_t)b * 256;
+  const bool warm = wave16 && w.v3valid[b] != 0;
+  STAMP_BEGIN();
+  DIAG_T0();
+  // ---- T1 = (Y - D3) Q: the first chunk of this wave's first two tiles is on its way while Q' is staged (coalesced reads of Q)
+  double ya[2][4 * SMALL_T1_NC], da[2][4 * SMALL_T1_NC];
+  auto first_chunk = [&](int t, int tile) {
+    const int ia = (tile << 4) + li, iac = (ia < n) ? ia : 0;
+#pragma unroll
+    for (int u = 0; u < 4 * SMALL_T1_NC; ++u) { const int kk = 4 * u + lk, kc = (kk < n) ? kk : 0; ya[t][u] = Y[(size_t)kc * n + iac]; da[t][u] = D3[(size_t)kc * n + iac]; }
+  };
+  if (wv < nt) first_chunk(0, wv);
+  if (wv + nw < nt) first_chunk(1, wv + nw);
+  const double vprev = (warm && tid < 256) ? Vp[tid] : 0.0;
+  {
+    const int qd = T / n, qr = T - qd * n;
+    int a = tid / n, j = tid - a * n;
+    for (int e = tid; e < n * 16; e += T) {
+      Qs[j * 16 + a] = (a < r) ? Q[(size_t)a * n + j] : 0.0;
+      a += qd; j += qr; if (j >= n) { j -= n; ++a; }
+    }
+  }
+  __syncthreads();
+  for (int tb = wv; tb < nt; tb += 2 * nw) {
+    const bool two = tb + nw < nt;
+    if (tb != wv) { first_chunk(0, tb); if (two) first_chunk(1, tb + nw); }
+    if (two) small_T1_tiles<true>(Y, D3, Qs, T1, n, r, tb, tb + nw, li, lk, ya, da);
+    else small_T1_tiles<false>(Y, D3, Qs, T1, n, r, tb, tb, li, lk, ya, da);
+  }
+  __syncthreads();
+  STAMP(16);
+  // ---- M3
+  for (int e = tid; e < N3 * N3; e += T) {
+    int i = e % N3, j = e / N3;
+    double v;
+    if (i < r && j < r) { v = 0.0; for (int t = 0; t < n; ++t) v += Qs[t * 16 + i] * T1[(size_t)j * n + t]; }
+    else if (i < r) v = Vt[(size_t)(j - r) * rm + i] - w.D3V[(size_t)b * rm * k + (size_t)(j - r) * rm + i];
+    else if (j < r) v = Vt[(size_t)(i - r) * rm + j] - w.D3V[(size_t)b * rm * k + (size_t)(i - r) * rm + j];
+    else v = ((i == j) ? 1.0 : 0.0) - w.D3T[(size_t)b * k * k + (size_t)(j - r) * k + (i - r)];
+    M3[(size_t)j * ld3 + i] = v;
+  }
+  __syncthreads();
+  STAMP(17);
+  auto entry = [&](int i, int j) { return M3[(size_t)j * ld3 + i]; };
+  double sigma;
+  if (wave16) {
+    if (tid < 256) Vs[tid] = vprev;
+    double fro = 0.0;
+    for (int e = tid; e < N3 * N3; e += T) { const int i = e % N3, j = e / N3; const double v = 0.5 * (entry(i, j) + entry(j, i)); fro += v * v; Ss[j * 16 + i] = v; }
+    fro = sqrt(block_sum(fro, red));
+    sigma = 1.5 * fro + 1e-300;
+    for (int e = tid; e < Np * Np; e += T) {
+      const int i = e % Np, t = e / Np;
+      double v = 0.0;
+      if (i < N3 && t < N3) {
+        if (warm) { for (int j = 0; j < N3; ++j) v += (Ss[j * 16 + i] + ((i == j) ? sigma : 0.0)) * Vs[t * 16 + j]; }
+        else v = Ss[t * 16 + i] + ((i == t) ? sigma : 0.0);
+      }
+      Gm[(size_t)t * ld + i] = v;
+    }
+    __syncthreads();
+    STAMP(30);
+    if (tid < WAVE) {
+      jacobi_sweeps_wave16(Gm, ev, N3, Np, ld, 1e-14, 30);
+      WAVE_SYNC();
+      double a = 0.0;
+      if (tid < N3) { for (int i = 0; i < N3; ++i) { const double x = Gm[(size_t)tid * ld + i]; a += x * x; } ev[tid] = a; }
+      small_select_wave(a, sigma, N3, sel, wgt, s_nsel, s_base);
+    }
+    __syncthreads();
+    for (int e = tid; e < N3 * N3; e += T) { const int i = e % N3, t = e / N3; Vp[t * 16 + i] = Gm[(size_t)t * ld + i] * rsqrt(ev[t]); }
+    if (tid == 0) w.v3valid[b] = 1;
+  } else {
+    sigma = eig_frontend(Gm, ev, N3, Np, ld, entry, red, s_cnt, nullptr);
+    if (N3 <= WAVE) { if (tid < WAVE) small_select_wave((tid < N3) ? ev[tid] : 0.0, sigma, N3, sel, wgt, s_nsel, s_base); }
+    else if (tid == 0) {
+      int npos = 0, nneg = 0;
+      for (int t = 0; t < N3; ++t) { double lamv = sqrt(ev[t]) - sigma; if (lamv > 0.0) ++npos; else if (lamv < 0.0) ++nneg; }
+      const bool use_neg = nneg <= npos;
+      int c = 0;
+      for (int t = 0; t < N3; ++t) {
+        double nu2 = ev[t], lamv = sqrt(nu2) - sigma;
+        if (use_neg ? (lamv < 0.0) : (lamv > 0.0)) { sel[c] = t; wgt[c] = fabs(lamv) / nu2; ++c; }
+      }
+      *s_nsel = c; *s_base = use_neg ? 1.0 : 0.0;
+    }
+    __syncthreads();
+  }
+  STAMP(18);
+  // ---- Q3 = P3 - M3 = sum_{lam<0} |lam| v v'   (or P3 directly when fewer positive eigenvalues)
+  const double sb = *s_base;
+  const bool acc_is_Q3 = (sb == 1.0);
+  double* dS = w.dS + (size_t)b * rm * rm;
+  auto store = [&](int i, int j, double v, double Mv) {
+    double accv = v - sb * Mv;
+    double q3 = acc_is_Q3 ? accv : (accv - Mv);
+    double p3 = acc_is_Q3 ? (Mv + accv) : accv;
+    if (i < r && j < r) { dS[(size_t)j * rm + i] = q3; dS[(size_t)i * rm + j] = q3; dSs[j * 16 + i] = q3; dSs[i * 16 + j] = q3; }
+    else if (i >= r && j < r) {
+      w.W3V[(size_t)b * rm * k + (size_t)(i - r) * rm + j] = p3;
+      w.Q3V[(size_t)b * rm * k + (size_t)(i - r) * rm + j] = q3;
+    } else if (i >= r && j >= r) {
+      w.W3T[(size_t)b * k * k + (size_t)(j - r) * k + (i - r)] = p3; w.W3T[(size_t)b * k * k + (size_t)(i - r) * k + (j - r)] = p3;
+      w.Q3T[(size_t)b * k * k + (size_t)(j - r) * k + (i - r)] = q3; w.Q3T[(size_t)b * k * k + (size_t)(i - r) * k + (j - r)] = q3;
+    }
+  };
+  {
+    // spectral_rebuild's sum entry by entry (acc += g[i] * (g[j] * wgt), the pairs in list order) with a thread per entry of the lower
+    // triangle instead of a thread per 4 x 4 tile: ten threads would carry the order-13 matrix of config 2
+    const int nsel = *s_nsel;
+    for (int e = tid; e < N3 * N3; e += T) {
+      const int i = e % N3, j = e / N3;
+      if (i < j) continue;
+      double acc = 0.0;
+      for (int s = 0; s < nsel; ++s) { const double* gt = Gm + (size_t)sel[s] * ld; const double gj = gt[j] * wgt[s]; acc += gt[i] * gj; }
+      const double Mv = entry(i, j);
+      store(i, j, sb * Mv + acc, Mv);
+    }
+  }
+  __syncthreads();
+  STAMP(19);
+  // ---- T1 <- Q dS (n x r).  dS is symmetric (the store writes both mirror entries): lane a reads its column as the row dSs[. * 16 + a],
+  // once; the sum over c2 ascends as in k_small
+  {
+    const int a = tid & 15;
+    double dcol[16];
+#pragma unroll
+    for (int c2 = 0; c2 < 16; ++c2) dcol[c2] = (c2 < r && a < r) ? dSs[c2 * 16 + a] : 0.0;
+    if (a < r)
+      for (int i = tid >> 4; i < n; i += T >> 4) {
+        double q[16];
+#pragma unroll
+        for (int c2 = 0; c2 < 16; ++c2) q[c2] = Qs[i * 16 + c2];
+        double acc = 0.0;
+#pragma unroll
+        for (int c2 = 0; c2 < 16; ++c2) if (c2 < r) acc += q[c2] * dcol[c2];
+        T1[(size_t)a * n + i] = acc;
+      }
+  }
+  __syncthreads();
+  STAMP(29);
+  // ---- E3 = T1 Q' on the matrix cores, written through the transposed position as in k_small.  A wave owns the column tiles wv, wv + 4, ..:
+  // the B operand (16 lanes read Qs at a stride of 128 bytes, an eight-way bank conflict) is fetched once per column tile, not once per tile
+  double* E3 = w.E3 + (size_t)b * n * n;
+  for (int tj = wv; tj < nt; tj += nw) {
+    const int jb = (tj << 4) + li; const bool vb = jb < n; const int jbc = vb ? jb : 0;
+    double bq[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { const double bv = Qs[jbc * 16 + 4 * u + lk]; bq[u] = vb ? bv : 0.0; }
+    for (int ti = 0; ti < nt; ++ti) {
+      const int ia = (ti << 4) + li; const bool va = ia < n; const int iac = va ? ia : 0;
+      double4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int a = 4 * u + lk; const bool vk = a < r;
+        const double av = T1[(size_t)(vk ? a : 0) * n + iac];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64((va && vk) ? av : 0.0, bq[u], acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) {
+        const int row = (ti << 4) + lk + 4 * r4, col = (tj << 4) + li;
+        if (row < n && col < n) E3[(size_t)row * n + col] = acc[r4];
+      }
+    }
+  }
+  STAMP(20);
+  if (tid == 0) DIAG_CYC(5, b);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // k_small: the small cone  [S Vt; Vt' T] >= 0,  S = Q'(Y - D3)Q (r x r),  Vt - D3V (r x k),  T = I - D3T.
 //   mode SMALL_PROJ   : P3 = P_+(M3);  Q3 = P3 - M3 (>= 0: the multiplier direction);
 //                       dS = Q3_11, E3 = Q dS Q' (n x n), W3V = P3_12, W3T = P3_22, Q3V = Q3_12, Q3T = Q3_22
@@ -1775,10 +2022,13 @@ __global__ void __launch_bounds__(256) k_small(OmcWS w, int mode) {
   const double* Y = w.Y + (size_t)b * n * n;
   const double* D3 = w.D3 + (size_t)b * n * n;
   const double* Vt = w.Vt + (size_t)b * rm * k;
+  constexpr int T1_RS = 16;
+  if constexpr (USE_LDS) {
+    if (w.small_chain && mode == SMALL_PROJ && r <= T1_RS && n <= T && N3 > 0) { small_proj_chain(w, b, nb, base, red, &s_cnt, &s_nsel, &s_base); return; }
+  }
   STAMP_BEGIN();
   DIAG_T0();
   // T1 = (Y - D3) Q   or  Y Q
-  constexpr int T1_RS = 16;
   if (USE_LDS && r <= T1_RS && n <= T) {
     // Q' staged in LDS, padded to 16 columns (zero beyond column r)
     for (int e = tid; e < n * T1_RS; e += T) { const int j = e / T1_RS, a = e % T1_RS; Qs[e] = (a < r) ? Q[(size_t)a * n + j] : 0.0; }
@@ -1944,6 +2194,7 @@ __global__ void __launch_bounds__(256) k_small(OmcWS w, int mode) {
     T1[(size_t)a * n + i] = acc;
   }
   __syncthreads();
+  STAMP(29);
   double* E3 = w.E3 + (size_t)b * n * n;
   if (USE_LDS && r <= 16 && n <= T) {
     // rank-r product T1 Q' on the matrix cores: 16 x 16 tiles, K = 16 (the staged Q' is zero beyond column r), operands from LDS; the

@@ -128,6 +128,7 @@ struct Tuning {
   int harvest_async_min_live = 256;   // OMC_HARVEST_ASYNC_MIN_LIVE: live slots from which a harvest runs beside the next interval (omc_harvest_plan)
   int plain_multi_min = 1025;      // OMC_PLAIN_MULTI_MIN: cone orders from this value on (never below 145) run separation, rounding and the left singular vectors on the multi-workgroup eigen-kernels; the default is where only the cold kernel existed
   int shor_index_device_min = 0;   // OMC_SHOR_INDEX_DEVICE_MIN: Shor lists with at least this many minors get their index structure built on the device (omc_shor_index.hip); 0 = every list on the host
+  int small_chain = 1;             // OMC_SMALL_CHAIN: 0 = k_small's projection runs the body it had before its chain was shortened (small_proj_chain), the A/B arm with bit-identical results
   int shor_select_kb = 1048576;    // OMC_SHOR_SELECT_KB: violated-minor selection streams (no materialised keys) when 16 B per candidate exceed this many KiB; 0 = always materialise
   int streams = 4;                 // OMC_STREAMS: <= 1 serialises a solve on one stream
   int sub_debug = 0;               // OMC_SUB_DEBUG: diagnostics of k_cone_sub (3: histograms for omc_debug_stamps)
@@ -154,6 +155,7 @@ inline const Knob OMC_KNOBS[] = {
   {"OMC_WS_QUIET", nullptr, &Tuning::ws_quiet},
   {"OMC_STREAMS", nullptr, &Tuning::streams},                {"OMC_PLAIN_MULTI_MIN", nullptr, &Tuning::plain_multi_min},
   {"OMC_SUB_DEBUG", nullptr, &Tuning::sub_debug},            {"OMC_SUB_QMAX", nullptr, &Tuning::sub_qmax},
+  {"OMC_SMALL_CHAIN", nullptr, &Tuning::small_chain},
   {"OMC_TIMING_STRIDE", nullptr, &Tuning::timing_stride},
 };
 

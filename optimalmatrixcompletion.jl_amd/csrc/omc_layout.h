@@ -80,13 +80,16 @@ OMC_HD SubLayout sub_layout(int np16) {
   return {LD, zglob, blk, Cs, Cs + 4 * 256, Cs + 4 * 256 + 16 * 17, th, th + 16, th + 32, th + 64, th + 80, (th + 80 + 8) * 8};
 }
 // ---- k_small: T1 = (Y - D3) Q (n x rmax), M3 (ld3 x ld3), Jacobi work Gm (Npm x ldm), ev, wgt (Npm each), sel (Npm ints), recovery
-// coefficients Cc (rmax x k, + 2), staged Q' Qs (n x 16, LDS variant only); 104 bytes of margin -------------------------------------------
+// coefficients Cc (rmax x k, + 2), staged Q' Qs (n x 16, LDS variant only), SMALL_CS doubles for small_proj_chain (the symmetrised M3 and
+// the previous eigenvectors, 16 x 16 each, until the sweep starts; then the 16 x 16 copy of dS); 104 bytes of margin ---------------------
 #define SMALL_STATIC_LDS 1024      // allowance for the kernel's __shared__ scalars and reduction arrays (528 bytes as compiled)
-struct SmallLayout { int ld3; size_t M3, Gm, ev, wgt, sel, Cc, Qs, bytes; };
+#define SMALL_CS 512
+struct SmallLayout { int ld3; size_t M3, Gm, ev, wgt, sel, Cc, Qs, Cs, bytes; };
 OMC_HD SmallLayout small_layout(int n, int rmax, int k) {
   const int ld3 = rmax + k, Npm = (ld3 + 1) & ~1, ldm = Npm | 1;
   const size_t M3 = (size_t)n * rmax, Gm = M3 + (size_t)ld3 * ld3, ev = Gm + (size_t)Npm * ldm, sel = ev + 2 * Npm, Cc = sel + Npm / 2, Qs = Cc + (size_t)rmax * k + 2;
-  return {ld3, M3, Gm, ev, ev + Npm, sel, Cc, Qs, (Qs + (size_t)n * 16) * 8 + 104};
+  const size_t Cs = Qs + (size_t)n * 16;
+  return {ld3, M3, Gm, ev, ev + Npm, sel, Cc, Qs, Cs, (Cs + SMALL_CS) * 8 + 104};
 }
 // ---- k_global: packed lower triangle of the target (tY), tU (n x k), tV (rmax x k), cvec, mu (Rmax each), staged cut vectors xs
 // (GL_XS x n), qrow (Rmax); 80 bytes of margin --------------------------------------------------------------------------------------------

@@ -266,6 +266,7 @@ struct SolveLoop {
     if (multi) { im = T_M; ib = T_B; ic = T_C; }
     hip_events.st[T_S] = s; hip_events.st[T_M] = sm; hip_events.st[T_B] = sb; hip_events.st[T_C] = sc;
     h->ws.setup_gram_inline = tun.setup_gram_inline ? 1 : 0;
+    h->ws.small_chain = tun.small_chain ? 1 : 0;
     h->ws.check_xs = std::min(std::max(0, tun.check_xs), CB_XS);      // at most CB_XS doubles are staged: more vectors than that never fit
     // with omc_relax_reserve there may be more slots than nodes staged so far: the others start idle
     done = h->pin_done.as<int>(); jobs = h->pin_jobs.as<int>();
