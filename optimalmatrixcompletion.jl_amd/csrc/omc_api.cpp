@@ -476,6 +476,7 @@ int stage_base(omc_instance* h, int B, const omc_relax_params* params, int cut_t
   w.cp_nslab = h->nslab; w.cp_slab = h->nslab ? h->dslab.as<int>() : nullptr;
   w.cp_isblock = (h->nblock + h->nslab) ? h->disblock.as<unsigned char>() : nullptr; w.cp_nrest = h->nrest; w.cp_nfact = nullptr;
   w.cone_512 = h->tun.cone_512 ? 1 : 0; w.cp_series = CP_SERIES; w.cp_maxpass = CP_MAXPASS; w.cp_xcd = h->tun.colprox_no_xcd ? 0 : 1;
+  w.cp_dpp = h->tun.colprox_dpp ? 1 : 0;
   w.cp_nsolo = h->nsolo; w.cp_solo = h->nsolo ? h->dsolo.as<int>() : nullptr;
   w.cp_nwide = h->nwide; w.cp_wide = h->nwide ? h->dwide.as<int>() : nullptr;
   w.Ncnt = h->dNcnt.as<double>(); w.wY1 = h->dwY.as<double>();

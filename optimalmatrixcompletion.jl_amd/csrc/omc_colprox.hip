@@ -15,13 +15,16 @@
 // and its solves on a dependent chain of one broadcast per row.  Here each half-wave (32 lanes) owns one column, lane l of a half owns
 // matrix row l, and the whole row lives in REGISTERS.  Instead of a factorisation and triangular solves the half computes the inverse:
 //   -(B + cp s I)^-1 by the symmetric sweep operator (the Gauss-Jordan form that keeps the matrix symmetric, so that row k is available as
-//   column k): at step k every lane stages its entry of column k in LDS (one ds_write), reads the pivot and the column back as
-//   half-uniform (broadcast) ds_reads and updates its row with one fma per entry -- no cross-lane VALU traffic, no SGPR round trip;
+//   column k): at step k every lane updates its row with one fma per entry, whose other factor is lane q's entry of column k;
 //   the pivots are those of L D L', so their sign is the positive-definiteness test the secular iteration needs;
-//   every solve (y = A^-1 a, z = A^-1 y, w = A^-1 z) is then one staged vector and 32 fma per lane, with no dependent chain.
-// The staged row is read back 16 bytes at a time (ds_read_b128: half the LDS cycles of ds_read2_b64 per byte).
+//   every solve (y = A^-1 a, z = A^-1 y, w = A^-1 z) is then 32 fma per lane on the lanes' values of one vector, with no dependent chain.
+// Lane q's value reaches the fma as its DPP operand (v_fmac_f64_dpp row_newbcast, after one v_permlane16_swap per dword and step: half_rows
+// below), so a step is 31 fmacs, two swaps and one broadcast move, with no LDS instruction; the gather broadcasts the row indices and the
+// previous alpha the same way and the kernel uses no LDS.  The body it replaces (OMC_COLPROX_DPP=0, and k_colprox_wide) stages the column
+// in LDS (one ds_write) and reads it back as half-uniform ds_read_b128: ~400 LDS instructions per pass and wave, whose return path bound the
+// launch (608 -> 512 us per launch at saturation, profiles/colprox_lane_bcast.txt).
 // (A first form with L D L' in registers and substitutions by DPP row_newbcast / v_permlane16_swap broadcasts took 813 us per launch at
-// ~950 live slots against 620 us for this one and 1111 us for k_colprox; the launch is bound by the LDS return path of the broadcast reads.)
+// ~950 live slots against 620 us for the staged sweep and 1111 us for k_colprox: there every broadcast was an instruction of a dependent chain.)
 // The secular iteration of colprox_reg is carried per half (all of its scalars are half-uniform lane values); a half that has finished
 // idles while the other one goes on.  Columns with more than 32 rows and unpaired last columns stay with k_colprox (w.cp_solo).
 // ---------------------------------------------------------------------------------------------------------
@@ -41,6 +44,28 @@ __device__ __forceinline__ double half_sum(double v) {        // sum over the 32
   auto c = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
   return __hiloint2double(c[0], a[0]) + __hiloint2double(c[1], a[1]);
 }
+// The lane broadcasts of the pair kernel without LDS (DPP = true of colprox_sweep).  half_rows(v) holds the half-wave's 32 values of v twice over:
+// .e = the values of lanes 0..15 in BOTH rows of 16 of the half, .o = those of lanes 16..31 (one v_permlane16_swap per dword, the convention
+// of half_bcast).  Lane q's value is then operand 0 of a 64-bit DPP instruction with row_newbcast:(q & 15) on .e (q < 16) or .o -- the
+// update's own v_fmac_f64, so a broadcast costs no instruction.  The DPP forms are inline asm (the compiler does not fold a DPP move into
+// an fma).  Rules: (1) every one of them stands where all 64 lanes are active (the branches around them are wave-uniform); (2) a VGPR written
+// by the VALU or by the swap needs two wait states before a DPP operand reads it, and the compiler pads only its own instructions: the
+// first DPP instruction after the swaps opens with s_nop 1 inside its string; q and the row are compile-time values of unrolled loops.
+struct HalfRows { double e, o; };
+__device__ __forceinline__ HalfRows half_rows(double v) {
+  const int lo = __double2loint(v), hi = __double2hiint(v);
+  auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  auto c = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  return {__hiloint2double(c[0], a[0]), __hiloint2double(c[1], a[1])};
+}
+#define CPP_ROW(r, q) (((q) < 16) ? (r).e : (r).o)
+#define CPP_DPP(q) " row_newbcast:%" q " row_mask:0xf bank_mask:0xf"
+// d = value of lane q; the first reader of freshly swapped rows
+#define CPP_BCAST_PAD(d, r, q) asm volatile("s_nop 1\n\tv_mov_b64_dpp %0, %1" CPP_DPP("2") : "=&v"(d) : "v"(CPP_ROW(r, q)), "i"((q) & 15))
+// acc = fma(lane q's value, +-t, acc)
+#define CPP_FMAC(acc, r, q, t) asm volatile("v_fmac_f64_dpp %0, %1, %2" CPP_DPP("3") : "+v"(acc) : "v"(CPP_ROW(r, q)), "v"(t), "i"((q) & 15))
+#define CPP_FMAC_PAD(acc, r, q, t) asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2" CPP_DPP("3") : "+v"(acc) : "v"(CPP_ROW(r, q)), "v"(t), "i"((q) & 15))
+#define CPP_FMAC_NEG(acc, r, q, t) asm volatile("v_fmac_f64_dpp %0, %1, -%2" CPP_DPP("3") : "+v"(acc) : "v"(CPP_ROW(r, q)), "v"(t), "i"((q) & 15))
 #define CPP_LDS_DOUBLES (64 + 64 + 32)      // per wave: staged column, previous alpha, row indices (64 ints)
 
 // The body for LPC lanes per column: 32 (two columns per wave, k_colprox_pair) or 64 (one column per wave, up to 64 observed rows: k_colprox_wide --
@@ -49,10 +74,14 @@ template <int LPC>
 __device__ __forceinline__ double lanes_sum(double v) { if constexpr (LPC == 32) return half_sum(v); else return wave_sum(v); }
 #define RQ(q) (((q) < 32) ? R0[(q) & 31] : R1[((NC > 32) ? (q) : 0) & 31])
 typedef double dbl2_lds __attribute__((ext_vector_type(2), may_alias));      // 16-byte view of the staged vector: one ds_read_b128 per two entries
-template <int LPC>
+// DPP (LPC == 32 only): gather(), invert() and apply() read the other lanes' values by lane broadcast -- no LDS at all, st, vo_s and sidx are not
+// touched; false = the staged body (pivot row, solve vector, row indices and previous alpha through LDS: k_colprox_wide, and the A/B arm
+// OMC_COLPROX_DPP=0 of k_colprox_pair).  Every product and sum has the same operands in the same order in both: results are bit-identical.
+template <int LPC, bool DPP>
 __device__ __forceinline__ void colprox_sweep(const OmcWS& w, const int b, const int lane, const int j, const int off, const int c, const int cmax,
                                               double* st, double* vo_s, int* sidx) {
   constexpr int NC = LPC;
+  static_assert(!DPP || LPC == 32, "the lane-broadcast body is the pair kernel's");
   const int h = (LPC == 32) ? (lane >> 5) : 0, l = lane & (LPC - 1), hb = h * LPC;
   const bool act = l < c;
   const int n = w.n;
@@ -64,7 +93,15 @@ __device__ __forceinline__ void colprox_sweep(const OmcWS& w, const int b, const
   const double a_reg = act ? w.col_val[off + l] : 0.0;
   const int my = act ? w.col_idx[off + l] : 0;
   const double vo_r = act ? alpha[l] : 0.0;
-  sidx[lane] = my; vo_s[lane] = vo_r;
+  HalfRows vo_h = {0.0, 0.0}; int my_e = 0, my_o = 0;      // DPP: the rows' indices and previous alpha, broadcast from registers by gather()
+  if constexpr (DPP) {
+    vo_h = half_rows(vo_r);
+    auto a = __builtin_amdgcn_permlane16_swap(my, my, false, false);
+    my_e = a[0]; my_o = a[1];
+    asm volatile("s_nop 1" : "+v"(my_e), "+v"(my_o), "+v"(vo_h.e), "+v"(vo_h.o));      // the swaps' wait states, once: every DPP reader comes after this
+  } else {
+    sidx[lane] = my; vo_s[lane] = vo_r;
+  }
   const double rho_f = w.rho_b[b] * w.rho_f_ratio;
   const double coef = gm / (2.0 * rho_f), cp = gm * gm / (2.0 * rho_f);
   // ---- B + shift I, B = I + gamma ((2 Y - Yp)[O, O] - coef a_old a_old'): the whole row l in registers (entry (l, q) and entry (q, l) read the
@@ -80,8 +117,14 @@ __device__ __forceinline__ void colprox_sweep(const OmcWS& w, const int b, const
         double y1[8], y2[8], vq[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-          const int iq = sidx[hb + qb + u];
-          vq[u] = vo_s[hb + qb + u];
+          int iq;
+          if constexpr (DPP) {
+            asm("v_mov_b32_dpp %0, %1" CPP_DPP("2") : "=&v"(iq) : "v"((qb + u < 16) ? my_e : my_o), "i"((qb + u) & 15));
+            asm("v_mov_b64_dpp %0, %1" CPP_DPP("2") : "=&v"(vq[u]) : "v"(CPP_ROW(vo_h, qb + u)), "i"((qb + u) & 15));
+          } else {
+            iq = sidx[hb + qb + u];
+            vq[u] = vo_s[hb + qb + u];
+          }
           const size_t a = (l > qb + u) ? (size_t)iq * n + my : (size_t)my * n + iq;
           y1[u] = Yx ? Yx[a] : Y[a]; y2[u] = Yx ? 0.0 : Yp[a];
         }
@@ -113,8 +156,15 @@ __device__ __forceinline__ void colprox_sweep(const OmcWS& w, const int b, const
     for (int k = 0; k < NC; ++k) {
       if (k < cm) {                                              // wave-uniform
         const double ak = RQ(k) * sc;                             // a(l, k); lane k: the pivot
-        st[lane] = ak;
-        const double d = st[hb + k];
+        double d;
+        HalfRows ah = {0.0, 0.0};
+        if constexpr (DPP) {
+          ah = half_rows(ak);                                     // column k in the lanes of every row of 16
+          CPP_BCAST_PAD(d, ah, k);
+        } else {
+          st[lane] = ak;
+          d = st[hb + k];
+        }
         good = good && (d > 1e-290);
         const double pinv = fast_rcp(d);
         const bool piv = (lv == k);
@@ -122,7 +172,13 @@ __device__ __forceinline__ void colprox_sweep(const OmcWS& w, const int b, const
 #pragma unroll
         for (int qb = 0; qb < NC; qb += 4) {
           if (qb < cm) {                                         // wave-uniform; rows beyond a column's size are identity rows
-            if constexpr (LPC == 32) {      // half-uniform ds_read_b128: 4 LDS cycles per 16 B (ds_read2_b64: 8); the wide form keeps
+            if constexpr (DPP) {            // RQ(q) = fma(ak of lane q, -tt, RQ(q)): the same product and sum, the entry read from lane q's register
+#pragma unroll
+              for (int u = 0; u < 4; ++u) {
+                const int q = qb + u;
+                if (q != k) CPP_FMAC_NEG(R0[q & 31], ah, q, tt);
+              }
+            } else if constexpr (LPC == 32) {      // half-uniform ds_read_b128: 4 LDS cycles per 16 B (ds_read2_b64: 8); the wide form keeps
               const dbl2_lds s01 = st2[(hb + qb) >> 1], s23 = st2[((hb + qb) >> 1) + 1];      // ds_read2_b64 (its 256 VGPRs spill more with b128)
               if (qb != k) RQ(qb) = fma(-tt, s01.x, RQ(qb));
               if (qb + 1 != k) RQ(qb + 1) = fma(-tt, s01.y, RQ(qb + 1));
@@ -148,12 +204,18 @@ __device__ __forceinline__ void colprox_sweep(const OmcWS& w, const int b, const
   auto apply = [&](double v) __attribute__((always_inline)) -> double {
     int cm = cmax;
     asm volatile("" : "+s"(cm));
-    st[lane] = v;
+    HalfRows vh = {0.0, 0.0};
+    if constexpr (DPP) vh = half_rows(v);
+    else st[lane] = v;
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
 #pragma unroll
     for (int qb = 0; qb < NC; qb += 4) {
       if (qb < cm) {
-        if constexpr (LPC == 32) {
+        if constexpr (DPP) {
+          if (qb == 0) CPP_FMAC_PAD(a0, vh, qb, R0[qb & 31]); else CPP_FMAC(a0, vh, qb, R0[qb & 31]);
+          CPP_FMAC(a1, vh, qb + 1, R0[(qb + 1) & 31]);
+          CPP_FMAC(a2, vh, qb + 2, R0[(qb + 2) & 31]); CPP_FMAC(a3, vh, qb + 3, R0[(qb + 3) & 31]);
+        } else if constexpr (LPC == 32) {
           const dbl2_lds s01 = st2[(hb + qb) >> 1], s23 = st2[((hb + qb) >> 1) + 1];
           a0 = fma(RQ(qb), s01.x, a0); a1 = fma(RQ(qb + 1), s01.y, a1);
           a2 = fma(RQ(qb + 2), s23.x, a2); a3 = fma(RQ(qb + 3), s23.y, a3);
@@ -286,6 +348,7 @@ __device__ __forceinline__ void colprox_sweep(const OmcWS& w, const int b, const
 
 
 #undef RQ
+template <bool DPP>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k_colprox_pair(OmcWS w) {
   extern __shared__ double smem[];
   const int wave_in_blk = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, wpb = blockDim.x >> 6;      // scalar: every guard below is a wave-uniform branch
@@ -305,7 +368,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) k
   double* vo_s = st + 64;                                       // 64: alpha of the previous iteration
   int* sidx = (int*)(vo_s + 64);                                // 64: row indices
   const int h = lane >> 5;
-  colprox_sweep<32>(w, b, lane, j0 + h, h ? off1 : off0, h ? c1 : c0, cmax, st, vo_s, sidx);
+  colprox_sweep<32, DPP>(w, b, lane, j0 + h, h ? off1 : off0, h ? c1 : c0, cmax, st, vo_s, sidx);
 }
 
 // one column per wave for the columns k_colprox_pair leaves that hold at most 64 observed rows (w.cp_wide)
@@ -324,23 +387,26 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
   double* st = smem + (size_t)wave_in_blk * CPP_LDS_DOUBLES;
   double* vo_s = st + 64;
   int* sidx = (int*)(vo_s + 64);
-  colprox_sweep<64>(w, b, lane, j, off, c, cmax, st, vo_s, sidx);
+  colprox_sweep<64, false>(w, b, lane, j, off, c, cmax, st, vo_s, sidx);
 }
 
 
 extern "C" void omc_launch_colprox_sweep(const OmcWS* w, hipStream_t s) {
   const int wpb = 4;
   const int wp = w->nB * ((w->m + 1) / 2);
-  hipLaunchKernelGGL(k_colprox_pair, dim3((wp + wpb - 1) / wpb), dim3(wpb * 64), (size_t)wpb * CPP_LDS_DOUBLES * sizeof(double), s, *w);
+  const dim3 grid((wp + wpb - 1) / wpb), block(wpb * 64);
+  if (w->cp_dpp) hipLaunchKernelGGL(k_colprox_pair<true>, grid, block, 0, s, *w);      // the lane-broadcast body uses no LDS
+  else hipLaunchKernelGGL(k_colprox_pair<false>, grid, block, (size_t)wpb * CPP_LDS_DOUBLES * sizeof(double), s, *w);
   if (w->cp_nwide > 0) {
     const int ww = w->nB * w->cp_nwide;
     hipLaunchKernelGGL(k_colprox_wide, dim3((ww + wpb - 1) / wpb), dim3(wpb * 64), (size_t)wpb * CPP_LDS_DOUBLES * sizeof(double), s, *w);
   }
 }
 
-extern "C" void omc_colprox_sweep_residency(int* pair, int* wide) {
+extern "C" void omc_colprox_sweep_residency(const OmcWS* w, int* pair, int* wide) {      // the instantiation omc_launch_colprox_sweep launches
   const int wpb = 4;
   const size_t lds = (size_t)wpb * CPP_LDS_DOUBLES * sizeof(double);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(pair, (const void*)k_colprox_pair, wpb * 64, lds) != hipSuccess) *pair = -1;
+  const void* kp = w->cp_dpp ? (const void*)k_colprox_pair<true> : (const void*)k_colprox_pair<false>;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(pair, kp, wpb * 64, w->cp_dpp ? 0 : lds) != hipSuccess) *pair = -1;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(wide, (const void*)k_colprox_wide, wpb * 64, lds) != hipSuccess) *wide = -1;
 }

@@ -148,6 +148,7 @@ struct OmcWS {
   int cone_512;              // diagnostics (OMC_CONE_512): the 512-thread form of the L2-resident eigen-kernel at orders 193..256
   int cp_series;             // Neumann-series order of k_colprox_pair's finish (6; 3 = the second-order finish of colprox_reg)
   int cp_maxpass;            // cap on the secular passes of k_colprox_pair (CP_MAXPASS = 60 in omc_api.cpp: the algorithm)
+  int cp_dpp;                // k_colprox_pair's body (OMC_COLPROX_DPP): 1 = gather, sweep and solves by lane broadcast (DPP operands of the fmacs), no LDS; 0 = the staged (LDS) body
   int cp_xcd;                // 1: column-prox workgroups placed XCD-locally (xcd_block); 0 (OMC_COLPROX_NO_XCD): plain blockIdx.x
   double *cone_scratch, *glob_scratch, *small_scratch;   // per-slot slabs of the kernels whose block does not fit the LDS (strides in geo)
   double* chk_scratch;   // B*n*k
@@ -212,7 +213,7 @@ void omc_launch_eval_objective(int B, int n, int m, double gamma, const double* 
                                double* out, hipStream_t s);
 int omc_set_max_lds(void);
 void omc_query_residency(const OmcWS* w, int* out /* OMC_RES_N */);      /* workgroups per CU of the iteration kernels at w->geo (omc_kernel_residency) */
-void omc_colprox_sweep_residency(int* pair, int* wide);                /* omc_colprox.hip: k_colprox_pair, k_colprox_wide as omc_launch_colprox_sweep launches them */
+void omc_colprox_sweep_residency(const OmcWS* w, int* pair, int* wide);                /* omc_colprox.hip: k_colprox_pair, k_colprox_wide as omc_launch_colprox_sweep launches them */
 void omc_launch_gram_XXt(const OmcWS* w, const double* X, int B, hipStream_t s);
 void omc_launch_colprox_sweep(const OmcWS* w, hipStream_t s);      /* omc_colprox.hip */
 void omc_launch_colprox_block(const OmcWS* w, int mode, hipStream_t s);      /* omc_colprox_block.hip: nothing to launch when both lists are empty */

@@ -3479,7 +3479,7 @@ void omc_query_residency(const OmcWS* w, int* out) {
   out[OMC_RES_CONE_SUB_SEP] = residency_of((const void*)k_cone_sub<2>, 256, g.sub_lds);
   out[OMC_RES_GLOBAL] = g.glob.use_lds ? residency_of((const void*)k_global<true>, 512, g.glob.lds_bytes) : residency_of((const void*)k_global<false>, 512, 0);
   out[OMC_RES_SMALL] = g.small.use_lds ? residency_of((const void*)k_small<true>, 256, g.small.lds_bytes) : residency_of((const void*)k_small<false>, 256, 0);
-  omc_colprox_sweep_residency(&out[OMC_RES_COLPROX_PAIR], &out[OMC_RES_COLPROX_WIDE]);
+  omc_colprox_sweep_residency(w, &out[OMC_RES_COLPROX_PAIR], &out[OMC_RES_COLPROX_WIDE]);
   out[OMC_RES_COLPROX] = residency_of((const void*)k_colprox, 256, (size_t)4 * g.cp_lds_doubles * sizeof(double));
   out[OMC_RES_CONE] = g.cone.use_lds ? residency_of((const void*)k_cone<true>, 512, g.cone.lds_bytes) : residency_of((const void*)k_cone<false>, 512, 0);
   // k_cone_ws: the variant omc_launch_cone_ws takes

@@ -120,6 +120,7 @@ struct Tuning {
   bool shor_explicit = false;      // OMC_SHOR_EXPLICIT: rank k > 1 Shor batches by the Shor engine even where the base engine would serve them
   bool shor_no_subspace = false;   // OMC_SHOR_NO_SUBSPACE: no tracked subspace for the order-(n+m) cone of Shor mode
   int check_xs = 16;               // OMC_CHECK_XS: cut vectors of the rows with a nonzero multiplier that k_check_build stages in LDS (the rest is read from global memory)
+  int colprox_dpp = 1;             // OMC_COLPROX_DPP: k_colprox_pair's gather, sweep and solves by lane broadcast (DPP operands, no LDS); 0 = the staged body, the A/B arm with bit-identical results
   int colprox_block_min = 65;      // OMC_COLPROX_BLOCK_MIN: columns with at least this many observed rows take k_colprox_block (one workgroup per column, blocked MFMA Cholesky); a value above every column length is the path without it
   int cone_multi_min = 1025;       // OMC_CONE_MULTI_MIN: cone orders from this value on (never below 145) take the multi-workgroup eigen-kernels; the default is where only the cold kernel existed
   int event_merge = 1;             // OMC_EVENT_MERGE: 0 = every timed launch records two events of its own and the forks and joins of an iteration theirs (EventTape, omc_events.h)
@@ -146,7 +147,7 @@ inline const Knob OMC_KNOBS[] = {
   {"OMC_NO_WS_SPLIT", &Tuning::no_ws_split, nullptr},        {"OMC_SEGV_TRACE", &Tuning::segv_trace, nullptr},
   {"OMC_SETUP_GRAM_INLINE", &Tuning::setup_gram_inline, nullptr},
   {"OMC_SHOR_EXPLICIT", &Tuning::shor_explicit, nullptr},    {"OMC_SHOR_NO_SUBSPACE", &Tuning::shor_no_subspace, nullptr},
-  {"OMC_COLPROX_BLOCK_MIN", nullptr, &Tuning::colprox_block_min},
+  {"OMC_COLPROX_BLOCK_MIN", nullptr, &Tuning::colprox_block_min},  {"OMC_COLPROX_DPP", nullptr, &Tuning::colprox_dpp},
   {"OMC_CHECK_XS", nullptr, &Tuning::check_xs},              {"OMC_CONE_MULTI_MIN", nullptr, &Tuning::cone_multi_min},
   {"OMC_EVENT_MERGE", nullptr, &Tuning::event_merge},
   {"OMC_GRAPH_MAX", nullptr, &Tuning::graph_max},            {"OMC_SHOR_SELECT_KB", nullptr, &Tuning::shor_select_kb},

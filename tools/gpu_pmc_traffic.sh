@@ -19,7 +19,7 @@ def parse(f):
     return out
 fe, wr = parse("gpurun_out/r03_fetch_pmc.txt"), parse("gpurun_out/r03_write_pmc.txt")
 res = {"regime": "the bench command itself: 2048 warm-started config-2 nodes streamed through 1024 slots (~0.9 GB of state: beyond the 256 MiB Infinity Cache), ancestor relaxations included; separate rocprofv3 --pmc passes for FETCH_SIZE and WRITE_SIZE; FETCH x2 (gfx950 under-reports wide coalesced reads, MI355X_MICROARCH.md); per unit = per workgroup (one per live slot and iteration)"}
-alg = {"k_cone_sub<0>": 188672.0, "k_global<true>": 960000.0, "k_small<true>": None, "k_colprox_pair": None}
+alg = {"k_cone_sub<0>": 188672.0, "k_global<true>": 960000.0, "k_small<true>": None, "k_colprox_pair<true>": None}
 for k in alg:
     if k in fe and k in wr:
         n, wg, f = fe[k]; _, wg2, w_ = wr[k]
