@@ -36,6 +36,8 @@ extern "C" {
 #define OMC_SLOW_PROGRESS 1  /* MOI.SLOW_PROGRESS: iteration cap reached, values available              */
 #define OMC_TIME_LIMIT 2     /* MOI.TIME_LIMIT: time limit reached, values available                    */
 #define OMC_INFEASIBLE 3     /* MOI.INFEASIBLE family: "feasible" = false (OMC.jl:1921-1935)            */
+#define OMC_CUTOFF 4         /* MOI.OBJECTIVE_LIMIT: the node's rigorous dual_bound exceeds the cutoff of omc_relax_set_cutoff; values
+                                available as they stand (not converged), as for OMC_SLOW_PROGRESS              */
 
 /* disjunctive_cuts_type (OMC.jl:150, 1456) */
 #define OMC_CUT_LINEAR 0
@@ -202,6 +204,20 @@ int omc_relax_fetch_done(omc_instance* h, int max_nodes, int* node_ids, double* 
 /* omc_relax_hold(h, 1) after staging: the submitted solve waits for omc_relax_append when it runs dry instead of ending (until omc_relax_hold(h, 0)
  * or the time limit of the parameters). */
 int omc_relax_hold(omc_instance* h, int on);
+/* Objective cutoff: the upper bound a branch-and-bound driver holds (its incumbent).  A node whose rigorous dual bound exceeds it at a
+ * certificate check is pruned whatever it would converge to, so it ends there with status OMC_CUTOFF and dual_bound > cutoff (the cutoff as
+ * read at that check; the comparison is strict and the engine adds no tolerance of its own).  The test comes after the OMC_OPTIMAL and
+ * OMC_INFEASIBLE tests of the check and before stall, iteration cap and time limit; with kept certificates the node exports the multipliers
+ * of the check that proved the prune.  A property of the handle: it applies to the staged batch, to every later batch and to appended nodes
+ * until it is set again; +inf (the default) is off and then no node behaves differently; -inf and finite values are accepted, NaN or a NULL
+ * handle returns OMC_ERR_ARGUMENT.  omc_relax_set_cutoff may be called at any time and from any thread, also between omc_relax_submit and
+ * omc_relax_wait: it then takes effect at the first certificate check that starts after the call returns (one 8-byte copy on a stream of its
+ * own; the running kernels read the value through a pointer).  A node that has already been returned is not revisited.
+ * omc_last_cutoff_stats, of the last (or running) solve: out[0] nodes that ended OMC_CUTOFF, out[1] the sum of their iterations, out[2] calls
+ * of omc_relax_set_cutoff taken while that solve ran, out[3] 0. */
+int omc_relax_set_cutoff(omc_instance* h, double cutoff);
+int omc_relax_get_cutoff(omc_instance* h, double* cutoff);
+int omc_last_cutoff_stats(omc_instance* h, int64_t out[4]);
 int omc_relax_reserve(omc_instance* h, int extra_nodes, int max_cuts);
 int omc_relax_append(omc_instance* h, int B, const int* L, const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir,
                      const int* load_from, const int* save_to);

@@ -24,6 +24,7 @@ EXPORTS = [
     "omc_relax_keep_shor_certificates", "omc_relax_fetch_shor_certificate", "omc_shor_certificate_plan",
     "omc_shor_dual_bound_batch", "omc_shor_dual_bound_plan", "omc_last_shor_dual_bound_ms",
     "omc_shor_index_build", "omc_shor_index_plan", "omc_last_shor_index_stats",
+    "omc_relax_set_cutoff", "omc_relax_get_cutoff", "omc_last_cutoff_stats",
     "omc_altmin_master_objectives", "omc_altmin_plan", "omc_comm_unique_id", "omc_comm_init", "omc_allreduce_bounds", "omc_bcast_incumbent", "omc_allgather_records", "omc_comm_destroy",
 ]
 
@@ -115,6 +116,10 @@ def load():
         lib.omc_harvest_plan.argtypes = [C.c_int] * 5
     lib.omc_relax_reserve.argtypes = [vp, C.c_int, C.c_int]
     lib.omc_relax_hold.argtypes = [vp, C.c_int]
+    if hasattr(lib, "omc_relax_set_cutoff"):      # absent from an older A/B build; the cutoff methods of Engine raise there
+        lib.omc_relax_set_cutoff.argtypes = [vp, C.c_double]
+        lib.omc_relax_get_cutoff.argtypes = [vp, vp]
+        lib.omc_last_cutoff_stats.argtypes = [vp, vp]
     lib.omc_relax_fetch_done.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.omc_relax_append.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.omc_relax_reserve_shor.argtypes = [vp, C.c_int64, C.c_int]

@@ -30,7 +30,7 @@ from ._lib import RelaxParams, OmcError
 CUT_TYPES = {"linear": 0, "linear2": 1, "linear3": 2}
 DIR_CODES = {"left": 0, "middle": 1, "right": 2, "inner_left": 3, "inner_right": 4}
 BREAKPOINTS = {"smallest_1_eigvec": 1, "smallest_2_eigvec": 2}
-STATUS_NAMES = {0: "OPTIMAL", 1: "SLOW_PROGRESS", 2: "TIME_LIMIT", 3: "INFEASIBLE"}
+STATUS_NAMES = {0: "OPTIMAL", 1: "SLOW_PROGRESS", 2: "TIME_LIMIT", 3: "INFEASIBLE", 4: "OBJECTIVE_LIMIT"}      # 4: dual_bound > the cutoff of set_cutoff
 KERNEL_CLASSES = ["colprox", "cone", "global", "check", "setup", "small", "accel", "cone_sub", "check_col", "check_build", "harvest",
                   "shor_bigcone", "shor_minors", "shor_cols"]
 # omc_last_host_phases, in the order of OMC_HOST_* (include/omc.h)
@@ -392,6 +392,31 @@ class Engine:
     def hold(self, on=True):
         """Keep the submitted solve open when it runs dry (omc_relax_hold): it waits for append() until hold(False)."""
         _lib.check(self._lib.omc_relax_hold(self._h, 1 if on else 0))
+
+    # ---- objective cutoff ------------------------------------------------------------------------------
+    def set_cutoff(self, value):
+        """Objective cutoff of this engine (omc_relax_set_cutoff): a node whose rigorous dual_bound exceeds it at a certificate check ends there
+        with status 4, "OBJECTIVE_LIMIT".  Holds for every batch until set again; inf (the default) is off.  May be called while a submitted
+        solve runs: it takes effect at the first check that starts after the call returns."""
+        if not hasattr(self._lib, "omc_relax_set_cutoff"):
+            raise OmcError(-100, "this build of the library has no omc_relax_set_cutoff")
+        _lib.check(self._lib.omc_relax_set_cutoff(self._h, float(value)))
+
+    def get_cutoff(self):
+        if not hasattr(self._lib, "omc_relax_get_cutoff"):
+            raise OmcError(-100, "this build of the library has no omc_relax_get_cutoff")
+        v = np.zeros(1)
+        _lib.check(self._lib.omc_relax_get_cutoff(self._h, _lib.ptr(v)))
+        return float(v[0])
+
+    def cutoff_stats(self):
+        """(nodes of the last or running solve that ended OBJECTIVE_LIMIT, the sum of their iterations, set_cutoff calls taken while it ran, 0)
+        (omc_last_cutoff_stats)."""
+        if not hasattr(self._lib, "omc_last_cutoff_stats"):
+            raise OmcError(-100, "this build of the library has no omc_last_cutoff_stats")
+        o = np.zeros(4, np.int64)
+        _lib.check(self._lib.omc_last_cutoff_stats(self._h, _lib.ptr(o)))
+        return tuple(int(x) for x in o)
 
     def fetch_done(self, max_nodes=4096, want_Y=False):
         """Results of the nodes finished since the last call (omc_relax_fetch_done), also while the submitted solve is running: a list of dicts

@@ -193,7 +193,7 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
                      add_Shor_valid_inequalities_fraction=1.0, add_Shor_valid_inequalities_iterative=False,
                      max_update_Shor_indices_probability=1.0, min_update_Shor_indices_probability=0.1,
                      update_Shor_indices_probability_decay_rate=1.1, update_Shor_indices_n_minors=100, shor_params=None,
-                     warm_start=True, warm_pool_bytes=6 << 30, shor_warm_start=False, shor_warm_depth=32):
+                     warm_start=True, warm_pool_bytes=6 << 30, shor_warm_start=False, shor_warm_depth=32, objective_cutoff=False):
     """Behavioural counterpart of the reference driver for use_disjunctive_cuts = true, no Shor, one altmin run at the
     root (altmin_root_n_iters = 1).  Differences, all deliberate: (1) up to `batch` nodes are popped per round in the
     reference's selection order and relaxed in ONE GPU batch (batch=1 reproduces the serial order); (2) the node bound
@@ -213,6 +213,11 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
     entries as the base branch (Engine.state_pool_reserve_shor); the pool is sized from warm_pool_bytes for lists of the root's length plus
     shor_warm_depth updates of update_Shor_indices_n_minors minors, and a node whose list has outgrown that starts cold and is not saved
     (counter shor_warm_outgrown).  counters["warm_started"] counts the loads the library accepted.
+    objective_cutoff (off by default): the incumbent is given to the engine before every relaxation batch (Engine.set_cutoff; every rank sets
+    the all-reduced value), so a node that the incumbent prunes ends at the first certificate check whose rigorous bound exceeds it, with
+    status 4 (OBJECTIVE_LIMIT).  Such a node is pruned on its dual_bound whatever use_certified_bound says (its primal value is not
+    converged) and is counted in nodes_relax_feasible, nodes_relax_feasible_pruned and nodes_relax_cutoff; the coins of every other node are
+    drawn as before.  instance["relax_log"] lists every relaxed node as (id, status, iterations (-1: relaxed by another rank), how it ended).
     Returns (solution, instance) dicts with the reference's key names where they apply (OMC.jl:604-621, 391-454)."""
     import heapq
     import time
@@ -240,7 +245,9 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
                     nodes_relax_feasible_pruned=0, nodes_master_feasible=0, nodes_master_feasible_improvement=0,
                     nodes_relax_feasible_split=0, nodes_relax_feasible_split_altmin=0,
                     nodes_relax_feasible_split_altmin_improvement=0)
-    run_log = []
+    if objective_cutoff:
+        counters["nodes_relax_cutoff"] = 0
+    run_log = []; relax_log = []
     # ---- root altmin (OMC.jl:521-621) ------------------------------------------------------------------------
     A0 = np.where(indices, A, 0.0)
     U0 = left_singular(engine, A0, k)                                                      # OMC.jl:524
@@ -360,6 +367,8 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
                 todo.append((nid, nd))
         if todo:
             t0 = time.time()
+            if objective_cutoff:
+                engine.set_cutoff(ub)          # ub is the all-reduced incumbent: the same value on every rank
             mine = todo[rank::world_size] if world_size > 1 else todo                        # round-robin in queue order
             need = [(nid, nd) for nid, nd in mine if nid not in precomputed]
             if pool_cap and need:
@@ -412,25 +421,35 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
             for nid, nd in todo:
                 row = rec[nid]
                 status, objective, bound_cert = int(row[1]), float(row[2]), float(row[3])
+                its = int(local[nid]["iters"]) if nid in local else -1
                 if status == 3:                                                              # OMC.jl:777-779
                     counters["nodes_relax_infeasible"] += 1
+                    relax_log.append((nid, status, its, "infeasible"))
                     continue
                 counters["nodes_relax_feasible"] += 1                                       # OMC.jl:786
-                bound = bound_cert if use_certified_bound else objective
+                bound = bound_cert if (use_certified_bound or status == 4) else objective    # 4: stopped by the cutoff, its primal value is not converged
                 nd["LB"] = bound
                 if nid == 1:
                     lb = bound                                                              # OMC.jl:793-795
+                if status == 4:                                                              # dual_bound > the incumbent it was given: pruned
+                    counters["nodes_relax_feasible_pruned"] += 1
+                    counters["nodes_relax_cutoff"] = counters.get("nodes_relax_cutoff", 0) + 1
+                    relax_log.append((nid, status, its, "cutoff"))
+                    continue
                 if bound > ub:                                                               # OMC.jl:797-800
                     counters["nodes_relax_feasible_pruned"] += 1
+                    relax_log.append((nid, status, its, "pruned"))
                     continue
                 if status == 0 and row[4] >= -1e-6:                                          # OMC.jl:807-837
                     counters["nodes_master_feasible"] += 1
+                    relax_log.append((nid, status, its, "master"))
                     if nid in local:
                         # the reference takes the relaxation value as the incumbent (OMC.jl:818-828); a first-order solve certifies that
                         # value only to eps_gap, so the incumbent is the master objective of the rank-k projection of X instead
                         Xk, _ = rank_k_projection(local[nid]["X"], k, engine)
                         cand.append((float(engine.evaluate_objective(Xk)), Xk, "master"))
                     continue
+                relax_log.append((nid, status, its, "split"))
                 split.append((nid, nd, row))
             # altmin at split nodes w.p. p(depth)  (OMC.jl:856-949): every rank draws the same coins, runs its own share
             if altmin_flag and split:
@@ -499,11 +518,13 @@ def branch_and_bound(engine, A, indices, *, node_selection="bestfirst", bestfirs
             print("| %10d | %10d | %10d | %10f | %10f | %10f | %10.3f  s  |" % run_log[-1], flush=True)
         if root_only:
             break
+    if objective_cutoff:
+        engine.set_cutoff(math.inf)          # the handle leaves the driver without a cutoff
     elapsed = time.time() - start
     solution.update(lower_bound=lb, gap=now_gap, MSE_in=compute_MSE(solution["X"], A, indices, "in"),
                     MSE_out=compute_MSE(solution["X"], A, indices, "out"), MSE_all=compute_MSE(solution["X"], A, indices, "all"))   # OMC.jl:1079-1081
     # run_log columns as the reference's DataFrame (OMC.jl:457-465): explored, total, remaining, lower, upper, gap, runtime
-    instance = dict(run_log=run_log, run_log_columns=("explored", "total", "remaining", "lower", "upper", "gap", "runtime"),
+    instance = dict(run_log=run_log, run_log_columns=("explored", "total", "remaining", "lower", "upper", "gap", "runtime"), relax_log=relax_log,
                     run_details=dict(counters, time_taken=elapsed, solve_time_relaxation=t_relax, solve_time_altmin=t_altmin,
                                                       rho_scale=float(rho_scale), batch=batch, n=n, m=m, k=k))
     return solution, instance

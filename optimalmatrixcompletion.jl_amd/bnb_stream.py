@@ -53,9 +53,14 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                                add_Shor_valid_inequalities_fraction=1.0, add_Shor_valid_inequalities_iterative=False,
                                max_update_Shor_indices_probability=1.0, min_update_Shor_indices_probability=0.1,
                                update_Shor_indices_probability_decay_rate=1.1, update_Shor_indices_n_minors=100, shor_params=None,
-                               shor_warm_start=False, shor_warm_depth=32, shor_list_capacity=1024):
+                               shor_warm_start=False, shor_warm_depth=32, shor_list_capacity=1024, objective_cutoff=False):
     """Queue-driven branch and bound (module docstring).  The Shor keywords are those of bnb.branch_and_bound; shor_list_capacity is the
-    number of lists new to a running solve that one epoch reserves room for (iterative mode; the static mode needs none)."""
+    number of lists new to a running solve that one epoch reserves room for (iterative mode; the static mode needs none).
+    objective_cutoff (off by default): the incumbent is given to the solving handle before every epoch's submit and again whenever it
+    improves while the solve runs (Engine.set_cutoff), so that the nodes in flight which the new incumbent prunes end at their next
+    certificate check with status 4 (OBJECTIVE_LIMIT); the epoch's clean-up sets the cutoff back to inf.  Such a node is counted in
+    nodes_relax_feasible, nodes_relax_feasible_pruned and nodes_relax_cutoff and takes no further part.  The second handle is untouched.
+    instance["relax_log"] lists every relaxed node as (id, status, iterations, how it ended)."""
     from .api import default_params, BREAKPOINTS, Engine
     from .data import compute_MSE
     n, m, k = engine.n, engine.m, engine.k
@@ -75,6 +80,10 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                     nodes_relax_feasible_pruned=0, nodes_master_feasible=0, nodes_master_feasible_improvement=0,
                     nodes_relax_feasible_split=0, nodes_relax_feasible_split_altmin=0, nodes_relax_feasible_split_altmin_improvement=0,
                     warm_started=0, epochs=0)
+    if objective_cutoff:
+        counters["nodes_relax_cutoff"] = 0
+    relax_log = []
+    epoch_open = False          # a submitted solve runs on `engine`: an improved incumbent goes to it at once
     # ---- root altmin (OMC.jl:521-621) on the second handle ----------------------------------------------------------------
     A0 = np.where(indices, A, 0.0)
     U0 = left_singular(engine2, A0, k)
@@ -136,6 +145,8 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
             counters["nodes_master_feasible_improvement" if kind == "master" else "nodes_relax_feasible_split_altmin_improvement"] += 1
             for nid in [i for i, nd in nodes.items() if nd["LB"] > ub]:       # prune dominated nodes (OMC.jl:1220-1244)
                 del nodes[nid]
+            if objective_cutoff and epoch_open:
+                engine.set_cutoff(ub)          # the nodes in flight see it at their next certificate check
 
     def node_X(o):
         """X of a finished Shor node: the root's result carries it, a node of the running solve is fetched (fetch_done_shor)."""
@@ -147,6 +158,7 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
         counters["nodes_explored"] += 1
         if o["status_code"] == 3:
             counters["nodes_relax_infeasible"] += 1
+            relax_log.append((nid, 3, o["iters"], "infeasible"))
             return
         counters["nodes_relax_feasible"] += 1
         if shor and len(nd["shor"]):
@@ -154,11 +166,18 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
         bound = o["dual_bound"]
         if nid == 1:
             lb = bound
+        if o["status_code"] == 4:            # stopped by the cutoff: dual_bound > the incumbent it was given (and ub has not risen since)
+            counters["nodes_relax_feasible_pruned"] += 1
+            counters["nodes_relax_cutoff"] = counters.get("nodes_relax_cutoff", 0) + 1
+            relax_log.append((nid, 4, o["iters"], "cutoff"))
+            return
         if bound > ub:
             counters["nodes_relax_feasible_pruned"] += 1
+            relax_log.append((nid, o["status_code"], o["iters"], "pruned"))
             return
         if o["status_code"] == 0 and o["lambda_min"][0] >= -1e-6:
             counters["nodes_master_feasible"] += 1
+            relax_log.append((nid, 0, o["iters"], "master"))
             if shor:                         # as bnb.branch_and_bound: the master objective of the rank-k projection of the node's X
                 Xk, _ = rank_k_projection(node_X(o), k, engine2)
                 val = float(engine2.evaluate_objective(Xk))
@@ -167,6 +186,7 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
             consider(val, Xk, "master")
             return
         counters["nodes_relax_feasible_split"] += 1
+        relax_log.append((nid, o["status_code"], o["iters"], "split"))
         if altmin_flag and "Y" in o:
             p = min_altmin_probability if nd["depth"] > altmin_decay_depth else max_altmin_probability / (altmin_probability_decay_rate ** nd["depth"])
             if rng.random() < p:
@@ -279,7 +299,10 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
             engine.stage([nd["cuts"] for _, nd in first], disjunctive_cuts_type, P, load_from=lf, save_to=sv)
         engine.hold(True)
         t_epoch = time.time()
+        if objective_cutoff:
+            engine.set_cutoff(ub)
         engine.submit()
+        epoch_open = True
         in_flight = {i: first[i] for i in range(len(first))}
         sent = len(first); stop_push = False
         while True:
@@ -329,6 +352,9 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                 time.sleep(0.0005)
         engine.hold(False)
         engine.wait()
+        epoch_open = False
+        if objective_cutoff:
+            engine.set_cutoff(math.inf)          # the handle leaves the epoch as it entered
         for o in engine.fetch_done(max_nodes=1 << 15, want_Y=False):      # nodes that finished after the loop decided to stop: their bounds still count
             if o["node"] in in_flight:
                 nid, nd = in_flight.pop(o["node"])
@@ -350,7 +376,7 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                     MSE_out=compute_MSE(solution["X"], A, indices, "out"), MSE_all=compute_MSE(solution["X"], A, indices, "all"))
     engine2.close()
     engine.tuning_set("OMC_NO_GRAPH", None)
-    instance = dict(run_log=run_log, run_log_columns=("explored", "total", "remaining", "lower", "upper", "gap", "runtime"),
+    instance = dict(run_log=run_log, run_log_columns=("explored", "total", "remaining", "lower", "upper", "gap", "runtime"), relax_log=relax_log,
                     run_details=dict(counters, time_taken=elapsed, solve_time_relaxation=relax_seconds, solve_time_altmin=t_altmin,
                                      rho_scale=float(rho_scale), slots=slots, in_flight_target=target, n=n, m=m, k=k))
     return solution, instance

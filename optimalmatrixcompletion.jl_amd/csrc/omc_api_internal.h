@@ -34,6 +34,9 @@ int check_cut_type(int cut_type);
 int stage_base(omc_instance* h, int B, const omc_relax_params* params, int cut_type, const int* L, const double* cut_x, const double* cut_Uhat,
                const int8_t* cut_dir, const double* U_lower, const double* U_upper, const StageMode& mode);
 
+// ---- omc_api.cpp: objective cutoff ---------------------------------------------------------------------------------------------------------
+void cutoff_solve_begin(omc_instance* h);      // a solve begins: its counters start at zero, its checks know whether a cutoff is set
+
 // ---- omc_api.cpp: fetches -----------------------------------------------------------------------------------------------------------------
 int require_finished_ids(omc_instance* h, int n_ids, const int* ids, bool upto_read_only, const char* who);
 int require_certificates(const OmcWS& w, int n_ids, const int* ids, hipStream_t fs, const char* who);

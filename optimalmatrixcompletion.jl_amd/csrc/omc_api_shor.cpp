@@ -689,7 +689,7 @@ int omc_relax_stage_shor(omc_instance* h, int B, const omc_relax_params* params,
   // ---- base workspace in Shor mode, and the view through which its eigen-kernels project the order-(n+m) cone -------------------------
   w.shor = 1; w.shN = N; w.shP0 = sh.P0; w.shD0 = sh.D0; w.inv_s2 = 1.0 / (sc * sc);
   OmcWS& wb = h->wbig;
-  wb = w;
+  wb = w;      // with the cutoff pointer stage_base has just set: the view carries whatever the base workspace does
   wb.n = N; wb.np16 = NPb; wb.Mbuf = sh.MbufB; wb.Vrow = sh.VrowB; wb.vvalid = sh.vvalidB; wb.fro2 = sh.fro2B; wb.W1 = sh.P0;
   wb.sub_enable = 0; wb.cert_enable = 0; wb.ws_mode = 0; wb.clip_hi = 1e300; wb.sub_debug = 0; wb.ws_first = nullptr; wb.ws_need = nullptr; wb.ws_phase = 0;
   // the view's own geometry (only the eigen-kernels are launched through it)

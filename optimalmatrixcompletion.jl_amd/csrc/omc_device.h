@@ -22,6 +22,7 @@
 #define OMC_ST_SLOW 1
 #define OMC_ST_TIME 2
 #define OMC_ST_INFEASIBLE 3
+#define OMC_ST_CUTOFF 4      // the rigorous bound exceeds the caller's objective cutoff (OMC_CUTOFF of omc.h)
 
 #include "omc_layout.h"
 
@@ -169,7 +170,13 @@ struct OmcWS {
   int *cert_flag, *cert_have;                    // B: snapshot wanted at this check ; the slot holds one
   double *cb_rho, *cbLam, *cblam, *cbPsi, *cbBound;   // per slot
   double *ocLam, *oclam, *ocPsi, *ocBound; int* ocHave;   // per node
+  // Objective cutoff (omc_relax_set_cutoff): one double on the device in a buffer of the instance's own, +inf = off.  k_check_final reads the
+  // value through the pointer at every check, so the caller may change it while a solve runs and a captured iteration graph never holds it.
+  // Set by every stage call (the value lives on the handle); the Shor big-cone view carries the same pointer.
+  const double* cutoff;
 };
+// OmcWS travels to every kernel by value: the kernel-argument segment holds 4 KiB
+static_assert(sizeof(OmcWS) <= 4096, "OmcWS no longer fits a kernel's argument segment");
 #define AA_MAXMEM 10
 // caller-supplied multipliers of omc_dual_bound_batch (k_dual_assemble): Lam (nnz per node), lam (Rmax), Psi3 (order r + k, column-major,
 // leading dimension r + k, at the head of a (rmax + k)^2 stride; NULL = zero), and the n x rmax scratch of Q Psi3_11.

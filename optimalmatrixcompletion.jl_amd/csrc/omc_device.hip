@@ -2830,6 +2830,9 @@ __global__ void k_check_final(OmcWS w, int last, int phase) {
   if (fabs(obj - lb_dec) <= w.eps_gap * fmax(1.0, fabs(obj)) && feas) term = OMC_ST_OPTIMAL;
   // f(Y) <= f(0) = 1/2 ||A_Omega||^2 on the feasible set: a larger certified bound proves infeasibility
   else if (lb_dec > 0.5 * w.sumA2 * (1.0 + 1e-9) + 1e-9) term = OMC_ST_INFEASIBLE;
+  // objective cutoff (omc_relax_set_cutoff): the caller's incumbent prunes this node already.  Strict, no tolerance of the engine's own; the
+  // value is read at this check (+inf: never true).  Phase 0 only flags the slot below: what is reported was decided on the rigorous bound
+  else if (lb_dec > *w.cutoff) term = OMC_ST_CUTOFF;
   else {
     // stationary primal value and no progress of the bound: give up with values (MOI.SLOW_PROGRESS)
     if (fabs(obj - w.objprev[b]) <= 1e-7 * fmax(1.0, fabs(obj)) && lbv <= w.lbprev[b] + 1e-7 * fmax(1.0, fabs(obj))) stall_new += 1;

@@ -3,6 +3,7 @@
 // events.  Private.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <atomic>
 #include <mutex>
@@ -257,6 +258,13 @@ struct omc_instance {
   std::vector<PoolSig> pool_sig, node_sig; std::mutex sig_mu;
   std::vector<int> save_host;      // per node of the staged batch: the entry its final state goes to (-1: none), as the device sees it
   int64_t shor_warm_stats[4] = {0, 0, 0, 0};      // omc_last_shor_warm_stats
+  // Objective cutoff (omc_relax_set_cutoff): the value lives here and survives staging; the device holds a copy in a buffer of its own
+  // (OmcWS::cutoff points at it, set again by every stage call) that the setter refreshes with one 8-byte copy from its page-locked image on
+  // a stream of its own (created by the first call), under cutoff_mu.  The setter touches nothing else: not the workspace, no DevBuf::ensure, not the tuning map.
+  // cutoff_armed: some value other than +inf has been given since the running solve began (or before it) -- only then does a check read the
+  // slots' statuses back for the counters.  The counters are reset where a solve begins (omc_relax_submit, or omc_relax_solve called directly).
+  DevBuf bcutoff; PinBuf pin_cutoff; hipStream_t cutoff_stream = nullptr; std::mutex cutoff_mu; std::atomic<double> cutoff{HUGE_VAL};
+  std::atomic<int> cutoff_armed{0}, solve_active{0}; std::atomic<int64_t> cutoff_nodes{0}, cutoff_iters{0}, cutoff_live{0};
   // kernel stats
   int64_t launches[OMC_KERNEL_NCLASS] = {0}; double ms[OMC_KERNEL_NCLASS] = {0}; int64_t units[OMC_KERNEL_NCLASS] = {0};
   size_t nnz_rows() const { return row_idx.size(); }

@@ -8,6 +8,7 @@
 #include <stdio.h>
 
 #include "omc_events.h"
+#include "omc_api_internal.h"
 #include "omc_host.h"
 #include "omc_slots.h"
 
@@ -64,10 +65,11 @@ using Tape = EventTape<HipEvents>;
 // destroys the graph executables (GraphGuard).
 struct SolveLoop {
   struct CloseGuard { omc_instance* h; ~CloseGuard() { std::lock_guard<std::mutex> lk(h->append_mu); h->append_closed = true; h->ws.Btot = h->Btot_live.load(); h->Btot = h->ws.Btot; if (h->shor_on) h->sh.Btot = h->ws.Btot; } };
+  struct ActiveGuard { omc_instance* h; ~ActiveGuard() { h->solve_active.store(0); } };      // omc_relax_set_cutoff counts the calls it takes while a solve runs
   struct GraphGuard { hipGraphExec_t e[2] = {nullptr, nullptr}; ~GraphGuard() { for (int q = 0; q < 2; ++q) if (e[q]) (void)hipGraphExecDestroy(e[q]); } };
 
   omc_instance* const h;
-  CloseGuard close_guard;
+  CloseGuard close_guard; ActiveGuard active_guard;
   const OmcWS& w; const ShWS& sw; const omc_relax_params& P;
   const Tuning tun;      // copied once: omc_tuning_set may run on the caller's thread while a submitted solve runs on the worker
   const int S, check_every;
@@ -94,7 +96,7 @@ struct SolveLoop {
   int Btot;      // nodes staged so far: omc_relax_append may add more while the loop runs (re-read at every check)
   int* done = nullptr; int* jobs = nullptr;      // page-locked images of the done flags and of the k_setup_gram jobs (prepare)
   SlotBook book;
-  std::vector<int> harvested_ids;
+  std::vector<int> harvested_ids, cut_img;
   int harvested = 0, it = 0, nlist = 0, flags_cur = 0, list_cur = 0;
   bool timed_out = false;
   int drain_pool = -1;       // timing-event pool that waits to be read (finish_events): filled up to the last check, read after the next iteration is enqueued
@@ -134,7 +136,7 @@ struct SolveLoop {
   const Clock::time_point t0; Clock::time_point t_last, t_check;
 
   explicit SolveLoop(omc_instance* h_)
-      : h(h_), close_guard{h_}, w(h_->ws), sw(h_->sh), P(h_->params), tun(h_->tun), S(h_->ws.B), check_every(std::max(1, h_->params.check_every)),
+      : h(h_), close_guard{h_}, active_guard{h_}, w(h_->ws), sw(h_->sh), P(h_->params), tun(h_->tun), S(h_->ws.B), check_every(std::max(1, h_->params.check_every)),
         multi(h_->tun.streams > 1), shor(h_->shor_on), s(h_->stream),
         hip_events{h_}, tape(&hip_events, T_NSTREAM, h_->tun.event_merge != 0), Btot(h_->Btot_live.load()), book(h_->ws.B, nullptr, nullptr), t0(Clock::now()), t_last(t0), t_check(t0) {}
 
@@ -490,6 +492,18 @@ struct SolveLoop {
     return 0;
   }
 
+  // omc_last_cutoff_stats: the slots this check finished (done in the image that has just come back, not yet parked by the scan) whose status
+  // is OMC_CUTOFF, and their iterations.  Only while a cutoff other than +inf has been given: without one no check copies anything more.
+  int count_cutoffs() {
+    cut_img.resize(2 * (size_t)S);
+    HIPCHK(hipMemcpyAsync(cut_img.data(), w.status, sizeof(int) * S, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(cut_img.data() + S, w.iters, sizeof(int) * S, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int b = 0; b < S; ++b)
+      if (book.node(b) >= 0 && done[b] && !book.is_parked(b) && cut_img[b] == OMC_ST_CUTOFF) { h->cutoff_nodes.fetch_add(1); h->cutoff_iters.fetch_add(cut_img[S + b]); }
+    return 0;
+  }
+
   // the done flags (and the word of the quiet intervals) come back; the timing pools swap; Btot is re-read; first_wins is decided
   int read_check() {
     stamp_begin();
@@ -508,6 +522,7 @@ struct SolveLoop {
     if (drain_pool >= 0) { finish_events(drain_pool); drain_pool = -1; }
     drain_pool = tape.current(); tape.swap();
     Btot = h->Btot_live.load();
+    if (h->cutoff_armed.load()) { int rc = count_cutoffs(); if (rc) return rc; }
     if (!P.first_wins) return 0;
     // the first certified node ends the batch (penalty autotune): everything still running is harvested as it stands
     std::vector<int> stv(S);
@@ -663,7 +678,9 @@ int omc_harvest_plan(int nlive, int nfin, int pending, int check_index, int asyn
 
 int omc_relax_solve(omc_instance* h) {
   if (!h || !h->staged) return fail(OMC_ERR_ARGUMENT, "omc_relax_solve: nothing staged");
+  if (!h->ws.cutoff) return fail(OMC_ERR_ARGUMENT, "omc_relax_solve: the staged workspace has no cutoff pointer");      // k_check_final reads through it
   HIPCHK(hipSetDevice(h->device));
+  if (!h->worker_running.load()) cutoff_solve_begin(h);      // a submitted solve began in omc_relax_submit
   SolveLoop L(h);
   int rc = L.prepare(); if (rc) return rc;
   for (;;) {
