@@ -221,6 +221,34 @@ int omc_last_cutoff_stats(omc_instance* h, int64_t out[4]);
 int omc_relax_reserve(omc_instance* h, int extra_nodes, int max_cuts);
 int omc_relax_append(omc_instance* h, int B, const int* L, const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir,
                      const int* load_from, const int* save_to);
+/* Children by reference: the children of a finished node without a round trip of its cut list (create_matrix_cut_child_nodes,
+ * OMC.jl:2520-2542).  A child is its parent plus one cut whose x is the parent's breakpoint_x and whose Uhat is the parent's U -- the two
+ * vectors omc_relax_fetch_done copies back -- so its descriptor (2k + 1 new rows, at most one new column of the row basis) is built on the
+ * device from the parent's, bit for bit what omc_relax_append builds on the host from the full cut list.  Base (disjunctive) mode.
+ *   omc_branch_plan   (host only, no handle, no device) the children of one node: dirs[c * k + j] = direction code of child c in column j,
+ *       the Cartesian product of the cut type's codes with the FIRST column varying fastest (Iterators.product; linear: left, right;
+ *       linear2: left, middle, right; linear3: left, inner_left, inner_right, right), *n_children = 2^k, 3^k or 4^k of them.
+ *       OMC_ERR_INVALID_ENUM for a bad cut type; OMC_ERR_ARGUMENT for NULL, k outside 1..8 or capacity < *n_children (which is still set).
+ *   omc_relax_append_children   adds C nodes, child c = node parent_id[c] + one cut (x = that node's breakpoint_x, Uhat = its U, directions
+ *       dirs[c * k ..]); load_from / save_to as in omc_relax_append (or NULL).  It is omc_relax_append for nodes given by reference: same
+ *       lock and end-of-batch decision, descriptors before the node counter, same stream, same handling of the pool indices, the batch's
+ *       default penalty.  The children get the consecutive ids *first_child_id ... in the order given and are ordinary appended nodes for
+ *       every later call, this one included.  Before omc_relax_submit or while a submitted (or held) solve runs.  Every refusal is decided
+ *       on the host before anything is written, leaves the batch as it was and names its cause: nothing staged, C <= 0, parent_id / dirs /
+ *       first_child_id NULL: OMC_ERR_ARGUMENT; a Shor-mode batch: OMC_ERR_UNSUPPORTED; a parent that omc_relax_fetch_done has not returned
+ *       (nor an ended solve harvested), the solve has ended, beyond the node capacity of omc_relax_reserve, a child with more cuts than
+ *       Lmax, more rows than Rmax (R_parent + 2k + 1) or possibly more basis columns than rmax (min(n, r_parent + 1), r an upper bound
+ *       the handle keeps per node), a pool index beyond the pool: OMC_ERR_ARGUMENT; a direction code the staged cut type does not have:
+ *       OMC_ERR_INVALID_ENUM; n > 4096: OMC_ERR_UNSUPPORTED.  The strides are those fixed when the batch was staged (omc_relax_reserve).
+ *   omc_relax_fetch_descriptor   one node's staged descriptor as the kernels read it, whole strides with their padding (tests, diagnostics):
+ *       R, r, L (1 each); rkind, rcut, rbi, rbj, rrhs (Rmax); rcoef (Rmax * k); cutx (Lmax * n); Q (n * rmax).  Any pointer may be NULL.
+ *       Rmax and rmax: omc_last_solver_info [7], [3]; Lmax = max(1, most cuts of a staged node, max_cuts of omc_relax_reserve).
+ *       OMC_ERR_ARGUMENT for an id that is not a node of the batch. */
+int omc_branch_plan(int cut_type, int k, int capacity, int8_t* dirs, int* n_children);
+int omc_relax_append_children(omc_instance* h, int C, const int* parent_id, const int8_t* dirs, const int* load_from, const int* save_to,
+                              int* first_child_id);
+int omc_relax_fetch_descriptor(omc_instance* h, int node_id, int* R, int* rkind, int* rcut, int* rbi, int* rbj, double* rcoef, double* rrhs,
+                               int* L, double* cutx, int* r, double* Q);
 int omc_relax_poll(omc_instance* h, int* running, int* nodes_done, int* nodes_total);
 int omc_relax_wait(omc_instance* h);
 int omc_relax_fetch(omc_instance* h, double* objective, double* dual_bound, int* status, int* iters, double* Y,

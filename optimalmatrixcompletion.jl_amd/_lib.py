@@ -25,6 +25,7 @@ EXPORTS = [
     "omc_shor_dual_bound_batch", "omc_shor_dual_bound_plan", "omc_last_shor_dual_bound_ms",
     "omc_shor_index_build", "omc_shor_index_plan", "omc_last_shor_index_stats",
     "omc_relax_set_cutoff", "omc_relax_get_cutoff", "omc_last_cutoff_stats",
+    "omc_branch_plan", "omc_relax_append_children", "omc_relax_fetch_descriptor",
     "omc_altmin_master_objectives", "omc_altmin_plan", "omc_comm_unique_id", "omc_comm_init", "omc_allreduce_bounds", "omc_bcast_incumbent", "omc_allgather_records", "omc_comm_destroy",
 ]
 
@@ -120,6 +121,10 @@ def load():
         lib.omc_relax_set_cutoff.argtypes = [vp, C.c_double]
         lib.omc_relax_get_cutoff.argtypes = [vp, vp]
         lib.omc_last_cutoff_stats.argtypes = [vp, vp]
+    if hasattr(lib, "omc_relax_append_children"):      # absent from an older A/B build; the branch methods of Engine raise there
+        lib.omc_branch_plan.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp]
+        lib.omc_relax_append_children.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+        lib.omc_relax_fetch_descriptor.argtypes = [vp, C.c_int] + [vp] * 11
     lib.omc_relax_fetch_done.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.omc_relax_append.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.omc_relax_reserve_shor.argtypes = [vp, C.c_int64, C.c_int]

@@ -7,6 +7,7 @@ backed by the HIP library.  Reference = /root/reference/src/OptimalMatrixComplet
                                                   (add_Shor_valid_inequalities = true, rank 1)
     .reserve / .append / .fetch_done / .hold      nodes pushed into a staged or running batch as their parents finish (the queue of OMC.jl:700-719);
     .reserve_shor / .append_shor / .fetch_done_shor   the same for a Shor-mode batch (rank 1)
+    .branch_plan / .append_children / .fetch_descriptor   the children of finished nodes by reference: their descriptors are built on the device
     .keep_certificates / .fetch_certificate       the multipliers behind a node's dual_bound, for certificate.py (numpy) or .dual_bound (device) to re-evaluate
     .keep_shor_certificates / .fetch_shor_certificate   the same for Shor-mode nodes (rank 1), for certificate.shor_dual_bound (numpy)
     .matrix_completion_master_feasible(Y, U)      OMC.jl:1261-1277
@@ -29,6 +30,7 @@ from ._lib import RelaxParams, OmcError
 
 CUT_TYPES = {"linear": 0, "linear2": 1, "linear3": 2}
 DIR_CODES = {"left": 0, "middle": 1, "right": 2, "inner_left": 3, "inner_right": 4}
+DIR_NAMES = {v: k_ for k_, v in DIR_CODES.items()}
 BREAKPOINTS = {"smallest_1_eigvec": 1, "smallest_2_eigvec": 2}
 STATUS_NAMES = {0: "OPTIMAL", 1: "SLOW_PROGRESS", 2: "TIME_LIMIT", 3: "INFEASIBLE", 4: "OBJECTIVE_LIMIT"}      # 4: dual_bound > the cutoff of set_cutoff
 KERNEL_CLASSES = ["colprox", "cone", "global", "check", "setup", "small", "accel", "cone_sub", "check_col", "check_build", "harvest",
@@ -132,6 +134,19 @@ def _close_all():
 
 
 atexit.register(_close_all)
+
+
+def branch_plan(cut_type, k):
+    """omc_branch_plan (host only, no GPU): the direction tuples of one node's children in the order of bnb.child_directions."""
+    if cut_type not in CUT_TYPES:
+        raise ValueError(f"Invalid input for disjunctive cuts type: {cut_type}")
+    lib = _lib.load()
+    if not hasattr(lib, "omc_branch_plan"):
+        raise OmcError(-100, "this build of the library has no omc_branch_plan")
+    cap = 4 ** int(k)
+    d = np.zeros((cap, int(k)), np.int8); cnt = np.zeros(1, np.int32)
+    _lib.check(lib.omc_branch_plan(CUT_TYPES[cut_type], int(k), cap, _lib.ptr(d), _lib.ptr(cnt)))
+    return [tuple(DIR_NAMES[int(c)] for c in row) for row in d[:int(cnt[0])]]
 
 
 def colprox_plan(n, cmax, block_min=65):
@@ -287,6 +302,10 @@ class Engine:
         _lib.check(self._lib.omc_relax_stage(self._h, B, C.byref(p), CUT_TYPES[disjunctive_cuts_type], _lib.ptr(L), _lib.ptr(cx),
                                              _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(lo), _lib.ptr(hi)))
         self._B = B
+        # what fetch_descriptor and append_children need of this batch: its cut type and the cut stride (include/omc.h: Lmax); reserve() is consumed
+        extra_nodes, max_cuts = getattr(self, "_reserved", (0, 0)); self._reserved = (0, 0)
+        self._cut_type = disjunctive_cuts_type
+        self._Lmax = max(1, int(L.max()) if len(L) else 0, max_cuts if extra_nodes > 0 else 0)
 
     def stage_shor(self, nodes, shor_info, disjunctive_cuts_type="linear", params=None, U_lower=None, U_upper=None, penalties=None, keep_V=False,
                    load_from=None, save_to=None):
@@ -314,6 +333,7 @@ class Engine:
             hi = np.ascontiguousarray(np.stack([np.asfortranarray(u).ravel(order="F") for u in U_upper]))
         nsh, nso, shi, soi = _pack_shor(shor_info)
         self._keep = (L, cx, cU, cd, lo, hi, p, nsh, nso, shi, soi)
+        self._reserved = (0, 0); self._cut_type = disjunctive_cuts_type      # the reservation is consumed by this stage call
         _lib.check(self._lib.omc_relax_stage_shor(self._h, B, C.byref(p), CUT_TYPES[disjunctive_cuts_type], _lib.ptr(L), _lib.ptr(cx),
                                                   _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(nsh), _lib.ptr(shi),
                                                   _lib.ptr(nso), _lib.ptr(soi)))
@@ -334,6 +354,7 @@ class Engine:
     def reserve(self, extra_nodes, max_cuts):
         """Room for nodes appended to the NEXT staged batch (omc_relax_reserve): extra_nodes more nodes with at most max_cuts cuts each."""
         _lib.check(self._lib.omc_relax_reserve(self._h, int(extra_nodes), int(max_cuts)))
+        self._reserved = (int(extra_nodes), int(max_cuts))
 
     def append(self, nodes, disjunctive_cuts_type="linear", load_from=None, save_to=None):
         """Add nodes to the staged batch -- also while a submitted solve is running (omc_relax_append): the reference's queue keeps receiving
@@ -347,6 +368,57 @@ class Engine:
             raise ValueError("load_from / save_to must hold one pool index per node")
         _lib.check(self._lib.omc_relax_append(self._h, len(nodes), _lib.ptr(L), _lib.ptr(cx), _lib.ptr(cU), _lib.ptr(cd), _lib.ptr(lf), _lib.ptr(sv)))
         self._B += len(nodes)
+
+    def branch_plan(self, cut_type):
+        """The direction tuples of one node's children, in the order of bnb.child_directions (omc_branch_plan; host only)."""
+        return branch_plan(cut_type, self.k)
+
+    def append_children(self, parent_ids, dirs=None, load_from=None, save_to=None):
+        """Add children of finished nodes to the staged batch by reference (omc_relax_append_children): child c is node parent_ids[c] plus
+        one cut (x = that node's breakpoint_vec, Uhat = its U, directions dirs[c]), its descriptor is built on the device.  With dirs = None
+        every child of every parent, in branch_plan order.  The parents must have been returned by fetch_done().  Returns the children's
+        node ids (consecutive, in the order given); load_from / save_to as in append().  Raises OmcError when the library refuses: the
+        batch is then as it was."""
+        if not hasattr(self._lib, "omc_relax_append_children"):
+            raise OmcError(-100, "this build of the library has no omc_relax_append_children")
+        k = self.k
+        parents = [int(p) for p in parent_ids]
+        if dirs is None:
+            plan = self.branch_plan(self._cut_type)
+            dirs = [d for _ in parents for d in plan]
+            parents = [p for p in parents for _ in plan]
+        if len(dirs) != len(parents) or any(len(d) != k for d in dirs):
+            raise ValueError("dirs must hold one tuple of k directions per child")
+        Cn = len(parents)
+        pv = np.ascontiguousarray(np.asarray(parents, dtype=np.int32))
+        dv = np.zeros((max(Cn, 1), k), np.int8)
+        for c, d in enumerate(dirs):
+            for j, x in enumerate(d):
+                dv[c, j] = DIR_CODES[x] if isinstance(x, str) else int(x)
+        lf = None if load_from is None else np.ascontiguousarray(np.asarray(load_from, dtype=np.int32))
+        sv = None if save_to is None else np.ascontiguousarray(np.asarray(save_to, dtype=np.int32))
+        if (lf is not None and lf.shape != (Cn,)) or (sv is not None and sv.shape != (Cn,)):
+            raise ValueError("load_from / save_to must hold one pool index per child")
+        first = np.zeros(1, np.int32)
+        _lib.check(self._lib.omc_relax_append_children(self._h, Cn, _lib.ptr(pv), _lib.ptr(dv), _lib.ptr(lf), _lib.ptr(sv), _lib.ptr(first)))
+        self._B += Cn
+        return list(range(int(first[0]), int(first[0]) + Cn))
+
+    def fetch_descriptor(self, node_id):
+        """One node's staged descriptor as the kernels read it, whole strides with their padding (omc_relax_fetch_descriptor): dict(R, rkind,
+        rcut, rbi, rbj (Rmax each), rcoef (Rmax, k), rrhs (Rmax), L, cutx (Lmax, n), r, Q (n, rmax) with the basis in its first r columns)."""
+        if not hasattr(self._lib, "omc_relax_fetch_descriptor"):
+            raise OmcError(-100, "this build of the library has no omc_relax_fetch_descriptor")
+        n, k = self.n, self.k
+        info = self.solver_info()
+        Rmax, rmax, Lmax = max(info["R_max"], 1), max(info["r_max"], 1), self._Lmax
+        R = np.zeros(1, np.int32); L = np.zeros(1, np.int32); r = np.zeros(1, np.int32)
+        rkind = np.zeros(Rmax, np.int32); rcut = np.zeros(Rmax, np.int32); rbi = np.zeros(Rmax, np.int32); rbj = np.zeros(Rmax, np.int32)
+        rcoef = np.zeros(Rmax * k); rrhs = np.zeros(Rmax); cutx = np.zeros(Lmax * n); Q = np.zeros(n * rmax)
+        _lib.check(self._lib.omc_relax_fetch_descriptor(self._h, int(node_id), _lib.ptr(R), _lib.ptr(rkind), _lib.ptr(rcut), _lib.ptr(rbi), _lib.ptr(rbj),
+                                                        _lib.ptr(rcoef), _lib.ptr(rrhs), _lib.ptr(L), _lib.ptr(cutx), _lib.ptr(r), _lib.ptr(Q)))
+        return dict(R=int(R[0]), rkind=rkind, rcut=rcut, rbi=rbi, rbj=rbj, rcoef=rcoef.reshape(Rmax, k), rrhs=rrhs, L=int(L[0]),
+                    cutx=cutx.reshape(Lmax, n), r=int(r[0]), Q=Q.reshape((n, rmax), order="F"))
 
     def reserve_shor(self, nq_max, extra_lists):
         """With reserve(): room in the NEXT stage_shor batch for appended nodes whose lists hold at most nq_max minors, extra_lists of them

@@ -25,7 +25,7 @@ import time
 
 import numpy as np
 
-from .bnb import make_children, autotune_rho_scale, compute_gap, left_singular, rank_k_projection
+from .bnb import make_children, child_directions, autotune_rho_scale, compute_gap, left_singular, rank_k_projection
 from .shor_lists import ShorLists
 
 
@@ -53,18 +53,27 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                                add_Shor_valid_inequalities_fraction=1.0, add_Shor_valid_inequalities_iterative=False,
                                max_update_Shor_indices_probability=1.0, min_update_Shor_indices_probability=0.1,
                                update_Shor_indices_probability_decay_rate=1.1, update_Shor_indices_n_minors=100, shor_params=None,
-                               shor_warm_start=False, shor_warm_depth=32, shor_list_capacity=1024, objective_cutoff=False):
+                               shor_warm_start=False, shor_warm_depth=32, shor_list_capacity=1024, objective_cutoff=False,
+                               device_branching=False, use_max_steps=False, max_steps=1000000):
     """Queue-driven branch and bound (module docstring).  The Shor keywords are those of bnb.branch_and_bound; shor_list_capacity is the
     number of lists new to a running solve that one epoch reserves room for (iterative mode; the static mode needs none).
     objective_cutoff (off by default): the incumbent is given to the solving handle before every epoch's submit and again whenever it
     improves while the solve runs (Engine.set_cutoff), so that the nodes in flight which the new incumbent prunes end at their next
     certificate check with status 4 (OBJECTIVE_LIMIT); the epoch's clean-up sets the cutoff back to inf.  Such a node is counted in
     nodes_relax_feasible, nodes_relax_feasible_pruned and nodes_relax_cutoff and takes no further part.  The second handle is untouched.
+    device_branching (off by default; base mode only, with the Shor keywords it raises): a child whose parent was relaxed in the running solve
+    goes in by reference (Engine.append_children: the library builds its descriptor on the device from the parent's) instead of through
+    its whole cut list; the host list is still kept, for altmin and for the epoch that restages the node.  The descriptors are the same bit
+    for bit, so selection, coins, counters and pruning see the same tree.  counters["nodes_appended_by_reference"] counts those children.
+    use_max_steps / max_steps: the node cap of the reference (OMC.jl:128-129, 702) as bnb.branch_and_bound applies it: no new solve is
+    staged and nothing more is pushed once nodes_total has reached max_steps.
     instance["relax_log"] lists every relaxed node as (id, status, iterations, how it ended)."""
     from .api import default_params, BREAKPOINTS, Engine
     from .data import compute_MSE
     n, m, k = engine.n, engine.m, engine.k
     shor = bool(add_Shor_valid_inequalities)
+    if shor and device_branching:
+        raise ValueError("device_branching is for the base mode: a Shor child inherits its parent's list (append_shor)")
     if shor:
         if k > 1:
             raise NotImplementedError("Shor mode of the queue-driven driver is rank 1 (omc_relax_append_shor); rank k > 1 runs in bnb.branch_and_bound")
@@ -82,6 +91,8 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                     warm_started=0, epochs=0)
     if objective_cutoff:
         counters["nodes_relax_cutoff"] = 0
+    if device_branching:
+        counters["nodes_appended_by_reference"] = 0
     relax_log = []
     epoch_open = False          # a submitted solve runs on `engine`: an improved incumbent goes to it at once
     # ---- root altmin (OMC.jl:521-621) on the second handle ----------------------------------------------------------------
@@ -135,6 +146,7 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
     nodes = {}         # id -> dict(cuts, LB, depth, pstate)
     lb = -math.inf
     t_altmin = 0.0
+    t_append = 0.0          # host time inside append / append_shor / append_children (run_details["append_seconds"])
     pending_altmin = []          # (Y, cuts) of split nodes that won the altmin coin: relaxed in batches on the second handle
 
     def consider(cand_val, cand_X, kind):
@@ -195,10 +207,12 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
         child_shor = None
         if shor:                             # OMC.jl:956-967, 2495-2518; the scan runs on the second handle
             child_shor = lists.child(engine2, nd["shor"], nd["depth"], lambda: node_X(o), rng, k, counters)
-        for cuts in make_children(nd["cuts"], o, disjunctive_cuts_type, k):
+        for cuts, dirs in zip(make_children(nd["cuts"], o, disjunctive_cuts_type, k), child_directions(disjunctive_cuts_type, k)):
             counters["nodes_total"] += 1
             cid = counters["nodes_total"]
             nodes[cid] = dict(cuts=cuts, LB=bound, depth=nd["depth"] + 1, pstate=nd.get("state"))
+            if device_branching and "node" in o:      # relaxed in a solve of `engine`: (its id there, that solve's epoch, the new cut's directions)
+                nodes[cid]["ref"] = (o["node"], counters["epochs"], dirs)
             if shor:
                 nodes[cid]["shor"] = child_shor
             heapq.heappush(heap, (bound, cid))
@@ -273,7 +287,10 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
         vals += [nd["LB"] for _, nd in in_flight.values()]
         return min(vals) if vals else None
 
-    while now_gap > gap and time.time() - start <= time_limit and nodes:
+    def capped():
+        return use_max_steps and counters["nodes_total"] >= max_steps
+
+    while now_gap > gap and not capped() and time.time() - start <= time_limit and nodes:
         # ---- one epoch = one running solve; a new one is staged when the tree outgrows the reserved cut depth or the node capacity ----------
         counters["epochs"] += 1
         best = [nid for _, nid in heapq.nsmallest(slots, heap) if nid in nodes]          # the nodes this epoch starts with decide the cut depth it reserves
@@ -319,7 +336,7 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                 run_log.append((counters["nodes_explored"], counters["nodes_total"], len(nodes) + len(in_flight), lb, ub, now_gap, time.time() - start))
                 if verbose:
                     print("| %10d | %10d | %10d | %10f | %10f | %10f | %10.3f  s  |" % run_log[-1], flush=True)
-            done = now_gap <= gap or time.time() - start > time_limit or (not nodes and not in_flight)
+            done = now_gap <= gap or capped() or time.time() - start > time_limit or (not nodes and not in_flight)
             if done:
                 break
             if not stop_push and len(in_flight) < target:
@@ -328,19 +345,37 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
                 push = pop_best(room, depth_cap, nq_cap, known, n_staged_lists + list_cap - len(known)) if room > 0 else []
                 if push:
                     lf, sv = warm_indices(push)
+                    taken = 0
+                    t_push = time.time()
                     try:
                         if shor:
                             engine.append_shor([nd["cuts"] for _, nd in push], [(nd["shor"], None) for _, nd in push], disjunctive_cuts_type,
                                                load_from=lf, save_to=sv)
+                            taken = len(push)
                         else:
-                            engine.append([nd["cuts"] for _, nd in push], disjunctive_cuts_type, load_from=lf, save_to=sv)
+                            # in queue order, so that the ids are the ones one append call would give: runs of children whose parent
+                            # belongs to this solve go in by reference, the runs between them through their cut lists
+                            by_ref = [device_branching and nd.get("ref") is not None and nd["ref"][1] == counters["epochs"] for _, nd in push]
+                            while taken < len(push):
+                                end = taken + 1
+                                while end < len(push) and by_ref[end] == by_ref[taken]:
+                                    end += 1
+                                run = push[taken:end]
+                                wl = None if lf is None else lf[taken:end]; ws_ = None if sv is None else sv[taken:end]
+                                if by_ref[taken]:
+                                    engine.append_children([nd["ref"][0] for _, nd in run], [nd["ref"][2] for _, nd in run], load_from=wl, save_to=ws_)
+                                    counters["nodes_appended_by_reference"] += len(run)
+                                else:
+                                    engine.append([nd["cuts"] for _, nd in run], disjunctive_cuts_type, load_from=wl, save_to=ws_)
+                                taken = end
                     except Exception:                              # the solve ended on its time limit between our checks: back into the queue
                         if shor:
                             known.clear(); known.update(snapshot)
-                        for nid, nd in push:
+                        for nid, nd in push[taken:]:
                             nodes[nid] = nd; heapq.heappush(heap, (nd["LB"], nid))
                         stop_push = True
-                        push = []
+                        push = push[:taken]
+                    t_append += time.time() - t_push
                     for q, item in enumerate(push):
                         in_flight[sent + q] = item
                     sent += len(push)
@@ -377,6 +412,6 @@ def branch_and_bound_streaming(engine, A, indices, *, gap=1e-4, time_limit=3600.
     engine2.close()
     engine.tuning_set("OMC_NO_GRAPH", None)
     instance = dict(run_log=run_log, run_log_columns=("explored", "total", "remaining", "lower", "upper", "gap", "runtime"), relax_log=relax_log,
-                    run_details=dict(counters, time_taken=elapsed, solve_time_relaxation=relax_seconds, solve_time_altmin=t_altmin,
+                    run_details=dict(counters, time_taken=elapsed, solve_time_relaxation=relax_seconds, solve_time_altmin=t_altmin, append_seconds=t_append,
                                      rho_scale=float(rho_scale), slots=slots, in_flight_target=target, n=n, m=m, k=k))
     return solution, instance

@@ -212,29 +212,7 @@ void omc_instance_destroy(omc_instance* h) {
   delete h;      // the device buffers free themselves
 }
 
-// piece table of the disjunctive cuts (OMC.jl:1580-1678): lo <= v <= hi, g(v) = slope*v + icpt
-int cut_piece(int cut_type, int dir, double vhat, int q1, double* lo, double* hi, double* slope, double* icpt) {
-  const double a = fabs(vhat);
-  if (cut_type == OMC_CUT_LINEAR) {
-    if (dir == OMC_DIR_LEFT) { *lo = -1; *hi = vhat; *slope = vhat - 1; *icpt = vhat; return 0; }      // 1582-1591
-    if (dir == OMC_DIR_RIGHT) { *lo = vhat; *hi = 1; *slope = vhat + 1; *icpt = -vhat; return 0; }     // 1592-1601
-  } else if (cut_type == OMC_CUT_LINEAR2) {
-    if (dir == OMC_DIR_LEFT) { *lo = -1; *hi = -a; *slope = -(1 + a); *icpt = -a; return 0; }          // 1604-1613
-    if (dir == OMC_DIR_MIDDLE) { *lo = -a; *hi = a; *slope = 0; *icpt = vhat * vhat; return 0; }       // 1614-1623
-    if (dir == OMC_DIR_RIGHT) { *lo = a; *hi = 1; *slope = 1 + a; *icpt = -a; return 0; }              // 1624-1633
-  } else if (cut_type == OMC_CUT_LINEAR3) {
-    if (dir == OMC_DIR_LEFT) { *lo = -1; *hi = -a; *slope = -(1 + a); *icpt = -a; return 0; }          // 1636-1645
-    if (dir == OMC_DIR_INNER_LEFT) { *lo = -a; *hi = 0; *slope = -a; *icpt = 0; return 0; }            // 1646-1655
-    if (dir == OMC_DIR_INNER_RIGHT) { *lo = 0; *hi = a; *slope = a; *icpt = 0; return 0; }             // 1656-1665
-    if (dir == OMC_DIR_RIGHT) {                                                                        // 1666-1675
-      *lo = a; *hi = 1;
-      if (q1) { *slope = a; *icpt = 0; } else { *slope = 1 + a; *icpt = -a; }
-      return 0;
-    }
-  }
-  return -1;
-}
-
+// (the piece table of the disjunctive cuts, cut_piece: omc_cut_piece.h, shared with the device)
 
 // rows (OMC.jl:1558-1685) and row subspace of a set of nodes, on the host: shared by omc_relax_stage and omc_relax_append
 int pack_nodes(omc_instance* h, const omc_relax_params& P, int cut_type, int B, const int* L, const double* cut_x, const double* cut_Uhat,
@@ -585,6 +563,17 @@ int stage_base(omc_instance* h, int B, const omc_relax_params* params, int cut_t
     if (h->warm_save.size() != (size_t)B) h->warm_save.clear();
   }
   h->save_host.assign(sN, -1);
+  // cuts, rows and row-subspace columns per node on the host, and with room for appended nodes in base mode the scratch of the branch kernels
+  // (omc_relax_append_children): sized here, so that an append never allocates
+  h->node_L.assign(sN, 0); h->node_R.assign(sN, 0); h->node_r.assign(sN, 0);
+  for (int b = 0; b < B; ++b) { h->node_L[b] = L ? L[b] : 0; h->node_R[b] = (int)pk.rk[b].size(); h->node_r[b] = pk.rrv[b]; }
+  h->br_ready = false;
+  if (extra_nodes > 0 && !shor) {
+    BranchWS bw{};
+    ENS_CARVE(h->bbrS, [&](Carve& c) { walk_branch_scratch(c, BRANCH_CHUNK, (size_t)n, (size_t)k, bw); });
+    ENS_CARVE(h->bbrI, [&](Carve& c) { walk_branch_ints(c, BRANCH_CHUNK, BRANCH_CHUNK, (size_t)k, bw); });
+    h->br_ready = true;
+  }
   if (h->pool_cap > 0 && !shor && h->warm_load.size() == sN) {      // entries saved by a Shor solve do not hold what the base engine loads (alpha, sval)
     std::lock_guard<std::mutex> lk(h->sig_mu);
     for (int& e : h->warm_load) if (e >= 0 && (size_t)e < h->pool_sig.size() && h->pool_sig[e].kind == 2) e = -1;
@@ -691,12 +680,13 @@ int omc_relax_reserve(omc_instance* h, int extra_nodes, int max_cuts) {
 }
 
 // The one append path: omc_relax_append, and with `lists` omc_relax_append_shor, whose list step (known lists share their group, new ones
-// are built and may be refused) sits between the checks and the writes.  Lock, end-of-batch decision, capacity, rows, strides and pool
+// are built and may be refused) sits between the checks and the writes; with `refs` omc_relax_append_children, whose nodes are given by
+// reference: branch_check stands in for pack_nodes and its stride check, branch_write (two kernels) for put_descriptors.  Lock, end-of-batch decision, capacity, rows, strides and pool
 // indices first: every refusal is decided before anything is written, and a refused call leaves the batch as it was.  Then the new groups,
 // the descriptors, rho_node and the warm-start indices on the append stream, and the counter last: the running kernels read the
 // descriptors of nodes below Btot_live only, so these rows are not visible to them until it moves.
 int append_nodes(omc_instance* h, const char* who, int B2, const int* L, const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir,
-                 const int* load_from, const int* save_to, const ShorAppendLists* lists) {
+                 const int* load_from, const int* save_to, const ShorAppendLists* lists, const BranchRefs* refs) {
   const std::string pre = std::string(who) + ": ";
   HIPCHK(hipSetDevice(h->device));
   std::lock_guard<std::mutex> lk(h->append_mu);
@@ -704,9 +694,12 @@ int append_nodes(omc_instance* h, const char* who, int B2, const int* L, const d
   const OmcWS& w = h->ws;
   const int first = h->Btot_live.load();
   if (first + B2 > h->node_cap) return fail(OMC_ERR_ARGUMENT, pre + (lists ? "beyond the node capacity given to omc_relax_reserve" : "beyond the capacity given to omc_relax_reserve"));
-  NodePack pk;
-  { int rcp = pack_nodes(h, h->params, h->staged_cut_type, B2, L, cut_x, cut_Uhat, cut_dir, nullptr, nullptr, pk); if (rcp) return rcp; }
-  if (pk.Rmax > w.Rmax || pk.rmax > w.rmax || pk.Lmax > w.Lmax) return fail(OMC_ERR_ARGUMENT, pre + "a node has more cuts than omc_relax_reserve allowed for");
+  NodePack pk;      // nodes given by reference (refs) have no pack: their rows are written on the device, their strides checked from the host copies
+  if (refs) { int rcb = branch_check(h, first, B2, *refs, pre); if (rcb) return rcb; }
+  else {
+    { int rcp = pack_nodes(h, h->params, h->staged_cut_type, B2, L, cut_x, cut_Uhat, cut_dir, nullptr, nullptr, pk); if (rcp) return rcp; }
+    if (pk.Rmax > w.Rmax || pk.rmax > w.rmax || pk.Lmax > w.Lmax) return fail(OMC_ERR_ARGUMENT, pre + "a node has more cuts than omc_relax_reserve allowed for");
+  }
   if ((load_from || save_to) && !(w.load_from && w.save_to))
     return fail(OMC_ERR_ARGUMENT, pre + (lists ? "warm-start indices need a state pool with its Shor extension (omc_state_pool_reserve_shor) before the batch was staged"
                                                : "warm-start indices need a state pool created before the batch was staged"));
@@ -738,7 +731,8 @@ int append_nodes(omc_instance* h, const char* who, int B2, const int* L, const d
   const size_t f = (size_t)first;
   ShorGroupImages img;
   if (lists) { int rcw = shor_append_write(h, grouping, first, as, img); if (rcw) return rcw; }
-  { int rc = put_descriptors(w, pk, B2, B2, f, L, cut_x, as); if (rc) return rc; }
+  if (refs) { int rc = branch_write(h, first, B2, *refs, as); if (rc) return rc; }
+  else { int rc = put_descriptors(w, pk, B2, B2, f, L, cut_x, as); if (rc) return rc; }
   std::vector<double> hrho(B2, w.rho);
   HIPCHK(hipMemcpyAsync(const_cast<double*>(w.rho_node) + f, hrho.data(), 8 * (size_t)B2, hipMemcpyHostToDevice, as));
   if (!lfv.empty()) HIPCHK(hipMemcpyAsync(const_cast<int*>(w.load_from) + f, lfv.data(), sizeof(int) * B2, hipMemcpyHostToDevice, as));
@@ -748,6 +742,10 @@ int append_nodes(omc_instance* h, const char* who, int B2, const int* L, const d
   }
   HIPCHK(hipStreamSynchronize(as));
   if (lists) shor_append_commit(h, grouping);
+  // cuts, rows and row-subspace columns of the new nodes on the host (omc_relax_append_children decides its refusals from them)
+  if (refs) branch_commit(h, first, B2, *refs);
+  else if (h->node_L.size() >= f + (size_t)B2)
+    for (int b = 0; b < B2; ++b) { h->node_L[f + b] = L ? L[b] : 0; h->node_R[f + b] = (int)pk.rk[b].size(); h->node_r[f + b] = pk.rrv[b]; }
   h->Btot_live.store(first + B2); h->Btot = first + B2;
   if (!h->worker_running.load()) { h->ws.Btot = first + B2; if (lists) h->sh.Btot = first + B2; }      // no solve in flight: the staged batch simply grew (a running solve sets both when it ends)
   return 0;

@@ -1,16 +1,17 @@
 // omc_api_internal.h -- what more than one of the omc_api*.cpp sources needs: declared here once, defined in exactly one of them (named at
 // each group).  Private to the host side of libomc_hip.so; nothing here is exported.
 #pragma once
+#include <string>
 #include <unordered_map>
 #include <vector>
 
+#include "omc_cut_piece.h"
 #include "omc_host.h"
 
 #pragma GCC visibility push(hidden)
 
 // ---- omc_api.cpp: staging ----------------------------------------------------------------------------------------------------------------
 int upload(DevBuf& b, const void* src, size_t bytes, hipStream_t s);
-int cut_piece(int cut_type, int dir, double vhat, int q1, double* lo, double* hi, double* slope, double* icpt);
 
 // rows (OMC.jl:1558-1685) and row subspace of a set of nodes, on the host: shared by omc_relax_stage and omc_relax_append
 struct NodePack {
@@ -91,9 +92,15 @@ struct ShorAppendLists { const int64_t *n_shor, *shor_idx, *n_soc, *soc_idx; };
 int shor_append_plan(omc_instance* h, int first, int B2, const ShorAppendLists& l, std::vector<int>& load, std::vector<int>& save, ShorGrouping& g);
 int shor_append_write(omc_instance* h, const ShorGrouping& g, int first, hipStream_t s, ShorGroupImages& img);
 void shor_append_commit(omc_instance* h, ShorGrouping& g);
-// the one append path (omc_api.cpp): omc_relax_append, and with `lists` omc_relax_append_shor
+// the branch half of the one append path (omc_api_branch.cpp): the nodes of an omc_relax_append_children call are given by reference, child c =
+// node parent_id[c] + one cut with the directions dirs[c * k ..]; *first_out receives the id of the first child
+struct BranchRefs { const int* parent_id; const int8_t* dirs; int* first_out; };
+int branch_check(omc_instance* h, int first, int C, const BranchRefs& refs, const std::string& pre);      // every refusal, from the host copies (node_L ...)
+int branch_write(omc_instance* h, int first, int C, const BranchRefs& refs, hipStream_t s);               // the two kernels, chunk by chunk
+void branch_commit(omc_instance* h, int first, int C, const BranchRefs& refs);                            // the children's host copies
+// the one append path (omc_api.cpp): omc_relax_append, with `lists` omc_relax_append_shor, with `refs` omc_relax_append_children
 int append_nodes(omc_instance* h, const char* who, int B2, const int* L, const double* cut_x, const double* cut_Uhat, const int8_t* cut_dir,
-                 const int* load_from, const int* save_to, const ShorAppendLists* lists);
+                 const int* load_from, const int* save_to, const ShorAppendLists* lists, const BranchRefs* refs = nullptr);
 
 #pragma GCC visibility pop
 

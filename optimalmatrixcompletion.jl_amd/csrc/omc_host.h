@@ -209,6 +209,10 @@ struct omc_instance {
   // appending nodes to a staged / running batch (omc_relax_reserve, omc_relax_append): descriptor and output arrays are sized for node_cap nodes,
   // the strides (rows, row-subspace columns, cuts per node) for reserve_cuts cuts; Btot_live is what the solve loop reads at its refill points
   int reserve_nodes = 0, reserve_cuts = 0, node_cap = 0, staged_cut_type = 0; std::atomic<int> Btot_live{0}; bool append_closed = true; std::mutex append_mu; hipStream_t append_stream = nullptr;
+  // omc_relax_append_children: per node of the capacity its cuts, rows and an upper bound of its row-subspace columns (staged and appended nodes:
+  // from their NodePack; a child: L + 1, R + 2k + 1, min(n, r + 1)), written at stage time and under append_mu, so that every refusal is
+  // decided without a device read; scratch and index image of the branch kernels (walk_branch_*), sized at stage time for BRANCH_CHUNK children
+  std::vector<int> node_L, node_R, node_r; DevBuf bbrS, bbrI; bool br_ready = false;
   std::atomic<int> hold{0};      // omc_relax_hold: a solve that has run dry waits for omc_relax_append instead of ending
   std::vector<int> done_q; size_t done_read = 0; std::mutex done_mu; hipStream_t fetch_stream = nullptr;      // nodes harvested so far, in harvest order (omc_relax_fetch_done)
   void* comm = nullptr; int comm_rank = 0, comm_world = 1; DevBuf bcomm, amobj; int amobj_B = 0;

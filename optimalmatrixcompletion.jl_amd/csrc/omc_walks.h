@@ -6,6 +6,7 @@
 #pragma once
 #include "omc_carve.h"
 #include "omc_device.h"
+#include "omc_branch.h"
 #include "omc_shor_relax.h"
 #include "omc_shor_cert.h"
 #include "omc_shor_index.h"
@@ -88,6 +89,15 @@ inline void walk_cert_node(Carve& c, const StageDims& d, size_t cnnz, OmcWS& w) 
   const size_t ps = (d.rmax + d.k) * (d.rmax + d.k);
   w.ocBound = c.take<double>(d.N);
   w.ocLam = c.take<double>(d.N * cnnz); w.oclam = c.take<double>(d.N * d.Rmax); w.ocPsi = c.take<double>(d.N * ps);
+}
+
+// omc_relax_append_children (omc_branch.h): bbrS, the scratch of `slots` distinct parents; bbrI, the index image of one chunk -- the host
+// fills an image laid out by this same walk and uploads it with one copy from slot_node to the walk's end
+inline void walk_branch_scratch(Carve& c, size_t slots, size_t n, size_t k, BranchWS& b) {
+  b.vhat = c.take<double>(slots * k); b.q = c.take<double>(slots * n); b.keep = c.take<int>(slots);
+}
+inline void walk_branch_ints(Carve& c, size_t slots, size_t children, size_t k, BranchWS& b) {
+  b.slot_node = c.take<int>(slots); b.slot_L = c.take<int>(slots); b.child_slot = c.take<int>(children); b.dirs = c.take<int8_t>(children * k);
 }
 
 // ---- omc_relax_stage_shor ----------------------------------------------------------------------------------------------------------------
