@@ -20,6 +20,11 @@ def load(f):
     return z, nodes
 
 
+def options(z):
+    """Relaxation options a fixture was made with, where it records any (the rank-k fixtures): as keyword arguments of the parameters."""
+    return {"reference_quirk_q1": bool(z["reference_quirk_q1"])} if "reference_quirk_q1" in z.files else {}
+
+
 def test_fixtures_exist():
     assert len(FILES) >= 3
 
@@ -31,7 +36,7 @@ def test_oracle_reproduces_golden(f, orc):
     for b in (0, len(nodes) - 2):       # two nodes per fixture keep the CPU suite short
         if int(z["iters"][b]) > 1000:
             continue
-        r = orc.sdp_relaxation(inst, nodes[b], str(z["cut_type"]), params=orc.RelaxParams(rho_scale=float(z["rho_scale"])), want_certificate=False)
+        r = orc.sdp_relaxation(inst, nodes[b], str(z["cut_type"]), params=orc.RelaxParams(rho_scale=float(z["rho_scale"]), **options(z)), want_certificate=False)
         assert r["objective"] == pytest.approx(float(z["objective"][b]), rel=1e-9)
         assert r["dual_bound"] == pytest.approx(float(z["dual_bound"][b]), rel=1e-9)
         assert r["iters"] == int(z["iters"][b]) and r["termination_status"] == int(z["status"][b])
@@ -42,7 +47,7 @@ def test_oracle_reproduces_golden(f, orc):
 def test_hip_reproduces_golden(f, omc):
     z, nodes = load(f)
     eng = omc.Engine(z["A"], z["mask"], float(z["gamma"]), int(z["k"]))
-    out = eng.matrix_completion_SDP_relaxation(nodes, str(z["cut_type"]), params=omc.default_params(rho_scale=float(z["rho_scale"])))
+    out = eng.matrix_completion_SDP_relaxation(nodes, str(z["cut_type"]), params=omc.default_params(rho_scale=float(z["rho_scale"]), **{key: int(v) for key, v in options(z).items()}))
     for b, o in enumerate(out):
         assert o["objective"] == pytest.approx(float(z["objective"][b]), rel=REL), (b, o["termination_status"])
         if int(z["status"][b]) == 0:

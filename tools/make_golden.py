@@ -45,6 +45,89 @@ def main():
                             iters=np.array([r["iters"] for r in recs]), lmin=np.array([r["lmin"] for r in recs]),
                             eval_obj=np.array([r["eval_obj"] for r in recs]))
 
+# Ranks 3 to 8 ("Rank-k relaxation fixtures").  Every case: make_instance(kind="lowrank", noise=0.1) with n_obs observed cells,
+# GAMMA = 80.  `dir_seed` seeds the per-column draw of the pieces; `breakpoints` is the separation rule that made the cut vectors;
+# `q1` is RelaxParams.reference_quirk_q1.  A prefix of the cut path becomes a node of the fixture only when the oracle certified it.
+RANK_K_CASES = [
+    dict(name="lowrank_16x20_k3_linear", n=16, m=20, k=3, n_obs=110, seed=21, cut_type="linear", rho_scale=4.0, depth=9,
+         breakpoints="smallest_1_eigvec", q1=True, dir_seed=3),
+    dict(name="lowrank_16x20_k4_linear3", n=16, m=20, k=4, n_obs=150, seed=21, cut_type="linear3", rho_scale=4.0, depth=8,
+         breakpoints="smallest_1_eigvec", q1=False, dir_seed=3),
+    dict(name="lowrank_16x20_k5_linear2", n=16, m=20, k=5, n_obs=200, seed=21, cut_type="linear2", rho_scale=4.0, depth=9,
+         breakpoints="smallest_1_eigvec", q1=True, dir_seed=3),
+    dict(name="lowrank_20x26_k8_linear2", n=20, m=26, k=8, n_obs=380, seed=21, cut_type="linear2", rho_scale=4.0, depth=9,
+         breakpoints="smallest_2_eigvec", q1=True, dir_seed=3),
+]
+
+
+def rank_k_path(c, log=print):
+    """Walk one cut path of `c["depth"]` levels with the oracle; returns (A, mask, cuts, recs), recs[d] = the node with the first d cuts."""
+    A, mask = orc.make_instance(c["n"], c["m"], c["k"], seed=c["seed"], kind="lowrank", n_indices=c["n_obs"], noise=0.1)
+    inst = orc.Instance(A, mask, 80.0, c["k"])
+    rng = np.random.default_rng(c["dir_seed"])
+    labels = orc.DIRECTIONS_OF[c["cut_type"]]
+    P = orc.RelaxParams(rho_scale=c["rho_scale"], reference_quirk_q1=c["q1"])
+    cuts = []; recs = []
+    for d in range(c["depth"] + 1):
+        r = orc.sdp_relaxation(inst, cuts, c["cut_type"], params=P, want_certificate=False)
+        x, _ = orc.breakpoint_vector(r["Y"], r["U"], c["breakpoints"])
+        _, ev = orc.breakpoint_vector(r["Y"], r["U"])
+        kinds = np.array(r["rows"].kinds)
+        recs.append(dict(L=len(cuts), R=len(r["rows"]), r=r["Q"].shape[1], n_active=int(((r["lam"] > 1e-9) & (kinds != "trace")).sum()),
+                         lam=r["lam"].copy(), objective=r["objective"], dual_bound=r["dual_bound"], status=r["termination_status"],
+                         iters=r["iters"], lmin=ev[0], eval_obj=orc.evaluate_objective(r["X"], A, mask, 80.0)))
+        log(c["name"], {k_: v for k_, v in recs[-1].items() if k_ != "lam"})
+        # one piece per column (the full product has up to 4^8 members); the inner pieces need |v-hat| away from 0, as in main()
+        vhat = r["U"].T @ x
+        dr = []
+        for j in range(c["k"]):
+            ok = [s for s in labels if abs(vhat[j]) > 0.05 or s in ("left", "right")]
+            dr.append(ok[int(rng.integers(len(ok)))])
+        cuts = cuts + [(x, r["U"].copy(), dr)]
+    return A, mask, cuts[:-1], recs
+
+
+def check_rank_k_conditions(name, recs):
+    """Condition 1 of the rank-k fixtures (active cuts, a moved objective), on the oracle alone; returns the certified nodes.
+    tests/test_rank_k_cpu.py asserts the conditions again from the stored arrays."""
+    listed = [q for q in recs if q["status"] == 0]
+    assert listed and listed[0]["L"] == 0, (name, "the root must certify")
+    root = listed[0]["objective"]
+    moved = [q for q in listed if q["n_active"] >= 3 and q["objective"] > root * (1.0 + 1e-3)]
+    assert len(moved) >= 2, (name, "fewer than two certified nodes with active cut rows and a moved objective")
+    return listed
+
+
+def make_rank_k_golden(names=None):
+    out_dir = os.path.join(ROOT, "tests", "golden")
+    seen = []
+    for c in RANK_K_CASES:
+        if names and c["name"] not in names:
+            continue
+        A, mask, cuts, recs = rank_k_path(c)
+        listed = check_rank_k_conditions(c["name"], recs)
+        seen += [(c["k"], q["L"], q["r"], q["R"]) for q in listed]
+        cuts = cuts[:listed[-1]["L"]]                    # cuts past the deepest certified node are of no use to a test
+        Rmax = max(q["R"] for q in listed)
+        lam = np.zeros((len(listed), Rmax))
+        for b, q in enumerate(listed):
+            lam[b, :q["R"]] = q["lam"]
+        col = lambda key, src=listed: np.array([q[key] for q in src])
+        np.savez_compressed(os.path.join(out_dir, c["name"] + ".npz"),
+                            A=A, mask=mask, gamma=80.0, k=c["k"], cut_type=c["cut_type"], rho_scale=c["rho_scale"],
+                            breakpoints=c["breakpoints"], reference_quirk_q1=c["q1"],
+                            cut_x=np.stack([q[0] for q in cuts]), cut_U=np.stack([q[1] for q in cuts]),
+                            cut_dir=np.array([[orc.DIR_CODES[s] for s in q[2]] for q in cuts], dtype=np.int8),
+                            node_L=col("L"), objective=col("objective"), dual_bound=col("dual_bound"), status=col("status"),
+                            iters=col("iters"), lmin=col("lmin"), eval_obj=col("eval_obj"),
+                            R=col("R"), r=col("r"), n_active=col("n_active"), lam=lam,
+                            path_status=col("status", recs), path_iters=col("iters", recs), path_objective=col("objective", recs),
+                            path_n_active=col("n_active", recs))
+    if not names:       # condition 2 spans the fixtures
+        assert any(r_ >= 17 for _, _, r_, _ in seen), "no certified node beyond the r = 16 boundary of k_small"
+        assert any(k_ == 8 and r_ <= 16 and L >= 2 and R >= 71 for k_, L, r_, R in seen), "no certified rank-8 node with r <= 16 and R >= 71"
+
+
 def make_shor_golden():
     """Shor-minor fixtures (integer work): mask, X and the oracle's index lists / top violated minors."""
     out_dir = os.path.join(ROOT, "tests", "golden")
@@ -87,5 +170,7 @@ if __name__ == "__main__":
         make_colprox_block_golden()
     elif len(sys.argv) > 1 and sys.argv[1] == "shor":
         make_shor_golden()
+    elif len(sys.argv) > 1 and sys.argv[1] == "rank_k":      # optionally followed by fixture names; without them condition 2 is checked too
+        make_rank_k_golden(sys.argv[2:])
     else:
-        main(); make_shor_golden()
+        main(); make_shor_golden(); make_rank_k_golden()
